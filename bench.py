@@ -12,6 +12,15 @@ region; only 700 poses (39 KB) are re-uploaded per solve.
 
 N > 1: launched by torch.distributed.run, one rank per GPU, observations sharded by camera, the
 reduced system all-reduced over RCCL -> "scaling": "strong" (the scene is fixed).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line.  --full adds
+what takes runs of its own: the per-kernel table and roofline of one LM iteration (vmm_ba_time_kernels) and the
+CPU baseline (oracle/liboracle.so, unless --no-cpu-baseline).
+
+--dump-outputs DIR writes what the last timed solve hands its caller, as float64 .npy files: cam_poses.npy
+(n_cams x 7) and tag_poses.npy (n_tags x 7), rows (qw,qx,qy,qz,tx,ty,tz) as vmm_ba_get_state returns them, and
+cost.npy = [initial_cost, final_cost, num_lm_iterations] of that solve (--workload incremental: rows (id, pose) of
+the reconstructed cameras and tags).  The scene is seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -39,7 +48,12 @@ def parse():
     ap.add_argument("--wall-rows", type=int, default=0,
                     help="with --neighbors: the tags hang in this many rows (1 or 2: a corridor) instead of a wall")
     ap.add_argument("--poll", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the kernels of one LM iteration (per-kernel table, roofline) and the CPU baseline; "
+                         "a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--collective", choices=["rccl", "callback"], default="rccl",
                     help="N > 1: 'rccl' = the library's own ncclAllReduce recorded into the iteration graph "
                          "(vmm_ba_enable_rccl); 'callback' = host callback into torch.distributed per collective")
@@ -58,6 +72,18 @@ def parse():
                     help="f32 = J^T J blocks accumulated/stored in f32, everything else f64 (default for --config 4, "
                          "as BASELINE.json configs[3] words it); f64 otherwise")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every array as out_dir/<name>.npy in float64 (at most 64 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes exceed 64 MB" % total)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def run_steps(ba, eng, s, opts_kw, n_steps):
@@ -79,6 +105,10 @@ def run_steps(ba, eng, s, opts_kw, n_steps):
         solves += 1
         last = out
     return done, evals, solves, last
+
+
+def _pose_row(p):
+    return [float(v) for v in p.q] + [float(v) for v in p.t]
 
 
 def incremental_workload(a):
@@ -105,6 +135,11 @@ def incremental_workload(a):
         dt = time.perf_counter() - t0
         res[mode] = dict(seconds=dt, bundle_adjustments=buf.getvalue().count("Solution "),
                          cameras=len(rec.getReconstructedCameras()), tags=len(rec.getReconstructedTags()))
+        if a.dump_outputs and mode == "resident":
+            # poses of the reconstruction, by id: rows (id, qw,qx,qy,qz,tx,ty,tz)
+            cams, tags = rec.getReconstructedCameras(), rec.getReconstructedTags()
+            res["dump"] = {"cam_poses": [[k] + _pose_row(cams[k]) for k in sorted(cams)],
+                           "tag_poses": [[k] + _pose_row(tags[k]) for k in sorted(tags)]}
         rec.close()
     n_ba = res["resident"]["bundle_adjustments"]
     line = {"metric": "incremental_reconstruction_wall_time", "value": res["resident"]["seconds"], "unit": "s",
@@ -116,6 +151,8 @@ def incremental_workload(a):
                                    "PnP initialisation on the host (pnp.py) included" % (n_cams, n_tags, vis, s.n_obs, n_ba)},
             "resident_handle_s": res["resident"]["seconds"], "handle_per_problem_s": res["per_problem"]["seconds"],
             "reconstructed": {k: res["resident"][k] for k in ("cameras", "tags")}}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res["dump"])
     print(json.dumps(line))
 
 
@@ -225,6 +262,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert done == a.steps, (done, a.steps)
+    if a.dump_outputs and rank == 0:
+        cam, tag = ba.get_state()
+        dump_outputs(a.dump_outputs, {"cam_poses": cam, "tag_poses": tag,
+                                      "cost": [last["initial_cost"], last["final_cost"], last["num_lm_iterations"]]})
 
     line = None
     # what the scene is: BASELINE's configurations are visibility-1.0 walls; --visibility / --neighbors / --wall-rows
@@ -266,6 +307,10 @@ def main():
         if collective_used is not None:
             line["collective"] = collective_used
     if world == 1 and not use_dist:
+        # where the device time of the timed solves went, measured on the device (vmm_ba_summary.time_*_s of the last one)
+        line["phase_report_last_solve_s"] = {k: last[k] for k in ("time_eval_s", "time_eliminate_s", "time_factor_solve_s",
+                                                                    "time_step_s", "time_control_s", "time_solve_s")}
+    if a.full and world == 1 and not use_dist:
         ba.set_state(s.cam_init, s.tag_init)
         kt = ba.time_kernels(eng.default_options(**opts_kw), reps=10)
         n_obs = kt["n_obs"]
@@ -362,9 +407,6 @@ def main():
         line["kernels"]["form_z"] = {"ms": kt["form_z_ms"]}
         line["kernels"]["backsub"] = {"ms": kt["backsub_ms"]}
         line["kernels"]["lm_iteration_enqueued"] = {"ms": kt["lm_iteration_ms"]}
-        # where the device time of the timed solves went, measured on the device (vmm_ba_summary.time_*_s of the last one)
-        line["phase_report_last_solve_s"] = {k: last[k] for k in ("time_eval_s", "time_eliminate_s", "time_factor_solve_s",
-                                                                    "time_step_s", "time_control_s", "time_solve_s")}
         if not a.no_cpu_baseline:
             from oracle import oracle as O
             # Thread counts tried: every visible core (capped at 64) and the CPU share of a one-GPU box (16: with a

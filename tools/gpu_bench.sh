@@ -1,4 +1,5 @@
 set -x
+export OUT=${OUT:-out}   # where this script writes
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; tail -5 gpurun_out/bench.err; cat gpurun_out/bench.json
+mkdir -p $OUT
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -5 $OUT/bench.err; cat $OUT/bench.json

@@ -1,11 +1,13 @@
 # per-launch durations of k_chol_step on the 2000 x 1000 problem
+export OUT=${OUT:-out}   # where this script writes
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/prof4
+mkdir -p $OUT/prof4
 export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof4 -o p4 -- python bench.py --config 4 --steps 2 --warmup 0 --no-cpu-baseline > gpurun_out/prof4/bench.json 2> gpurun_out/prof4/err.log || exit 1
+timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof4 -o p4 -- python bench.py --full --config 4 --steps 2 --warmup 0 --no-cpu-baseline > $OUT/prof4/bench.json 2> $OUT/prof4/err.log || exit 1
 python - <<'PY'
+import os
 import csv, glob, collections
-f = glob.glob("gpurun_out/prof4/*kernel_trace.csv")[0]
+f = glob.glob(os.environ["OUT"] + "/prof4/*kernel_trace.csv")[0]
 rows = []
 with open(f) as fh:
     for r in csv.DictReader(fh):
@@ -19,7 +21,7 @@ for w in range(0, len(idx) - 93, 94):
     tot = sum(rows[i][1] - rows[i][0] for i in idx[w:w + 94])
     if tot > best:
         best, seq = tot, idx[w:w + 94]
-out = open("gpurun_out/prof4/chol_steps.txt", "w")
+out = open(os.environ["OUT"] + "/prof4/chol_steps.txt", "w")
 tot = 0
 for n, i in enumerate(seq):
     d = (rows[i][1] - rows[i][0]) / 1e3
@@ -33,5 +35,5 @@ for r in rows:
 for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])[:12]:
     out.write("%-60s calls=%d total_us=%.0f avg_us=%.1f\n" % (k[:60], v[0], v[1], v[1] / v[0]))
 PY
-find gpurun_out/prof4 -name '*.csv' -size +2M -delete
-cat gpurun_out/prof4/chol_steps.txt | awk 'NR%6==1 || /total|calls/'
+find $OUT/prof4 -name '*.csv' -size +2M -delete
+cat $OUT/prof4/chol_steps.txt | awk 'NR%6==1 || /total|calls/'

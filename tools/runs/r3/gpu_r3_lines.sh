@@ -8,13 +8,13 @@ export TMPDIR=/tmp PYTHONPATH=$GRAFT_REPO_ROOT
 O=gpurun_out/r3lines
 b() { name=$1; shift; "$@" > $O/$name.json 2> $O/$name.err || { tail -5 $O/$name.err; exit 1; }; python -c "
 import json; d=json.loads([l for l in open('$O/$name.json') if l.startswith('{')][-1]); print('$name', round(d['value'],1), d['unit'], round(d.get('ms_per_step', 0),4)); print('   ', {k:round(v['ms']*1000,1) for k,v in d.get('kernels', {}).items()})"; }
-b v025_auto timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.25 --steps 70
-VMM_BA_SCHUR=dense b v025_dense timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.25 --steps 70
-b v050_auto timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.5 --steps 70
-VMM_BA_SCHUR=sparse b v050_sparse timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.5 --steps 70
-b closeup_auto timeout -k 10 300 python bench.py --no-cpu-baseline --neighbors 6 10 --steps 70
-VMM_BA_SCHUR=dense b closeup_dense timeout -k 10 300 python bench.py --no-cpu-baseline --neighbors 6 10 --steps 70
-b incremental timeout -k 10 600 python bench.py --no-cpu-baseline --workload incremental
+b v025_auto timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.25 --steps 70
+VMM_BA_SCHUR=dense b v025_dense timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.25 --steps 70
+b v050_auto timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.5 --steps 70
+VMM_BA_SCHUR=sparse b v050_sparse timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.5 --steps 70
+b closeup_auto timeout -k 10 300 python bench.py --full --no-cpu-baseline --neighbors 6 10 --steps 70
+VMM_BA_SCHUR=dense b closeup_dense timeout -k 10 300 python bench.py --full --no-cpu-baseline --neighbors 6 10 --steps 70
+b incremental timeout -k 10 600 python bench.py --full --no-cpu-baseline --workload incremental
 cut -c1-1500 $O/incremental.json
 cat > /tmp/mid.py <<'PY'
 import json, numpy as np

@@ -9,8 +9,8 @@ b() { name=$1; shift; "$@" > gpurun_out/r3c/$name.json 2> gpurun_out/r3c/$name.e
 import json; d=json.load(open('gpurun_out/r3c/$name.json')); print('$name', round(d['value'],1), round(d['ms_per_step'],4)); print('   ', {k:round(v['ms']*1000,1) for k,v in d['kernels'].items()})"; }
 export VMM_BA_EVAL=twopass
 for v in 0.25 0.5; do
-VMM_BA_SCHUR=sparse b sparse_v$v timeout -k 10 300 python bench.py --no-cpu-baseline --visibility $v --steps 70
+VMM_BA_SCHUR=sparse b sparse_v$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility $v --steps 70
 done
-VMM_BA_SCHUR=dense b dense_v0.25 timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.25 --steps 70
-b cfg4 timeout -k 10 300 python bench.py --no-cpu-baseline --config 4 --steps 20 --warmup 5
-b cfg2 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 70
+VMM_BA_SCHUR=dense b dense_v0.25 timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.25 --steps 70
+b cfg4 timeout -k 10 300 python bench.py --full --no-cpu-baseline --config 4 --steps 20 --warmup 5
+b cfg2 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 70

@@ -9,10 +9,10 @@ b() { name=$1; shift; "$@" > gpurun_out/r3f/$name.json 2> gpurun_out/r3f/$name.e
 import json; d=json.load(open('gpurun_out/r3f/$name.json')); print('$name', round(d['value'],1), round(d['ms_per_step'],4)); print('   ', {k:round(v['ms']*1000,1) for k,v in d['kernels'].items()})"; }
 for t in N4T8 N4T4 N2T8 N8T4 N1T4; do
 lib=$PWD/visual_marker_mapping_amd/libvmm_ba_$t.so; [ $t = N4T8 ] && lib=$PWD/visual_marker_mapping_amd/libvmm_ba.so
-VMM_BA_LIB=$lib VMM_BA_SCHUR=sparse b sparse_v0.25_$t timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.25 --steps 70
+VMM_BA_LIB=$lib VMM_BA_SCHUR=sparse b sparse_v0.25_$t timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.25 --steps 70
 done
-VMM_BA_SCHUR=sparse b sparse_v0.5 timeout -k 10 300 python bench.py --no-cpu-baseline --visibility 0.5 --steps 70
-b closeup_sparse timeout -k 10 300 python bench.py --no-cpu-baseline --neighbors 6 10 --steps 70
+VMM_BA_SCHUR=sparse b sparse_v0.5 timeout -k 10 300 python bench.py --full --no-cpu-baseline --visibility 0.5 --steps 70
+b closeup_sparse timeout -k 10 300 python bench.py --full --no-cpu-baseline --neighbors 6 10 --steps 70
 timeout -k 10 300 python - <<'PY'
 from visual_marker_mapping_amd import engine as eng
 from visual_marker_mapping_amd.synthetic import make_scene

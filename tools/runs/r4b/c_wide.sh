@@ -17,5 +17,5 @@ for rep in range(2):
         del ba
 PY
 cat $O/wide.txt
-for w in 0 1; do VMM_BA_SYRK_WIDE=$w timeout -k 10 300 python bench.py --no-cpu-baseline --steps 70 2>/dev/null | python -c "
+for w in 0 1; do VMM_BA_SYRK_WIDE=$w timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 70 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('wide $w', round(d['value'],1), round(d['ms_per_step'],4), {k:round(v['ms']*1000,1) for k,v in d['kernels'].items()})"; done

@@ -1,7 +1,8 @@
 cd $GRAFT_REPO_ROOT
+REPO=$(pwd)   # the repository root: the scripts run from it
 export TMPDIR=/tmp PYTHONPATH=$GRAFT_REPO_ROOT
 O=gpurun_out/r4b_k; mkdir -p $O
-cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O -o prof -- python3 $GRAFT_REPO_ROOT/bench.py --config 4 --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2> $GRAFT_REPO_ROOT/$O/prof_err.log
+cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $REPO/$O -o prof -- python3 $REPO/bench.py --full --config 4 --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2> $REPO/$O/prof_err.log
 cd $GRAFT_REPO_ROOT
 python - <<'PY'
 import csv, glob

@@ -18,11 +18,11 @@ b() { name=$1; shift; "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('$name', round(d['value'],1), round(d.get('ms_per_step', 0),4), {k:round(v['ms']*1000,1) for k,v in d.get('kernels', {}).items() if k in ('cholesky_solve',)})"; }
 for h in 0 1; do
 export VMM_BA_DF_HELP=$h
-b "headline help=$h" timeout -k 10 300 python bench.py --no-cpu-baseline --steps 140
-b "closeup help=$h" timeout -k 10 300 python bench.py --no-cpu-baseline --neighbors 6 10 --steps 70
-b "corridor help=$h" timeout -k 10 300 python bench.py --no-cpu-baseline --neighbors 6 10 --wall-rows 2 --steps 70
-b "closeup2000 help=$h" timeout -k 10 400 python bench.py --no-cpu-baseline --config 4 --neighbors 6 10 --precision f64 --steps 30 --warmup 10
-b "cfg4 help=$h" timeout -k 10 400 python bench.py --config 4 --steps 24 --warmup 8 --no-cpu-baseline
+b "headline help=$h" timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 140
+b "closeup help=$h" timeout -k 10 300 python bench.py --full --no-cpu-baseline --neighbors 6 10 --steps 70
+b "corridor help=$h" timeout -k 10 300 python bench.py --full --no-cpu-baseline --neighbors 6 10 --wall-rows 2 --steps 70
+b "closeup2000 help=$h" timeout -k 10 400 python bench.py --full --no-cpu-baseline --config 4 --neighbors 6 10 --precision f64 --steps 30 --warmup 10
+b "cfg4 help=$h" timeout -k 10 400 python bench.py --full --config 4 --steps 24 --warmup 8 --no-cpu-baseline
 done
 unset VMM_BA_DF_HELP
 timeout -k 10 400 python - <<'PY'

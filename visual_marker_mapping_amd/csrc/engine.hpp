@@ -8,25 +8,12 @@
 
 #include "../../include/vmm_ba.h"
 #include "geom.hpp"
+#include "plan.hpp"
 
 namespace vmm {
 
-constexpr int kWave = 64;          // gfx950 wavefront
-constexpr int kPart = 32;          // doubles per task partial: 21 (H lower) + 6 (g) + 1 (cost) + pad
-constexpr int kNB = 64;            // dense block size of the reduced system
-constexpr int kDfMaskWords = 4;    // 64-bit words of a block row's structure mask (tree orderings): up to 255 block columns
-constexpr int kDfMaxBlk = 256;
-constexpr int kKT = 16;            // K tile of the MFMA f64 rank-k update (rows of Z per LDS stage)
-constexpr int kST = 128;           // output tile of the rank-k update (the leading dimension is a multiple of it)
 constexpr int kLdsRow = 80;        // LDS row stride (doubles) for 64-wide tiles: rows k, k+1 land in
                                    // opposite 32-bank halves for ds_read_b64 (MI355X_MICROARCH LDS)
-
-// One wave's work: up to 64 consecutive observations of one pose in a family-sorted order.
-struct Task {
-    int32_t pose;
-    int32_t begin;
-    int32_t end;
-};
 
 // Observations sorted by one pose family ("own"); SoA so that lane = observation is coalesced.
 struct ObsOrder {
@@ -107,6 +94,7 @@ struct Engine {
     int n_cu = 256;                 // compute units of the device (workgroup counts of the persistent loops)
     hipStream_t stream = nullptr;
     int rank = 0, world = 1;
+    Switches sw;                    // environment switches, read at create (read_switches)
     bool multi = false;             // world > 1 (or forced for tests): staging buffers, eager launches, all-reduces
     vmm_ba_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -216,16 +204,9 @@ struct Engine {
     double* Linv = nullptr;         // [n_blk][64][64] their inverses (all but the last block)
     unsigned* flags = nullptr;      // [256] unused | epoch word | abort word | two tile counters of k_chol_step | agreement word
     unsigned long long* gran = nullptr;   // [2 * ld] {epoch, 32 value bits} granules of the chain's hand-offs
-    bool no_chain = false;          // VMM_BA_NO_CHAIN=1: per-block back-substitution kernels
     unsigned long long* df_gran = nullptr;   // published 64x8 slices of the dataflow factorisation (<= 21 blocks)
     double* df_compact = nullptr;            // the same blocks once they are COMPLETE, as plain doubles [slot][column][row]
     unsigned* df_done = nullptr;             // [slot] == factorisation epoch: the block's compact copy is written
-    bool no_dataflow = false;       // VMM_BA_NO_DATAFLOW=1: one k_chol_step launch per block column
-    // debugging: VMM_BA_DEBUG_SPIN_LIMIT=<polls> [VMM_BA_DEBUG_SPIN_KERNEL=df|chain|both] [VMM_BA_DEBUG_SPIN_ONCE=1]
-    // force spin give-ups in the one-launch factorisation / back-substitution (tests/test_gpu_edge_cases.py)
-    uint32_t dbg_spin_df = 0, dbg_spin_chain = 0;
-    bool dbg_spin_once = false;
-    int dbg_spin_wg = -1;           // VMM_BA_DEBUG_SPIN_WG=<blockIdx.x>: only that workgroup gives up
     double* yf = nullptr;           // [ldz] solution of the reduced system (scaled coordinates)
     double* step_comm = nullptr;    // [7*n_e + 1]: delta of the eliminated family | per-pose cross terms | votes
     double* cost_comm = nullptr;    // [2] candidate cost (all-reduced)
@@ -257,10 +238,7 @@ struct Engine {
     hipGraphExec_t iter_graph_seg[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // world > 1: the groups between the all-reduces
     int graph_robustify = -1;
     double graph_huber_a = 0.0;
-    bool use_graph = true;
-    int graph_passes = 2;           // LM passes recorded into one iteration graph (VMM_BA_GRAPH_PASSES; 2 measured best)
-    int last_passes = 1;            // passes the last run_iteration enqueued
-    bool eager_first = false;       // VMM_BA_EAGER_FIRST=1: the handle's first iteration is enqueued without capture
+    int last_passes = 1;            // passes the last run_iteration enqueued (sw.graph_passes per graph; 2 measured best)
     bool launched_eagerly = false;
 
     std::vector<void*> allocs;
@@ -287,7 +265,6 @@ void launch_sum(Engine& e, bool guard, const double* in, int n, double* out);
 // kernels_schur.hip
 void launch_elim(Engine& e);
 void launch_schur_rows(Engine& e, bool add_diag);   // block-sparse: S from the pair lists (k_schur_pairs)
-int schur_pairs_per_item();                           // pairs of one row a workgroup of k_schur_pairs takes
 void launch_syrk_only(Engine& e);
 void launch_syrk_reduced(Engine& e);
 void launch_pack_lower(Engine& e, bool unpack);
@@ -297,8 +274,8 @@ void launch_reduce_plan(hipStream_t st, const LmCtl* ctl, const SyrkPlan& p, int
 // safe: the launch-per-block-column factorisation and the per-block back-substitution (no workgroup waits on another)
 void launch_cholesky_solve(Engine& e, double* S, int n_pad, int ld, double* y, LmCtl* ctl, bool safe = false);
 void launch_chol_inverse(Engine& e, int k);
-int dataflow_max_workgroups(int n_cu);
-int dataflow_blocks(int n_blk, int n_cu);
+int dataflow_max_workgroups(int n_cu, const Switches& sw);
+int dataflow_blocks(int n_blk, int n_cu, const Switches& sw);
 struct CholLaunch {   // one k_chol_step launch of the launch-per-column factorisation
     int k;            // block column its panel workgroups factor; -1: the update-only hand-over launch
     int lazy[2];      // panels those workgroups first apply to their own column (older first; -1: none)

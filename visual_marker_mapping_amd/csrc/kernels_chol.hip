@@ -2724,14 +2724,10 @@ int dataflow_workgroups(int n_blk) { return n_blk * (n_blk + 1) / 2 + n_blk; }
 // waiting (k_chol_step) make a wrong guess slow, not wrong.  Measured (MI355X, us per factorisation, this kernel vs one
 // k_chol_step launch per column): 24 blocks 328 vs 584, 30: 461 vs 744, 38: 701 vs 975, 47: 1097 vs 1232,
 // 60: 1948 vs 1711, 94: 6254 vs 3713 -- hence 48.  VMM_BA_DF_MAX_WG overrides the limit (experiments).
-int dataflow_max_workgroups(int n_cu)
+int dataflow_max_workgroups(int n_cu, const Switches& sw)
 {
-    static const int env = [] {
-        const char* v = getenv("VMM_BA_DF_MAX_WG");
-        return v ? atoi(v) : 0;
-    }();
-    if (env > 0)
-        return env;
+    if (sw.df_max_wg > 0)
+        return sw.df_max_wg;
     const int kMaxBlocks = 48;
     return n_cu > kMaxBlocks ? std::max(n_cu, dataflow_workgroups(kMaxBlocks)) : n_cu;
 }
@@ -2740,16 +2736,12 @@ int dataflow_max_workgroups(int n_cu)
 // (dataflow_max_workgroups), else a tail -- the launches of k_chol_step near the end are bound by their panel chain
 // (~25-31 us per block column at n = 6000, whatever the trailing update costs) while the dataflow kernel needs ~14 us
 // per column at 24 to 38 columns.  VMM_BA_CHOL_TAIL sets the tail length (0: none).
-int dataflow_blocks(int n_blk, int n_cu)
+int dataflow_blocks(int n_blk, int n_cu, const Switches& sw)
 {
-    if (dataflow_workgroups(n_blk) <= dataflow_max_workgroups(n_cu))
+    if (dataflow_workgroups(n_blk) <= dataflow_max_workgroups(n_cu, sw))
         return n_blk;
-    static const int env = [] {
-        const char* v = getenv("VMM_BA_CHOL_TAIL");
-        return v ? atoi(v) : -1;
-    }();
-    int tail = env >= 0 ? env : 34;
-    if (dataflow_workgroups(tail) > dataflow_max_workgroups(n_cu) || n_blk > n_cu)
+    int tail = sw.chol_tail >= 0 ? sw.chol_tail : 34;
+    if (dataflow_workgroups(tail) > dataflow_max_workgroups(n_cu, sw) || n_blk > n_cu)
         return 0;
     tail = std::min(tail, n_blk - 2);
     return tail - ((n_blk - tail) & 1);   // the step launches come in pairs: an even number of them in front
@@ -2836,20 +2828,17 @@ static void launch_dataflow(Engine& e, double* S, int n_pad, int ld, LmCtl* ctl,
     a.slot = a.nz ? e.df_slot : nullptr;
     a.Gc = e.df_compact;
     a.done = e.df_done;
-    const char* const bulk_v = getenv("VMM_BA_DF_BULK");   // (read per launch: tests switch it within one process)
-    const int bulk_env = bulk_v ? atoi(bulk_v) : -1;
     // Dense systems: measured (MI355X, us per factorisation, granules only / compact copies): 24 block columns 278 / 295,
     // 30: 387 / 390, 38: 582 / 583, 47: 896 / 891, the 34-column tail at n = 6000: 3023 / 3041 -- a late workgroup there is
     // bound by its two worker waves (26 MFMAs per slice each), not by its sweeps; so only on request (VMM_BA_DF_BULK=1, tested).
     // Tree orderings (k_chol_dataflow_tree) always: 2000 x 1000 close-up 1004 -> 874 us, 500 x 200 close-up 205 -> 200.
-    const bool bulk = e.df_compact && e.df_done && bulk_env > 0;
+    const bool bulk = e.df_compact && e.df_done && e.sw.df_bulk;
     // Helper waves (six waves per workgroup, the same bits): measured (MI355X, factorisation + solve, four / six waves) --
     // tree orderings: 2000 x 1000 close-up (109 block columns) 876 / 810 us, 500 x 200 close-up (22) 202 / 202, corridor
     // 120 / 124; dense: 19 block columns 226 / 238, 24: 281 / 294, 30: 389 / 410, 38: 582 / 617, 47: 892 / 954, the 34-column
     // tail at n = 6000 3042 / 3070.  So: large tree-ordered factors only (VMM_BA_DF_HELP=0 / 1 decides otherwise; the dense
     // kernels were measured with an instantiation that is not kept).
-    const char* const help_v = getenv("VMM_BA_DF_HELP");
-    const bool help = help_v ? help_v[0] == '1' : a.n_blk >= 64;
+    const bool help = e.sw.df_help >= 0 ? e.sw.df_help == 1 : a.n_blk >= 64;
     if (a.nz && help)
         hipLaunchKernelGGL(k_chol_dataflow_tree_help, dim3(e.n_df_wg), dim3(384), 0, e.stream, a);
     else if (a.nz)
@@ -2875,9 +2864,9 @@ static void launch_backsolve_chain(Engine& e, double* S, int n_pad, int ld, doub
 void launch_cholesky_solve(Engine& e, double* S, int n_pad, int ld, double* y, LmCtl* ctl, bool safe)
 {
     const int n_blk = n_pad / kNB;
-    const bool chain = n_blk <= e.n_cu && e.flags && e.gran && !e.no_chain && !safe;
+    const bool chain = n_blk <= e.n_cu && e.flags && e.gran && !e.sw.no_chain && !safe;
     // a tree-ordered handle: the one-launch kernel whatever the size (only the non-zero blocks have workgroups)
-    const int n_df = (chain && e.df_gran && !e.no_dataflow) ? (e.chol_nz_on ? n_blk : dataflow_blocks(n_blk, e.n_cu)) : 0;
+    const int n_df = (chain && e.df_gran && !e.sw.no_dataflow) ? (e.chol_nz_on ? n_blk : dataflow_blocks(n_blk, e.n_cu, e.sw)) : 0;
     if (n_df == n_blk) {
         // one launch for the factorisation + forward substitution, one for the back-substitution chain (which
         // bumps the epoch both kernels tag their granules with)
@@ -2902,7 +2891,7 @@ void launch_cholesky_solve(Engine& e, double* S, int n_pad, int ld, double* y, L
         hipLaunchKernelGGL(k_chol_step, dim3(grid), dim3(256), 0, e.stream, ctl, S, ld, n_pad, n_blk, k, n_panel,
                            L.k >= 0 ? e.P4[k & 3] : (double*)nullptr, panel(L.lazy[1]), panel(L.lazy[0]), e.dinv, e.Ldiag,
                            e.Linv, panel(L.upd[0]), panel(L.upd[1]), L.c0, L.t0, L.t1, n_upd_wg, e.flags + 258);
-        if (getenv("VMM_BA_DEBUG")) {
+        if (e.sw.debug) {
             const hipError_t le = hipPeekAtLastError();
             if (le != hipSuccess)
                 fprintf(stderr, "[vmm_ba debug] k_chol_step k=%d grid=%d: %s\n", k, grid, hipGetErrorString(le));

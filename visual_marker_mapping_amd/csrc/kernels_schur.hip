@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_form_z(LmCtl* ctl, int64_t n_obs, int64
 // at 8 flop/B); 128x128 tiles double the intensity to 16 flop/B and halve the traffic.
 //
 // Work decomposition: the unit of work is one K stage (16 rows of Z) of one output tile; every workgroup
-// gets a contiguous range of units and its first segment id by blockIdx (host plan, make_syrk_plan):
+// gets a contiguous range of units and its first segment id by blockIdx (host plan, plan_syrk in plan.cpp):
 //   * few tiles (500 x 200: 55 tiles on 512 workgroup slots): "stream-K" -- all units, tile-major, cut into
 //     equal ranges, so every workgroup issues the same number of MFMAs whatever the tile count;
 //   * more tiles than slots (2000 x 1000: 1128): whole rounds of one tile per workgroup, ordered so that the
@@ -593,17 +593,8 @@ struct PairArgs {
     const int32_t* row_of;      // explicit form: [n_f] first row of kept pose f in S
 };
 
-#ifndef VMM_PAIR_NS
-#define VMM_PAIR_NS 2
-#endif
 constexpr int kPairChunk = 128;   // left blocks staged per pass: 38 KB of LDS, four workgroups per CU
-constexpr int kPairSplit = VMM_PAIR_NS;                  // lanes that share one output column: each takes every
-                                                         // kPairSplit-th term, the partial sums meet in a fixed shuffle tree
-#ifndef VMM_PAIR_THREADS
-#define VMM_PAIR_THREADS 256
-#endif
-constexpr int kPairThreads = VMM_PAIR_THREADS;           // workgroup size of k_schur_pairs
-constexpr int kPairsPerItem = kPairThreads / (6 * kPairSplit);    // 6 x kPairSplit lanes per pair
+// kPairSplit, kPairThreads, kPairsPerItem: plan.hpp (the host plan cuts the rows into work items of kPairsPerItem pairs)
 constexpr int kPairBlk = 38;      // doubles per staged block: 36 + 2, so that consecutive blocks start 12 banks apart
 
 __global__ __launch_bounds__(kPairThreads) void k_schur_pairs(PairArgs a)
@@ -859,8 +850,6 @@ void launch_reduce_plan(hipStream_t st, const LmCtl* ctl, const SyrkPlan& p, int
         hipLaunchKernelGGL((k_reduce_partials<false>), dim3(16 * p.n_tiles), dim3(256), 0, st, ctl, plan_dev(p), ld, n_rows,
                            S, da);
 }
-
-int schur_pairs_per_item() { return kPairsPerItem; }
 
 void launch_schur_rows(Engine& e, bool add_diag)
 {

@@ -54,8 +54,6 @@ static int upload(Engine& e, T* dst, const std::vector<T>& src)
     return VMM_BA_OK;
 }
 
-static int round_up(int64_t v, int m) { return (int)(((v + m - 1) / m) * m); }
-
 // ---- optional libraries, resolved at run time (libvmm_ba.so itself links only the HIP runtime) ----
 // roctx ranges around the solve and its iterations (rocprofv3 --marker-trace / the reference prints
 // summary.FullReport(), src/TagReconstructor.cpp:741-742; the numeric phase report is in vmm_ba_summary).
@@ -122,300 +120,59 @@ static Rccl& rccl()
     return r;
 }
 
-// VMM_BA_DEBUG_SPIN_LIMIT=<polls> [VMM_BA_DEBUG_SPIN_KERNEL=df|chain|both] [VMM_BA_DEBUG_SPIN_ONCE=1] [VMM_BA_DEBUG_SPIN_WG=<b>]:
-// shrink the bounded spins of k_chol_dataflow / k_backsolve_chain so that they give up (tests of the recovery path only).
-// A limit of 1 makes every wait give up at its first poll, arrived data or not: every pass is then redone,
-// deterministically.  With _WG only workgroup b of the launch gets the shrunk limit -- a give-up that the other workgroups
-// learn of through the abort word only (or not at all, when their part of the factor does not depend on b's).
-static void read_spin_debug_env(Engine& e)
-{
-    const char* sl = getenv("VMM_BA_DEBUG_SPIN_LIMIT");
-    if (!sl)
-        return;
-    const unsigned lim = (unsigned)std::max(1L, atol(sl));
-    const char* sk = getenv("VMM_BA_DEBUG_SPIN_KERNEL");
-    const std::string which = sk ? sk : "both";
-    if (which == "df" || which == "both")
-        e.dbg_spin_df = lim;
-    if (which == "chain" || which == "both")
-        e.dbg_spin_chain = lim;
-    const char* so = getenv("VMM_BA_DEBUG_SPIN_ONCE");
-    e.dbg_spin_once = so && so[0] == '1';
-    const char* sw = getenv("VMM_BA_DEBUG_SPIN_WG");
-    e.dbg_spin_wg = sw ? atoi(sw) : -1;
-}
+// ---- uploads of the host plan (plan.hpp) ----
 
-// Sorts the observations by one pose family (stable counting sort) and cuts each pose's run into
-// wave-sized tasks.
-static int build_order(Engine& e, ObsOrder& o, int n_own, const int32_t* own_idx, const int32_t* other_idx,
-                       const double* px, int64_t n, std::vector<int32_t>* caller_out = nullptr,
-                       std::vector<int32_t>* start_out = nullptr, std::vector<int32_t>* other_out = nullptr)
+static int upload_order(Engine& e, ObsOrder& o, const OrderPlan& p)
 {
-    std::vector<int64_t> start((size_t)n_own + 1, 0);
-    for (int64_t i = 0; i < n; ++i)
-        start[own_idx[i] + 1]++;
-    for (int p = 0; p < n_own; ++p)
-        start[p + 1] += start[p];
-    std::vector<int64_t> pos(start.begin(), start.end() - 1);
-    const int64_t n_pad = std::max<int64_t>(64, round_up(n, 64));
-    std::vector<int32_t> own((size_t)n), other((size_t)n), caller((size_t)n);
-    std::vector<double> pxs((size_t)8 * n_pad, 0.0);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t d = pos[own_idx[i]]++;
-        own[d] = own_idx[i];
-        other[d] = other_idx[i];
-        caller[d] = (int32_t)i;
-        for (int k = 0; k < 8; ++k)
-            pxs[(size_t)k * n_pad + d] = px[8 * i + k];
-    }
-    std::vector<Task> tasks;
-    std::vector<int32_t> pose_task((size_t)n_own + 1, 0);
-    for (int p = 0; p < n_own; ++p) {
-        pose_task[p] = (int32_t)tasks.size();
-        for (int64_t b = start[p]; b < start[p + 1]; b += kWave) {
-            Task t;
-            t.pose = p;
-            t.begin = (int32_t)b;
-            t.end = (int32_t)std::min<int64_t>(b + kWave, start[p + 1]);
-            tasks.push_back(t);
-        }
-    }
-    pose_task[n_own] = (int32_t)tasks.size();
-    o.n = n;
-    o.n_pad = n_pad;
-    o.n_tasks = (int32_t)tasks.size();
+    o.n = p.n;
+    o.n_pad = p.n_pad;
+    o.n_tasks = (int32_t)p.tasks.size();
     int rc;
-    if ((rc = dev_alloc(e, &o.own, (size_t)n))) return rc;
-    if ((rc = dev_alloc(e, &o.other, (size_t)n))) return rc;
-    if ((rc = dev_alloc(e, &o.caller, (size_t)n))) return rc;
-    if ((rc = dev_alloc(e, &o.px, (size_t)8 * n_pad))) return rc;
-    if ((rc = dev_alloc(e, &o.tasks, tasks.size()))) return rc;
-    if ((rc = dev_alloc(e, &o.pose_task, pose_task.size()))) return rc;
-    if ((rc = dev_alloc(e, &o.part, tasks.size() * kPart))) return rc;
-    std::vector<int32_t> start32(start.begin(), start.end());
-    if ((rc = dev_alloc(e, &o.start, start32.size()))) return rc;
-    if ((rc = upload(e, o.start, start32))) return rc;
-    if ((rc = upload(e, o.own, own))) return rc;
-    if ((rc = upload(e, o.other, other))) return rc;
-    if ((rc = upload(e, o.caller, caller))) return rc;
-    if ((rc = upload(e, o.px, pxs))) return rc;
-    if ((rc = upload(e, o.tasks, tasks))) return rc;
-    if ((rc = upload(e, o.pose_task, pose_task))) return rc;
-    HIP_TRY(hipStreamSynchronize(e.stream));  // host vectors go out of scope
-    if (caller_out)
-        caller_out->swap(caller);
-    if (start_out)
-        start_out->swap(start32);
-    if (other_out)
-        other_out->swap(other);
+    if ((rc = dev_alloc(e, &o.own, (size_t)p.n))) return rc;
+    if ((rc = dev_alloc(e, &o.other, (size_t)p.n))) return rc;
+    if ((rc = dev_alloc(e, &o.caller, (size_t)p.n))) return rc;
+    if ((rc = dev_alloc(e, &o.px, (size_t)8 * p.n_pad))) return rc;
+    if ((rc = dev_alloc(e, &o.tasks, p.tasks.size()))) return rc;
+    if ((rc = dev_alloc(e, &o.pose_task, p.pose_task.size()))) return rc;
+    if ((rc = dev_alloc(e, &o.part, p.tasks.size() * kPart))) return rc;
+    if ((rc = dev_alloc(e, &o.start, p.start.size()))) return rc;
+    if ((rc = upload(e, o.start, p.start))) return rc;
+    if ((rc = upload(e, o.own, p.own))) return rc;
+    if ((rc = upload(e, o.other, p.other))) return rc;
+    if ((rc = upload(e, o.caller, p.caller))) return rc;
+    if ((rc = upload(e, o.px, p.px))) return rc;
+    if ((rc = upload(e, o.tasks, p.tasks))) return rc;
+    if ((rc = upload(e, o.pose_task, p.pose_task))) return rc;
     return VMM_BA_OK;
 }
 
-// Work plan of the rank-k update: lower 128x128 tiles with row blocks 0..n_row_blk-1 and column blocks
-// 0..n_col_blk-1 (bj <= bi), K stages of 16 rows; the unit of work is one K stage of one tile.
-//   * At most slots / 8 tiles (500 x 200: 55 tiles, 512 slots): one K slice per XCD -- workgroup b takes the
-//     (b % 8)-th eighth of K of tile b / 8 (see below).
-//   * Otherwise fewer tiles than workgroup slots: "stream-K" -- all units, tile-major, are cut into equal contiguous
-//     ranges, one per workgroup.
-//   * More tiles than slots (2000 x 1000: 1128 tiles): whole rounds of one-tile-per-workgroup first, XCD-aware:
-//     workgroup b runs on XCD b % 8, so the 64 workgroups an XCD holds at a time get 64 CONSECUTIVE tiles of
-//     the row-major tile list -- one or two block rows -- and sweep K in step: the A panel of a block row and
-//     the B panels of its columns are fetched into that XCD's L2 once per K stage and shared (with the plain
-//     stream-K order every workgroup streams its own two panels from HBM: 16 flop/B, measured HBM-bound at
-//     63 TFLOP/s).  The tiles left over after the last full round are split stream-K over one more round.
-// Every workgroup gets its unit range and first segment id by blockIdx; segments (one partial tile each) are
-// numbered in unit order, so a tile's partials are consecutive and summed in that order.
+// The rank-k schedule of plan_syrk on the device: a fresh plan every time, and one partial tile per segment.
 static int make_syrk_plan(Engine& e, SyrkPlan& p, int n_row_blk, int n_col_blk, int k_pad)
 {
-    std::vector<int32_t> bi, bj;
-    for (int r = 0; r < n_row_blk; ++r)
-        for (int c = 0; c <= std::min(r, n_col_blk - 1); ++c) {
-            bi.push_back(r);
-            bj.push_back(c);
-        }
-    p.n_tiles = (int)bi.size();
-    p.n_kt = k_pad / kKT;
-    if (const char* v = getenv("VMM_BA_DEBUG_SYRK_KT"))   // timing experiments only: a product over the first rows of Z
-        p.n_kt = std::max(2, std::min(atoi(v), p.n_kt));
-    // two workgroups (72 KB of LDS each) per CU
-    int hw = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, e.device) == hipSuccess)
-        hw = prop.multiProcessorCount;
-    if (hw <= 0)
-        hw = 256;
-    int per_cu = 2;
-    if (const char* v = getenv("VMM_BA_SYRK_WG_PER_CU"))
-        per_cu = std::max(1, atoi(v));
-    const int64_t slots = per_cu * (int64_t)hw;
-    const bool xcd_rounds = !(getenv("VMM_BA_SYRK_NO_XCD") && getenv("VMM_BA_SYRK_NO_XCD")[0] == '1');
-    const int n_xcd = 8;
-    std::vector<int64_t> wg_u0, wg_u1;
-    std::vector<int32_t> wg_seg0, tile_seg0((size_t)p.n_tiles + 1, 0);
-    int seg = 0;
-    if (xcd_rounds && (int64_t)p.n_tiles * n_xcd <= slots && p.n_kt >= n_xcd) {
-        // Few tiles (500 x 200: 55): one K slice per XCD.  Workgroup b runs on XCD b % 8 (round-robin dispatch)
-        // and owns the (b % 8)-th eighth of K of tile b / 8, so the 55 workgroups of an XCD sweep the SAME rows of
-        // Z in step: every row is fetched into that XCD's L2 once and shared (Z crosses the fabric once per launch
-        // instead of once per workgroup), and every tile leaves exactly eight partials.  Off-diagonal tiles come
-        // first in the tile list: the second workgroup a CU receives is then one of the cheaper diagonal tiles.
-        std::vector<int> order;
-        for (int t = 0; t < p.n_tiles; ++t)
-            if (bi[t] != bj[t])
-                order.push_back(t);
-        for (int t = 0; t < p.n_tiles; ++t)
-            if (bi[t] == bj[t])
-                order.push_back(t);
-        std::vector<int32_t> bi2(bi.size()), bj2(bj.size());
-        for (int t = 0; t < p.n_tiles; ++t) {
-            bi2[t] = bi[order[t]];
-            bj2[t] = bj[order[t]];
-        }
-        bi.swap(bi2);
-        bj.swap(bj2);
-        // Round 4: one 8-wave workgroup per CU (k_syrk_wide), one K slice of ONE tile each; a diagonal tile costs 9/16 of
-        // an off-diagonal one there and gets as many fewer workgroups.  500 x 200: 45 x 5 + 10 x 3 = 255 workgroups on
-        // 256 CUs, 255 partial tiles instead of 495.  VMM_BA_SYRK_WIDE=0: the two-workgroups-per-CU kernel below.
-        const bool want_wide = !(getenv("VMM_BA_SYRK_WIDE") && getenv("VMM_BA_SYRK_WIDE")[0] == '0');
-        if (want_wide && !getenv("VMM_BA_SYRK_SLICES") && !getenv("VMM_BA_SYRK_WG_PER_CU")) {
-            int n_diag = 0;
-            for (int t = 0; t < p.n_tiles; ++t)
-                n_diag += bi[t] == bj[t];
-            const int n_off = p.n_tiles - n_diag;
-            const double kDiagCost = 9.0 / 16.0;
-            const int max_w = std::max(1, p.n_kt / 2);   // at least one 32-row stage per workgroup
-            int w_off = (int)std::floor(hw / (n_off + kDiagCost * n_diag));
-            w_off = std::max(1, std::min(w_off, max_w));
-            int w_diag = std::max(1, std::min((int)std::lround(kDiagCost * w_off), max_w));
-            while (w_off > 1 && (int64_t)w_off * n_off + (int64_t)w_diag * n_diag > hw) {
-                --w_off;
-                w_diag = std::max(1, std::min((int)std::lround(kDiagCost * w_off), max_w));
-            }
-            std::vector<int> w_of((size_t)p.n_tiles);
-            int n_items = 0;
-            for (int t = 0; t < p.n_tiles; ++t) {
-                w_of[t] = bi[t] == bj[t] ? w_diag : w_off;
-                tile_seg0[t] = n_items;
-                n_items += w_of[t];
-            }
-            tile_seg0[p.n_tiles] = n_items;
-            // items slice-major (all tiles' first slices, then the second ones, ...): XCD x takes the x-th run of them, so
-            // the workgroups an XCD holds sweep the same rows of Z
-            std::vector<std::pair<int, int>> items;
-            for (int sl = 0; sl < std::max(w_off, w_diag); ++sl)
-                for (int t = 0; t < p.n_tiles; ++t)
-                    if (sl < w_of[t])
-                        items.emplace_back(t, sl);
-            const int per_x = (n_items + n_xcd - 1) / n_xcd;
-            p.n_wg = per_x * n_xcd;
-            p.wide = true;
-            wg_u0.assign((size_t)p.n_wg, 0);
-            wg_u1.assign((size_t)p.n_wg, 0);
-            wg_seg0.assign((size_t)p.n_wg, 0);
-            for (int b = 0; b < p.n_wg; ++b) {
-                const int x = b % n_xcd, j = b / n_xcd;
-                const int it = x * per_x + j;
-                if (j >= per_x || it >= n_items)
-                    continue;
-                const int t = items[(size_t)it].first, sl = items[(size_t)it].second;
-                wg_u0[b] = (int64_t)t * p.n_kt + (int64_t)p.n_kt * sl / w_of[t];
-                wg_u1[b] = (int64_t)t * p.n_kt + (int64_t)p.n_kt * (sl + 1) / w_of[t];
-                wg_seg0[b] = tile_seg0[t] + sl;
-            }
-            seg = n_items;
-        } else {
-        // K slices per tile: as many as fit the workgroup slots (two per CU), so that every SIMD carries about the
-        // same number of MFMAs (8 slices on 440 of 512 slots left 184 CUs with two workgroups and 72 with one)
-        int n_sl = (int)std::min<int64_t>(slots / p.n_tiles, p.n_kt);
-        if (const char* v = getenv("VMM_BA_SYRK_SLICES"))
-            n_sl = std::max(1, std::min(atoi(v), p.n_kt));
-        const int n_items = p.n_tiles * n_sl;
-        const int per_x = (n_items + n_xcd - 1) / n_xcd;
-        p.n_wg = per_x * n_xcd;
-        wg_u0.assign((size_t)p.n_wg, 0);
-        wg_u1.assign((size_t)p.n_wg, 0);
-        wg_seg0.assign((size_t)p.n_wg, 0);
-        for (int b = 0; b < p.n_wg; ++b) {
-            // items in slice-major order; XCD x (blockIdx % 8) takes the x-th run of per_x items: one or two slices of K
-            const int x = b % n_xcd, j = b / n_xcd;
-            const int it = x * per_x + j;
-            if (j >= per_x || it >= n_items)
-                continue;
-            const int sl = it / p.n_tiles, t = it % p.n_tiles;
-            wg_u0[b] = (int64_t)t * p.n_kt + (int64_t)p.n_kt * sl / n_sl;
-            wg_u1[b] = (int64_t)t * p.n_kt + (int64_t)p.n_kt * (sl + 1) / n_sl;
-            wg_seg0[b] = n_sl * t + sl;
-        }
-        for (int t = 0; t <= p.n_tiles; ++t)
-            tile_seg0[t] = n_sl * t;
-        seg = n_sl * p.n_tiles;
-        }
-    } else {
-    const int64_t full_rounds = (xcd_rounds && slots % n_xcd == 0) ? p.n_tiles / slots : 0;
-    const int64_t tiles_a = full_rounds * slots;                      // one tile per workgroup
-    const int64_t units_b = (int64_t)(p.n_tiles - tiles_a) * p.n_kt;  // the rest: stream-K
-    int64_t n_wg_b = std::min<int64_t>(units_b, slots);
-    if (full_rounds == 0 && units_b > 64 * slots)
-        n_wg_b = 4 * slots;   // xcd_rounds switched off: several waves of stream-K workgroups
-    const int64_t upw_b = n_wg_b > 0 ? (units_b + n_wg_b - 1) / n_wg_b : 0;
-    n_wg_b = upw_b > 0 ? (units_b + upw_b - 1) / upw_b : 0;
-    p.n_wg = (int)(tiles_a + n_wg_b);
-    // logical workgroup l (unit order) -> [u0, u1); segments numbered in unit order
-    std::vector<int64_t> lu0((size_t)p.n_wg + 1, 0);
-    for (int64_t l = 0; l < tiles_a; ++l)
-        lu0[(size_t)l] = l * p.n_kt;
-    for (int64_t l = 0; l <= n_wg_b; ++l)
-        lu0[(size_t)(tiles_a + l)] = std::min<int64_t>(tiles_a * p.n_kt + l * upw_b, (int64_t)p.n_tiles * p.n_kt);
-    std::vector<int32_t> lseg0((size_t)p.n_wg + 1, 0);
-    for (int l = 0; l < p.n_wg; ++l) {
-        lseg0[l] = seg;
-        int64_t u = lu0[l];
-        const int64_t u_end = lu0[l + 1];
-        while (u < u_end) {
-            const int t = (int)(u / p.n_kt);
-            const int kt0 = (int)(u % p.n_kt);
-            const int64_t take = std::min<int64_t>(p.n_kt - kt0, u_end - u);
-            if (kt0 == 0)
-                tile_seg0[t] = seg;
-            u += take;
-            ++seg;
-        }
-    }
-    tile_seg0[p.n_tiles] = seg;
-    // blockIdx -> logical workgroup: inside a full round, XCD x (blockIdx % 8) takes the x-th run of slots/8 tiles
-    wg_u0.resize((size_t)p.n_wg);
-    wg_u1.resize((size_t)p.n_wg);
-    wg_seg0.resize((size_t)p.n_wg);
-    for (int b = 0; b < p.n_wg; ++b) {
-        int64_t l = b;
-        if (b < tiles_a) {
-            const int64_t r = b / slots, o = b % slots;
-            l = r * slots + (o % n_xcd) * (slots / n_xcd) + o / n_xcd;
-        }
-        wg_u0[b] = lu0[(size_t)l];
-        wg_u1[b] = lu0[(size_t)l + 1];
-        wg_seg0[b] = lseg0[(size_t)l];
-    }
-    }
-    p.n_segments = seg;
+    const SyrkSchedule s = plan_syrk(n_row_blk, n_col_blk, k_pad, e.n_cu, e.sw);
+    p = SyrkPlan();
+    p.n_tiles = s.n_tiles;
+    p.n_kt = s.n_kt;
+    p.n_wg = s.n_wg;
+    p.n_segments = s.n_segments;
+    p.wide = s.wide;
     int rc;
-    if ((rc = dev_alloc(e, &p.tile_bi, bi.size()))) return rc;
-    if ((rc = dev_alloc(e, &p.tile_bj, bj.size()))) return rc;
-    if ((rc = dev_alloc(e, &p.wg_u0, wg_u0.size()))) return rc;
-    if ((rc = dev_alloc(e, &p.wg_u1, wg_u1.size()))) return rc;
-    if ((rc = dev_alloc(e, &p.wg_seg0, wg_seg0.size()))) return rc;
-    if ((rc = dev_alloc(e, &p.tile_seg0, tile_seg0.size()))) return rc;
-    if ((rc = dev_alloc(e, &p.partials, (size_t)std::max(seg, 1) * kST * kST, false))) return rc;
-    if ((rc = upload(e, p.tile_bi, bi))) return rc;
-    if ((rc = upload(e, p.tile_bj, bj))) return rc;
-    if ((rc = upload(e, p.wg_u0, wg_u0))) return rc;
-    if ((rc = upload(e, p.wg_u1, wg_u1))) return rc;
-    if ((rc = upload(e, p.wg_seg0, wg_seg0))) return rc;
-    if ((rc = upload(e, p.tile_seg0, tile_seg0))) return rc;
-    HIP_TRY(hipStreamSynchronize(e.stream));
+    if ((rc = dev_alloc(e, &p.tile_bi, s.tile_bi.size()))) return rc;
+    if ((rc = dev_alloc(e, &p.tile_bj, s.tile_bj.size()))) return rc;
+    if ((rc = dev_alloc(e, &p.wg_u0, s.wg_u0.size()))) return rc;
+    if ((rc = dev_alloc(e, &p.wg_u1, s.wg_u1.size()))) return rc;
+    if ((rc = dev_alloc(e, &p.wg_seg0, s.wg_seg0.size()))) return rc;
+    if ((rc = dev_alloc(e, &p.tile_seg0, s.tile_seg0.size()))) return rc;
+    if ((rc = dev_alloc(e, &p.partials, (size_t)std::max(s.n_segments, 1) * kST * kST, false))) return rc;
+    if ((rc = upload(e, p.tile_bi, s.tile_bi))) return rc;
+    if ((rc = upload(e, p.tile_bj, s.tile_bj))) return rc;
+    if ((rc = upload(e, p.wg_u0, s.wg_u0))) return rc;
+    if ((rc = upload(e, p.wg_u1, s.wg_u1))) return rc;
+    if ((rc = upload(e, p.wg_seg0, s.wg_seg0))) return rc;
+    if ((rc = upload(e, p.tile_seg0, s.tile_seg0))) return rc;
+    HIP_TRY(hipStreamSynchronize(e.stream));   // the schedule goes out of scope
     return VMM_BA_OK;
 }
-
 // the two alternating transposed-panel buffers of the look-ahead Cholesky; P must be allocated
 static int setup_lookahead(Engine& e, int n_blk_max, int ld)
 {
@@ -425,24 +182,7 @@ static int setup_lookahead(Engine& e, int n_blk_max, int ld)
     return VMM_BA_OK;
 }
 
-// ---- point landmarks: tag pose <-> its four world corners ----
-// computeMarkerCorners3D (include/visual_marker_mapping/TagReconstructor.h:33-52, called at
-// src/TagReconstructor.cpp:483): R = Eigen::Quaterniond::toRotationMatrix() (no normalisation), corner = R local + t,
-// corners LL, LR, UR, UL.
-static void tag_to_points(const double* qt, const double* wh, double* pts)
-{
-    const double w = qt[0], x = qt[1], y = qt[2], z = qt[3];
-    const double R[9] = { 1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
-                          2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
-                          2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y) };
-    static const double sx[4] = { -1.0, 1.0, 1.0, -1.0 }, sy[4] = { -1.0, -1.0, 1.0, 1.0 };
-    for (int k = 0; k < 4; ++k) {
-        const double lx = sx[k] * wh[0] / 2.0, ly = sy[k] * wh[1] / 2.0;
-        for (int a = 0; a < 3; ++a)
-            pts[3 * k + a] = (R[3 * a] * lx + R[3 * a + 1] * ly) + qt[4 + a];
-    }
-}
-
+// ---- point landmarks: four world corners -> tag pose (the other way: pairs_from_tags, plan.cpp) ----
 // The tag pose of four optimised corners, src/TagReconstructor.cpp:608-639: x along corner 0 -> 1, y along corner
 // 0 -> 3, z = x cross y, t = the mean of the corners.  The dead code stores R.col(0) = y, R.col(1) = -x (its comments
 // name the corners ul, ur, or, ol: an older corner order); with today's order LL, LR, UR, UL
@@ -501,21 +241,6 @@ static void points_to_tag(const double* pts, double* qt)
         qt[a] = q[a];
     for (int a = 0; a < 3; ++a)
         qt[4 + a] = (pts[a] + pts[3 + a] + pts[6 + a] + pts[9 + a]) / 4.0;
-}
-
-// caller's tag poses -> the device's point pairs [2 * n_tags][7] (slot 6 unused)
-static std::vector<double> pairs_from_tags(const double* tag_qt, const double* tag_wh, int n_tags)
-{
-    std::vector<double> pairs((size_t)14 * n_tags, 0.0);
-    for (int t = 0; t < n_tags; ++t) {
-        double pts[12];
-        tag_to_points(tag_qt + 7 * (size_t)t, tag_wh + 2 * (size_t)t, pts);
-        for (int k = 0; k < 6; ++k) {
-            pairs[(size_t)14 * t + k] = pts[k];
-            pairs[(size_t)14 * t + 7 + k] = pts[6 + k];
-        }
-    }
-    return pairs;
 }
 
 // Dense Z and the plan of its rank-k update (the default at high visibility; a handle on the block-sparse path
@@ -741,9 +466,9 @@ static const char* const kSegName[kNumSeg] = { "evaluation at the candidate", "d
 static int run_iteration(Engine& e, const vmm_ba_options& o)
 {
     e.last_passes = 1;
-    if (!e.use_graph)
+    if (!e.sw.use_graph)
         return enqueue_iteration(e, o);
-    if (e.eager_first && !e.launched_eagerly) {
+    if (e.sw.eager_first && !e.launched_eagerly) {
         e.launched_eagerly = true;
         return enqueue_iteration(e, o);
     }
@@ -756,7 +481,7 @@ static int run_iteration(Engine& e, const vmm_ba_options& o)
             // graph_passes passes in one graph: nothing separates two passes inside a graph (~9 us between two graph
             // launches); the passes behind the terminating one find `done` set and return at once
             rc = capture_graph(e, &e.iter_graph, [&](const char** where) -> int {
-                for (int pass = 0; pass < e.graph_passes; ++pass)
+                for (int pass = 0; pass < e.sw.graph_passes; ++pass)
                     for (int seg = 0; seg < kNumSeg; ++seg) {
                         enqueue_segment(e, o, seg);
                         int r;
@@ -775,10 +500,7 @@ static int run_iteration(Engine& e, const vmm_ba_options& o)
                 const std::string why = rc ? g_err : std::string();
                 // VMM_BA_DEBUG_CAPTURE_FAIL=<rank>: that rank votes "my capture failed" although it did not -- the path of a
                 // rank whose RCCL refuses the capture, without such an RCCL (tests/test_gpu_distributed.py)
-                bool mine = rc == VMM_BA_OK;
-                if (const char* v = getenv("VMM_BA_DEBUG_CAPTURE_FAIL"))
-                    if (v[0] && atoi(v) == e.rank)
-                        mine = false;
+                const bool mine = rc == VMM_BA_OK && e.sw.capture_fail_rank != e.rank;
                 int arc;
                 if ((arc = rccl_agree(e, mine, &all_ok)))
                     return arc;
@@ -787,7 +509,7 @@ static int run_iteration(Engine& e, const vmm_ba_options& o)
                     // enqueued collectives, on every rank
                     drop_graphs(e);
                     e.rccl_graph = false;
-                    if (getenv("VMM_BA_DEBUG"))
+                    if (e.sw.debug)
                         fprintf(stderr, "[vmm_ba debug] rank %d: RCCL not recorded into the iteration graph (%s)\n", e.rank,
                                 rc ? why.c_str() : "another rank could not");
                     return run_iteration(e, o);
@@ -813,7 +535,7 @@ static int run_iteration(Engine& e, const vmm_ba_options& o)
     Range r("vmm_ba lm_iteration");
     if (one_graph) {
         HIP_TRY(hipGraphLaunch(e.iter_graph, e.stream));
-        e.last_passes = e.graph_passes;
+        e.last_passes = e.sw.graph_passes;
         return VMM_BA_OK;
     }
     int rc;
@@ -842,7 +564,7 @@ static int recover_sync_timeout(Engine& e, const vmm_ba_options& o)
     c.sync_timeout = 0;
     c.lin_fail = 0;
     c.done = 0;
-    if (e.dbg_spin_once)
+    if (e.sw.spin_once)
         c.spin_limit_df = c.spin_limit_chain = 0;
     HIP_TRY(hipMemcpyAsync(e.ctl, e.ctl_host, sizeof(LmCtl), hipMemcpyHostToDevice, e.stream));
     Range r("vmm_ba sync time-out recovery");
@@ -892,9 +614,9 @@ static int flush_state(Engine& e)
 static void init_ctl(Engine& e, LmCtl& c, const vmm_ba_options& o, int trace_capacity)
 {
     memset(&c, 0, sizeof(c));
-    c.spin_limit_df = e.dbg_spin_df;
-    c.spin_limit_chain = e.dbg_spin_chain;
-    c.spin_wg = e.dbg_spin_wg;
+    c.spin_limit_df = e.sw.spin_df;
+    c.spin_limit_chain = e.sw.spin_chain;
+    c.spin_wg = e.sw.spin_wg;
     c.max_num_iterations = o.max_num_iterations;
     c.robustify = o.robustify;
     c.jacobi_scaling = o.jacobi_scaling;
@@ -915,6 +637,272 @@ static void init_ctl(Engine& e, LmCtl& c, const vmm_ba_options& o, int trace_cap
     c.trace_capacity = trace_capacity;
 }
 
+// ---- vmm_ba_create: validate, expand, open the device, read the switches, plan, allocate and upload ----
+
+// Everything that can be checked without a device (the caller's problem, before any point-landmark expansion).
+static int validate_problem(const vmm_ba_problem* p, const vmm_ba_create_options& co)
+{
+    if (p->n_cams <= 0 || p->n_tags <= 0 || p->n_obs < 0 || !p->cam_qt || !p->tag_qt || !p->tag_wh
+        || (p->n_obs > 0 && (!p->obs_cam || !p->obs_tag || !p->obs_px))) {
+        set_error("problem needs >= 1 camera, >= 1 tag and non-null arrays");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (p->n_obs >= (int64_t)1 << 31) {
+        set_error("n_obs must fit in 31 bits");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    for (int64_t i = 0; i < p->n_obs; ++i)
+        if (p->obs_cam[i] < 0 || p->obs_cam[i] >= p->n_cams || p->obs_tag[i] < 0 || p->obs_tag[i] >= p->n_tags) {
+            set_error("observation " + std::to_string(i) + " references a camera or tag index out of range");
+            return VMM_BA_ERR_ARGUMENT;
+        }
+    if (p->fixed_tag >= p->n_tags) {
+        set_error("fixed_tag out of range");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (co.landmarks != VMM_BA_LANDMARK_TAG_POSES && co.landmarks != VMM_BA_LANDMARK_POINTS) {
+        set_error("create_options.landmarks must be VMM_BA_LANDMARK_TAG_POSES or VMM_BA_LANDMARK_POINTS");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (co.landmarks == VMM_BA_LANDMARK_POINTS && co.precision != VMM_BA_PRECISION_F64) {
+        set_error("point landmarks run in f64 only");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (co.landmarks == VMM_BA_LANDMARK_POINTS && (p->n_obs >= (int64_t)1 << 30 || p->n_tags >= 1 << 30)) {
+        set_error("problem too large for point landmarks");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (co.precision != VMM_BA_PRECISION_F64 && co.precision != VMM_BA_PRECISION_F32_ACCUM) {
+        set_error("create_options.precision must be VMM_BA_PRECISION_F64 or VMM_BA_PRECISION_F32_ACCUM");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (co.world_size < 1 || co.rank < 0 || co.rank >= co.world_size) {
+        set_error("bad rank / world_size");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    return VMM_BA_OK;
+}
+
+// Stream and compute units of the engine's device, and every kernel touched once per process and device before
+// anything is captured.
+static int open_device(Engine& e, int device)
+{
+    e.device = device;
+    if (hipSetDevice(e.device) != hipSuccess || hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking) != hipSuccess) {
+        set_error("hipSetDevice / hipStreamCreate failed");
+        e.stream = nullptr;
+        return VMM_BA_ERR_HIP;
+    }
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, e.device) == hipSuccess && prop.multiProcessorCount > 0)
+        e.n_cu = prop.multiProcessorCount;
+    static bool preloaded[64] = {};
+    if (e.device < 64 && !preloaded[e.device] && !e.sw.no_preload) {
+        const int bad = preload_eval_kernels() + preload_schur_kernels() + preload_chol_kernels() + preload_lm_kernels()
+            + preload_cov_kernels();
+        if (bad) {
+            set_error("hipFuncGetAttributes failed for " + std::to_string(bad) + " kernels (code object not loadable on this device)");
+            return VMM_BA_ERR_HIP;
+        }
+        preloaded[e.device] = true;
+    }
+    return VMM_BA_OK;
+}
+
+// The plan's sizes and decisions, kept by the engine.
+static void take_plan(Engine& e, const Plan& P)
+{
+    e.n_e = P.n_e;
+    e.n_f = P.n_f;
+    e.fused_eval = P.fused_eval;
+    e.fused_n_e_act = P.fused_n_e_act;
+    e.fused_f_pad = P.fused_f_pad;
+    e.fused_chunks = P.fused_chunks;
+    e.fused_group = P.fused_group;
+    e.fused_groups = P.fused_groups;
+    e.n_red = P.n_red;
+    e.n_pad = P.n_pad;
+    e.n_blk = P.n_blk;
+    e.ldz = P.ldz;
+    e.k_dim = P.k_dim;
+    e.k_pad = P.k_pad;
+    e.sparse_schur = P.sparse_schur;
+    e.co_terms = P.co_terms;
+    e.schur_flops = P.schur_flops;
+    e.h_row_of = P.h_row_of;
+    e.nd_node_first_blk = P.nd_node_first_blk;
+    e.explicit_pairs = P.explicit_pairs;
+    e.n_row_items = P.n_row_items;
+    e.chol_flops = P.chol_flops;
+    e.n_df_wg = P.n_df_wg;
+    e.df_tree_slots = P.df_tree_slots;
+    e.chol_nz_on = !P.chol_nz.empty();
+}
+
+// Device buffers of the engine, the plan's tables copied into them (the poses from the caller's problem `p`).
+static int allocate_and_upload(Engine& e, const Plan& P, const vmm_ba_problem& p)
+{
+    const int n_pose = e.n_cams + e.n_tags;
+    int rc;
+    // poses
+    if ((rc = dev_alloc(e, &e.cam_qt, (size_t)7 * e.n_cams))) return rc;
+    if ((rc = dev_alloc(e, &e.tag_qt, (size_t)7 * e.n_tags))) return rc;
+    if ((rc = dev_alloc(e, &e.cam_cand, (size_t)7 * e.n_cams))) return rc;
+    if ((rc = dev_alloc(e, &e.tag_cand, (size_t)7 * e.n_tags))) return rc;
+    if ((rc = dev_alloc(e, &e.tag_wh, (size_t)2 * e.n_tags))) return rc;
+    if (hipMemcpyAsync(e.cam_qt, p.cam_qt, sizeof(double) * 7 * e.n_cams, hipMemcpyHostToDevice, e.stream) != hipSuccess
+        || hipMemcpyAsync(e.tag_qt, p.tag_qt, sizeof(double) * 7 * e.n_tags, hipMemcpyHostToDevice, e.stream) != hipSuccess
+        || hipMemcpyAsync(e.tag_wh, p.tag_wh, sizeof(double) * 2 * e.n_tags, hipMemcpyHostToDevice, e.stream) != hipSuccess
+        || hipStreamSynchronize(e.stream) != hipSuccess) {
+        set_error("pose upload failed");
+        return VMM_BA_ERR_HIP;
+    }
+    // observation orders
+    if ((rc = upload_order(e, e.ordE, P.ordE))) return rc;
+    if ((rc = upload_order(e, e.ordF, P.ordF))) return rc;
+    if (e.fused_eval) {
+        if ((rc = dev_alloc(e, &e.pair_obs, P.pair_obs.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.fused_e_list, P.fused_e_list.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.fused_e_part0, P.fused_e_part0.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.fused_pose_task, P.fused_pose_task.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.fused_partE, (size_t)std::max(P.fused_slots, 1) * kPart))) return rc;
+        if ((rc = dev_alloc(e, &e.fused_partF, (size_t)e.fused_groups * 28 * e.fused_f_pad))) return rc;
+        if ((rc = upload(e, e.pair_obs, P.pair_obs))) return rc;
+        if ((rc = upload(e, e.fused_e_list, P.fused_e_list))) return rc;
+        if ((rc = upload(e, e.fused_e_part0, P.fused_e_part0))) return rc;
+        if ((rc = upload(e, e.fused_pose_task, P.fused_pose_task))) return rc;
+    }
+
+    // normal-equation blocks
+    e.small_count = (size_t)42 * n_pose + 2;
+    if ((rc = dev_alloc(e, &e.small, e.small_count))) return rc;
+    e.H_cam = e.small;
+    e.H_tag = e.H_cam + (size_t)36 * e.n_cams;
+    e.g_cam = e.H_tag + (size_t)36 * e.n_tags;
+    e.g_tag = e.g_cam + (size_t)6 * e.n_cams;
+    e.cost_slot = e.g_tag + (size_t)6 * e.n_tags;
+    // the LM loop evaluates at the candidate into this staging copy (all-reduced when world > 1); it replaces the
+    // working copy when the step is accepted
+    // (+ n_e per-pose costs of the eliminated family behind it: world > 1 sums them over the ranks with the blocks)
+    if ((rc = dev_alloc(e, &e.small_stage, e.small_count + (size_t)e.n_e))) return rc;
+    e.ev_pose_cost = e.small_stage + e.small_count;
+    e.small_alt_off = e.multi ? 0 : (int64_t)(e.small_stage - e.small);
+    e.ev_H_cam = e.small_stage;
+    e.ev_H_tag = e.ev_H_cam + (size_t)36 * e.n_cams;
+    e.ev_g_cam = e.ev_H_tag + (size_t)36 * e.n_tags;
+    e.ev_g_tag = e.ev_g_cam + (size_t)6 * e.n_cams;
+    e.ev_cost = e.ev_g_tag + (size_t)6 * e.n_tags;
+    if ((rc = dev_alloc(e, &e.obs_mask, (size_t)std::max<int64_t>(e.n_obs, 1), false))) return rc;
+    if (hipMemsetAsync(e.obs_mask, 1, (size_t)std::max<int64_t>(e.n_obs, 1), e.stream) != hipSuccess) {
+        set_error("hipMemsetAsync(obs_mask) failed");
+        return VMM_BA_ERR_HIP;
+    }
+    const size_t n_stat = (size_t)e.ordE.n_tasks + (size_t)e.ordF.n_tasks + 1;
+    if ((rc = dev_alloc(e, &e.stats_part, n_stat))) return rc;
+    if ((rc = dev_alloc(e, &e.stats_cnt, n_stat))) return rc;
+    if ((rc = dev_alloc(e, &e.stats_pose, (size_t)2 * n_pose))) return rc;
+    if (e.f32_accum) {
+        if ((rc = dev_alloc(e, &e.Wf, (size_t)36 * e.ordE.n_pad))) return rc;
+        if ((rc = dev_alloc(e, &e.Wf2, (size_t)36 * e.ordE.n_pad))) return rc;
+    } else {
+        if ((rc = dev_alloc(e, &e.W, (size_t)36 * e.ordE.n_pad))) return rc;
+        if ((rc = dev_alloc(e, &e.W2, (size_t)36 * e.ordE.n_pad))) return rc;
+    }
+    if ((rc = dev_alloc(e, &e.scale, (size_t)6 * n_pose))) return rc;
+    if ((rc = dev_alloc(e, &e.diag, (size_t)6 * n_pose))) return rc;
+    if ((rc = dev_alloc(e, &e.D2, (size_t)6 * n_pose))) return rc;
+    if ((rc = dev_alloc(e, &e.delta, (size_t)6 * n_pose))) return rc;
+    if ((rc = dev_alloc(e, &e.active, (size_t)n_pose))) return rc;
+
+    // elimination: block-sparse (the plan's pair lists, and the tree-ordered factor's structure) or dense Z
+    if ((rc = dev_alloc(e, &e.Le, (size_t)36 * e.n_e))) return rc;
+    if ((rc = dev_alloc(e, &e.ze, (size_t)6 * e.n_e))) return rc;
+    if (e.sparse_schur) {
+        if ((rc = dev_alloc(e, &e.Zc, (size_t)36 * std::max<int64_t>(e.n_obs, 1)))) return rc;
+        if ((rc = dev_alloc(e, &e.f2e, P.f2e.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.pair_start, P.pair_start.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.pair_tstart, P.pair_tstart.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.pair_terms, P.pair_terms.size()))) return rc;
+        if ((rc = dev_alloc(e, &e.row_items, P.row_items.size()))) return rc;
+        if ((rc = upload(e, e.f2e, P.f2e))) return rc;
+        if ((rc = upload(e, e.pair_start, P.pair_start))) return rc;
+        if ((rc = upload(e, e.pair_tstart, P.pair_tstart))) return rc;
+        if ((rc = upload(e, e.pair_terms, P.pair_terms))) return rc;
+        if ((rc = upload(e, e.row_items, P.row_items))) return rc;
+        if (e.chol_nz_on) {
+            if ((rc = dev_alloc(e, &e.chol_nz, P.chol_nz.size()))) return rc;
+            if ((rc = upload(e, e.chol_nz, P.chol_nz))) return rc;
+            if ((rc = dev_alloc(e, &e.chol_order, P.chol_order.size()))) return rc;
+            if ((rc = upload(e, e.chol_order, P.chol_order))) return rc;
+            if ((rc = dev_alloc(e, &e.df_wg, P.df_wg.size()))) return rc;
+            if ((rc = upload(e, e.df_wg, P.df_wg))) return rc;
+            if ((rc = dev_alloc(e, &e.df_slot, P.df_slot.size()))) return rc;
+            if ((rc = upload(e, e.df_slot, P.df_slot))) return rc;
+        }
+        if (e.explicit_pairs) {
+            if ((rc = dev_alloc(e, &e.pair_col, P.pair_col.size()))) return rc;
+            if ((rc = dev_alloc(e, &e.row_of, P.row_of.size()))) return rc;
+            if ((rc = upload(e, e.pair_col, P.pair_col))) return rc;
+            if ((rc = upload(e, e.row_of, P.row_of))) return rc;
+            if (!P.pose_of_row.empty()) {
+                if ((rc = dev_alloc(e, &e.pose_of_row, P.pose_of_row.size()))) return rc;
+                if ((rc = upload(e, e.pose_of_row, P.pose_of_row))) return rc;
+            }
+        }
+    } else {
+        if ((rc = ensure_dense_schur(e))) return rc;
+    }
+    if ((rc = dev_alloc(e, &e.S, (size_t)e.ldz * e.ldz))) return rc;
+    if (e.multi && (rc = dev_alloc(e, &e.S_packed, (size_t)(e.n_pad + 1) * (e.n_pad + 2) / 2))) return rc;
+    if ((rc = dev_alloc(e, &e.P, (size_t)4 * kNB * e.ldz))) return rc;
+    if ((rc = setup_lookahead(e, e.n_blk, e.ldz))) return rc;
+    if ((rc = dev_alloc(e, &e.dinv, (size_t)e.ldz))) return rc;
+    if ((rc = dev_alloc(e, &e.Ldiag, (size_t)(e.n_blk + 1) * 4096))) return rc;
+    if ((rc = dev_alloc(e, &e.Linv, (size_t)(e.n_blk + 1) * 4096))) return rc;
+    if ((rc = dev_alloc(e, &e.flags, 264))) return rc;
+    if ((rc = dev_alloc(e, &e.gran, (size_t)2 * e.ldz))) return rc;
+    {
+        // published slices of the one-launch factorisation: 64 KB per block below the diagonal (dense: of the block columns
+        // that kernel takes; tree ordering: of the non-zero blocks, and of the dense kernel's share when the handle is
+        // switched to the natural dense system for a call)
+        const size_t nd = e.sw.no_dataflow ? 0 : (size_t)dataflow_blocks(e.n_blk, e.n_cu, e.sw);
+        const size_t slots = std::max(nd * (nd + 1) / 2, e.sw.no_dataflow ? (size_t)0 : e.df_tree_slots);
+        if (slots > 0 && (rc = dev_alloc(e, &e.df_gran, slots * 8 * 1024)))
+            return rc;
+        if (slots > 0 && (rc = dev_alloc(e, &e.df_compact, slots * 4096, false)))
+            return rc;
+        if (slots > 0 && (rc = dev_alloc(e, &e.df_done, slots)))
+            return rc;
+    }
+    if ((rc = dev_alloc(e, &e.yf, (size_t)e.ldz))) return rc;
+    if ((rc = dev_alloc(e, &e.step_comm, (size_t)7 * e.n_e + 1))) return rc;
+    if ((rc = dev_alloc(e, &e.cost_comm, 2))) return rc;
+    const size_t n_part = (size_t)std::max<int>(e.ordE.n_tasks, e.n_e) + 1;
+    if ((rc = dev_alloc(e, &e.part_cost, n_part))) return rc;
+    if ((rc = dev_alloc(e, &e.part_cross, n_part))) return rc;
+    if ((rc = dev_alloc(e, &e.part_k1, n_part))) return rc;
+    if ((rc = dev_alloc(e, &e.pose_part, (size_t)5 * n_pose))) return rc;
+    if ((rc = dev_alloc(e, &e.pose_gm, (size_t)n_pose))) return rc;
+    if ((rc = dev_alloc(e, &e.ctl, 1))) return rc;
+    if (hipHostMalloc((void**)&e.ctl_host, sizeof(LmCtl)) != hipSuccess) {
+        set_error("hipHostMalloc failed");
+        e.ctl_host = nullptr;
+        return VMM_BA_ERR_HIP;
+    }
+    memset(e.ctl_host, 0, sizeof(LmCtl));
+    if (hipHostMalloc((void**)&e.pose_stage, sizeof(double) * 7 * (size_t)n_pose, hipHostMallocMapped) != hipSuccess
+        || hipHostGetDevicePointer((void**)&e.pose_stage_dev, e.pose_stage, 0) != hipSuccess
+        || hipEventCreateWithFlags(&e.pose_ev, hipEventDisableTiming) != hipSuccess) {
+        set_error("hipHostMalloc / hipEventCreate (pose staging) failed");
+        return VMM_BA_ERR_HIP;
+    }
+    e.trace_capacity = 0;
+    if (hipStreamSynchronize(e.stream) != hipSuccess) {   // the plan's vectors go out of scope
+        set_error("create: device synchronisation failed");
+        return VMM_BA_ERR_HIP;
+    }
+    return VMM_BA_OK;
+}
 } // namespace vmm
 
 using namespace vmm;
@@ -955,178 +943,6 @@ void vmm_ba_default_create_options(vmm_ba_create_options* o)
     o->world_size = 1;
 }
 
-// ---- block structure of the factor under a tree ordering ---------------------------------------------------------
-// One mask per 64-row block row (kDfMaskWords words: up to 255 block columns), bit k = block (i, k) of the factor may be
-// non-zero: the blocks the kept poses' 6x6 blocks touch (rows = first row of every kept pose, nbr = the co-observation
-// graph), then symbolic fill (eliminating block column k couples every two block rows with an entry in it).  Row nb is the
-// right-hand side row: all ones.
-struct BlkMask {
-    unsigned long long w[kDfMaskWords] = {};
-    void set(int k) { w[k >> 6] |= 1ull << (k & 63); }
-    bool test(int k) const { return (w[k >> 6] >> (k & 63)) & 1ull; }
-};
-
-static std::vector<BlkMask> symbolic_factor(int nb, const std::vector<int32_t>& rows,
-                                            const std::vector<std::vector<int32_t>>& nbr)
-{
-    std::vector<BlkMask> nz((size_t)nb + 1);
-    for (int i = 0; i < nb; ++i)
-        nz[(size_t)i].set(i);
-    const int n_f = (int)rows.size();
-    auto touch = [&](int f1, int f2) {
-        const int r1 = rows[(size_t)f1], r2 = rows[(size_t)f2];
-        for (int bi = r1 / kNB; bi <= (r1 + 5) / kNB; ++bi)
-            for (int bj = r2 / kNB; bj <= (r2 + 5) / kNB; ++bj)
-                nz[(size_t)std::max(bi, bj)].set(std::min(bi, bj));
-    };
-    for (int fq = 0; fq < n_f; ++fq) {
-        touch(fq, fq);
-        for (const int32_t f2 : nbr[(size_t)fq])
-            touch(fq, f2);
-    }
-    for (int k = 0; k < nb; ++k)
-        for (int i = k + 1; i < nb; ++i)
-            if (nz[(size_t)i].test(k))
-                for (int j2 = k + 1; j2 <= i; ++j2)
-                    if (nz[(size_t)j2].test(k))
-                        nz[(size_t)i].set(j2);
-    for (int k = 0; k < nb; ++k)
-        nz[(size_t)nb].set(k);
-    return nz;
-}
-
-// The model of the one-launch kernel the ordering decisions use (microseconds; measured in round 4: a block column's own
-// eight rounds 7.1; a panel's eight slices are 8 of work for the workgroup that applies them, which it does while they are
-// produced -- it is 2.7 behind when the panel ends): when block column j is done if it takes its panels in the order they
-// finish.  Also fills the order and the longest chain of dependent columns.
-static double model_tree_factorisation(int nb, const std::vector<BlkMask>& nz, std::vector<unsigned char>* ord, int* path_max)
-{
-    std::vector<double> t_done((size_t)nb, 0.0);
-    std::vector<int> path((size_t)nb, 1);
-    int pm = 0;
-    static const bool old_model = [] {
-        const char* v = getenv("VMM_BA_TREE_MODEL");
-        return v && !strcmp(v, "r3");
-    }();
-    for (int j2 = 0; j2 < nb; ++j2) {
-        std::vector<int> ks;
-        for (int k = 0; k < j2; ++k)
-            if (nz[(size_t)j2].test(k))
-                ks.push_back(k);
-        std::stable_sort(ks.begin(), ks.end(), [&](int x, int y) { return t_done[(size_t)x] < t_done[(size_t)y]; });
-        double t = 0.0;
-        for (size_t q = 0; q < ks.size(); ++q) {
-            if (ord)
-                (*ord)[(size_t)j2 * kDfMaxBlk + q] = (unsigned char)ks[q];
-            t = old_model ? std::max(t, t_done[(size_t)ks[q]]) + 5.6 : std::max(t + 8.0, t_done[(size_t)ks[q]] + 2.7);
-            path[(size_t)j2] = std::max(path[(size_t)j2], path[(size_t)ks[q]] + 1);
-        }
-        t_done[(size_t)j2] = t + (old_model ? 11.0 : 7.1);
-        pm = std::max(pm, path[(size_t)j2]);
-    }
-    if (path_max)
-        *path_max = pm;
-    double t_end = 0.0;
-    for (const double t : t_done)
-        t_end = std::max(t_end, t);
-    return t_end;
-}
-
-// ---- tree ordering of the kept family (block-sparse path) -------------------------------------------------------
-// Nested dissection of the co-observation graph of the kept poses (two kept poses are neighbours when one eliminated
-// pose sees both: exactly the non-zero blocks of the reduced system).  A part is cut at the breadth-first level (from a
-// pseudo-peripheral vertex) that balances the two sides; the level is the separator and is ordered BEHIND both sides,
-// recursively.  `nodes` comes out in elimination order (children before their separator); parts of one level do not
-// touch each other, so their block columns of the factor do not depend on each other.
-static void nd_dissect(const std::vector<std::vector<int32_t>>& nbr, std::vector<int32_t> verts, int leaf_max, int depth,
-                       std::vector<int32_t>& stamp, int32_t& stamp_next, std::vector<std::vector<int32_t>>& nodes)
-{
-    if (verts.empty())
-        return;
-    if ((int)verts.size() <= leaf_max || depth <= 0) {
-        nodes.push_back(std::move(verts));
-        return;
-    }
-    // connected components of the induced subgraph
-    const int32_t in_set = stamp_next++;
-    for (const int32_t v : verts)
-        stamp[(size_t)v] = in_set;
-    std::vector<std::vector<int32_t>> comps;
-    {
-        const int32_t seen = stamp_next++;
-        for (const int32_t v0 : verts) {
-            if (stamp[(size_t)v0] != in_set)
-                continue;
-            comps.emplace_back();
-            std::vector<int32_t>& c = comps.back();
-            c.push_back(v0);
-            stamp[(size_t)v0] = seen;
-            for (size_t h = 0; h < c.size(); ++h)
-                for (const int32_t w : nbr[(size_t)c[h]])
-                    if (stamp[(size_t)w] == in_set) {
-                        stamp[(size_t)w] = seen;
-                        c.push_back(w);
-                    }
-        }
-    }
-    if (comps.size() > 1) {
-        // independent already: two groups of about equal size, no separator
-        std::sort(comps.begin(), comps.end(),
-                  [](const std::vector<int32_t>& a, const std::vector<int32_t>& b) { return a.size() > b.size(); });
-        std::vector<int32_t> A, B;
-        for (auto& c : comps) {
-            std::vector<int32_t>& dst = A.size() <= B.size() ? A : B;
-            dst.insert(dst.end(), c.begin(), c.end());
-        }
-        nd_dissect(nbr, std::move(A), leaf_max, depth - 1, stamp, stamp_next, nodes);
-        nd_dissect(nbr, std::move(B), leaf_max, depth - 1, stamp, stamp_next, nodes);
-        return;
-    }
-    // level structure from a pseudo-peripheral vertex (two sweeps)
-    std::vector<int32_t> order, level_of_pos;
-    int32_t root = verts[0];
-    for (int sweep = 0; sweep < 2; ++sweep) {
-        const int32_t mark = stamp_next++, todo = stamp_next++;
-        for (const int32_t v : verts)
-            stamp[(size_t)v] = todo;
-        order.assign(1, root);
-        level_of_pos.assign(1, 0);
-        stamp[(size_t)root] = mark;
-        for (size_t h = 0; h < order.size(); ++h)
-            for (const int32_t w : nbr[(size_t)order[h]])
-                if (stamp[(size_t)w] == todo) {
-                    stamp[(size_t)w] = mark;
-                    order.push_back(w);
-                    level_of_pos.push_back(level_of_pos[h] + 1);
-                }
-        root = order.back();
-    }
-    const int n_levels = level_of_pos.back() + 1;
-    if (n_levels < 3) {   // (nearly) complete graph: nothing to cut
-        nodes.push_back(std::move(verts));
-        return;
-    }
-    std::vector<int32_t> cnt((size_t)n_levels, 0);
-    for (const int32_t l : level_of_pos)
-        cnt[(size_t)l]++;
-    int best = 1;
-    long long best_cost = -1;
-    for (int l = 1, below = cnt[0]; l + 1 < n_levels; below += cnt[(size_t)l], ++l) {
-        const int above = (int)order.size() - below - cnt[(size_t)l];
-        const long long cost = (long long)std::abs(below - above) * 4 + cnt[(size_t)l];
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = l;
-        }
-    }
-    std::vector<int32_t> A, B, S;
-    for (size_t h = 0; h < order.size(); ++h)
-        (level_of_pos[h] < best ? A : level_of_pos[h] > best ? B : S).push_back(order[h]);
-    nd_dissect(nbr, std::move(A), leaf_max, depth - 1, stamp, stamp_next, nodes);
-    nd_dissect(nbr, std::move(B), leaf_max, depth - 1, stamp, stamp_next, nodes);
-    nodes.push_back(std::move(S));
-}
-
 int vmm_ba_create(const vmm_ba_problem* p, const vmm_ba_create_options* copt, vmm_ba_handle* out)
 {
     if (!p || !out) {
@@ -1139,74 +955,24 @@ int vmm_ba_create(const vmm_ba_problem* p, const vmm_ba_create_options* copt, vm
         co = *copt;
     else
         vmm_ba_default_create_options(&co);
-    if (p->n_cams <= 0 || p->n_tags <= 0 || p->n_obs < 0 || !p->cam_qt || !p->tag_qt || !p->tag_wh
-        || (p->n_obs > 0 && (!p->obs_cam || !p->obs_tag || !p->obs_px))) {
-        set_error("problem needs >= 1 camera, >= 1 tag and non-null arrays");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (p->n_obs >= (int64_t)1 << 31) {
-        set_error("n_obs must fit in 31 bits");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    for (int64_t i = 0; i < p->n_obs; ++i)
-        if (p->obs_cam[i] < 0 || p->obs_cam[i] >= p->n_cams || p->obs_tag[i] < 0 || p->obs_tag[i] >= p->n_tags) {
-            set_error("observation " + std::to_string(i) + " references a camera or tag index out of range");
-            return VMM_BA_ERR_ARGUMENT;
-        }
-    if (p->fixed_tag >= p->n_tags) {
-        set_error("fixed_tag out of range");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (co.landmarks != VMM_BA_LANDMARK_TAG_POSES && co.landmarks != VMM_BA_LANDMARK_POINTS) {
-        set_error("create_options.landmarks must be VMM_BA_LANDMARK_TAG_POSES or VMM_BA_LANDMARK_POINTS");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (co.landmarks == VMM_BA_LANDMARK_POINTS && co.precision != VMM_BA_PRECISION_F64) {
-        set_error("point landmarks run in f64 only");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    // Point landmarks (doBundleAdjustment_points, src/TagReconstructor.cpp:457-644): every tag becomes its four world
-    // corners (:483-491), kept as two 6-dof blocks of two points each; every tag observation becomes the two corner-pair
-    // observations of those blocks (:549-560).  From here on `p` is that expanded problem.
+    int rc;
+    if ((rc = validate_problem(p, co)))
+        return rc;
+    // Point landmarks (expand_points): from here on `p` is the expanded problem, `user` the caller's.
     const vmm_ba_problem* const user = p;
-    vmm_ba_problem expanded;
-    std::vector<double> x_tag, x_wh, x_px;
-    std::vector<int32_t> x_cam, x_tagidx;
+    PointProblem expanded;
     if (co.landmarks == VMM_BA_LANDMARK_POINTS) {
-        if (p->n_obs >= (int64_t)1 << 30 || p->n_tags >= 1 << 30) {
-            set_error("problem too large for point landmarks");
-            return VMM_BA_ERR_ARGUMENT;
-        }
-        x_tag = pairs_from_tags(p->tag_qt, p->tag_wh, p->n_tags);
-        x_wh.assign((size_t)4 * p->n_tags, 0.0);
-        x_cam.resize((size_t)2 * p->n_obs);
-        x_tagidx.resize((size_t)2 * p->n_obs);
-        x_px.assign((size_t)16 * p->n_obs, 0.0);
-        for (int64_t i = 0; i < p->n_obs; ++i)
-            for (int h2 = 0; h2 < 2; ++h2) {
-                x_cam[(size_t)2 * i + h2] = p->obs_cam[i];
-                x_tagidx[(size_t)2 * i + h2] = 2 * p->obs_tag[i] + h2;
-                for (int k = 0; k < 4; ++k)
-                    x_px[(size_t)8 * (2 * i + h2) + k] = p->obs_px[8 * i + 4 * h2 + k];
-            }
-        expanded = *p;
-        expanded.n_tags = 2 * p->n_tags;
-        expanded.tag_qt = x_tag.data();
-        expanded.tag_wh = x_wh.data();
-        expanded.n_obs = 2 * p->n_obs;
-        expanded.obs_cam = x_cam.data();
-        expanded.obs_tag = x_tagidx.data();
-        expanded.obs_px = x_px.data();
-        p = &expanded;
+        expand_points(*user, expanded);
+        p = &expanded.problem;
     }
-    if (co.precision != VMM_BA_PRECISION_F64 && co.precision != VMM_BA_PRECISION_F32_ACCUM) {
-        set_error("create_options.precision must be VMM_BA_PRECISION_F64 or VMM_BA_PRECISION_F32_ACCUM");
+    int elim = co.elimination;
+    if (elim == VMM_BA_ELIM_AUTO)
+        elim = (p->n_cams >= p->n_tags) ? VMM_BA_ELIM_CAMERAS : VMM_BA_ELIM_TAGS;
+    if (elim != VMM_BA_ELIM_CAMERAS && elim != VMM_BA_ELIM_TAGS) {
+        set_error("bad elimination mode");
         return VMM_BA_ERR_ARGUMENT;
     }
-    if (co.world_size < 1 || co.rank < 0 || co.rank >= co.world_size) {
-        set_error("bad rank / world_size");
-        return VMM_BA_ERR_ARGUMENT;
-    }
+
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available: libvmm_ba has no CPU fallback");
@@ -1218,56 +984,18 @@ int vmm_ba_create(const vmm_ba_problem* p, const vmm_ba_create_options* copt, vm
     }
     Engine* ep = new Engine();
     Engine& e = *ep;
-    int rc = VMM_BA_OK;
     auto fail = [&](int code) {
         destroy_engine(ep);
         return code;
     };
-    e.device = co.device;
-    if (hipSetDevice(e.device) != hipSuccess || hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("hipSetDevice / hipStreamCreate failed");
-        e.stream = nullptr;
-        return fail(VMM_BA_ERR_HIP);
-    }
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, e.device) == hipSuccess && prop.multiProcessorCount > 0)
-            e.n_cu = prop.multiProcessorCount;
-    }
+    e.sw = read_switches();
+    if ((rc = open_device(e, co.device)))
+        return fail(rc);
     e.rank = co.rank;
     e.world = co.world_size;
     e.f32_accum = co.precision == VMM_BA_PRECISION_F32_ACCUM;
-    e.multi = e.world > 1;
-    if (const char* fw = getenv("VMM_BA_FORCE_COLLECTIVES"))
-        if (fw[0] == '1')
-            e.multi = true;   // test hook: one rank, but staging buffers + eager launches + all-reduce callbacks
-    {
-        // every kernel is touched once per process and device before anything is captured
-        static bool preloaded[64] = {};
-        const char* np = getenv("VMM_BA_NO_PRELOAD");   // diagnosis of the round-1 capture failure only
-        if (e.device < 64 && !preloaded[e.device] && !(np && np[0] == '1')) {
-            const int bad = preload_eval_kernels() + preload_schur_kernels() + preload_chol_kernels() + preload_lm_kernels()
-                + preload_cov_kernels();
-            if (bad) {
-                set_error("hipFuncGetAttributes failed for " + std::to_string(bad) + " kernels (code object not loadable on this device)");
-                return fail(VMM_BA_ERR_HIP);
-            }
-            preloaded[e.device] = true;
-        }
-        const char* ef = getenv("VMM_BA_EAGER_FIRST");
-        e.eager_first = ef && ef[0] == '1';
-        const char* rg = getenv("VMM_BA_RCCL_GRAPH");
-        e.rccl_graph = !(rg && rg[0] == '0');
-        const char* ng = getenv("VMM_BA_NO_GRAPH");
-        e.use_graph = !(ng && ng[0] == '1');
-        if (const char* gp = getenv("VMM_BA_GRAPH_PASSES"))
-            e.graph_passes = std::min(std::max(atoi(gp), 1), 8);
-        const char* nc = getenv("VMM_BA_NO_CHAIN");
-        e.no_chain = nc && nc[0] == '1';
-        const char* nd = getenv("VMM_BA_NO_DATAFLOW");
-        e.no_dataflow = nd && nd[0] == '1';
-        read_spin_debug_env(e);
-    }
+    e.multi = e.world > 1 || e.sw.force_collectives;   // test hook: one rank, but staging buffers + eager launches + all-reduce callbacks
+    e.rccl_graph = e.sw.rccl_graph;
     e.K.fx = p->intr[0]; e.K.fy = p->intr[1]; e.K.cx = p->intr[2]; e.K.cy = p->intr[3];
     e.K.k1 = p->dist[0]; e.K.k2 = p->dist[1]; e.K.p1 = p->dist[2]; e.K.p2 = p->dist[3]; e.K.k3 = p->dist[4];
     e.n_cams = p->n_cams;
@@ -1277,632 +1005,21 @@ int vmm_ba_create(const vmm_ba_problem* p, const vmm_ba_create_options* copt, vm
     e.points = co.landmarks == VMM_BA_LANDMARK_POINTS;
     e.n_tags_user = user->n_tags;
     e.n_obs_user = user->n_obs;
-    if (e.points) {
+    if (e.points)
         std::vector<double>(user->tag_wh, user->tag_wh + 2 * (size_t)user->n_tags).swap(e.user_tag_wh);
-    }
-    int elim = co.elimination;
-    if (elim == VMM_BA_ELIM_AUTO)
-        elim = (p->n_cams >= p->n_tags) ? VMM_BA_ELIM_CAMERAS : VMM_BA_ELIM_TAGS;
-    if (elim != VMM_BA_ELIM_CAMERAS && elim != VMM_BA_ELIM_TAGS) {
-        set_error("bad elimination mode");
+    e.elim_cams = (elim == VMM_BA_ELIM_CAMERAS);
+
+    const Plan plan = make_plan(*p, co, e.elim_cams, e.multi, e.world, e.points, e.sw);
+    if (!plan.error.empty()) {
+        set_error(plan.error);
         return fail(VMM_BA_ERR_ARGUMENT);
     }
-    e.elim_cams = (elim == VMM_BA_ELIM_CAMERAS);
-    e.n_e = e.elim_cams ? e.n_cams : e.n_tags;
-    e.n_f = e.elim_cams ? e.n_tags : e.n_cams;
-    const int n_pose = e.n_cams + e.n_tags;
-
-    // poses
-    if ((rc = dev_alloc(e, &e.cam_qt, (size_t)7 * e.n_cams))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.tag_qt, (size_t)7 * e.n_tags))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.cam_cand, (size_t)7 * e.n_cams))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.tag_cand, (size_t)7 * e.n_tags))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.tag_wh, (size_t)2 * e.n_tags))) return fail(rc);
-    if (hipMemcpyAsync(e.cam_qt, p->cam_qt, sizeof(double) * 7 * e.n_cams, hipMemcpyHostToDevice, e.stream) != hipSuccess
-        || hipMemcpyAsync(e.tag_qt, p->tag_qt, sizeof(double) * 7 * e.n_tags, hipMemcpyHostToDevice, e.stream) != hipSuccess
-        || hipMemcpyAsync(e.tag_wh, p->tag_wh, sizeof(double) * 2 * e.n_tags, hipMemcpyHostToDevice, e.stream) != hipSuccess
-        || hipStreamSynchronize(e.stream) != hipSuccess) {
-        set_error("pose upload failed");
-        return fail(VMM_BA_ERR_HIP);
-    }
-
-    // observation orders
-    const int32_t* own_e = e.elim_cams ? p->obs_cam : p->obs_tag;
-    const int32_t* own_f = e.elim_cams ? p->obs_tag : p->obs_cam;
-    std::vector<int32_t> callerE, callerF, startE, startF, otherE;
-    if ((rc = build_order(e, e.ordE, e.n_e, own_e, own_f, p->obs_px, p->n_obs, &callerE, &startE, &otherE))) return fail(rc);
-    if ((rc = build_order(e, e.ordF, e.n_f, own_f, own_e, p->obs_px, p->n_obs, &callerF, &startF))) return fail(rc);
-
-    // Fused evaluation (k_eval_fused: one evaluation per observation, lane = kept pose, both families' sums in
-    // registers).  Opt-in, VMM_BA_EVAL=fused: it needs ~370 registers per lane, so one wave per SIMD, and measured
-    // SLOWER than the two-pass kernel at two waves per SIMD (500 x 200: 59-68 us against 28.4; 2000 x 1000 f32:
-    // 291 against 308).
-    {
-        int n_act = 0;
-        for (int q = 0; q < e.n_e; ++q)
-            n_act += startE[q + 1] > startE[q];
-        e.fused_eval = false;
-        if (const char* ev = getenv("VMM_BA_EVAL"))
-            e.fused_eval = !strcmp(ev, "fused") && n_act > 0;
-        if (e.fused_eval) {
-            e.fused_n_e_act = n_act;
-            e.fused_f_pad = round_up(e.n_f, 64);
-            e.fused_chunks = e.fused_f_pad / 64;
-            // eliminated poses per wave: about one wave per SIMD in flight (1024 SIMDs), at most 16
-            e.fused_group = std::min(16, std::max(1, (int)(((int64_t)n_act * e.fused_chunks + 500) / 1000)));
-            if (const char* gv = getenv("VMM_BA_FUSED_GROUP"))
-                e.fused_group = std::min(64, std::max(1, atoi(gv)));
-            e.fused_groups = (n_act + e.fused_group - 1) / e.fused_group;
-            std::vector<int32_t> pair((size_t)e.n_e * e.fused_f_pad, -1), e_list, part0((size_t)e.n_e, 0),
-                ptask((size_t)e.n_e + 1, 0);
-            int slot = 0;
-            for (int q = 0; q < e.n_e; ++q) {
-                ptask[(size_t)q] = slot;
-                part0[(size_t)q] = slot;
-                if (startE[q + 1] > startE[q]) {
-                    e_list.push_back(q);
-                    slot += e.fused_chunks;
-                }
-                // a pair observed twice keeps its last observation here: such input is not supported by the dense
-                // elimination either (one Z block per pair)
-                for (int32_t d = startE[q]; d < startE[q + 1]; ++d)
-                    pair[(size_t)q * e.fused_f_pad + otherE[(size_t)d]] = d;
-            }
-            ptask[(size_t)e.n_e] = slot;
-            // the lookup table cannot hold two observations of one pair: fall back to the two-pass kernel then
-            int64_t n_in_table = 0;
-            for (const int32_t v : pair)
-                n_in_table += v >= 0;
-            if (n_in_table != e.n_obs) {
-                e.fused_eval = false;
-            } else {
-                if ((rc = dev_alloc(e, &e.pair_obs, pair.size()))) return fail(rc);
-                if ((rc = dev_alloc(e, &e.fused_e_list, e_list.size()))) return fail(rc);
-                if ((rc = dev_alloc(e, &e.fused_e_part0, part0.size()))) return fail(rc);
-                if ((rc = dev_alloc(e, &e.fused_pose_task, ptask.size()))) return fail(rc);
-                if ((rc = dev_alloc(e, &e.fused_partE, (size_t)std::max(slot, 1) * kPart))) return fail(rc);
-                if ((rc = dev_alloc(e, &e.fused_partF, (size_t)e.fused_groups * 28 * e.fused_f_pad))) return fail(rc);
-                if ((rc = upload(e, e.pair_obs, pair))) return fail(rc);
-                if ((rc = upload(e, e.fused_e_list, e_list))) return fail(rc);
-                if ((rc = upload(e, e.fused_e_part0, part0))) return fail(rc);
-                if ((rc = upload(e, e.fused_pose_task, ptask))) return fail(rc);
-                if (hipStreamSynchronize(e.stream) != hipSuccess) {   // host vectors go out of scope
-                    set_error("create: upload of the fused-evaluation tables failed");
-                    return fail(VMM_BA_ERR_HIP);
-                }
-            }
-        }
-    }
-
-    // normal-equation blocks
-    e.small_count = (size_t)42 * n_pose + 2;
-    if ((rc = dev_alloc(e, &e.small, e.small_count))) return fail(rc);
-    e.H_cam = e.small;
-    e.H_tag = e.H_cam + (size_t)36 * e.n_cams;
-    e.g_cam = e.H_tag + (size_t)36 * e.n_tags;
-    e.g_tag = e.g_cam + (size_t)6 * e.n_cams;
-    e.cost_slot = e.g_tag + (size_t)6 * e.n_tags;
-    // the LM loop evaluates at the candidate into this staging copy (all-reduced when world > 1); it replaces the
-    // working copy when the step is accepted
-    // (+ n_e per-pose costs of the eliminated family behind it: world > 1 sums them over the ranks with the blocks)
-    if ((rc = dev_alloc(e, &e.small_stage, e.small_count + (size_t)e.n_e))) return fail(rc);
-    e.ev_pose_cost = e.small_stage + e.small_count;
-    e.small_alt_off = e.multi ? 0 : (int64_t)(e.small_stage - e.small);
-    e.ev_H_cam = e.small_stage;
-    e.ev_H_tag = e.ev_H_cam + (size_t)36 * e.n_cams;
-    e.ev_g_cam = e.ev_H_tag + (size_t)36 * e.n_tags;
-    e.ev_g_tag = e.ev_g_cam + (size_t)6 * e.n_cams;
-    e.ev_cost = e.ev_g_tag + (size_t)6 * e.n_tags;
-    if ((rc = dev_alloc(e, &e.obs_mask, (size_t)std::max<int64_t>(e.n_obs, 1), false))) return fail(rc);
-    if (hipMemsetAsync(e.obs_mask, 1, (size_t)std::max<int64_t>(e.n_obs, 1), e.stream) != hipSuccess) {
-        set_error("hipMemsetAsync(obs_mask) failed");
-        return fail(VMM_BA_ERR_HIP);
-    }
-    {
-        const size_t n_stat = (size_t)e.ordE.n_tasks + (size_t)e.ordF.n_tasks + 1;
-        if ((rc = dev_alloc(e, &e.stats_part, n_stat))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.stats_cnt, n_stat))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.stats_pose, (size_t)2 * n_pose))) return fail(rc);
-    }
-    if (e.f32_accum) {
-        if ((rc = dev_alloc(e, &e.Wf, (size_t)36 * e.ordE.n_pad))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.Wf2, (size_t)36 * e.ordE.n_pad))) return fail(rc);
-    } else {
-        if ((rc = dev_alloc(e, &e.W, (size_t)36 * e.ordE.n_pad))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.W2, (size_t)36 * e.ordE.n_pad))) return fail(rc);
-    }
-    if ((rc = dev_alloc(e, &e.scale, (size_t)6 * n_pose))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.diag, (size_t)6 * n_pose))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.D2, (size_t)6 * n_pose))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.delta, (size_t)6 * n_pose))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.active, (size_t)n_pose))) return fail(rc);
-
-    // elimination / reduced system geometry
-    e.n_red = 6 * e.n_f;
-    e.n_pad = round_up(e.n_red, kNB);
-    e.n_blk = e.n_pad / kNB;
-    // >= n_pad + 64; the rank-k update reads whole 128-wide tiles.  The extra 32 doubles (256 B) make the row
-    // stride an odd multiple of 256 B, so the 64 rows of a tile spread over the HBM channels instead of
-    // hitting a few of them (a 48 KB stride at 2000 x 1000 does)
-    e.ldz = round_up(e.n_pad + 1, kST) + 32;
-    e.k_dim = 6 * e.n_e;
-    e.k_pad = round_up(e.k_dim, kKT);
-    if ((rc = dev_alloc(e, &e.Le, (size_t)36 * e.n_e))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.ze, (size_t)6 * e.n_e))) return fail(rc);
-    // Reduced-system formation: dense Z + MFMA rank-k update, or compressed Z + the pair-list kernel.  Both are
-    // priced per launch from the block structure (measured at 500 x 200, profiles/r03_sparse_*: the dense update + its
-    // partial-tile sum take 118 us whatever the fill = 44 TFLOP/s; k_schur_pairs 16 us at 6-10 tags per image, 57 us at
-    // 25 % and 116 us at 50 % visibility, priced as 18 us + 9 TFLOP/s of useful 6x6x6 block products);
-    // VMM_BA_SCHUR=dense|sparse overrides.
-    // World > 1: every decision that shapes the reduced system (its form is free per rank, its LAYOUT is not: the ranks'
-    // systems are summed) is taken from the structure of ALL ranks' observations when the caller passes it
-    // (vmm_ba_create_options.structure_obs_*), else from this rank's own -- and then the layout stays the natural one.
-    // gStart / gOther: per eliminated pose the kept poses it sees (family-local indices), this rank's or everybody's.
-    std::vector<int32_t> gStartV, gOtherV;
-    const bool have_structure = co.n_structure_obs > 0 && co.structure_obs_cam && co.structure_obs_tag;
-    if (e.multi && have_structure) {
-        gStartV.assign((size_t)e.n_e + 1, 0);
-        for (int64_t d = 0; d < co.n_structure_obs; ++d) {
-            const int32_t c = co.structure_obs_cam[d], t = co.structure_obs_tag[d];
-            if (c < 0 || c >= p->n_cams || t < 0 || t >= p->n_tags) {
-                set_error("structure_obs index out of range");
-                return fail(VMM_BA_ERR_ARGUMENT);
-            }
-            if (e.points) {
-                set_error("structure_obs is not supported with point landmarks");
-                return fail(VMM_BA_ERR_ARGUMENT);
-            }
-            gStartV[(size_t)(e.elim_cams ? c : t) + 1]++;
-        }
-        for (int q = 0; q < e.n_e; ++q)
-            gStartV[(size_t)q + 1] += gStartV[(size_t)q];
-        gOtherV.resize((size_t)co.n_structure_obs);
-        std::vector<int32_t> fillg(gStartV.begin(), gStartV.end() - 1);
-        for (int64_t d = 0; d < co.n_structure_obs; ++d) {
-            const int32_t c = co.structure_obs_cam[d], t = co.structure_obs_tag[d];
-            gOtherV[(size_t)fillg[(size_t)(e.elim_cams ? c : t)]++] = e.elim_cams ? t : c;
-        }
-    }
-    const bool global_lists = !gStartV.empty();
-    const std::vector<int32_t>& gStart = global_lists ? gStartV : startE;
-    const std::vector<int32_t>& gOther = global_lists ? gOtherV : otherE;
-    // one layout for all ranks: this rank alone (also the one-rank test hook), or everybody's structure in hand
-    const bool layout_free = !e.multi || e.world == 1 || global_lists;
-    {
-        double pairs = 0.0;   // 6x6 block products of the lower triangle: sum over e of deg (deg + 1) / 2
-        e.co_terms = 0.0;
-        for (int q = 0; q < e.n_e; ++q) {
-            const double deg = (double)(gStart[q + 1] - gStart[q]);
-            pairs += 0.5 * deg * (deg + 1.0);
-            e.co_terms += deg * deg;   // entries the host's adjacency lists of the kept family would hold before merging
-        }
-        const double dense_flops = (double)(e.n_pad + 1) * (e.n_pad + 2) * e.k_dim;
-        const double n_obs_model = global_lists ? (double)co.n_structure_obs : (double)e.n_obs;
-        const double sparse_flops = 432.0 * pairs + 72.0 * n_obs_model;
-        const double dense_us = dense_flops / 44e6 + 12.0, sparse_us = sparse_flops / 9e6 + 18.0;
-        // The plan of the block-sparse form lists every term: one (left, right) position pair per product plus the
-        // right-hand-side term of every observation -- known from the degrees alone, before anything is allocated.  16 bytes
-        // per term on the host while it is built, 8 on the device: the automatic choice stays below 4e7 terms (0.64 GB
-        // transient, 0.32 GB resident; 2000 x 1000 at 25 % visibility would be 6e7), a forced one below the 2^31 the
-        // 32-bit positions can address.
-        const double plan_terms = pairs + n_obs_model;
-        e.sparse_schur = n_obs_model > 0 && sparse_us < dense_us && plan_terms <= 4e7;
-        if (const char* sv = getenv("VMM_BA_SCHUR")) {
-            if (!strcmp(sv, "dense"))
-                e.sparse_schur = false;
-            else if (!strcmp(sv, "sparse"))
-                e.sparse_schur = n_obs_model > 0;
-        }
-        if (e.sparse_schur && plan_terms >= 2147483647.0) {
-            set_error("block-sparse elimination: more than 2^31 block products (set VMM_BA_SCHUR=dense)");
-            return fail(VMM_BA_ERR_ARGUMENT);
-        }
-        e.schur_flops = e.sparse_schur ? sparse_flops : dense_flops;
-    }
-    std::vector<std::vector<int32_t>> tree_nbr;   // co-observation graph of the kept family (all ranks' when known)
-    // Tree ordering of the kept family (VMM_BA_ORDER=nd; block-sparse path; world > 1: with the global structure): every node of the dissection tree
-    // starts on a 64-row boundary of the reduced system (padding rows with a unit diagonal in between), so that whole
-    // block columns of the factor belong to one node and the block columns of two parts of one level are independent.
-    {
-        const char* ov = getenv("VMM_BA_ORDER");
-        const bool forced = ov && !strcmp(ov, "nd"), forbidden = ov && !strcmp(ov, "natural");
-        // (the host-side graph work is bounded: 5e7 list entries, and a natural order beyond the one-launch kernel's 48 block
-        // columns cannot become a tree order within them)
-        if (e.sparse_schur && layout_free && !forbidden && e.n_f > 1 && e.n_blk >= 4 && e.co_terms <= 5e7) {
-            std::vector<std::vector<int32_t>>& nbr = tree_nbr;
-            nbr.assign((size_t)e.n_f, {});
-            for (int q = 0; q < e.n_e; ++q)
-                for (int32_t d1 = gStart[q]; d1 < gStart[q + 1]; ++d1)
-                    for (int32_t d2 = gStart[q]; d2 < gStart[q + 1]; ++d2)
-                        if (d1 != d2)
-                            nbr[(size_t)gOther[(size_t)d1]].push_back(gOther[(size_t)d2]);
-            for (auto& v : nbr) {
-                std::sort(v.begin(), v.end());
-                v.erase(std::unique(v.begin(), v.end()), v.end());
-            }
-            std::vector<int32_t> all((size_t)e.n_f), stamp((size_t)e.n_f, 0);
-            for (int fq = 0; fq < e.n_f; ++fq)
-                all[(size_t)fq] = fq;
-            int32_t stamp_next = 1;
-            int leaf_max = 42;   // tags per leaf (four 64-row blocks; 21 and 10 measured slower on the close-up scene)
-            if (const char* lv = getenv("VMM_BA_ND_LEAF"))
-                leaf_max = std::max(1, atoi(lv));
-            std::vector<std::vector<int32_t>> nodes;
-            nd_dissect(nbr, all, leaf_max, 12, stamp, stamp_next, nodes);
-            std::vector<int32_t> rows((size_t)e.n_f, -1);
-            int row = 0;
-            for (const auto& nd : nodes) {
-                row = round_up(row, kNB);
-                for (const int32_t v : nd) {
-                    rows[(size_t)v] = row;
-                    row += 6;
-                }
-            }
-            const int n_pad_nd = round_up(row, kNB);
-            // Worth it?  The factorisation is a chain of dependent block columns (~11 us each): the longest chain under
-            // the tree ordering (block structure after symbolic fill, nodes as dense blocks: an upper bound) against the
-            // n_blk of the natural order.  Taken when it is at most 0.7 of it (VMM_BA_ORDER=nd: always).
-            // (the block structure is kept as kDfMaskWords 64-bit words per block row, the panel order in bytes: at most 255
-            // block columns; only the non-zero blocks of the factor get a workgroup, so the one-launch kernel takes the
-            // system whatever its order -- counted below)
-            const int nb = n_pad_nd / kNB;
-            bool take = nodes.size() > 2 && nb <= kDfMaxBlk - 1;
-            if (take) {
-                const std::vector<BlkMask> nzr = symbolic_factor(nb, rows, nbr);
-                int n_wg = nb;
-                for (int i = 0; i < nb; ++i)
-                    for (int k = 0; k < i; ++k)
-                        n_wg += nzr[(size_t)i].test(k) ? 1 : 0;
-                n_wg += nb;   // the right-hand side row's block of every column
-                int path_max = 1;
-                const double t_tree = model_tree_factorisation(nb, nzr, nullptr, &path_max);
-                // natural order: the one-launch kernel up to 48 block columns (~9.8 us each), one launch per column beyond
-                // (~32 us each at 94 columns)
-                const double t_nat = e.n_blk <= 48 ? 9.8 * e.n_blk : 32.0 * e.n_blk;
-                static const int max_wg = [] {
-                    const char* v = getenv("VMM_BA_TREE_MAX_WG");
-                    return v ? atoi(v) : 16384;
-                }();
-                take = n_wg <= max_wg && (forced || (path_max * 10 <= e.n_blk * 7 && t_tree <= 0.9 * t_nat));
-                if (getenv("VMM_BA_DEBUG"))
-                    fprintf(stderr, "[vmm_ba debug] tree ordering candidate: longest chain %d of %d block columns against %d in "
-                                    "natural order, %d workgroups, modelled %.0f against %.0f us -> %s\n", path_max, nb, e.n_blk,
-                            n_wg, t_tree, t_nat, take ? "taken" : "not taken");
-            }
-            if (take) {
-                e.h_row_of = rows;
-                e.nd_node_first_blk.clear();
-                int r2 = 0;
-                for (const auto& nd : nodes) {
-                    r2 = round_up(r2, kNB);
-                    e.nd_node_first_blk.push_back(r2 / kNB);
-                    r2 += 6 * (int)nd.size();
-                }
-                e.n_pad = n_pad_nd;
-                e.n_blk = e.n_pad / kNB;
-                e.ldz = round_up(e.n_pad + 1, kST) + 32;
-                if (getenv("VMM_BA_DEBUG")) {
-                    fprintf(stderr, "[vmm_ba debug] tree ordering: %zu nodes, %d rows (%d blocks) for %d kept poses; node sizes:",
-                            nodes.size(), e.n_pad, e.n_blk, e.n_f);
-                    for (const auto& nd : nodes)
-                        fprintf(stderr, " %zu", nd.size());
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-    }
-    if (e.sparse_schur) {
-        if ((rc = dev_alloc(e, &e.Zc, (size_t)36 * std::max<int64_t>(e.n_obs, 1)))) return fail(rc);
-        // F-order <-> E-order positions of an observation
-        std::vector<int32_t> posE((size_t)e.n_obs), f2e((size_t)e.n_obs), row_pos((size_t)e.n_obs);
-        for (int64_t d = 0; d < e.n_obs; ++d)
-            posE[(size_t)callerE[(size_t)d]] = (int32_t)d;
-        for (int fq = 0; fq < e.n_f; ++fq)
-            for (int32_t d = startF[fq]; d < startF[fq + 1]; ++d) {
-                f2e[(size_t)d] = posE[(size_t)callerF[(size_t)d]];
-                row_pos[(size_t)f2e[(size_t)d]] = d - startF[fq];   // position of the observation in its kept pose's row
-            }
-        // The symbolic structure of S -= Z^T Z, once per problem (the counterpart of the symbolic phase of the sparse
-        // Cholesky behind ceres::Solve): row f owns the pairs (f, f' = 0..f) and, last, its right-hand side entry.
-        // A term of pair (f, f') = two observations (e, f), (e, f') of one eliminated pose; terms are listed in e
-        // order (that is the summation order), the left block by its position in f's row (the kernel stages the
-        // row's blocks in LDS), the right block by its E-order index.
-        // Two forms of the pair list.  Implicit (every pair of the lower triangle, the empty ones written as zeros:
-        // pair j of row f is f' = j): visibility-type scenes, where nearly every pair exists.  Explicit (only the pairs
-        // that share an eliminated pose, their column in `pair_col`; S is zero-filled by a kernel of its own first):
-        // scenes where an image sees a handful of tags -- at 6-10 tags per image 3.4 k of the 20.1 k pairs exist.  The
-        // explicit form also carries the position of every kept pose in the reduced system (`row_of`), which need not
-        // be 6 f (tree orderings of the kept family).
-        std::vector<int32_t> rank_of((size_t)e.n_f);                  // order of the kept poses in the reduced system
-        for (int fq = 0; fq < e.n_f; ++fq)
-            rank_of[(size_t)fq] = e.h_row_of.empty() ? fq : e.h_row_of[(size_t)fq];
-        std::vector<std::vector<int32_t>> partners;                    // explicit form: f' of every pair of row f
-        {
-            double co = 0.0;   // co-observed pairs incl. the diagonal, counted once
-            std::vector<int32_t> mark((size_t)e.n_f, -1);
-            std::vector<std::vector<int32_t>> adj((size_t)e.n_f);
-            const bool list_pairs = !e.h_row_of.empty() || e.co_terms <= 5e7;   // else: the implicit form
-            for (int q = 0; q < e.n_e && list_pairs; ++q)
-                for (int32_t d1 = startE[q]; d1 < startE[q + 1]; ++d1)
-                    for (int32_t d2 = startE[q]; d2 < startE[q + 1]; ++d2) {
-                        const int f1 = otherE[(size_t)d1], f2 = otherE[(size_t)d2];
-                        if (rank_of[(size_t)f2] < rank_of[(size_t)f1])
-                            adj[(size_t)f1].push_back(f2);
-                    }
-            for (int fq = 0; fq < e.n_f; ++fq) {
-                std::vector<int32_t>& a = adj[(size_t)fq];
-                std::sort(a.begin(), a.end(), [&](int32_t x, int32_t y) { return rank_of[(size_t)x] < rank_of[(size_t)y]; });
-                a.erase(std::unique(a.begin(), a.end()), a.end());
-                a.push_back(fq);   // the diagonal pair: always there (it carries the kept pose's own block)
-                co += (double)a.size();
-            }
-            const double all = 0.5 * (double)e.n_f * (e.n_f + 1.0);
-            e.explicit_pairs = !e.h_row_of.empty() || (list_pairs && co < 0.5 * all);
-            if (const char* pv = getenv("VMM_BA_PAIRS"))
-                e.explicit_pairs = !e.h_row_of.empty() || (list_pairs && !strcmp(pv, "explicit"));
-            if (e.explicit_pairs)
-                partners.swap(adj);
-            (void)mark;
-        }
-        std::vector<int32_t> pstart((size_t)e.n_f + 1, 0), pcol;
-        for (int fq = 0; fq < e.n_f; ++fq)
-            pstart[(size_t)fq + 1] = pstart[(size_t)fq] + (e.explicit_pairs ? (int32_t)partners[(size_t)fq].size() + 1 : fq + 2);
-        const size_t n_pairs = (size_t)pstart[(size_t)e.n_f];
-        // pair id of (f1, f2) inside row f1; explicit form: through a per-row look-up table
-        std::vector<int32_t> slot_of;
-        if (e.explicit_pairs) {
-            pcol.assign(n_pairs, -1);
-            for (int fq = 0; fq < e.n_f; ++fq)
-                for (size_t k = 0; k < partners[(size_t)fq].size(); ++k)
-                    pcol[(size_t)pstart[(size_t)fq] + k] = e.h_row_of.empty() ? 6 * partners[(size_t)fq][k]
-                                                                              : e.h_row_of[(size_t)partners[(size_t)fq][k]];
-        }
-        // (f1, f2) -> pair id or -1.  Explicit: binary search in row f1's partner list (sorted by rank).
-        auto pair_id = [&](int f1, int f2) -> int64_t {
-            if (!e.explicit_pairs)
-                return f2 <= f1 ? (int64_t)pstart[(size_t)f1] + f2 : -1;
-            if (rank_of[(size_t)f2] > rank_of[(size_t)f1])
-                return -1;
-            const std::vector<int32_t>& a = partners[(size_t)f1];
-            const auto it = std::lower_bound(a.begin(), a.end(), f2,
-                                             [&](int32_t x, int32_t y) { return rank_of[(size_t)x] < rank_of[(size_t)y]; });
-            return (int64_t)pstart[(size_t)f1] + (it - a.begin());
-        };
-        auto rhs_id = [&](int f1) -> int64_t { return (int64_t)pstart[(size_t)f1 + 1] - 1; };
-        std::vector<int32_t> tstart(n_pairs + 1, 0);
-        for (int q = 0; q < e.n_e; ++q)
-            for (int32_t d1 = startE[q]; d1 < startE[q + 1]; ++d1) {
-                const int f1 = otherE[(size_t)d1];
-                tstart[(size_t)rhs_id(f1) + 1]++;   // rhs pair of row f1
-                for (int32_t d2 = startE[q]; d2 < startE[q + 1]; ++d2) {
-                    const int64_t id = pair_id(f1, otherE[(size_t)d2]);
-                    if (id >= 0)
-                        tstart[(size_t)id + 1]++;
-                }
-            }
-        for (size_t k = 0; k < n_pairs; ++k)
-            tstart[k + 1] += tstart[k];
-        const size_t n_terms = (size_t)tstart[n_pairs];
-        if (n_terms >= ((size_t)1 << 31)) {
-            set_error("block-sparse elimination: more than 2^31 block products (set VMM_BA_SCHUR=dense)");
-            return fail(VMM_BA_ERR_ARGUMENT);
-        }
-        std::vector<int32_t> ta(n_terms), tb(n_terms), fill(tstart.begin(), tstart.end() - 1);
-        for (int q = 0; q < e.n_e; ++q)
-            for (int32_t d1 = startE[q]; d1 < startE[q + 1]; ++d1) {
-                const int f1 = otherE[(size_t)d1];
-                {
-                    const int32_t k = fill[(size_t)rhs_id(f1)]++;
-                    ta[(size_t)k] = row_pos[(size_t)d1];
-                    tb[(size_t)k] = q;
-                }
-                for (int32_t d2 = startE[q]; d2 < startE[q + 1]; ++d2) {
-                    const int64_t id = pair_id(f1, otherE[(size_t)d2]);
-                    if (id < 0)
-                        continue;
-                    const int32_t k = fill[(size_t)id]++;
-                    ta[(size_t)k] = row_pos[(size_t)d1];
-                    tb[(size_t)k] = d2;
-                }
-            }
-        // the kernel walks a pair's terms pass by pass of 128 left blocks: terms must be ordered by left position.
-        // They are listed in e order; a row's positions follow the caller's order, which need not be e order.
-        for (size_t k = 0; k < n_pairs; ++k) {
-            const int32_t t0 = tstart[k], t1 = tstart[k + 1];
-            bool sorted = true;
-            for (int32_t t = t0 + 1; t < t1 && sorted; ++t)
-                sorted = ta[(size_t)t - 1] <= ta[(size_t)t];
-            if (!sorted) {
-                std::vector<std::pair<int32_t, int32_t>> tmp;
-                for (int32_t t = t0; t < t1; ++t)
-                    tmp.emplace_back(ta[(size_t)t], tb[(size_t)t]);
-                std::stable_sort(tmp.begin(), tmp.end(),
-                                 [](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) { return x.first < y.first; });
-                for (int32_t t = t0; t < t1; ++t) {
-                    ta[(size_t)t] = tmp[(size_t)(t - t0)].first;
-                    tb[(size_t)t] = tmp[(size_t)(t - t0)].second;
-                }
-            }
-        }
-        // work items: up to pairs_per_item() consecutive pairs of one row; rows with many pairs first
-        std::vector<int32_t> item_row, item_p0;
-        const int ppi = schur_pairs_per_item();
-        std::vector<int32_t> rows_by_len((size_t)e.n_f);
-        for (int fq = 0; fq < e.n_f; ++fq)
-            rows_by_len[(size_t)fq] = e.n_f - 1 - fq;
-        if (e.explicit_pairs)
-            std::stable_sort(rows_by_len.begin(), rows_by_len.end(), [&](int32_t x, int32_t y) {
-                return pstart[(size_t)x + 1] - pstart[(size_t)x] > pstart[(size_t)y + 1] - pstart[(size_t)y];
-            });
-        for (const int32_t fq : rows_by_len)
-            for (int j0 = 0; j0 < pstart[(size_t)fq + 1] - pstart[(size_t)fq]; j0 += ppi) {
-                item_row.push_back(fq);
-                item_p0.push_back(pstart[(size_t)fq] + j0);
-            }
-        e.n_row_items = (int)item_row.size();
-        std::vector<int32_t> items(item_row);
-        items.insert(items.end(), item_p0.begin(), item_p0.end());
-        if ((rc = dev_alloc(e, &e.f2e, f2e.size()))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.pair_start, pstart.size()))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.pair_tstart, tstart.size()))) return fail(rc);
-        std::vector<int32_t> tt(2 * std::max<size_t>(n_terms, 1), 0);
-        for (size_t k = 0; k < n_terms; ++k) {
-            tt[2 * k] = ta[k];
-            tt[2 * k + 1] = tb[k];
-        }
-        if ((rc = dev_alloc(e, &e.pair_terms, tt.size()))) return fail(rc);
-        if ((rc = dev_alloc(e, &e.row_items, items.size()))) return fail(rc);
-        if ((rc = upload(e, e.f2e, f2e))) return fail(rc);
-        if ((rc = upload(e, e.pair_start, pstart))) return fail(rc);
-        if ((rc = upload(e, e.pair_tstart, tstart))) return fail(rc);
-        if ((rc = upload(e, e.pair_terms, tt))) return fail(rc);
-        if ((rc = upload(e, e.row_items, items))) return fail(rc);
-        if (!e.h_row_of.empty()) {
-            // Block structure of the factor under the tree ordering (symbolic_factor): from the co-observation graph the
-            // ordering was made from -- ALL observations (an observation mask only removes entries), all ranks' with
-            // world > 1 (the summed system has an entry wherever any rank has one).
-            const std::vector<BlkMask> nzr = symbolic_factor(e.n_blk, e.h_row_of, tree_nbr);
-            std::vector<unsigned long long> nzw((size_t)(e.n_blk + 1) * kDfMaskWords);
-            for (int i = 0; i <= e.n_blk; ++i)
-                for (int w = 0; w < kDfMaskWords; ++w)
-                    nzw[(size_t)i * kDfMaskWords + w] = nzr[(size_t)i].w[w];
-            if ((rc = dev_alloc(e, &e.chol_nz, nzw.size()))) return fail(rc);
-            if ((rc = upload(e, e.chol_nz, nzw))) return fail(rc);
-            {
-                // what this factorisation computes: per block column the diagonal block (d^3 / 3), a triangular solve per
-                // non-zero block below it (d^3), a product per pair of them (2 d^3; d^3 on the diagonal), the right-hand
-                // side row with them (2 d^2 per block), and the back-substitution (2 d^2 per block)
-                const double d = (double)kNB;
-                double fl = 0.0;
-                for (int j2 = 0; j2 < e.n_blk; ++j2) {
-                    int nb = 0;
-                    for (int r = j2 + 1; r < e.n_blk; ++r)
-                        nb += nzr[(size_t)r].test(j2) ? 1 : 0;
-                    fl += d * d * d / 3.0 + nb * d * d * d + (double)nb * nb * d * d * d + 4.0 * (nb + 1) * d * d;
-                }
-                e.chol_flops = fl;
-            }
-            // In which order does block column j take the panels it depends on?  In the order they are expected to be
-            // finished, from the model of the kernel.
-            std::vector<unsigned char> ord((size_t)e.n_blk * kDfMaxBlk, 0);
-            int path_max = 0;
-            const double t_model = model_tree_factorisation(e.n_blk, nzr, &ord, &path_max);
-            if ((rc = dev_alloc(e, &e.chol_order, ord.size()))) return fail(rc);
-            if ((rc = upload(e, e.chol_order, ord))) return fail(rc);
-            // The launch: one workgroup per non-zero block below the diagonal (the right-hand side row's last) and the
-            // diagonal-only workgroup, panel-major -- a workgroup only ever waits for workgroups in front of it -- and one
-            // slot of published slices per block that has a workgroup.
-            std::vector<int32_t> wg, slot((size_t)e.n_blk * (e.n_blk + 1), -1);
-            int32_t n_slots = 0;
-            for (int j2 = 0; j2 < e.n_blk; ++j2) {
-                for (int r = j2 + 1; r <= e.n_blk; ++r)
-                    if (r == e.n_blk || nzr[(size_t)r].test(j2)) {
-                        wg.push_back(j2);
-                        wg.push_back(r);
-                        slot[(size_t)j2 * (e.n_blk + 1) + r] = n_slots++;
-                    }
-                wg.push_back(j2);
-                wg.push_back(j2);
-            }
-            e.n_df_wg = (int)(wg.size() / 2);
-            e.df_tree_slots = (size_t)n_slots;
-            if ((rc = dev_alloc(e, &e.df_wg, wg.size()))) return fail(rc);
-            if ((rc = upload(e, e.df_wg, wg))) return fail(rc);
-            if ((rc = dev_alloc(e, &e.df_slot, slot.size()))) return fail(rc);
-            if ((rc = upload(e, e.df_slot, slot))) return fail(rc);
-            e.chol_nz_on = true;
-            if (getenv("VMM_BA_DEBUG")) {
-                fprintf(stderr, "[vmm_ba debug] factor: longest chain %d of %d block columns, modelled %.0f us, %d workgroups, "
-                                "%d of %d lower blocks\n", path_max, e.n_blk, t_model, e.n_df_wg, n_slots - e.n_blk + e.n_blk,
-                        e.n_blk * (e.n_blk + 1) / 2);
-                if (e.n_blk <= 64)
-                    for (int i = 0; i < e.n_blk; ++i) {
-                        fprintf(stderr, "[vmm_ba debug]   %2d ", i);
-                        for (int k = 0; k <= i; ++k)
-                            fputc(nzr[(size_t)i].test(k) ? 'x' : '.', stderr);
-                        fputc('\n', stderr);
-                    }
-            }
-        }
-        if (e.explicit_pairs) {
-            std::vector<int32_t> rows((size_t)e.n_f);
-            for (int fq = 0; fq < e.n_f; ++fq)
-                rows[(size_t)fq] = e.h_row_of.empty() ? 6 * fq : e.h_row_of[(size_t)fq];
-            if ((rc = dev_alloc(e, &e.pair_col, pcol.size()))) return fail(rc);
-            if ((rc = dev_alloc(e, &e.row_of, rows.size()))) return fail(rc);
-            if ((rc = upload(e, e.pair_col, pcol))) return fail(rc);
-            if ((rc = upload(e, e.row_of, rows))) return fail(rc);
-            if (e.multi && !e.h_row_of.empty()) {
-                // world > 1 with a tree ordering: which kept pose a row of the reduced system belongs to (-1: padding), for the
-                // kernel that adds the kept family's diagonal blocks behind the all-reduce (k_unpack_diag)
-                std::vector<int32_t> pose_of((size_t)e.n_pad, -1);
-                for (int fq = 0; fq < e.n_f; ++fq)
-                    for (int k = 0; k < 6; ++k)
-                        pose_of[(size_t)rows[(size_t)fq] + k] = fq;
-                if ((rc = dev_alloc(e, &e.pose_of_row, pose_of.size()))) return fail(rc);
-                if ((rc = upload(e, e.pose_of_row, pose_of))) return fail(rc);
-            }
-        }
-        if (hipStreamSynchronize(e.stream) != hipSuccess) {   // host vectors go out of scope
-            set_error("create: upload of the block-sparse plan failed");
-            return fail(VMM_BA_ERR_HIP);
-        }
-    } else {
-        if ((rc = ensure_dense_schur(e))) return fail(rc);
-    }
-    if ((rc = dev_alloc(e, &e.S, (size_t)e.ldz * e.ldz))) return fail(rc);
-    if (e.multi && (rc = dev_alloc(e, &e.S_packed, (size_t)(e.n_pad + 1) * (e.n_pad + 2) / 2))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.P, (size_t)4 * kNB * e.ldz))) return fail(rc);
-    if ((rc = setup_lookahead(e, e.n_blk, e.ldz))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.dinv, (size_t)e.ldz))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.Ldiag, (size_t)(e.n_blk + 1) * 4096))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.Linv, (size_t)(e.n_blk + 1) * 4096))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.flags, 264))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.gran, (size_t)2 * e.ldz))) return fail(rc);
-    {
-        // published slices of the one-launch factorisation: 64 KB per block below the diagonal (dense: of the block columns
-        // that kernel takes; tree ordering: of the non-zero blocks, and of the dense kernel's share when the handle is
-        // switched to the natural dense system for a call)
-        const size_t nd = e.no_dataflow ? 0 : (size_t)dataflow_blocks(e.n_blk, e.n_cu);
-        const size_t slots = std::max(nd * (nd + 1) / 2, e.no_dataflow ? (size_t)0 : e.df_tree_slots);
-        if (slots > 0 && (rc = dev_alloc(e, &e.df_gran, slots * 8 * 1024)))
-            return fail(rc);
-        if (slots > 0 && (rc = dev_alloc(e, &e.df_compact, slots * 4096, false)))
-            return fail(rc);
-        if (slots > 0 && (rc = dev_alloc(e, &e.df_done, slots)))
-            return fail(rc);
-    }
-    if ((rc = dev_alloc(e, &e.yf, (size_t)e.ldz))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.step_comm, (size_t)7 * e.n_e + 1))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.cost_comm, 2))) return fail(rc);
-    const size_t n_part = (size_t)std::max<int>(e.ordE.n_tasks, e.n_e) + 1;
-    if ((rc = dev_alloc(e, &e.part_cost, n_part))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.part_cross, n_part))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.part_k1, n_part))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.pose_part, (size_t)5 * n_pose))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.pose_gm, (size_t)n_pose))) return fail(rc);
-    if ((rc = dev_alloc(e, &e.ctl, 1))) return fail(rc);
-    if (hipHostMalloc((void**)&e.ctl_host, sizeof(LmCtl)) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        e.ctl_host = nullptr;
-        return fail(VMM_BA_ERR_HIP);
-    }
-    memset(e.ctl_host, 0, sizeof(LmCtl));
-    if (hipHostMalloc((void**)&e.pose_stage, sizeof(double) * 7 * (size_t)n_pose, hipHostMallocMapped) != hipSuccess
-        || hipHostGetDevicePointer((void**)&e.pose_stage_dev, e.pose_stage, 0) != hipSuccess
-        || hipEventCreateWithFlags(&e.pose_ev, hipEventDisableTiming) != hipSuccess) {
-        set_error("hipHostMalloc / hipEventCreate (pose staging) failed");
-        return fail(VMM_BA_ERR_HIP);
-    }
-    e.trace_capacity = 0;
-    if (hipStreamSynchronize(e.stream) != hipSuccess) {
-        set_error("create: device synchronisation failed");
-        return fail(VMM_BA_ERR_HIP);
-    }
+    take_plan(e, plan);
+    if ((rc = allocate_and_upload(e, plan, *p)))
+        return fail(rc);
     *out = reinterpret_cast<vmm_ba_handle>(ep);
     return VMM_BA_OK;
 }
-
 void vmm_ba_destroy(vmm_ba_handle h) { destroy_engine(reinterpret_cast<Engine*>(h)); }
 
 int vmm_ba_set_allreduce(vmm_ba_handle h, vmm_ba_allreduce_fn fn, void* user)
@@ -2478,6 +1595,7 @@ int vmm_ba_eval_blocks(vmm_ba_handle h, int robustify, double huber_a, double* c
 static int make_scratch(Engine& e, int device, int ld)
 {
     e.device = device;
+    e.sw = read_switches();
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking));
     {
@@ -2493,12 +1611,9 @@ static int make_scratch(Engine& e, int device, int ld)
     if ((rc = dev_alloc(e, &e.Linv, (size_t)(ld / kNB + 1) * 4096))) return rc;
     if ((rc = dev_alloc(e, &e.flags, 264))) return rc;
     if ((rc = dev_alloc(e, &e.gran, (size_t)2 * ld))) return rc;
-    { const char* nc = getenv("VMM_BA_NO_CHAIN"); e.no_chain = nc && nc[0] == '1'; }
-    { const char* nd = getenv("VMM_BA_NO_DATAFLOW"); e.no_dataflow = nd && nd[0] == '1'; }
-    read_spin_debug_env(e);
     {
         const int nb = ld / kNB - 1;   // ld = n_pad + 64
-        const size_t nd = e.no_dataflow ? 0 : (size_t)dataflow_blocks(nb, e.n_cu);
+        const size_t nd = e.sw.no_dataflow ? 0 : (size_t)dataflow_blocks(nb, e.n_cu, e.sw);
         if (nd > 0 && (rc = dev_alloc(e, &e.df_gran, nd * (nd + 1) / 2 * 8 * 1024)))
             return rc;
         if (nd > 0 && (rc = dev_alloc(e, &e.df_compact, nd * (nd + 1) / 2 * 4096, false)))
@@ -2552,9 +1667,9 @@ int vmm_ba_dense_spd_solve(int device, int n, const double* A, const double* b, 
     for (int attempt = 0; attempt < 2 && err == hipSuccess; ++attempt) {
         memset(&c, 0, sizeof(c));
         if (attempt == 0) {
-            c.spin_limit_df = e.dbg_spin_df;
-            c.spin_limit_chain = e.dbg_spin_chain;
-            c.spin_wg = e.dbg_spin_wg;
+            c.spin_limit_df = e.sw.spin_df;
+            c.spin_limit_chain = e.sw.spin_chain;
+            c.spin_wg = e.sw.spin_wg;
         }
         err = hipMemcpyAsync(e.ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, e.stream);
         if (err == hipSuccess)
@@ -2735,7 +1850,7 @@ int vmm_ba_time_kernels(vmm_ba_handle h, const vmm_ba_options* opt, int reps, vm
                     &out->cholesky_ms)))
         return rc;
     if ((rc = timed([&] { launch_backsub(e); }, nop, &out->backsub_ms, 8))) return rc;
-    if (getenv("VMM_BA_DEBUG")) {
+    if (e.sw.debug) {
         HIP_TRY(hipMemcpy(e.ctl_host, e.ctl, sizeof(LmCtl), hipMemcpyDeviceToHost));
         fprintf(stderr, "[vmm_ba debug] after kernel timing: done=%d lin_fail=%d termination=%d iteration=%d\n",
                 e.ctl_host->done, e.ctl_host->lin_fail, e.ctl_host->termination, e.ctl_host->iteration);
@@ -2771,7 +1886,7 @@ int vmm_ba_debug_chol_schedule(int n_blk, int n_df, int n_cu, int32_t* launches,
         return VMM_BA_ERR_ARGUMENT;
     }
     if (n_df < 0) {
-        n_df = dataflow_blocks(n_blk, n_cu);
+        n_df = dataflow_blocks(n_blk, n_cu, read_switches());
         if (n_df == n_blk)
             n_df = 0;   // the one-launch kernel takes the whole system: what is returned is the fallback schedule
     }

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VMM_BA_ABI_VERSION 5
+#define VMM_BA_ABI_VERSION 6
 
 typedef struct vmm_ba_handle_s* vmm_ba_handle;
 
@@ -291,6 +291,45 @@ int vmm_ba_tag_translation_covariance(vmm_ba_handle h, int robustify, double hub
 /* Replaces CameraModel::projectPoint (src/CameraModel.cpp:6-26) for n camera-frame points. */
 int vmm_ba_project_points(const double intr[4], const double dist[5], int64_t n,
                           const double* points_cam, double* uv, int device);
+
+/* ABI 6.  n independent planar tag poses from each tag's own four corners; stateless like vmm_ba_project_points.
+ * Replaces solvePnPEigen on a tag's own four corners (src/TagReconstructor.cpp:208, src/EigenCVConversions.cpp:38-63):
+ * closed-form homography of the quad, decomposition, Levenberg-Marquardt on the 8 pixel residuals of
+ * CameraModel::projectPoint -- and then the second planar solution (the tag normal mirrored about the line of sight to
+ * the tag centre, refined the same way), which a small or distant tag makes nearly as good as the first.
+ * tag_wh[2*n]: width, height of observation i's tag; obs_px[8*n].
+ * qt2[14*n]: two tag->camera poses per observation, lower RMS first; rms2[2*n]: their RMS corner distance in pixels.
+ * A degenerate observation yields RMS = +inf and the pose (1,0,0,0, 0,0,1), never NaN. */
+int vmm_ba_quad_poses(const double intr[4], const double dist[5], int64_t n, const double* tag_wh,
+                      const double* obs_px, double* qt2, double* rms2, int device);
+
+/* ABI 6.  Initial poses for the bundle adjustment from the detections alone (the reference gets them from its
+ * incremental driver, src/TagReconstructor.cpp:86-278: one PnP + one bundle adjustment per image). */
+typedef struct vmm_ba_init_options {
+    int32_t sweeps;                /* 1: passes over all placed poses after the map stopped growing */
+    int32_t min_tag_observations;  /* 2: active observations a tag needs to be placed (src/TagReconstructor.cpp:192) */
+    double score_cap_px;           /* 100: a corner adds min(e^2, cap^2) to a candidate's score */
+    int32_t refine_iterations;     /* 30: Levenberg-Marquardt trials (accepted + rejected) of one pose's refinement */
+    int32_t reserved;
+} vmm_ba_init_options;
+typedef struct vmm_ba_init_report {
+    int32_t rounds;                /* growth rounds run, the last one (which placed nothing) included */
+    int32_t cams_reached, tags_reached, reserved;
+    double avg_reprojection_px;    /* mean corner distance over the active observations between reached poses */
+    double time_s;                 /* host wall time of the call */
+} vmm_ba_init_report;
+void vmm_ba_default_init_options(vmm_ba_init_options* o);
+/* Overwrites the device state of every pose reachable from the fixed (origin) tag, whose current pose is kept:
+ * planar poses of all active observations; then rounds -- every camera with an active observation of a placed tag,
+ * then every tag with >= min_tag_observations active observations that a placed camera sees: among the candidates
+ * (two per such observation, chained through the placed pose) the one with the lowest truncated squared reprojection
+ * error over all the pose's corners on placed counterparts, refined on its own -- until a round places nothing;
+ * then `sweeps` passes that redo selection and refinement for every placed pose except the origin.
+ * cam_reached[n_cams] / tag_reached[n_tags] (optional) receive 0/1; unreached poses keep their state.  Results are
+ * bit-identical from run to run.  VMM_BA_ERR_STATE for world_size > 1 or VMM_BA_LANDMARK_POINTS handles,
+ * VMM_BA_ERR_ARGUMENT for a handle without a fixed tag. */
+int vmm_ba_initialize(vmm_ba_handle h, const vmm_ba_init_options* o, vmm_ba_init_report* r,
+                      uint8_t* cam_reached, uint8_t* tag_reached);
 
 /* Test/diagnostic: one residual+Jacobian evaluation at the current state; copies out the
  * accumulated normal-equation blocks in the caller's index space.  Any output may be NULL.

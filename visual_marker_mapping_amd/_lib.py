@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VMM_BA_LIB selects another build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("VMM_BA_LIB") or os.path.join(_HERE, "libvmm_ba.so")
 
-ABI_VERSION = 5          # VMM_BA_ABI_VERSION of include/vmm_ba.h
+ABI_VERSION = 6          # VMM_BA_ABI_VERSION of include/vmm_ba.h
 RCCL_ID_BYTES = 128      # VMM_BA_RCCL_ID_BYTES
 PRECISION_F64, PRECISION_F32_ACCUM = 0, 1
 LANDMARK_TAG_POSES, LANDMARK_POINTS = 0, 1
@@ -25,7 +25,8 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_set_observation_mask", "vmm_ba_solve", "vmm_ba_cost",
            "vmm_ba_reprojection_stats", "vmm_ba_tag_translation_covariance", "vmm_ba_project_points", "vmm_ba_eval_blocks",
            "vmm_ba_dense_spd_solve", "vmm_ba_dense_syrk", "vmm_ba_time_kernels", "vmm_ba_pose_plus", "vmm_ba_debug_overlap",
-           "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile"]
+           "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
+           "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize"]
 
 
 class Problem(C.Structure):
@@ -82,6 +83,16 @@ class KernelTimes(C.Structure):
                 ("syrk_wide", C.c_int32), ("schur_flops", C.c_double), ("chol_flops", C.c_double)]
 
 
+class InitOptions(C.Structure):
+    _fields_ = [("sweeps", C.c_int32), ("min_tag_observations", C.c_int32), ("score_cap_px", C.c_double),
+                ("refine_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class InitReport(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("cams_reached", C.c_int32), ("tags_reached", C.c_int32),
+                ("reserved", C.c_int32), ("avg_reprojection_px", C.c_double), ("time_s", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 _LIB = None
@@ -135,6 +146,12 @@ def lib():
                                           C.POINTER(KernelTimes)]
         L.vmm_ba_debug_overlap.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.vmm_ba_debug_chol_schedule.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.vmm_ba_quad_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int]
+        L.vmm_ba_default_init_options.restype = None
+        L.vmm_ba_default_init_options.argtypes = [C.POINTER(InitOptions)]
+        L.vmm_ba_initialize.argtypes = [C.c_void_p, C.POINTER(InitOptions), C.POINTER(InitReport), C.c_void_p,
+                                        C.c_void_p]
         L.vmm_ba_debug_chol_tile.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB

@@ -222,6 +222,15 @@ struct Engine {
     double* stats_pose = nullptr;   // [2 * (n_cams + n_tags)]
     double* stats_corner = nullptr; // [8 * n_obs], allocated by the first call that asks for per-corner errors
 
+    // vmm_ba_initialize (kernels_init.hip), allocated by the first call
+    double* init_quad_qt = nullptr;   // [14 * n_obs] both planar tag->camera poses per observation, caller's order
+    double* init_quad_rms = nullptr;  // [2 * n_obs] their RMS reprojection errors (+inf: unusable)
+    int32_t* init_placed = nullptr;   // [n_cams + n_tags] pose has been placed (cameras first)
+    int32_t* init_todo = nullptr;     // [n_cams + n_tags] k_init_score -> k_init_refine
+    int32_t* init_counter = nullptr;  // poses placed in the current round
+    double* init_stats = nullptr;     // [2 + 2 * n_cams] sum of the corner errors | corners | the same per camera
+    double* init_host = nullptr;      // pinned, 4 doubles: the round's counter and the statistics as the host reads them
+
     LmCtl* ctl = nullptr;           // device
     LmCtl* ctl_host = nullptr;      // pinned
     // vmm_ba_set_state: the caller's poses are staged here (pinned) and copied on the stream without waiting for it
@@ -252,6 +261,7 @@ int preload_schur_kernels();
 int preload_chol_kernels();
 int preload_lm_kernels();
 int preload_cov_kernels();
+int preload_init_kernels();
 
 // ---- kernel launchers (defined in the .hip files) ----
 // kernels_eval.hip
@@ -290,6 +300,19 @@ void launch_cov_prepare(Engine& e);
 void launch_cov_rhs(Engine& e, double* B, int ldb, bool identity_rhs);
 void launch_cov_trsm(Engine& e, double* B, int ldb, int n_chunks, bool identity_rhs);
 void launch_cov_gram(Engine& e, const double* X, int ldb, double* cov_dev);
+// kernels_init.hip
+struct InitPass {   // one score + select + refine pass over a family
+    bool sweep = false;             // false: place what is not placed yet; true: redo every placed pose
+    int min_tag_observations = 2;
+    double score_cap_px = 100.0;
+    int refine_iterations = 30;
+};
+void launch_quad_poses(hipStream_t st, const Intrinsics& K, int64_t n, const double* tag_wh, const double* obs_px, double* qt2,
+                       double* rms2);
+void launch_init_quad(Engine& e);
+void launch_init_begin(Engine& e);
+void launch_init_pass(Engine& e, bool cam, const InitPass& s);
+void launch_init_stats(Engine& e, double* out);
 // kernels_lm.hip
 void launch_control(Engine& e);
 void launch_begin_loop(Engine& e, const LmCtl& init);

@@ -321,6 +321,8 @@ static void destroy_engine(Engine* e)
         (void)hipHostFree(e->ctl_host);
     if (e->pose_stage)
         (void)hipHostFree(e->pose_stage);
+    if (e->init_host)
+        (void)hipHostFree(e->init_host);
     if (e->pose_ev)
         (void)hipEventDestroy(e->pose_ev);
     if (e->stream)
@@ -699,7 +701,7 @@ static int open_device(Engine& e, int device)
     static bool preloaded[64] = {};
     if (e.device < 64 && !preloaded[e.device] && !e.sw.no_preload) {
         const int bad = preload_eval_kernels() + preload_schur_kernels() + preload_chol_kernels() + preload_lm_kernels()
-            + preload_cov_kernels();
+            + preload_cov_kernels() + preload_init_kernels();
         if (bad) {
             set_error("hipFuncGetAttributes failed for " + std::to_string(bad) + " kernels (code object not loadable on this device)");
             return VMM_BA_ERR_HIP;
@@ -1538,6 +1540,148 @@ int vmm_ba_pose_plus(int64_t n, const double* qt, const double* delta, double* o
     if (err != hipSuccess) {
         set_error(std::string("pose_plus: ") + hipGetErrorString(err));
         return VMM_BA_ERR_HIP;
+    }
+    return VMM_BA_OK;
+}
+
+int vmm_ba_quad_poses(const double intr[4], const double dist[5], int64_t n, const double* tag_wh, const double* obs_px,
+                      double* qt2, double* rms2, int device)
+{
+    if (!intr || !dist || n < 0 || (n > 0 && (!tag_wh || !obs_px || !qt2 || !rms2))) {
+        set_error("bad argument");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    if (n == 0)
+        return VMM_BA_OK;
+    HIP_TRY(hipSetDevice(device));
+    Intrinsics K;
+    K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3];
+    K.k1 = dist[0]; K.k2 = dist[1]; K.p1 = dist[2]; K.p2 = dist[3]; K.k3 = dist[4];
+    double* d = nullptr;   // tag_wh | obs_px | qt2 | rms2
+    HIP_TRY(hipMalloc((void**)&d, sizeof(double) * 26 * n));
+    double *d_wh = d, *d_px = d + 2 * n, *d_qt = d + 10 * n, *d_rms = d + 24 * n;
+    hipError_t err = hipMemcpy(d_wh, tag_wh, sizeof(double) * 2 * n, hipMemcpyHostToDevice);
+    if (err == hipSuccess)
+        err = hipMemcpy(d_px, obs_px, sizeof(double) * 8 * n, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        launch_quad_poses(nullptr, K, n, d_wh, d_px, d_qt, d_rms);
+        err = hipMemcpy(qt2, d_qt, sizeof(double) * 14 * n, hipMemcpyDeviceToHost);
+    }
+    if (err == hipSuccess)
+        err = hipMemcpy(rms2, d_rms, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (err != hipSuccess) {
+        set_error(std::string("quad_poses: ") + hipGetErrorString(err));
+        return VMM_BA_ERR_HIP;
+    }
+    return VMM_BA_OK;
+}
+
+void vmm_ba_default_init_options(vmm_ba_init_options* o)
+{
+    if (!o)
+        return;
+    memset(o, 0, sizeof(*o));
+    o->sweeps = 1;
+    o->min_tag_observations = 2;
+    o->score_cap_px = 100.0;
+    o->refine_iterations = 30;
+}
+
+int vmm_ba_initialize(vmm_ba_handle h, const vmm_ba_init_options* opt, vmm_ba_init_report* r, uint8_t* cam_reached,
+                      uint8_t* tag_reached)
+{
+    if (!h) {
+        set_error("null handle");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (e.world > 1 || e.points) {
+        set_error("vmm_ba_initialize needs a single-GPU handle with tag-pose landmarks");
+        return VMM_BA_ERR_STATE;
+    }
+    if (e.fixed_tag < 0) {
+        set_error("vmm_ba_initialize needs a fixed (origin) tag: the map grows from its pose");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    vmm_ba_init_options o;
+    if (opt)
+        o = *opt;
+    else
+        vmm_ba_default_init_options(&o);
+    if (o.sweeps < 0 || o.min_tag_observations < 1 || !(o.score_cap_px > 0.0) || o.refine_iterations < 0) {
+        set_error("bad initialisation options");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    HIP_TRY(hipSetDevice(e.device));
+    Range range("vmm_ba_initialize");
+    const auto t0 = std::chrono::steady_clock::now();
+    const int n_pose = e.n_cams + e.n_tags;
+    int rc;
+    if (!e.init_placed) {
+        const size_t n_obs = (size_t)std::max<int64_t>(e.n_obs, 1);
+        if ((rc = dev_alloc(e, &e.init_quad_qt, 14 * n_obs, false))) return rc;
+        if ((rc = dev_alloc(e, &e.init_quad_rms, 2 * n_obs, false))) return rc;
+        if ((rc = dev_alloc(e, &e.init_todo, (size_t)n_pose))) return rc;
+        if ((rc = dev_alloc(e, &e.init_counter, 1))) return rc;
+        if ((rc = dev_alloc(e, &e.init_stats, 2 + 2 * (size_t)e.n_cams))) return rc;
+        if (hipHostMalloc((void**)&e.init_host, sizeof(double) * 4) != hipSuccess) {
+            set_error("hipHostMalloc failed");
+            e.init_host = nullptr;
+            return VMM_BA_ERR_HIP;
+        }
+        if ((rc = dev_alloc(e, &e.init_placed, (size_t)n_pose))) return rc;
+    }
+    if ((rc = flush_state(e))) return rc;
+    launch_init_begin(e);
+    launch_init_quad(e);
+    InitPass pass;
+    pass.min_tag_observations = o.min_tag_observations;
+    pass.score_cap_px = o.score_cap_px;
+    pass.refine_iterations = o.refine_iterations;
+    int32_t* const placed_now = reinterpret_cast<int32_t*>(e.init_host);
+    int rounds = 0;
+    // every round but the last places at least one pose, so n_pose rounds are the most there can be
+    for (int round = 0; round < n_pose; ++round) {
+        HIP_TRY(hipMemsetAsync(e.init_counter, 0, sizeof(int32_t), e.stream));
+        launch_init_pass(e, true, pass);
+        launch_init_pass(e, false, pass);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(placed_now, e.init_counter, sizeof(int32_t), hipMemcpyDeviceToHost, e.stream));
+        HIP_TRY(hipStreamSynchronize(e.stream));
+        ++rounds;
+        if (*placed_now == 0)
+            break;
+    }
+    pass.sweep = true;
+    for (int s = 0; s < o.sweeps; ++s) {
+        launch_init_pass(e, true, pass);
+        launch_init_pass(e, false, pass);
+    }
+    launch_init_stats(e, e.init_stats);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> placed((size_t)n_pose);
+    HIP_TRY(hipMemcpyAsync(e.init_host + 2, e.init_stats, sizeof(double) * 2, hipMemcpyDeviceToHost, e.stream));
+    HIP_TRY(hipMemcpyAsync(placed.data(), e.init_placed, sizeof(int32_t) * n_pose, hipMemcpyDeviceToHost, e.stream));
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    int n_c = 0, n_t = 0;
+    for (int c = 0; c < e.n_cams; ++c) {
+        n_c += placed[(size_t)c] != 0;
+        if (cam_reached)
+            cam_reached[c] = placed[(size_t)c] != 0;
+    }
+    for (int t = 0; t < e.n_tags; ++t) {
+        n_t += placed[(size_t)e.n_cams + t] != 0;
+        if (tag_reached)
+            tag_reached[t] = placed[(size_t)e.n_cams + t] != 0;
+    }
+    if (r) {
+        memset(r, 0, sizeof(*r));
+        r->rounds = rounds;
+        r->cams_reached = n_c;
+        r->tags_reached = n_t;
+        r->avg_reprojection_px = e.init_host[3] > 0.0 ? e.init_host[2] / e.init_host[3] : 0.0;
+        r->time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     return VMM_BA_OK;
 }

@@ -152,6 +152,23 @@ class BundleAdjuster:
         out["trace"] = trace
         return out
 
+    def initialize(self, **options):
+        """Initial poses from the detections alone (vmm_ba_initialize): overwrites the device state of every pose
+        reachable from the fixed tag, whose current pose is kept.  options: the fields of vmm_ba_init_options
+        (sweeps, min_tag_observations, score_cap_px, refine_iterations).  Returns (report dict, cam_reached,
+        tag_reached) with boolean masks; unreached poses keep their state."""
+        o = _lib.InitOptions()
+        _lib.lib().vmm_ba_default_init_options(C.byref(o))
+        for k, v in options.items():
+            if k == "reserved" or not hasattr(o, k):
+                raise AttributeError("unknown initialisation option %r" % k)
+            setattr(o, k, v)
+        r = _lib.InitReport()
+        cam, tag = np.zeros(self.n_cams, np.uint8), np.zeros(self.n_tags, np.uint8)
+        _lib.check(_lib.lib().vmm_ba_initialize(self._h, C.byref(o), C.byref(r), _ptr(cam), _ptr(tag)))
+        report = {k: getattr(r, k) for k, _ in _lib.InitReport._fields_ if k != "reserved"}
+        return report, cam.astype(bool), tag.astype(bool)
+
     def cost(self, robustify=True, huber_a=1.0):
         c = C.c_double(0)
         _lib.check(_lib.lib().vmm_ba_cost(self._h, int(bool(robustify)), float(huber_a), C.byref(c)))
@@ -218,6 +235,22 @@ def project_points(intr, dist, points_cam, device=0):
     uv = np.zeros((len(pts), 2))
     _lib.check(_lib.lib().vmm_ba_project_points(_ptr(intr), _ptr(dist), len(pts), _ptr(pts), _ptr(uv), device))
     return uv
+
+
+def quad_poses(intr, dist, tag_wh, obs_px, device=0):
+    """Both planar tag->camera poses of n tag observations from each tag's own four corners (vmm_ba_quad_poses; the
+    role of solvePnPEigen at src/TagReconstructor.cpp:208 of the reference).  tag_wh (n, 2), obs_px (n, 8).
+    Returns qt2 (n, 2, 7), lower RMS first, and rms2 (n, 2) in pixels (+inf: degenerate)."""
+    intr = np.ascontiguousarray(intr, np.float64).reshape(4)
+    dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+    px = np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8)
+    wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
+    if len(wh) != len(px):
+        raise ValueError("tag_wh and obs_px differ in length")
+    qt2, rms2 = np.zeros((len(px), 2, 7)), np.zeros((len(px), 2))
+    _lib.check(_lib.lib().vmm_ba_quad_poses(_ptr(intr), _ptr(dist), len(px), _ptr(wh), _ptr(px), _ptr(qt2), _ptr(rms2),
+                                            device))
+    return qt2, rms2
 
 
 def pose_plus(qt, delta, device=0):

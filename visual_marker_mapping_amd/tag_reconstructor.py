@@ -152,6 +152,7 @@ class TagReconstructor:
         self.device = int(device)
         self.lastSummary = None                                # summary of the last doBundleAdjustment
         self.lastCovariances = None                            # tag id -> 3x3 (last printSummary call)
+        self.lastInitReport = None                             # report of vmm_ba_initialize (startReconstructionGlobal)
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
         self._obs_cache = None                                 # observation list as arrays (see _obs_arrays)
         self._resident = False                                 # device-resident packing (startReconstruction)
@@ -279,6 +280,73 @@ class TagReconstructor:
             if maxPairs == 0:
                 break
             print("----------------------------------------------------------")
+
+        print("Starting final bundle adjustment")
+        self.doBundleAdjustment(1500, numThreads, True, False)
+        self.removeBadMarkers(2.0)
+        self.removeBadCameras(2.0)
+        self.doBundleAdjustment(1500, numThreads, False, True)
+
+    def startReconstructionGlobal(self, numThreads=1, **init_options):
+        """Not in the reference API: the same map as startReconstruction without its N + 2 dependent bundle
+        adjustments.  Origin tag as there (lowest id when -1, at identity); ONE device handle over the whole
+        detection result; vmm_ba_initialize places every camera and tag reachable from the origin tag on the device
+        (planar pose of every observation, candidate selection by truncated reprojection error, per-pose refinement;
+        DESIGN.md section 9) -- these become the reconstructed sets; then the reference's closing sequence
+        (src/TagReconstructor.cpp:271-277): BA(1500, robust), both prunings, BA(1500, plain, summary).
+        init_options: fields of vmm_ba_init_options.  The report of the initialisation is kept in lastInitReport."""
+        self._resident = True
+        try:
+            self._start_reconstruction_global(numThreads, init_options)
+        finally:
+            self._resident = False
+            self._drop_cached()
+            self._full = None
+
+    def _start_reconstruction_global(self, numThreads, init_options):
+        if self.originTagId == -1:
+            self.originTagId = self.getLowestTag()
+        tagById = {t.tagId: t for t in self.detectionResults_.tags}
+        if self.originTagId not in tagById:
+            raise RuntimeError("Could not use tag with id %d as origin tag, because it was not detected."
+                               % self.originTagId)
+        o = tagById[self.originTagId]
+        self.reconstructedTags.setdefault(self.originTagId, ReconstructedTag(
+            id=self.originTagId, tagType=o.tagType, tagWidth=o.width, tagHeight=o.height))
+        # the resident packing with nothing but the origin tag reconstructed: every other pose is a placeholder that
+        # still gives finite residuals (cameras 1 m in front of tags at identity)
+        p = self._pack_resident(for_ba=True)
+        full = self._full
+        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
+        try:
+            ba.set_observation_mask(None)
+            report, cam_ok, tag_ok = ba.initialize(**init_options)
+            cam, tag = ba.get_state()
+        except Exception:
+            self._drop_cached()
+            raise
+        self.lastInitReport = report
+        print("Initialized %d of %d cameras and %d of %d tags in %d rounds, average reprojection error %g"
+              % (report["cams_reached"], len(cam_ok), report["tags_reached"], len(tag_ok), report["rounds"],
+                 report["avg_reprojection_px"]))
+        if not cam_ok.any():
+            raise RuntimeError("No reconstructed tags in image found. To reconstruct the image pose "
+                               "already reconstructed markers are needed. This should NOT happen.")
+        imagesOfTag = {}
+        for ob in self.detectionResults_.tagObservations:
+            imagesOfTag.setdefault(ob.tagId, set()).add(ob.imageId)
+        for r, cid in enumerate(full["cams"].tolist()):
+            if cam_ok[r]:
+                self.reconstructedCameras[cid] = Camera(cameraId=cid, q=cam[r, :4], t=cam[r, 4:])
+        for r, tid in enumerate(full["tags"].tolist()):
+            if tid == self.originTagId:
+                continue
+            if tag_ok[r] and tid in tagById:
+                d = tagById[tid]
+                self.reconstructedTags[tid] = ReconstructedTag(id=tid, tagType=d.tagType, q=tag[r, :4], t=tag[r, 4:],
+                                                               tagWidth=d.width, tagHeight=d.height)
+            elif len(imagesOfTag.get(tid, ())) == 1:
+                print("   Skipping reconstruction of tag %d: Only observed once!" % tid)
 
         print("Starting final bundle adjustment")
         self.doBundleAdjustment(1500, numThreads, True, False)

@@ -331,6 +331,58 @@ void vmm_ba_default_init_options(vmm_ba_init_options* o);
 int vmm_ba_initialize(vmm_ba_handle h, const vmm_ba_init_options* o, vmm_ba_init_report* r,
                       uint8_t* cam_reached, uint8_t* tag_reached);
 
+/* ABI 6, additive: new functions and structs only, no existing struct or signature changes.
+ * Localises n_imgs images against a finished map; stateless like the quad poses above, every image independent of the
+ * others in the batch.  Batch form of TagReconstructor::computeRelativeCameraPoseFromImg (src/TagReconstructor.cpp:
+ * 280-312: every correspondence between one image and the reconstructed tags, RANSAC PnP).  Per image:
+ *   candidates  the two planar solutions of each of its observations chained through the map tag, T_rel o T_tag^-1;
+ *               each scored by sum min(e^2, score_cap_px^2) over ALL the image's corners with the residual the bundle
+ *               adjustment minimises; lowest wins, ties to the lowest observation then solution 0, non-finite loses
+ *   passes      reclassify_passes times: an observation is an inlier when its largest corner distance is at most
+ *               inlier_px; then Levenberg-Marquardt on the 6 tangent degrees of freedom over the inliers, minimising
+ *               1/2 sum rho(|r_corner|^2), until the cost is at its rounding floor or refine_iterations trials are spent.
+ *               A pass that finds fewer than min_inlier_tags inliers ends the passes.  reclassify_passes == 0: one
+ *               refinement over all observations.
+ *   result      obs_inlier = the classification at the returned pose; cam_cov = row-major 6x6 (J^T J)^-1 in tangent
+ *               order over those inliers, the loss applied when robustify != 0 (as the tag translation covariance above).
+ * NO_OBSERVATIONS / NO_CANDIDATE: pose (1,0,0,0, 0,0,0), zero covariance, zero flags.  TOO_FEW_INLIERS (fewer than
+ * min_inlier_tags at the returned pose): the best-effort pose and its flags, zero covariance.  SINGULAR: J^T J is not
+ * positive definite; pose and flags are returned, the covariance is zeros.  No output is ever NaN; results are
+ * bit-identical from run to run and do not depend on what else is in the batch.
+ * VMM_BA_ERR_ARGUMENT (before any device call): null pointers, img_start not starting at 0 or decreasing, obs_tag
+ * outside [0, n_tags), non-finite map poses or sizes, bad options.  n_imgs == 0 returns VMM_BA_OK without a device call. */
+typedef struct vmm_ba_localize_options {
+    int32_t refine_iterations;   /* 30: LM trials (accepted + rejected) of one refinement */
+    int32_t robustify;           /* 1: HuberLoss(huber_a) per corner block, as doBundleAdjustment (:721) */
+    double  huber_a;             /* 1.0 */
+    double  score_cap_px;        /* 100: as vmm_ba_init_options */
+    double  inlier_px;           /* 8.0: solvePnPRansac's reprojectionError (pnp.py default) */
+    int32_t reclassify_passes;   /* 2: classify -> refine on the inliers, repeated this often */
+    int32_t min_inlier_tags;     /* 1 */
+} vmm_ba_localize_options;
+
+typedef struct vmm_ba_localize_result {   /* one per image */
+    int32_t status;              /* VMM_BA_LOC_* */
+    int32_t n_obs, n_inlier_obs, trials;
+    double  rms_px;              /* RMS corner distance over the inlier observations */
+    double  cost;                /* 1/2 sum rho(|r|^2) over the inlier observations at the result */
+} vmm_ba_localize_result;
+
+enum { VMM_BA_LOC_OK = 0, VMM_BA_LOC_NO_OBSERVATIONS = 1, VMM_BA_LOC_NO_CANDIDATE = 2,
+       VMM_BA_LOC_TOO_FEW_INLIERS = 3, VMM_BA_LOC_SINGULAR = 4 };
+
+void vmm_ba_default_localize_options(vmm_ba_localize_options* o);
+int vmm_ba_localize(const double intr[4], const double dist[5],
+                    int32_t n_tags, const double* tag_qt, const double* tag_wh,      /* the map */
+                    int32_t n_imgs, const int64_t* img_start,                         /* [n_imgs+1], CSR */
+                    const int32_t* obs_tag, const double* obs_px,                     /* [n_obs], [8*n_obs] */
+                    const vmm_ba_localize_options* o,
+                    double* cam_qt,              /* [7*n_imgs] world->camera */
+                    double* cam_cov,             /* [36*n_imgs] or NULL */
+                    uint8_t* obs_inlier,         /* [n_obs] or NULL */
+                    vmm_ba_localize_result* res, /* [n_imgs] or NULL */
+                    int device);
+
 /* Test/diagnostic: one residual+Jacobian evaluation at the current state; copies out the
  * accumulated normal-equation blocks in the caller's index space.  Any output may be NULL.
  *   V[36*n_cams], U[36*n_tags]  row-major 6x6 J^T J diagonal blocks (Huber-corrected, unscaled)

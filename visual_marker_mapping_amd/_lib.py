@@ -16,6 +16,9 @@ LANDMARK_TAG_POSES, LANDMARK_POINTS = 0, 1
 OK, ERR_ARGUMENT, ERR_HIP, ERR_COLLECTIVE, ERR_STATE, ERR_NUMERIC = 0, 1, 2, 3, 4, 5
 ELIM_AUTO, ELIM_TAGS, ELIM_CAMERAS = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
+# VMM_BA_LOC_*: status of one image of vmm_ba_localize
+LOC_OK, LOC_NO_OBSERVATIONS, LOC_NO_CANDIDATE, LOC_TOO_FEW_INLIERS, LOC_SINGULAR = 0, 1, 2, 3, 4
+LOC_STATUS_NAMES = ("ok", "no_observations", "no_candidate", "too_few_inliers", "singular")
 
 # every symbol include/vmm_ba.h declares
 EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
@@ -26,7 +29,8 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_reprojection_stats", "vmm_ba_tag_translation_covariance", "vmm_ba_project_points", "vmm_ba_eval_blocks",
            "vmm_ba_dense_spd_solve", "vmm_ba_dense_syrk", "vmm_ba_time_kernels", "vmm_ba_pose_plus", "vmm_ba_debug_overlap",
            "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
-           "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize"]
+           "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
+           "vmm_ba_default_localize_options", "vmm_ba_localize"]
 
 
 class Problem(C.Structure):
@@ -93,6 +97,17 @@ class InitReport(C.Structure):
                 ("reserved", C.c_int32), ("avg_reprojection_px", C.c_double), ("time_s", C.c_double)]
 
 
+class LocalizeOptions(C.Structure):
+    _fields_ = [("refine_iterations", C.c_int32), ("robustify", C.c_int32), ("huber_a", C.c_double),
+                ("score_cap_px", C.c_double), ("inlier_px", C.c_double), ("reclassify_passes", C.c_int32),
+                ("min_inlier_tags", C.c_int32)]
+
+
+class LocalizeResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_obs", C.c_int32), ("n_inlier_obs", C.c_int32), ("trials", C.c_int32),
+                ("rms_px", C.c_double), ("cost", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 _LIB = None
@@ -152,6 +167,11 @@ def lib():
         L.vmm_ba_default_init_options.argtypes = [C.POINTER(InitOptions)]
         L.vmm_ba_initialize.argtypes = [C.c_void_p, C.POINTER(InitOptions), C.POINTER(InitReport), C.c_void_p,
                                         C.c_void_p]
+        L.vmm_ba_default_localize_options.restype = None
+        L.vmm_ba_default_localize_options.argtypes = [C.POINTER(LocalizeOptions)]
+        L.vmm_ba_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(LocalizeOptions), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int]
         L.vmm_ba_debug_chol_tile.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB

@@ -307,8 +307,31 @@ struct InitPass {   // one score + select + refine pass over a family
     double score_cap_px = 100.0;
     int refine_iterations = 30;
 };
+// wh_index: row of tag_wh that holds observation i's size (null: row i)
 void launch_quad_poses(hipStream_t st, const Intrinsics& K, int64_t n, const double* tag_wh, const double* obs_px, double* qt2,
-                       double* rms2);
+                       double* rms2, const int32_t* wh_index = nullptr);
+// kernels_localize.hip
+struct LocalizeArgs {
+    Intrinsics K;
+    int n_imgs;
+    const int64_t* img_start;  // [n_imgs + 1]
+    const int32_t* obs_tag;    // [n_obs]
+    const double* obs_px;      // [8 * n_obs]
+    const double* tag_qt;      // [7 * n_tags]
+    const double* corners;     // [12 * n_tags] world corners (k_map_corners)
+    const double* quad_qt;     // [14 * n_obs] planar tag->camera poses (k_quad_pose)
+    const double* quad_rms;    // [2 * n_obs]
+    int max_trials, robustify, passes, min_inliers;
+    double huber_a, cap2, inlier2;
+    double* cam_qt;            // [7 * n_imgs]
+    double* cam_cov;           // [36 * n_imgs]
+    uint8_t* obs_inlier;       // [n_obs]: the active set of every pass, the final flags at the end
+    vmm_ba_localize_result* res;
+};
+void launch_map_corners(hipStream_t st, int n_tags, const double* tag_qt, const double* tag_wh, double* corners);
+void launch_localize(hipStream_t st, const LocalizeArgs& a, bool any_staged, bool any_unstaged);
+int localize_stage_capacity();   // observations of one image that k_localize stages in LDS
+int preload_localize_kernels();
 void launch_init_quad(Engine& e);
 void launch_init_begin(Engine& e);
 void launch_init_pass(Engine& e, bool cam, const InitPass& s);

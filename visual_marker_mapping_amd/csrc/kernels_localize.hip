@@ -1,0 +1,561 @@
+// Localisation of images against a finished map (gfx950): vmm_ba_localize.
+//
+// Batch form of TagReconstructor::computeRelativeCameraPoseFromImg (src/TagReconstructor.cpp:280-312,
+// solvePnPRansacEigen, src/EigenCVConversions.cpp:65-106), which the host mirror runs one image at a time:
+//   k_quad_pose     (kernels_init.hip, as it is) both planar tag->camera poses of every observation
+//   k_map_corners   thread = tag: the four world corners of every map tag, once per call -- eval_corner's tag half
+//                   hoisted out of the per-observation, per-trial arithmetic
+//   k_localize      workgroup = image, one launch from candidates to covariance:
+//                   scoring   thread = candidate (two per observation, chained through the map tag), truncated squared
+//                             reprojection error over all the image's corners; the waves' winners meet in LDS and are
+//                             taken in wave order (k_init_score's rules)
+//                   passes    classify the observations at the pose, Levenberg-Marquardt over the inliers: threads
+//                             stride the observation list, 21 + 6 + 2 sums reduced by one butterfly per wave
+//                             (wave_sum32) and combined in LDS in wave order; every thread runs the same 6 x 6 solve
+//                   result    flags at the returned pose, (J^T J)^-1 by a 6 x 6 Cholesky in registers
+// An image's pixels and world corners (20 doubles per observation) are staged in LDS when the image has at most
+// kStage observations (k_localize<true>); larger images read them from global memory (k_localize<false>).  Both run the
+// same arithmetic in the same order, and which one an image takes depends on its own length alone.
+// Nothing but the selection of the image depends on blockIdx, no workgroup waits on another, there is no floating-point
+// atomic and every sum has a fixed order (thread-private sums in list order, the wave butterfly, the waves in order):
+// an image gives the same bits alone, in any batch and from run to run.
+//
+// Registers (hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S, the .s file's .vgpr_count / .vgpr_spill_count /
+// .private_segment_fixed_size): k_localize<true> takes 350 and k_localize<false> 302 registers per lane with no spill and
+// a zero private segment, like k_quad_pose (kernels_init.hip).  The compiler keeps a thread's own observation (20
+// doubles and their LDS addresses) in registers across the passes, next to the 29 running sums, the pose and the 6 x 6
+// system; asked for two waves per SIMD (__launch_bounds__(256, 2), 256 registers) it spills about 40 of them to scratch,
+// so the kernel runs one wave per SIMD = one 256-thread workgroup per CU, and the 40 KiB of LDS never limit it.
+#include <limits.h>
+
+#include "engine.hpp"
+#include "pose_lm.hpp"
+
+namespace vmm {
+
+namespace {
+
+constexpr int kLocThreads = 256;
+constexpr int kLocWaves = kLocThreads / 64;
+constexpr int kStage = 256;   // observations staged in LDS: 20 x 8 B x 256 = 40 KiB per workgroup
+
+__global__ __launch_bounds__(256) void k_map_corners(int n_tags, const double* __restrict__ tag_qt,
+                                                     const double* __restrict__ tag_wh, double* __restrict__ corners)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tags)
+        return;
+    Rigid tag;
+    load_rigid<true>(tag_qt + 7 * (int64_t)t, tag);
+    const double hw = 0.5 * tag_wh[2 * t], hh = 0.5 * tag_wh[2 * t + 1];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // a = R_t p_l (p_l.z == 0), P_w = a + t_t, exactly as eval_corner (geom.hpp)
+        const double sxhw = corner_sx(k) * hw, syhh = corner_sy(k) * hh;
+        corners[12 * (int64_t)t + 3 * k] = (tag.R[0] * sxhw + tag.R[1] * syhh) + tag.t[0];
+        corners[12 * (int64_t)t + 3 * k + 1] = (tag.R[3] * sxhw + tag.R[4] * syhh) + tag.t[1];
+        corners[12 * (int64_t)t + 3 * k + 2] = (tag.R[6] * sxhw + tag.R[7] * syhh) + tag.t[2];
+    }
+}
+
+// eval_corner's camera half (geom.hpp) on a world corner: residual and, with JAC, the 2 x 6 camera Jacobian.
+template <bool JAC>
+__device__ __forceinline__ void world_corner(const Intrinsics& K, const Rigid& cam, const double w0, const double w1,
+                                             const double w2, const double u_obs, const double v_obs, double& ru, double& rv,
+                                             double (&j)[2][6])
+{
+    const double b0 = cam.R[0] * w0 + cam.R[1] * w1 + cam.R[2] * w2;
+    const double b1 = cam.R[3] * w0 + cam.R[4] * w1 + cam.R[5] * w2;
+    const double b2 = cam.R[6] * w0 + cam.R[7] * w1 + cam.R[8] * w2;
+    const double iz = 1.0 / (b2 + cam.t[2]);
+    const double x = (b0 + cam.t[0]) * iz, y = (b1 + cam.t[1]) * iz;
+    const double r2 = x * x + y * y;
+    const double rad = 1.0 + r2 * (K.k1 + r2 * (K.k2 + r2 * K.k3));
+    double xd, yd;
+    distort(K, false, x, y, r2, rad, xd, yd);
+    ru = K.fx * xd + K.cx - u_obs;
+    rv = K.fy * yd + K.cy - v_obs;
+    if (!JAC)
+        return;
+    const double dr = K.k1 + r2 * (2.0 * K.k2 + 3.0 * K.k3 * r2);
+    const double D00 = rad + 2.0 * x * x * dr + 2.0 * K.p1 * y + 6.0 * K.p2 * x;
+    const double D01 = 2.0 * x * y * dr + 2.0 * K.p1 * x + 2.0 * K.p2 * y;
+    const double D11 = rad + 2.0 * y * y * dr + 2.0 * K.p2 * x + 6.0 * K.p1 * y;
+    const double g[2][3] = { { K.fx * D00 * iz, K.fx * D01 * iz, -K.fx * (D00 * x + D01 * y) * iz },
+                             { K.fy * D01 * iz, K.fy * D11 * iz, -K.fy * (D01 * x + D11 * y) * iz } };
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        j[r][0] = g[r][0];
+        j[r][1] = g[r][1];
+        j[r][2] = g[r][2];
+        j[r][3] = 2.0 * (b1 * g[r][2] - b2 * g[r][1]);
+        j[r][4] = 2.0 * (b2 * g[r][0] - b0 * g[r][2]);
+        j[r][5] = 2.0 * (b0 * g[r][1] - b1 * g[r][0]);
+    }
+}
+
+// One image's observations: element k (0..7 pixels, 8..19 world corners) of local observation d.
+template <bool STAGED>
+struct ImageView {
+    const double* lds;        // STAGED: [20][m]
+    int m;
+    const double* px;         // obs_px + 8 * first observation
+    const int32_t* tag;       // obs_tag + first observation
+    const double* corners;
+    __device__ __forceinline__ double pixel(const int d, const int k) const
+    {
+        return STAGED ? lds[k * m + d] : px[8 * (int64_t)d + k];
+    }
+    __device__ __forceinline__ double world(const int d, const int k) const
+    {
+        return STAGED ? lds[(8 + k) * m + d] : corners[12 * (int64_t)tag[d] + k];
+    }
+};
+
+// Truncated score of camera pose `cam` over all the image's corners.
+template <bool STAGED>
+__device__ __forceinline__ double score_image(const Intrinsics& K, const ImageView<STAGED>& v, const Rigid& cam,
+                                              const double cap2)
+{
+    double sum = 0.0;
+    for (int d = 0; d < v.m; ++d) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double ru, rv, j[2][6];
+            world_corner<false>(K, cam, v.world(d, 3 * k), v.world(d, 3 * k + 1), v.world(d, 3 * k + 2), v.pixel(d, 2 * k),
+                                v.pixel(d, 2 * k + 1), ru, rv, j);
+            const double e2 = ru * ru + rv * rv;
+            sum += e2 < cap2 ? e2 : (finite_bits(e2) ? cap2 : kInf);
+        }
+    }
+    return sum;
+}
+
+// Flags the observations whose largest corner distance under q is at most sqrt(inlier2); every thread returns their
+// number.  A non-finite distance is an outlier.
+template <bool STAGED>
+__device__ __forceinline__ int classify_image(const Intrinsics& K, const ImageView<STAGED>& v, const double* q,
+                                              const double inlier2, uint8_t* flags, int* s_cnt)
+{
+    Rigid cam;
+    load_rigid<true>(q, cam);
+    int n = 0;
+    for (int d = threadIdx.x; d < v.m; d += kLocThreads) {
+        bool in = true;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double ru, rv, j[2][6];
+            world_corner<false>(K, cam, v.world(d, 3 * k), v.world(d, 3 * k + 1), v.world(d, 3 * k + 2), v.pixel(d, 2 * k),
+                                v.pixel(d, 2 * k + 1), ru, rv, j);
+            in = in && (ru * ru + rv * rv <= inlier2);
+        }
+        flags[d] = in ? 1 : 0;
+        n += in ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1)
+        n += __shfl_xor(n, s, 64);
+    if ((threadIdx.x & 63) == 0)
+        s_cnt[threadIdx.x >> 6] = n;
+    __syncthreads();   // also orders the flags (global memory, this workgroup only) before their readers
+    n = 0;
+#pragma unroll
+    for (int w = 0; w < kLocWaves; ++w)
+        n += s_cnt[w];
+    __syncthreads();
+    return n;
+}
+
+// Sums over the active observations (flags null: all) at pose q: returns 1/2-free cost sum rho(|r_corner|^2); with JAC
+// also J^T J (packed lower) and J^T r with the Huber corrector applied, and raw2 = sum |r|^2 without the loss.
+// Every thread returns the same totals.
+template <bool STAGED, bool JAC>
+__device__ __forceinline__ double image_sums(const Intrinsics& K, const ImageView<STAGED>& v, const double* q,
+                                             const uint8_t* flags, const bool robust, const double huber_a, double* s_red,
+                                             double (&A)[21], double (&g)[6], double& raw2)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    Rigid cam;
+    load_rigid<true>(q, cam);
+    double acc[32];   // 0..20 J^T J, 21..26 J^T r, 27 cost, 28 raw2
+    double cost = 0.0, raw = 0.0;
+    if (JAC) {
+#pragma unroll
+        for (int k = 0; k < 21; ++k)
+            A[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            g[k] = 0.0;
+    }
+    for (int d = threadIdx.x; d < v.m; d += kLocThreads) {
+        if (flags && flags[d] == 0)
+            continue;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            double ru, rv, j[2][6];
+            world_corner<JAC>(K, cam, v.world(d, 3 * k), v.world(d, 3 * k + 1), v.world(d, 3 * k + 2), v.pixel(d, 2 * k),
+                              v.pixel(d, 2 * k + 1), ru, rv, j);
+            const double s = ru * ru + rv * rv;
+            double rho0, wgt;
+            huber(robust, huber_a, s, rho0, wgt);
+            cost += rho0;
+            if (JAC) {
+                raw += s;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    j[0][c] *= wgt;
+                    j[1][c] *= wgt;
+                }
+                accumulate_rows(j, ru * wgt, rv * wgt, A, g);
+            }
+        }
+    }
+    if (JAC) {
+#pragma unroll
+        for (int k = 0; k < 21; ++k)
+            acc[k] = A[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            acc[21 + k] = g[k];
+        acc[27] = cost;
+        acc[28] = raw;
+        acc[29] = acc[30] = acc[31] = 0.0;
+        const double tot = wave_sum32(acc, lane);
+        s_red[wave * 32 + wave_sum32_index(lane)] = tot;   // lanes 2 m and 2 m + 1 hold (and store) the same value
+        __syncthreads();
+        double r[29];
+#pragma unroll
+        for (int k = 0; k < 29; ++k) {
+            double t = s_red[k];
+#pragma unroll
+            for (int w = 1; w < kLocWaves; ++w)
+                t += s_red[w * 32 + k];
+            r[k] = t;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 21; ++k)
+            A[k] = r[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            g[k] = r[21 + k];
+        raw2 = r[28];
+        return r[27];
+    }
+    cost = wave_sum(cost);
+    if (lane == 0)
+        s_red[wave] = cost;
+    __syncthreads();
+    double t = s_red[0];
+#pragma unroll
+    for (int w = 1; w < kLocWaves; ++w)
+        t += s_red[w];
+    __syncthreads();
+    return t;
+}
+
+// Levenberg-Marquardt on q (in place) over the active observations; returns the trials spent.
+template <bool STAGED>
+__device__ __forceinline__ int refine_image(const Intrinsics& K, const ImageView<STAGED>& v, double (&q)[7],
+                                            const uint8_t* flags, const bool robust, const double huber_a,
+                                            const int max_trials, double* s_red)
+{
+    double cand[7], A[21], g[6], step[6], raw2;
+    double lam = kLamInit;
+    // every thread holds the same sums, so the whole workgroup takes the same branches (and reaches the same barriers)
+    double cost = image_sums<STAGED, true>(K, v, q, flags, robust, huber_a, s_red, A, g, raw2);
+    int it = 0;
+    for (; it < max_trials; ++it) {
+        if (!finite_bits(cost) || lam > kLamMax)
+            break;
+        if (!solve6<true>(A, g, lam, step)) {
+            lam *= 10.0;
+            continue;
+        }
+        const double sm = max_abs6(step);
+        if (sm < 1e-14)
+            break;
+        pose_plus(q, step, cand);
+        double A2[21], g2[6];
+        const double cc = image_sums<STAGED, false>(K, v, cand, flags, robust, huber_a, s_red, A2, g2, raw2);
+        if (finite_bits(cc) && cc < cost) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k)
+                q[k] = cand[k];
+            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
+            cost = image_sums<STAGED, true>(K, v, q, flags, robust, huber_a, s_red, A, g, raw2);
+        } else {
+            if (sm < 1e-10 || cost_at_floor(cost, cc))
+                break;
+            lam *= 10.0;
+        }
+    }
+    return it;
+}
+
+// C = A^-1 for a packed lower 6 x 6 A by Cholesky, in registers; false: not positive definite (C is not valid).
+// One test at the end covers every pivot: a negative pivot makes its square root a NaN and a zero pivot its reciprocal
+// an infinity, and either reaches the last entry of every later row of L^-1 and from there C.
+__device__ __forceinline__ bool inverse6(const double (&A)[21], double (&C)[21])
+{
+    double L[21], M[21];   // A = L L^T, M = L^-1 (lower)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = A[tri6(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k)
+            d -= L[tri6(j, k)] * L[tri6(j, k)];
+        const double s = sqrt(d);
+        L[tri6(j, j)] = s;
+        const double is = 1.0 / s;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[tri6(i, j)];
+#pragma unroll
+            for (int k = 0; k < j; ++k)
+                v -= L[tri6(i, k)] * L[tri6(j, k)];
+            L[tri6(i, j)] = v * is;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        M[tri6(j, j)] = 1.0 / L[tri6(j, j)];
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = j; k < i; ++k)
+                v -= L[tri6(i, k)] * M[tri6(k, j)];
+            M[tri6(i, j)] = v / L[tri6(i, i)];
+        }
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b <= a; ++b) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = a; k < 6; ++k)
+                v += M[tri6(k, a)] * M[tri6(k, b)];
+            C[tri6(a, b)] = v;
+            sum += fabs(v);
+        }
+    return finite_bits(sum);
+}
+
+// What thread 0 stores for image p; have_cov false: a zero covariance.
+__device__ __forceinline__ void store_result(const LocalizeArgs& a, const int p, const double (&q)[7], const double (&C)[21],
+                                             const bool have_cov, const vmm_ba_localize_result& res)
+{
+    double* const out_q = a.cam_qt + 7 * (int64_t)p;
+    double* const out_cov = a.cam_cov + 36 * (int64_t)p;
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+        out_q[k] = q[k];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+            out_cov[6 * r + c] = have_cov ? (r >= c ? C[tri6(r, c)] : C[tri6(c, r)]) : 0.0;
+    a.res[p] = res;
+}
+
+// NO_OBSERVATIONS / NO_CANDIDATE: the identity pose, a zero covariance (the flags are zero already)
+__device__ __forceinline__ void store_failure(const LocalizeArgs& a, const int p, const int m, const int status, const int trials)
+{
+    const double q[7] = { 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    vmm_ba_localize_result res;
+    res.status = status;
+    res.n_obs = m;
+    res.n_inlier_obs = 0;
+    res.trials = trials;
+    res.rms_px = 0.0;
+    res.cost = 0.0;
+    const double C[21] = {};
+    store_result(a, p, q, C, false, res);
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(kLocThreads) void k_localize(const LocalizeArgs a)
+{
+    __shared__ double s_img[STAGED ? 20 * kStage : 1];
+    __shared__ double s_red[kLocWaves * 32];
+    __shared__ double s_best[kLocWaves];
+    __shared__ int s_c[kLocWaves];
+    __shared__ int s_cnt[kLocWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x;
+    const int64_t b = a.img_start[p];
+    const int m = (int)(a.img_start[p + 1] - b);
+    // every decision to leave depends on the image alone or on values all threads hold alike: the whole workgroup
+    // reaches the same barriers and leaves together
+    if ((m <= kStage) != STAGED)
+        return;
+    if (m == 0) {
+        if (tid == 0)
+            store_failure(a, p, m, VMM_BA_LOC_NO_OBSERVATIONS, 0);
+        return;
+    }
+    uint8_t* const flags = a.obs_inlier + b;
+    const Intrinsics K = a.K;
+    ImageView<STAGED> v;
+    v.lds = s_img;
+    v.m = m;
+    v.px = a.obs_px + 8 * b;
+    v.tag = a.obs_tag + b;
+    v.corners = a.corners;
+    for (int d = tid; d < m; d += kLocThreads)
+        flags[d] = 0;
+    if (STAGED) {
+        for (int i = tid; i < 8 * m; i += kLocThreads)   // coalesced read of the image's pixels, transposed store
+            s_img[(i & 7) * m + (i >> 3)] = v.px[i];
+        for (int i = tid; i < 12 * m; i += kLocThreads) {
+            const int d = i / 12, k = i - 12 * d;
+            s_img[(8 + k) * m + d] = a.corners[12 * (int64_t)v.tag[d] + k];
+        }
+        __syncthreads();
+    }
+    // ---- candidates ----
+    double best = kInf;
+    int best_c = INT_MAX;
+    for (int c = tid; c < 2 * m; c += kLocThreads) {
+        const int d = c >> 1, s = c & 1;
+        if (!(a.quad_rms[2 * (b + d) + s] < kInf))
+            continue;
+        Rigid rel, tag, cand;
+        load_rigid<true>(a.quad_qt + 14 * (b + d) + 7 * s, rel);
+        load_rigid<true>(a.tag_qt + 7 * (int64_t)v.tag[d], tag);
+        chain_camera(rel, tag, cand);
+        const double sc = score_image<STAGED>(K, v, cand, a.cap2);
+        if (sc < best) {   // NaN and +inf lose; within a thread c ascends, so ties keep the lowest
+            best = sc;
+            best_c = c;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double os = __shfl_xor(best, s, 64);
+        const int oc = __shfl_xor(best_c, s, 64);
+        if (os < best || (os == best && oc < best_c)) {
+            best = os;
+            best_c = oc;
+        }
+    }
+    if (lane == 0) {
+        s_best[wave] = best;
+        s_c[wave] = best_c;
+    }
+    __syncthreads();
+    best = s_best[0];
+    best_c = s_c[0];
+#pragma unroll
+    for (int w = 1; w < kLocWaves; ++w)
+        if (s_best[w] < best || (s_best[w] == best && s_c[w] < best_c)) {
+            best = s_best[w];
+            best_c = s_c[w];
+        }
+    if (!(best < kInf)) {
+        if (tid == 0)
+            store_failure(a, p, m, VMM_BA_LOC_NO_CANDIDATE, 0);
+        return;
+    }
+    double q[7];
+    {
+        const int d = best_c >> 1, s = best_c & 1;
+        Rigid rel, tag, win;
+        load_rigid<true>(a.quad_qt + 14 * (b + d) + 7 * s, rel);
+        load_rigid<true>(a.tag_qt + 7 * (int64_t)v.tag[d], tag);
+        chain_camera(rel, tag, win);
+        quat_from_R(win.R, q);
+        q[4] = win.t[0];
+        q[5] = win.t[1];
+        q[6] = win.t[2];
+    }
+    // ---- classify -> refine on the inliers ----
+    const bool robust = a.robustify != 0;
+    int trials = 0;
+    if (a.passes == 0)
+        trials += refine_image<STAGED>(K, v, q, nullptr, robust, a.huber_a, a.max_trials, s_red);
+    for (int pass = 0; pass < a.passes; ++pass) {
+        const int n_in = classify_image<STAGED>(K, v, q, a.inlier2, flags, s_cnt);
+        if (n_in < a.min_inliers)
+            break;
+        trials += refine_image<STAGED>(K, v, q, flags, robust, a.huber_a, a.max_trials, s_red);
+    }
+    // ---- the result: flags, covariance and statistics at the returned pose ----
+    const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    bool ok = finite_bits(qn);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        if (k < 4)
+            q[k] *= qn;
+        ok = ok && finite_bits(q[k]);
+    }
+    if (!ok) {   // cannot happen with finite inputs; keeps the no-NaN promise for any input
+        for (int d = tid; d < m; d += kLocThreads)
+            flags[d] = 0;
+        if (tid == 0)
+            store_failure(a, p, m, VMM_BA_LOC_NO_CANDIDATE, trials);
+        return;
+    }
+    vmm_ba_localize_result res;
+    res.status = VMM_BA_LOC_OK;
+    res.n_obs = m;
+    res.trials = trials;
+    res.rms_px = 0.0;
+    res.cost = 0.0;
+    res.n_inlier_obs = classify_image<STAGED>(K, v, q, a.inlier2, flags, s_cnt);
+    double C[21];
+    bool have_cov = false;
+    if (res.n_inlier_obs > 0) {
+        double A[21], g[6], raw2;
+        const double cost = image_sums<STAGED, true>(K, v, q, flags, robust, a.huber_a, s_red, A, g, raw2);
+        res.cost = 0.5 * cost;
+        res.rms_px = sqrt(raw2 / (4.0 * res.n_inlier_obs));
+        if (res.n_inlier_obs >= a.min_inliers) {
+            have_cov = inverse6(A, C);
+            if (!have_cov)
+                res.status = VMM_BA_LOC_SINGULAR;
+        }
+    }
+    if (res.n_inlier_obs < a.min_inliers)
+        res.status = VMM_BA_LOC_TOO_FEW_INLIERS;
+    if (tid == 0)
+        store_result(a, p, q, C, have_cov, res);
+}
+
+} // namespace
+
+void launch_map_corners(hipStream_t st, int n_tags, const double* tag_qt, const double* tag_wh, double* corners)
+{
+    if (n_tags <= 0)
+        return;
+    hipLaunchKernelGGL(k_map_corners, dim3((unsigned)((n_tags + 255) / 256)), dim3(256), 0, st, n_tags, tag_qt, tag_wh, corners);
+}
+
+int localize_stage_capacity() { return kStage; }
+
+// any_staged / any_unstaged: whether the batch holds an image of at most / more than localize_stage_capacity()
+// observations; every workgroup of a launch whose kind its image is not leaves at once
+void launch_localize(hipStream_t st, const LocalizeArgs& a, bool any_staged, bool any_unstaged)
+{
+    if (a.n_imgs <= 0)
+        return;
+    if (any_staged)
+        hipLaunchKernelGGL(k_localize<true>, dim3((unsigned)a.n_imgs), dim3(kLocThreads), 0, st, a);
+    if (any_unstaged)
+        hipLaunchKernelGGL(k_localize<false>, dim3((unsigned)a.n_imgs), dim3(kLocThreads), 0, st, a);
+}
+
+int preload_localize_kernels()
+{
+    hipFuncAttributes at;
+    int bad = 0;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_map_corners)) != hipSuccess;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_localize<true>)) != hipSuccess;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_localize<false>)) != hipSuccess;
+    return bad;
+}
+
+} // namespace vmm

@@ -153,6 +153,7 @@ class TagReconstructor:
         self.lastSummary = None                                # summary of the last doBundleAdjustment
         self.lastCovariances = None                            # tag id -> 3x3 (last printSummary call)
         self.lastInitReport = None                             # report of vmm_ba_initialize (startReconstructionGlobal)
+        self.lastLocalizationReport = None                     # image id -> report (computeRelativeCameraPosesFromImgs)
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
         self._obs_cache = None                                 # observation list as arrays (see _obs_arrays)
         self._resident = False                                 # device-resident packing (startReconstruction)
@@ -372,6 +373,47 @@ class TagReconstructor:
             return None
         R, t = _pnp.solvePnPRansac(np.asarray(X), np.asarray(px), intr, dist, seed=int(imageId) & 0x7FFFFFFF)
         return _pnp.quat_from_R(R), t
+
+    def computeRelativeCameraPosesFromImgs(self, imageIds=None, detectionResult=None, **options):
+        """Batch form of computeRelativeCameraPoseFromImg on the device (vmm_ba_localize): every image of
+        `detectionResult` (default: the reconstructor's own; `imageIds` restricts it) is localised against the
+        reconstructed tags.  Observations of tags that are not reconstructed are dropped.  options: the fields of
+        vmm_ba_localize_options.  Returns {imageId: Camera} for the images with status OK; lastLocalizationReport holds
+        per image id the status, counts, rms_px, cost, the pose, the 6x6 covariance and the inlier flag of each used
+        observation (index into detectionResult.tagObservations)."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        if imageIds is None:
+            ids = sorted({int(im.imageId) for im in det.images} | {int(ob.imageId) for ob in det.tagObservations})
+        else:
+            ids = [int(i) for i in imageIds]
+        tag_ids = sorted(self.reconstructedTags)
+        dense = {t: k for k, t in enumerate(tag_ids)}
+        tag_qt = np.array([np.concatenate([self.reconstructedTags[t].q, self.reconstructedTags[t].t]) for t in tag_ids],
+                          np.float64).reshape(-1, 7)
+        tag_wh = np.array([[self.reconstructedTags[t].tagWidth, self.reconstructedTags[t].tagHeight] for t in tag_ids],
+                          np.float64).reshape(-1, 2)
+        per_img = {i: [] for i in ids}
+        for k, ob in enumerate(det.tagObservations):
+            if ob.imageId in per_img and ob.tagId in dense:
+                per_img[ob.imageId].append(k)
+        order = [k for i in ids for k in per_img[i]]
+        img_start = np.zeros(len(ids) + 1, np.int64)
+        img_start[1:] = np.cumsum([len(per_img[i]) for i in ids])
+        obs_tag = np.array([dense[det.tagObservations[k].tagId] for k in order], np.int32)
+        obs_px = (np.stack([np.asarray(det.tagObservations[k].corners, np.float64).reshape(8) for k in order])
+                  if order else np.zeros((0, 8)))
+        m = self.camModel
+        cam_qt, cam_cov, inl, res = _engine.localize([m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, tag_qt, tag_wh,
+                                                     img_start, obs_tag, obs_px, device=self.device, **options)
+        cams, report = {}, {}
+        for n, i in enumerate(ids):
+            b, e = int(img_start[n]), int(img_start[n + 1])
+            report[i] = dict(res[n], pose=cam_qt[n].copy(), covariance=cam_cov[n].copy(),
+                             observations=list(order[b:e]), inliers=inl[b:e].copy())
+            if res[n]["status"] == _engine._lib.LOC_OK:
+                cams[i] = Camera(i, cam_qt[n, :4], cam_qt[n, 4:])
+        self.lastLocalizationReport = report
+        return cams
 
     def moveTagIntoOrigin(self, tagId):
         """src/TagReconstructor.cpp:314-338 (applies the same map to tags AND cameras, as the reference does)."""

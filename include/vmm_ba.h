@@ -267,6 +267,26 @@ int vmm_ba_enable_rccl(vmm_ba_handle h, const void* id128);
  * switched-off observations must still be finite numbers (they are evaluated and weighted 0). */
 int vmm_ba_set_observation_mask(vmm_ba_handle h, const uint8_t* mask);
 
+/* ABI 6, additive.  cam_const[n_cams], tag_const[n_tags]: non-zero = hold that pose constant
+ * (ceres::Problem::SetParameterBlockConstant, as src/TagReconstructor.cpp:669-673 does for the origin tag).  NULL = no
+ * pose of that family.  Replaces any earlier set; the problem's fixed_tag stays constant regardless.  Callable between
+ * solves like vmm_ba_set_observation_mask, and orthogonal to it.
+ *   - The observations of a constant pose still add their residuals to the cost, and to the OTHER pose's J^T J and J^T r.
+ *   - The constant pose's own columns are zero: its H block, its gradient, and W of every observation touching it.
+ *   - An observation between two constant poses adds to the cost and the statistics only.
+ *   - vmm_ba_solve never moves a constant pose: with H = 0 it is outside the reduced program exactly like the origin
+ *     tag (unit diagonal, zero step); vmm_ba_get_state returns its bits unchanged.
+ *   - VMM_BA_LANDMARK_POINTS handles: a constant tag fixes both of its pair blocks (its four corners,
+ *     src/TagReconstructor.cpp:494-497); vmm_ba_get_points returns them unchanged.
+ *   - world_size > 1: every rank passes the same arrays.  The flag is local to the evaluation and adds no collective.
+ *   - vmm_ba_eval_blocks reports the zeros described above.
+ *   - vmm_ba_tag_translation_covariance returns zeros for constant tags, as it does for the origin; the other tags'
+ *     blocks are the covariance conditional on the constants.
+ *   - vmm_ba_initialize grows the map from every constant pose (see there).
+ *   - VMM_BA_ELIM_AUTO was decided at create and does not change; a constant pose keeps its (unit-diagonal) rows.
+ * VMM_BA_ERR_ARGUMENT for a null handle; nothing else can be invalid. */
+int vmm_ba_set_constant_poses(vmm_ba_handle h, const uint8_t* cam_const, const uint8_t* tag_const);
+
 /* Replaces ceres::Solve at src/TagReconstructor.cpp:737-738. */
 int vmm_ba_solve(vmm_ba_handle h, const vmm_ba_options* opt, vmm_ba_summary* summary);
 
@@ -319,15 +339,17 @@ typedef struct vmm_ba_init_report {
     double time_s;                 /* host wall time of the call */
 } vmm_ba_init_report;
 void vmm_ba_default_init_options(vmm_ba_init_options* o);
-/* Overwrites the device state of every pose reachable from the fixed (origin) tag, whose current pose is kept:
- * planar poses of all active observations; then rounds -- every camera with an active observation of a placed tag,
+/* Overwrites the device state of every pose reachable from the constant poses: the fixed (origin) tag and whatever
+ * vmm_ba_set_constant_poses names, cameras included.  The constant poses keep their current values.  They count as
+ * placed from round 0, are never overwritten, are skipped by the sweeps and are reported reached.
+ * The steps: planar poses of all active observations; then rounds -- every camera with an active observation of a placed tag,
  * then every tag with >= min_tag_observations active observations that a placed camera sees: among the candidates
  * (two per such observation, chained through the placed pose) the one with the lowest truncated squared reprojection
  * error over all the pose's corners on placed counterparts, refined on its own -- until a round places nothing;
- * then `sweeps` passes that redo selection and refinement for every placed pose except the origin.
+ * then `sweeps` passes that redo selection and refinement for every placed pose except the constant ones.
  * cam_reached[n_cams] / tag_reached[n_tags] (optional) receive 0/1; unreached poses keep their state.  Results are
  * bit-identical from run to run.  VMM_BA_ERR_STATE for world_size > 1 or VMM_BA_LANDMARK_POINTS handles,
- * VMM_BA_ERR_ARGUMENT for a handle without a fixed tag. */
+ * VMM_BA_ERR_ARGUMENT for a handle with neither a fixed tag nor a constant pose. */
 int vmm_ba_initialize(vmm_ba_handle h, const vmm_ba_init_options* o, vmm_ba_init_report* r,
                       uint8_t* cam_reached, uint8_t* tag_reached);
 

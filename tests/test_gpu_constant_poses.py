@@ -1,0 +1,724 @@
+"""GPU tests of constant poses (vmm_ba_set_constant_poses) and of the map extension built on them.
+
+Yardsticks: a handle whose only constant is the problem's fixed_tag (same bits); the CPU oracle's per-observation
+residuals and Jacobians, accumulated here with the constant poses' columns zeroed (blocks, the restricted optimum, the
+covariance); exact data; and the optimum reached from the generator's perturbed truth.  Tolerances are those of the
+existing tests of the same quantities: blocks 1e-11 / 1e-10 (test_gpu_kernels.py), 1e-6 per pose between two optima
+(the form of test_gpu_init._pose_gap), 1e-6 of a block's largest entry for the covariance
+(test_gpu_solve.py).
+"""
+import contextlib
+import json
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+SCENES = {
+    "config1_20x10": (1, {}),
+    "100x60_vis0.30": (1, dict(n_cams=100, n_tags=60, visibility=0.30)),
+    "closeup_60x80": (2, dict(n_cams=60, n_tags=80, neighbors_min=6, neighbors_max=10)),
+    "config5_30x40": (5, dict(n_cams=30, n_tags=40, visibility=0.5)),
+}
+
+
+def _scene(name, **kw):
+    from visual_marker_mapping_amd.synthetic import make_scene
+    cfg, base = SCENES[name]
+    return make_scene(cfg, **dict(base, **kw))
+
+
+def _handle(eng, s, cam, tag, fixed_tag=-1, **kw):
+    return eng.BundleAdjuster(s.intr, s.dist, cam, tag, s.tag_wh, fixed_tag, s.obs_cam, s.obs_tag, s.obs_px, **kw)
+
+
+def _two_solves(eng, ba, trace_capacity=0):
+    """The two solves of test_gpu_init._two_solves."""
+    a = ba.solve(eng.default_options(robustify=1, max_num_iterations=1500), trace_capacity=trace_capacity)
+    b = ba.solve(eng.default_options(robustify=0, max_num_iterations=1500, function_tolerance=1e-14,
+                                     parameter_tolerance=1e-12), trace_capacity=trace_capacity)
+    return a, b
+
+
+def _pose_gap(a, b):
+    """test_gpu_init._pose_gap: max over the poses of |dq| (unit quaternions, sign-aligned) and |dt| / max(|t|, 1)."""
+    if len(a) == 0:
+        return 0.0, 0.0
+    qa = a[:, :4] / np.linalg.norm(a[:, :4], axis=1, keepdims=True)
+    qb = b[:, :4] / np.linalg.norm(b[:, :4], axis=1, keepdims=True)
+    sign = np.sign(np.sum(qa * qb, axis=1))[:, None]
+    dq = np.linalg.norm(qa * sign - qb, axis=1)
+    dt = np.linalg.norm(a[:, 4:] - b[:, 4:], axis=1) / np.maximum(np.linalg.norm(b[:, 4:], axis=1), 1.0)
+    return float(dq.max()), float(dt.max())
+
+
+def _flags(n, idx):
+    f = np.zeros(n, np.uint8)
+    f[list(idx)] = 1
+    return f
+
+
+def _trace_bits(out):
+    return [(t["cost"], t["trust_region_radius"], t["step_norm"], t["gradient_max_norm"], t["step_is_successful"])
+            for t in out["trace"]]
+
+
+def _oracle_blocks(O, s, cam, tag, robust, cam_const, tag_const):
+    """V, U, W, g, cost from the oracle's per-observation residuals and Jacobians, evaluated WITHOUT any fixed tag
+    (as test_gpu_kernels._blocks_from_oracle with fixed_tag = -1); the rows of the constant poses are zeroed here."""
+    n_c, n_t = len(cam), len(tag)
+    V, U = np.zeros((n_c, 6, 6)), np.zeros((n_t, 6, 6))
+    W = np.zeros((len(s.obs_cam), 6, 6))
+    gc, gt = np.zeros((n_c, 6)), np.zeros((n_t, 6))
+    cost = 0.0
+    for i, (c, t) in enumerate(zip(s.obs_cam, s.obs_tag)):
+        r, Jc, Jt = O.obs_eval(s.intr, s.dist, cam[c], tag[t], s.tag_wh[t], s.obs_px[i])
+        for k in range(4):
+            sq = r[2 * k] ** 2 + r[2 * k + 1] ** 2
+            rho = O.huber(1.0, sq) if robust else np.array([sq, 1.0, 0.0])
+            cost += 0.5 * rho[0]
+            w = np.sqrt(rho[1])
+            Jc[2 * k:2 * k + 2] *= w
+            Jt[2 * k:2 * k + 2] *= w
+            r[2 * k:2 * k + 2] *= w
+        V[c] += Jc.T @ Jc
+        U[t] += Jt.T @ Jt
+        W[i] = Jc.T @ Jt
+        gc[c] += Jc.T @ r
+        gt[t] += Jt.T @ r
+    cc, tc = np.asarray(cam_const, bool), np.asarray(tag_const, bool)
+    V[cc] = 0.0
+    gc[cc] = 0.0
+    U[tc] = 0.0
+    gt[tc] = 0.0
+    W[cc[s.obs_cam] | tc[s.obs_tag]] = 0.0
+    return dict(V=V, U=U, W=W, g_cam=gc, g_tag=gt, cost=cost)
+
+
+def _free_system(s, blk, cam_const, tag_const):
+    """Dense H and g over the free poses (cameras first, then tags) from the blocks; index of every free pose."""
+    fc = np.flatnonzero(~np.asarray(cam_const, bool))
+    ft = np.flatnonzero(~np.asarray(tag_const, bool))
+    pos_c = {int(c): k for k, c in enumerate(fc)}
+    pos_t = {int(t): len(fc) + k for k, t in enumerate(ft)}
+    n = 6 * (len(fc) + len(ft))
+    H, g = np.zeros((n, n)), np.zeros(n)
+    for c, k in pos_c.items():
+        H[6 * k:6 * k + 6, 6 * k:6 * k + 6] = blk["V"][c]
+        g[6 * k:6 * k + 6] = blk["g_cam"][c]
+    for t, k in pos_t.items():
+        H[6 * k:6 * k + 6, 6 * k:6 * k + 6] = blk["U"][t]
+        g[6 * k:6 * k + 6] = blk["g_tag"][t]
+    for i, (c, t) in enumerate(zip(s.obs_cam.tolist(), s.obs_tag.tolist())):
+        if c in pos_c and t in pos_t:
+            a, b = pos_c[c], pos_t[t]
+            H[6 * a:6 * a + 6, 6 * b:6 * b + 6] += blk["W"][i]
+            H[6 * b:6 * b + 6, 6 * a:6 * a + 6] += blk["W"][i].T
+    return H, g, fc, ft
+
+
+def _const_sets(s, n_tag_const, n_cam_const):
+    """Constant flags that contain observation 0's camera and tag: one observation between two constant poses."""
+    tags = [int(s.obs_tag[0])] + [t for t in range(len(s.tag_gt)) if t != s.obs_tag[0]][:n_tag_const - 1]
+    cams = ([int(s.obs_cam[0])] + [c for c in range(len(s.cam_gt)) if c != s.obs_cam[0]][:n_cam_const - 1]
+            if n_cam_const else [])
+    return _flags(len(s.cam_gt), cams), _flags(len(s.tag_gt), tags)
+
+
+# ---- 1. the same bits as fixed_tag ----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("robust", [1, 0])
+@pytest.mark.parametrize("schur", ["dense", "sparse"])
+@pytest.mark.parametrize("name", ["config1_20x10", "100x60_vis0.30"])
+def test_constant_tag_zero_gives_the_bits_of_fixed_tag_zero(monkeypatch, name, schur, robust):
+    from visual_marker_mapping_amd import engine as eng
+    monkeypatch.setenv("VMM_BA_SCHUR", schur)
+    s = _scene(name)
+    res = []
+    for fixed in (0, -1):
+        with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=fixed) as ba:
+            if fixed < 0:
+                ba.set_constant_poses(None, _flags(len(s.tag_gt), [0]))
+            out = ba.solve(eng.default_options(robustify=robust), trace_capacity=256)
+            res.append((out, ba.get_state()))
+    (a, (cam_a, tag_a)), (b, (cam_b, tag_b)) = res
+    assert a["block_sparse"] == b["block_sparse"] == (1 if schur == "sparse" else 0)
+    assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE
+    assert a["iterations"] == b["iterations"] and len(a["trace"]) == min(a["iterations"], 256) > 1
+    assert _trace_bits(a) == _trace_bits(b)
+    assert cam_a.tobytes() == cam_b.tobytes() and tag_a.tobytes() == tag_b.tobytes()
+    assert tag_b[0].tobytes() == np.ascontiguousarray(s.tag_init[0]).tobytes()
+
+
+def test_clearing_the_constants_gives_the_bits_of_a_fresh_handle():
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene("config1_20x10")
+    cam_const, tag_const = _const_sets(s, 3, 2)
+    opts = lambda: eng.default_options(robustify=1)
+    with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=0) as ba:
+        ba.set_constant_poses(cam_const, tag_const)
+        ba.set_observation_mask(np.arange(s.n_obs) % 5 != 0)
+        first = ba.solve(opts(), trace_capacity=256)
+        ba.set_constant_poses(None, None)
+        ba.set_observation_mask(None)
+        ba.set_state(s.cam_init, s.tag_init)
+        again = ba.solve(opts(), trace_capacity=256)
+        state = ba.get_state()
+    with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=0) as ba:
+        fresh = ba.solve(opts(), trace_capacity=256)
+        fresh_state = ba.get_state()
+    assert first["termination_type"] == again["termination_type"] == eng.CONVERGENCE
+    assert _trace_bits(again) == _trace_bits(fresh) and _trace_bits(first) != _trace_bits(fresh)
+    assert state[0].tobytes() == fresh_state[0].tobytes() and state[1].tobytes() == fresh_state[1].tobytes()
+
+
+# ---- 2. blocks against the oracle -----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("robust", [False, True])
+@pytest.mark.parametrize("elim", ["cams", "tags"])
+@pytest.mark.parametrize("name,n_tag_const,n_cam_const", [("config1_20x10", 3, 2), ("100x60_vis0.30", 20, 0)])
+def test_blocks_with_constant_poses_match_oracle(oracle, name, n_tag_const, n_cam_const, elim, robust):
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene(name)
+    cam_const, tag_const = _const_sets(s, n_tag_const, n_cam_const)
+    if n_cam_const:
+        assert cam_const[s.obs_cam[0]] and tag_const[s.obs_tag[0]]   # an observation between two constant poses
+    mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
+    with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=-1, elimination=mode) as ba:
+        ba.set_constant_poses(cam_const if n_cam_const else None, tag_const)
+        got = ba.eval_blocks(robustify=robust)
+        cost = ba.cost(robustify=robust)
+    ref = _oracle_blocks(oracle, s, s.cam_init, s.tag_init, robust, cam_const, tag_const)
+    print("%s elim %s robust %d: cost gpu %.15g oracle %.15g" % (name, elim, robust, got["cost"], ref["cost"]))
+    assert abs(got["cost"] - ref["cost"]) <= 1e-11 * ref["cost"]
+    assert abs(cost - ref["cost"]) <= 1e-11 * ref["cost"]
+    for k in ("V", "U", "W", "g_cam", "g_tag"):
+        print("   %s: max |gpu - oracle| %.3g of %.3g" % (k, np.abs(got[k] - ref[k]).max(), np.abs(ref[k]).max()))
+        np.testing.assert_allclose(got[k], ref[k], rtol=0, atol=1e-10 * np.abs(ref[k]).max(), err_msg=k)
+    # the zeros are zeros, not small numbers
+    assert not got["U"][tag_const.astype(bool)].any() and not got["g_tag"][tag_const.astype(bool)].any()
+    assert not got["V"][cam_const.astype(bool)].any() and not got["g_cam"][cam_const.astype(bool)].any()
+    touched = cam_const.astype(bool)[s.obs_cam] | tag_const.astype(bool)[s.obs_tag]
+    assert not got["W"][touched].any() and got["W"][~touched].any()
+
+
+def test_point_blocks_with_constant_poses_match_oracle(oracle):
+    """VMM_BA_LANDMARK_POINTS: cost, V and g_cam are what the handle reports in the caller's index space.  A constant
+    camera's rows are zero; a constant tag leaves the cameras' blocks as they are (its observations still count)."""
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene("config1_20x10")
+    cam_const, tag_const = _const_sets(s, 3, 2)
+    sc, pts = oracle.point_scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, -1, s.obs_cam, s.obs_tag, s.obs_px)
+    with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=-1, landmarks=eng.LANDMARK_POINTS) as ba:
+        ba.set_constant_poses(cam_const, tag_const)
+        blk = ba.eval_blocks(robustify=False, want_W=False)
+    V, g = np.zeros((len(s.cam_init), 6, 6)), np.zeros((len(s.cam_init), 6))
+    ref_cost = 0.0
+    for c, t, px in zip(s.obs_cam, s.obs_tag, s.obs_px):
+        for k in range(4):
+            r, Jc, _ = oracle.point_eval(s.intr, s.dist, s.cam_init[c], pts[t, k], px[2 * k:2 * k + 2])
+            V[c] += Jc.T @ Jc
+            g[c] += Jc.T @ r
+            ref_cost += 0.5 * (r @ r)
+    V[cam_const.astype(bool)] = 0.0
+    g[cam_const.astype(bool)] = 0.0
+    assert abs(blk["cost"] - ref_cost) <= 1e-11 * ref_cost
+    np.testing.assert_allclose(blk["V"], V, rtol=0, atol=1e-10 * np.abs(V).max())
+    np.testing.assert_allclose(blk["g_cam"], g, rtol=0, atol=1e-10 * np.abs(g).max())
+    assert not blk["V"][cam_const.astype(bool)].any() and not blk["g_cam"][cam_const.astype(bool)].any()
+
+
+# ---- 3. constant means constant -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("elim", ["cams", "tags"])
+def test_solves_never_move_a_constant_pose(elim):
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene("config1_20x10")
+    cam_const, tag_const = _const_sets(s, 3, 2)
+    cc, tc = cam_const.astype(bool), tag_const.astype(bool)
+    mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
+    cam0, tag0 = np.ascontiguousarray(s.cam_init), np.ascontiguousarray(s.tag_init)
+    with _handle(eng, s, cam0, tag0, fixed_tag=-1, elimination=mode) as ba:
+        ba.set_constant_poses(cam_const, tag_const)
+        for robust in (1, 0):
+            out = ba.solve(eng.default_options(robustify=robust))
+            assert out["termination_type"] == eng.CONVERGENCE, out
+            cam, tag = ba.get_state()
+            assert cam[cc].tobytes() == cam0[cc].tobytes() and tag[tc].tobytes() == tag0[tc].tobytes()
+            assert not np.array_equal(cam[~cc], cam0[~cc]) and not np.array_equal(tag[~tc], tag0[~tc])
+    # point landmarks: a constant tag's four corners stay; get_state rebuilds tag poses from the corners (it is not the
+    # inverse of set_state on such a handle, include/vmm_ba.h), so the tag poses are compared with get_state before
+    with _handle(eng, s, cam0, tag0, fixed_tag=-1, elimination=mode, landmarks=eng.LANDMARK_POINTS) as ba:
+        ba.set_constant_poses(cam_const, tag_const)
+        _, tag_before = ba.get_state()
+        pts_before = ba.get_points()
+        out = ba.solve(eng.default_options(robustify=0))
+        assert out["termination_type"] == eng.CONVERGENCE, out
+        cam, tag = ba.get_state()
+        pts = ba.get_points()
+    assert cam[cc].tobytes() == cam0[cc].tobytes()
+    assert pts[tc].tobytes() == pts_before[tc].tobytes() and tag[tc].tobytes() == tag_before[tc].tobytes()
+    assert not np.array_equal(pts[~tc], pts_before[~tc]) and not np.array_equal(cam[~cc], cam0[~cc])
+
+
+# ---- 4. the optimum of the restricted problem -----------------------------------------------------------------------
+
+def _gauss_newton(O, s, cam, tag, cam_const, tag_const, max_iter=25):
+    """Undamped dense Gauss-Newton on the plain cost over the free poses, from (cam, tag), until |step|_inf < 1e-12."""
+    cam, tag = cam.copy(), tag.copy()
+    step = np.inf
+    for it in range(max_iter):
+        blk = _oracle_blocks(O, s, cam, tag, False, cam_const, tag_const)
+        H, g, fc, ft = _free_system(s, blk, cam_const, tag_const)
+        d = np.linalg.solve(H, -g)
+        step = float(np.abs(d).max())
+        for k, c in enumerate(fc):
+            cam[c] = O.pose_plus(cam[c], d[6 * k:6 * k + 6])
+        for k, t in enumerate(ft):
+            tag[t] = O.pose_plus(tag[t], d[6 * (len(fc) + k):6 * (len(fc) + k) + 6])
+        if step < 1e-12:
+            break
+    return cam, tag, step, it + 1
+
+
+def _gradient_max_norm(O, blk, cam, tag, cam_const, tag_const):
+    """Ceres' gradient max-norm |Plus(x, -g) - x|_inf over the free poses."""
+    gm = 0.0
+    for x, g, const in ((cam, blk["g_cam"], cam_const), (tag, blk["g_tag"], tag_const)):
+        for p in np.flatnonzero(~np.asarray(const, bool)):
+            gm = max(gm, float(np.abs(O.pose_plus(x[p], -g[p]) - x[p]).max()))
+    return gm
+
+
+def _restricted_optimum_case(name, n_tag_const, n_cam_const):
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene(name)
+    cam_const, tag_const = _const_sets(s, n_tag_const, n_cam_const)
+    with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=-1) as ba:
+        ba.set_constant_poses(cam_const if n_cam_const else None, tag_const)
+        rob, plain = _two_solves(eng, ba, trace_capacity=2048)
+        cam, tag = ba.get_state()
+        cov = ba.tag_translation_covariance(robustify=False)
+    return eng, s, cam_const, tag_const, rob, plain, cam, tag, cov
+
+
+@pytest.mark.parametrize("name,n_tag_const,n_cam_const", [("config1_20x10", 3, 2), ("100x60_vis0.30", 20, 0)])
+def test_solve_reaches_the_optimum_of_the_restricted_problem(oracle, name, n_tag_const, n_cam_const):
+    eng, s, cam_const, tag_const, rob, plain, cam, tag, _ = _restricted_optimum_case(name, n_tag_const, n_cam_const)
+    assert rob["termination_type"] == plain["termination_type"] == eng.CONVERGENCE
+    ref_cam, ref_tag, step, iters = _gauss_newton(oracle, s, cam, tag, cam_const, tag_const)
+    assert step < 1e-12, (step, iters)
+    gq_c, gt_c = _pose_gap(cam, ref_cam)
+    gq_t, gt_t = _pose_gap(tag, ref_tag)
+    blk = _oracle_blocks(oracle, s, cam, tag, False, cam_const, tag_const)
+    gm = _gradient_max_norm(oracle, blk, cam, tag, cam_const, tag_const)
+    gtol = eng.default_options().gradient_tolerance
+    last = plain["trace"][-1]
+    ended_on = "gradient_tolerance" if last["gradient_max_norm"] <= gtol else "function_tolerance or parameter_tolerance"
+    print("%s: Gauss-Newton from the GPU result: %d iterations, last step %.3g; max |dq| cams %.3g tags %.3g, max |dt| "
+          "cams %.3g tags %.3g; oracle gradient max-norm at the GPU result %.3g (tolerance %.3g), the solve ended on %s "
+          "(its own gradient max-norm %.3g)" % (name, iters, step, gq_c, gq_t, gt_c, gt_t, gm, gtol, ended_on,
+                                                  last["gradient_max_norm"]))
+    assert max(gq_c, gq_t) <= 1e-6 and max(gt_c, gt_t) <= 1e-6, (gq_c, gq_t, gt_c, gt_t)
+    assert gm < gtol or last["gradient_max_norm"] > gtol, (gm, last)
+    # the constants are where they were put
+    cc, tc = cam_const.astype(bool), tag_const.astype(bool)
+    assert cam[cc].tobytes() == np.ascontiguousarray(s.cam_init)[cc].tobytes()
+    assert tag[tc].tobytes() == np.ascontiguousarray(s.tag_init)[tc].tobytes()
+
+
+# ---- 7. covariance --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,n_tag_const,n_cam_const", [("config1_20x10", 3, 2), ("100x60_vis0.30", 20, 0)])
+def test_covariance_is_conditional_on_the_constants(oracle, name, n_tag_const, n_cam_const):
+    eng, s, cam_const, tag_const, _, _, cam, tag, cov = _restricted_optimum_case(name, n_tag_const, n_cam_const)
+    blk = _oracle_blocks(oracle, s, cam, tag, False, cam_const, tag_const)
+    H, _, fc, ft = _free_system(s, blk, cam_const, tag_const)
+    Hinv = np.linalg.inv(H)
+    for t in np.flatnonzero(tag_const):
+        assert np.all(cov[t] == 0.0), t
+    worst = 0.0
+    for k, t in enumerate(ft):
+        o = 6 * (len(fc) + k)
+        ref = Hinv[o:o + 3, o:o + 3]
+        scale = np.abs(ref).max()
+        assert scale > 0
+        worst = max(worst, np.abs(cov[t] - ref).max() / scale)
+        np.testing.assert_allclose(cov[t], ref, rtol=0, atol=1e-6 * scale)
+    print("%s: covariance of %d free tags, worst |gpu - numpy| / max|block| %.3g" % (name, len(ft), worst))
+
+
+# ---- 5. / 6. extension at the handle level --------------------------------------------------------------------------
+
+class _Split:
+    """Tags [0, n_tags / 2) are the map at ground truth; the new images are the cameras that see a map tag."""
+
+    def __init__(self, s):
+        from visual_marker_mapping_amd.synthetic import SyntheticScene
+        n_t = len(s.tag_gt)
+        self.map_tags = np.arange(n_t) < n_t // 2
+        self.new_images = np.unique(s.obs_cam[self.map_tags[s.obs_tag]])
+        keep = np.isin(s.obs_cam, self.new_images)
+        self.sub = SyntheticScene(intr=s.intr, dist=s.dist, cam_gt=s.cam_gt[self.new_images],
+                                  cam_init=s.cam_init[self.new_images], tag_gt=s.tag_gt, tag_init=s.tag_init,
+                                  tag_wh=s.tag_wh, fixed_tag=-1,
+                                  obs_cam=np.searchsorted(self.new_images, s.obs_cam[keep]).astype(np.int32),
+                                  obs_tag=s.obs_tag[keep].copy(), obs_px=s.obs_px[keep].copy())
+        self.tag_const = self.map_tags.astype(np.uint8)
+
+    def placeholders(self):
+        """test_gpu_init._placeholders for everything that is not the map."""
+        s = self.sub
+        cam = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 1.0]), (len(s.cam_gt), 1))
+        tag = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0.0]), (len(s.tag_gt), 1))
+        tag[self.map_tags] = s.tag_gt[self.map_tags]
+        return cam, tag
+
+    def reach(self, min_tag_observations=2):
+        """Breadth-first search with the rules of vmm_ba_initialize: a camera needs one active observation of a placed
+        tag; a tag needs min_tag_observations active observations and one of them from a placed camera."""
+        s = self.sub
+        cam_ok, tag_ok = np.zeros(len(s.cam_gt), bool), self.map_tags.copy()
+        n_obs_tag = np.bincount(s.obs_tag, minlength=len(s.tag_gt))
+        while True:
+            before = cam_ok.sum() + tag_ok.sum()
+            cam_ok[np.unique(s.obs_cam[tag_ok[s.obs_tag]])] = True
+            seen = np.zeros(len(s.tag_gt), bool)
+            seen[np.unique(s.obs_tag[cam_ok[s.obs_cam]])] = True
+            tag_ok |= seen & (n_obs_tag >= min_tag_observations)
+            if cam_ok.sum() + tag_ok.sum() == before:
+                return cam_ok, tag_ok
+
+
+@contextlib.contextmanager
+def _extend(eng, sp, cam0, tag0, initialize):
+    """A handle over the new images with the map tags constant, initialised from them when asked."""
+    s = sp.sub
+    with _handle(eng, s, cam0, tag0, fixed_tag=-1) as ba:
+        ba.set_constant_poses(None, sp.tag_const)
+        report, cam_ok, tag_ok = ba.initialize() if initialize else (None, None, None)
+        yield ba, report, cam_ok, tag_ok
+
+
+@pytest.mark.parametrize("name", ["closeup_60x80", "100x60_vis0.30"])
+def test_extension_on_exact_data(name):
+    from visual_marker_mapping_amd import engine as eng
+    sp = _Split(_scene(name, noise_px=0.0))
+    s = sp.sub
+    cam0, tag0 = sp.placeholders()
+    want_cam, want_tag = sp.reach()
+    runs = []
+    for _ in range(2):
+        with _extend(eng, sp, cam0, tag0, True) as (ba, report, cam_ok, tag_ok):
+            # the reached sets are the problem (as in the driver): an unreached pose keeps its placeholder
+            ba.set_observation_mask(cam_ok[s.obs_cam] & tag_ok[s.obs_tag])
+            a, b = _two_solves(eng, ba)
+            runs.append((report, cam_ok, tag_ok, a, b) + ba.get_state())
+    report, cam_ok, tag_ok, a, b, cam, tag = runs[0]
+    print("%s exact: %d new images, %d map tags, %d new tags; reached %d cameras %d tags (search: %d, %d) in %d rounds, "
+          "average reprojection after initialize %.3g px" % (name, len(s.cam_gt), sp.map_tags.sum(), (~sp.map_tags).sum(),
+                                                              cam_ok.sum(), tag_ok.sum(), want_cam.sum(), want_tag.sum(),
+                                                              report["rounds"], report["avg_reprojection_px"]))
+    assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE
+    assert np.array_equal(cam_ok, want_cam) and np.array_equal(tag_ok, want_tag)
+    assert report["cams_reached"] == want_cam.sum() and report["tags_reached"] == want_tag.sum()
+    assert tag_ok[sp.map_tags].all() and cam_ok.any() and tag_ok[~sp.map_tags].any()
+    new_tags = tag_ok & ~sp.map_tags
+    gq_c, gt_c = _pose_gap(cam[cam_ok], s.cam_gt[cam_ok])
+    gq_t, gt_t = _pose_gap(tag[new_tags], s.tag_gt[new_tags])
+    print("   max |dq| cams %.3g new tags %.3g, max |dt| cams %.3g new tags %.3g" % (gq_c, gq_t, gt_c, gt_t))
+    assert max(gq_c, gq_t) <= 1e-6 and max(gt_c, gt_t) <= 1e-6
+    assert tag[sp.map_tags].tobytes() == np.ascontiguousarray(s.tag_gt[sp.map_tags]).tobytes()
+    assert tag[~tag_ok].tobytes() == tag0[~tag_ok].tobytes() and cam[~cam_ok].tobytes() == cam0[~cam_ok].tobytes()
+    assert cam.tobytes() == runs[1][5].tobytes() and tag.tobytes() == runs[1][6].tobytes()
+    assert np.array_equal(cam_ok, runs[1][1]) and np.array_equal(tag_ok, runs[1][2])
+
+
+@pytest.mark.parametrize("name", ["100x60_vis0.30", "config5_30x40"])
+def test_extension_under_noise_reaches_the_optimum_of_a_good_start(name):
+    from visual_marker_mapping_amd import engine as eng
+    sp = _Split(_scene(name))
+    s = sp.sub
+    cam0, tag0 = sp.placeholders()
+    good_tag = s.tag_init.copy()
+    good_tag[sp.map_tags] = s.tag_gt[sp.map_tags]
+    res = {}
+    mask = None
+    for label, (c0, t0), init in (("A", (cam0, tag0), True), ("B", (s.cam_init, good_tag), False)):
+        with _extend(eng, sp, c0, t0, init) as (ba, report, cam_ok, tag_ok):
+            if init:
+                # poses that were not reached keep their placeholders: their observations stay out of both solves
+                mask = cam_ok[s.obs_cam] & tag_ok[s.obs_tag]
+                res["reach"] = (report, cam_ok, tag_ok)
+            ba.set_observation_mask(mask)
+            a, b = _two_solves(eng, ba)
+            assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE, (label, a, b)
+            res[label] = ba.get_state() + (b["final_cost"],)
+    report, cam_ok, tag_ok = res["reach"]
+    gq_c, gt_c = _pose_gap(res["A"][0][cam_ok], res["B"][0][cam_ok])
+    gq_t, gt_t = _pose_gap(res["A"][1][tag_ok], res["B"][1][tag_ok])
+    print("%s: reached %d/%d cameras %d/%d tags in %d rounds; max |dq| cams %.3g tags %.3g, max |dt| cams %.3g tags "
+          "%.3g; final cost A %.12g B %.12g" % (name, cam_ok.sum(), len(cam_ok), tag_ok.sum(), len(tag_ok),
+                                                report["rounds"], gq_c, gq_t, gt_c, gt_t, res["A"][2], res["B"][2]))
+    assert cam_ok.any() and tag_ok[~sp.map_tags].any()
+    assert max(gq_c, gq_t) <= 1e-6 and max(gt_c, gt_t) <= 1e-6
+    for k in "AB":
+        assert res[k][1][sp.map_tags].tobytes() == np.ascontiguousarray(s.tag_gt[sp.map_tags]).tobytes()
+
+
+# ---- 8. initialize and its seeds ------------------------------------------------------------------------------------
+
+def test_initialize_needs_a_constant_pose_and_grows_from_a_constant_camera():
+    from visual_marker_mapping_amd import _lib, engine as eng
+    s = _scene("config1_20x10", noise_px=0.0)
+    cam0 = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 1.0]), (len(s.cam_gt), 1))
+    tag0 = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0.0]), (len(s.tag_gt), 1))
+    seed = int(s.obs_cam[0])
+    cam0[seed] = s.cam_gt[seed]
+    with _handle(eng, s, cam0, tag0, fixed_tag=-1) as ba:
+        with pytest.raises(_lib.VmmBaError) as ei:
+            ba.initialize()
+        assert ei.value.status == _lib.ERR_ARGUMENT
+        ba.set_constant_poses(_flags(len(cam0), [seed]), None)
+        # a tag needs two active observations by default: with one the constant camera's tags are placed at once
+        report, cam_ok, tag_ok = ba.initialize(min_tag_observations=1)
+        cam_i, tag_i = ba.get_state()
+        ba.set_observation_mask(cam_ok[s.obs_cam] & tag_ok[s.obs_tag])
+        a, b = _two_solves(eng, ba)
+        cam, tag = ba.get_state()
+        ba.set_constant_poses(None, None)
+        with pytest.raises(_lib.VmmBaError) as ei:
+            ba.initialize()
+        assert ei.value.status == _lib.ERR_ARGUMENT
+    sees = np.unique(s.obs_tag[s.obs_cam == seed])
+    assert cam_ok[seed] and tag_ok[sees].all() and report["rounds"] >= 1
+    assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE
+    assert cam_i[seed].tobytes() == cam[seed].tobytes() == cam0[seed].tobytes()
+    assert not np.array_equal(tag_i[sees], tag0[sees])
+    gq, gt = _pose_gap(tag[sees], s.tag_gt[sees])
+    print("constant camera %d sees %d tags: placed, max |dq| %.3g |dt| %.3g; reached %d cameras %d tags"
+          % (seed, len(sees), gq, gt, cam_ok.sum(), tag_ok.sum()))
+    assert gq <= 1e-6 and gt <= 1e-6
+
+
+# ---- 9. the driver and the command line -----------------------------------------------------------------------------
+
+def _write_extension_project(tmp_path, sp, extra_map_tag=None):
+    from visual_marker_mapping_amd import io as vio, synthetic
+    from visual_marker_mapping_amd.tag_reconstructor import ReconstructedTag
+    s = sp.sub
+    proj = str(tmp_path / "project")
+    model, _ = synthetic.write_project(s, proj)
+    tags = {int(t): ReconstructedTag(int(t), "apriltag_36h11", s.tag_gt[t, :4], s.tag_gt[t, 4:], s.tag_wh[t, 0],
+                                     s.tag_wh[t, 1]) for t in np.flatnonzero(sp.map_tags)}
+    if extra_map_tag is not None:   # a map tag no new image sees
+        tags[extra_map_tag] = ReconstructedTag(extra_map_tag, "apriltag_36h11", [0.6, 0.0, 0.8, 0.0],
+                                               [12.125, -3.0000000000000004, 0.1], 0.25, 0.3)
+    vio.exportReconstructions(os.path.join(proj, "reconstruction.json"), tags, {}, model)
+    return proj
+
+
+def test_extension_command_line(tmp_path, capsys):
+    from visual_marker_mapping_amd import extension, io as vio
+    sp = _Split(_scene("closeup_60x80", noise_px=0.0))
+    s = sp.sub
+    proj = _write_extension_project(tmp_path, sp, extra_map_tag=1000)
+    assert extension.main(["--project_path", proj]) == 0
+    out = capsys.readouterr().out
+    assert out.count("Solution ") == 2 and "Starting final bundle adjustment" in out
+    with open(os.path.join(proj, "reconstruction.json")) as f:
+        before = {t["id"]: t for t in json.load(f)["reconstructed_tags"]}
+    with open(os.path.join(proj, "reconstruction_extended.json")) as f:
+        after_tree = json.load(f)
+    after = {t["id"]: t for t in after_tree["reconstructed_tags"]}
+    assert "1000" in before and len(before) == sp.map_tags.sum() + 1
+    for tid, t in before.items():   # text-identical: every scalar is a quoted string in these files
+        for k in ("rotation", "translation", "width", "height", "type"):
+            assert after[tid][k] == t[k], (tid, k)
+    want_cam, want_tag = sp.reach()
+    tags, cams, _ = vio.parseReconstructions(os.path.join(proj, "reconstruction_extended.json"))
+    new = sorted(set(tags) - {int(k) for k in before})
+    assert new == np.flatnonzero(want_tag & ~sp.map_tags).tolist() and len(new) > 0
+    got = np.array([np.r_[tags[t].q, tags[t].t] for t in new])
+    gq, gt = _pose_gap(got, s.tag_gt[new])
+    n_see = len(np.unique(s.obs_cam[sp.map_tags[s.obs_tag]]))
+    print("command line: %d map tags kept, %d new tags (max |dq| %.3g |dt| %.3g), %d cameras of %d images"
+          % (len(before), len(new), gq, gt, len(cams), len(s.cam_gt)))
+    assert gq <= 1e-6 and gt <= 1e-6
+    assert len(cams) == n_see == len(s.cam_gt)
+    assert sorted(cams) == list(range(len(s.cam_gt)))
+
+
+def test_extension_driver_keeps_the_map_and_the_report(tmp_path, capsys):
+    from visual_marker_mapping_amd import io as vio
+    from visual_marker_mapping_amd.tag_reconstructor import TagReconstructor
+    sp = _Split(_scene("100x60_vis0.30"))
+    proj = _write_extension_project(tmp_path, sp)
+    tags, _, _ = vio.parseReconstructions(os.path.join(proj, "reconstruction.json"))
+    before = {t: (v.q.tobytes(), v.t.tobytes(), v.tagWidth, v.tagHeight) for t, v in tags.items()}
+    rec = TagReconstructor(vio.readDetectionResult(os.path.join(proj, "marker_detections.json")))
+    rec.setCameraModel(vio.readCameraModel(os.path.join(proj, "camera_intrinsics.json")))
+    rec.setReconstructedTags(tags)
+    rec.extendReconstruction(1)
+    capsys.readouterr()
+    assert rec.lastInitReport["tags_reached"] >= len(before) and rec.lastInitReport["cams_reached"] > 0
+    assert rec.lastSummary["termination_type"] == 0 and rec.constantTagIds == set()
+    for t, ref in before.items():
+        v = rec.reconstructedTags[t]
+        assert (v.q.tobytes(), v.t.tobytes(), v.tagWidth, v.tagHeight) == ref, t
+    assert len(rec.reconstructedTags) > len(before) and len(rec.reconstructedCameras) > 0
+    # a detection set that shows no tag of the map
+    far = {t + 5000: v for t, v in tags.items()}
+    rec = TagReconstructor(vio.readDetectionResult(os.path.join(proj, "marker_detections.json")))
+    rec.setCameraModel(vio.readCameraModel(os.path.join(proj, "camera_intrinsics.json")))
+    rec.setReconstructedTags(far)
+    with pytest.raises(RuntimeError, match="No reconstructed tags in image found."):
+        rec.extendReconstruction(1)
+    assert sorted(rec.reconstructedTags) == sorted(far)
+
+
+# ---- the fused evaluation kernel (VMM_BA_EVAL=fused) reads the same flags -------------------------------------------
+
+@pytest.mark.parametrize("robust", [False, True])
+@pytest.mark.parametrize("elim", ["cams", "tags"])
+@pytest.mark.parametrize("precision", ["f64", "f32_accum"])
+def test_fused_blocks_with_constant_poses_match_oracle(oracle, monkeypatch, precision, elim, robust):
+    """Item 2 on k_eval_fused: 3 constant tags and 2 constant cameras on 20 x 10 (full visibility, so every pair is in
+    the kernel's table), one observation between two constant poses, both instantiations of E_IS_CAM.  f64: the
+    tolerances of item 2.  PRECISION_F32_ACCUM keeps cost and gradient in f64 (same tolerances) and accumulates
+    J^T J in f32: a block entry is a sum of at most 8 rows x 20 observations = 160 products rounded to 2^-24, so
+    160 * 6e-8 = 1e-5 of the largest entry bounds it -- the figure test_gpu_fused_eval.py uses for the f32 blocks."""
+    from visual_marker_mapping_amd import engine as eng
+    monkeypatch.setenv("VMM_BA_EVAL", "fused")
+    s = _scene("config1_20x10")
+    cam_const, tag_const = _const_sets(s, 3, 2)
+    cc, tc = cam_const.astype(bool), tag_const.astype(bool)
+    assert cc[s.obs_cam[0]] and tc[s.obs_tag[0]] and s.n_obs == len(s.cam_gt) * len(s.tag_gt)
+    mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
+    kw = dict(precision=eng.PRECISION_F32_ACCUM) if precision == "f32_accum" else {}
+    with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=-1, elimination=mode, **kw) as ba:
+        ba.set_constant_poses(cam_const, tag_const)
+        got = ba.eval_blocks(robustify=robust)
+        cost = ba.cost(robustify=robust)
+    ref = _oracle_blocks(oracle, s, s.cam_init, s.tag_init, robust, cam_const, tag_const)
+    print("fused %s elim %s robust %d: cost gpu %.15g oracle %.15g" % (precision, elim, robust, got["cost"], ref["cost"]))
+    assert abs(got["cost"] - ref["cost"]) <= 1e-11 * ref["cost"]
+    assert abs(cost - ref["cost"]) <= 1e-11 * ref["cost"]
+    for k in ("V", "U", "W", "g_cam", "g_tag"):
+        rel = 1e-5 if kw and k in ("V", "U", "W") else 1e-10
+        print("   %s: max |gpu - oracle| %.3g of %.3g" % (k, np.abs(got[k] - ref[k]).max(), np.abs(ref[k]).max()))
+        np.testing.assert_allclose(got[k], ref[k], rtol=0, atol=rel * np.abs(ref[k]).max(), err_msg=k)
+    assert not got["U"][tc].any() and not got["g_tag"][tc].any()
+    assert not got["V"][cc].any() and not got["g_cam"][cc].any()
+    touched = cc[s.obs_cam] | tc[s.obs_tag]
+    assert not got["W"][touched].any() and got["W"][~touched].any()
+    # the free poses' blocks are not zero: a swapped index would have zeroed the wrong rows
+    assert all(got["U"][t].any() for t in np.flatnonzero(~tc)) and all(got["V"][c].any() for c in np.flatnonzero(~cc))
+
+
+@pytest.mark.parametrize("landmarks", ["tags", "points"])
+@pytest.mark.parametrize("elim", ["cams", "tags"])
+def test_fused_solves_never_move_a_constant_pose(monkeypatch, elim, landmarks):
+    """Item 3 on k_eval_fused, tag poses and point landmarks; the two-pass kernel is the yardstick of where the free
+    poses end (1e-9 of the largest entry, as test_gpu_fused_eval.py compares the two kernels' solves)."""
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene("config1_20x10")
+    cam_const, tag_const = _const_sets(s, 3, 2)
+    cc, tc = cam_const.astype(bool), tag_const.astype(bool)
+    mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
+    cam0, tag0 = np.ascontiguousarray(s.cam_init), np.ascontiguousarray(s.tag_init)
+    kw = dict(landmarks=eng.LANDMARK_POINTS) if landmarks == "points" else {}
+    res = {}
+    for ev in ("twopass", "fused"):
+        monkeypatch.setenv("VMM_BA_EVAL", ev)
+        with _handle(eng, s, cam0, tag0, fixed_tag=-1, elimination=mode, **kw) as ba:
+            ba.set_constant_poses(cam_const, tag_const)
+            _, tag_before = ba.get_state()
+            pts_before = ba.get_points() if kw else None
+            outs = [ba.solve(eng.default_options(robustify=r)) for r in ((0,) if kw else (1, 0))]
+            res[ev] = (outs, ba.get_state(), ba.get_points() if kw else None, tag_before, pts_before)
+    for ev, (outs, (cam, tag), pts, tag_before, pts_before) in res.items():
+        assert all(o["termination_type"] == eng.CONVERGENCE for o in outs), (ev, outs)
+        assert cam[cc].tobytes() == cam0[cc].tobytes(), ev
+        assert tag[tc].tobytes() == tag_before[tc].tobytes(), ev     # point handles rebuild tag poses from the corners
+        assert not np.array_equal(cam[~cc], cam0[~cc]) and not np.array_equal(tag[~tc], tag_before[~tc])
+        if kw:
+            assert pts[tc].tobytes() == pts_before[tc].tobytes() and not np.array_equal(pts[~tc], pts_before[~tc])
+        else:
+            assert tag[tc].tobytes() == tag0[tc].tobytes(), ev
+    (ot, (ct, tt), pt, _, _), (of, (cf, tf), pf, _, _) = res["twopass"], res["fused"]
+    assert [o["iterations"] for o in of] == [o["iterations"] for o in ot]
+    np.testing.assert_allclose(of[-1]["final_cost"], ot[-1]["final_cost"], rtol=1e-10)
+    np.testing.assert_allclose(cf, ct, rtol=0, atol=1e-9 * np.abs(ct).max())
+    np.testing.assert_allclose(tf, tt, rtol=0, atol=1e-9 * np.abs(tt).max())
+    if kw:
+        np.testing.assert_allclose(pf, pt, rtol=0, atol=1e-9 * np.abs(pt).max())
+
+
+# ---- point landmarks: the landmark side ------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("elim", ["cams", "tags"])
+def test_point_handle_constant_tag_gives_the_bits_of_fixed_tag(elim):
+    """vmm_ba_eval_blocks hands out only the camera side of a point-landmark handle, so the landmark side of a constant
+    tag (zero U, g and W for BOTH of its pair blocks) is pinned through the solve: tag_const = {t} must walk the same
+    LM trajectory, bit for bit, as fixed_tag = t, whose two pair blocks the create path has always fixed.  A flag that
+    reached only one of the two blocks would move the other block's corners and change every iteration."""
+    from visual_marker_mapping_amd import engine as eng
+    s = _scene("config1_20x10")
+    mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
+    for t in (0, 7):
+        res = []
+        for fixed in (t, -1):
+            with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=fixed, elimination=mode,
+                         landmarks=eng.LANDMARK_POINTS) as ba:
+                if fixed < 0:
+                    ba.set_constant_poses(None, _flags(len(s.tag_gt), [t]))
+                pts0 = ba.get_points()
+                blk = ba.eval_blocks(robustify=False, want_W=False)
+                out = ba.solve(eng.default_options(robustify=0), trace_capacity=256)
+                res.append((out, blk, ba.get_state()[0], ba.get_points(), pts0))
+        (a, blk_a, cam_a, pts_a, pts0), (b, blk_b, cam_b, pts_b, _) = res
+        assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE
+        assert a["iterations"] == b["iterations"] and len(a["trace"]) > 1
+        assert _trace_bits(a) == _trace_bits(b)
+        assert all(blk_a[k].tobytes() == blk_b[k].tobytes() for k in ("V", "g_cam")) and blk_a["cost"] == blk_b["cost"]
+        assert cam_a.tobytes() == cam_b.tobytes() and pts_a.tobytes() == pts_b.tobytes()
+        assert pts_b[t].tobytes() == pts0[t].tobytes() and not np.array_equal(pts_b[t - 1], pts0[t - 1])
+
+
+def test_points_bundle_adjustment_of_the_driver_keeps_constant_tags(capsys):
+    """TagReconstructor.doBundleAdjustment_points with constantTagIds: the constant tags' corners stay on the device and
+    their q and t are not rebuilt from the corners -- they keep their bits; every other tag is rebuilt as before."""
+    from visual_marker_mapping_amd import tag_reconstructor as tr
+    s = _scene("config1_20x10")
+    tag_ids = [230 + 3 * k for k in range(len(s.tag_init))]
+    cam_ids = [1000 - 7 * k for k in range(len(s.cam_init))]
+    det = tr.DetectionResult(
+        [tr.TagImg(cid, "i%d.jpg" % cid) for cid in cam_ids],
+        [tr.Tag(tid, "apriltag_36h11", *s.tag_wh[k]) for k, tid in enumerate(tag_ids)],
+        [tr.TagObservation(cam_ids[c], tag_ids[t], px.reshape(4, 2)) for c, t, px in zip(s.obs_cam, s.obs_tag, s.obs_px)])
+    rec = tr.TagReconstructor(det)
+    rec.setCameraModel(tr.CameraModel(*s.intr, s.dist, 4000, 6000))
+    rec.setReconstructedTags({tid: tr.ReconstructedTag(tid, "apriltag_36h11", s.tag_init[k, :4], s.tag_init[k, 4:],
+                                                        *s.tag_wh[k]) for k, tid in enumerate(tag_ids)})
+    rec.setReconstructedCameras({cid: tr.Camera(cid, s.cam_init[k, :4], s.cam_init[k, 4:])
+                                 for k, cid in enumerate(cam_ids)})
+    rec.setOriginTagId(tag_ids[0])
+    const = {tag_ids[2], tag_ids[5], tag_ids[9]}
+    rec.constantTagIds = set(const)
+    before = {t: (np.array(v.q, np.float64).tobytes(), np.array(v.t, np.float64).tobytes(),
+                  np.array(v.computeMarkerCorners3D())) for t, v in rec.reconstructedTags.items()}
+    rec.doBundleAdjustment_points(400, 1, False)
+    rec.close()
+    assert "Solution 0" in capsys.readouterr().out
+    for t, v in rec.reconstructedTags.items():
+        same = (np.array(v.q, np.float64).tobytes(), np.array(v.t, np.float64).tobytes()) == before[t][:2]
+        if t in const:
+            assert same, t
+            # the corners the device held are the corners of the untouched pose (computeMarkerCorners3D, to rounding)
+            np.testing.assert_allclose(rec.lastPoints[t], before[t][2], rtol=0, atol=1e-12)
+        elif t != tag_ids[0]:
+            assert not same, t
+            assert np.abs(rec.lastPoints[t] - before[t][2]).max() > 1e-9

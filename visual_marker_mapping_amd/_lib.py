@@ -30,7 +30,7 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_dense_spd_solve", "vmm_ba_dense_syrk", "vmm_ba_time_kernels", "vmm_ba_pose_plus", "vmm_ba_debug_overlap",
            "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
            "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
-           "vmm_ba_default_localize_options", "vmm_ba_localize"]
+           "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses"]
 
 
 class Problem(C.Structure):
@@ -144,6 +144,7 @@ def lib():
         L.vmm_ba_rccl_unique_id.argtypes = [C.c_void_p]
         L.vmm_ba_enable_rccl.argtypes = [C.c_void_p, C.c_void_p]
         L.vmm_ba_set_observation_mask.argtypes = [C.c_void_p, C.c_void_p]
+        L.vmm_ba_set_constant_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vmm_ba_solve.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(Summary)]
         L.vmm_ba_cost.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
         L.vmm_ba_reprojection_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,

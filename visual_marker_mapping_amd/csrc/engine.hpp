@@ -140,6 +140,11 @@ struct Engine {
                                     // which one belongs to x
     float* Wf2 = nullptr;
     uint8_t* obs_mask = nullptr;    // [n_obs] caller order, 1 = observation active (vmm_ba_set_observation_mask)
+    // [n_cams + n_tags] cameras then landmark blocks, non-zero = the pose is held constant: the evaluation zeroes its
+    // Jacobian columns, the initialisation starts from it.  Holds the problem's fixed_tag from create on;
+    // vmm_ba_set_constant_poses adds the caller's flags (point landmarks: both pair blocks of a constant tag)
+    uint8_t* pose_const = nullptr;
+    bool any_const = false;         // some pose is constant: vmm_ba_initialize has a seed
     float* Wf = nullptr;            // the same in f32 (VMM_BA_PRECISION_F32_ACCUM); exactly one of the two exists
     bool f32_accum = false;
 

@@ -26,8 +26,8 @@ struct EvalArgs {
     const double* own_pose;    // poses of the sorted family
     const double* other_pose;  // poses of the other family
     const double* tag_wh;
-    int fixed_tag;
-    int fixed_shift;           // point landmarks: two 6-dof blocks (point pairs) per tag, block >> 1 == fixed_tag
+    const uint8_t* cam_const;  // [n_cams] non-zero: the camera is held constant (vmm_ba_set_constant_poses)
+    const uint8_t* tag_const;  // [n_tags] the same per landmark block (point landmarks: both pair blocks of a constant tag)
     int robustify;
     double huber_a;
     double* part;              // [n_tasks][kPart]
@@ -75,8 +75,10 @@ __device__ __forceinline__ void eval_body(const EvalArgs& a, const int wave)
         load_rigid<true>(tagq, tag);
     }
     const double hw = POINTS ? 0.0 : 0.5 * a.tag_wh[2 * tag_idx], hh = POINTS ? 0.0 : 0.5 * a.tag_wh[2 * tag_idx + 1];
-    // a constant (origin) tag contributes no Jacobian columns (src/TagReconstructor.cpp:669-673, :494-497)
-    const double tag_on = ((tag_idx >> a.fixed_shift) == a.fixed_tag) ? 0.0 : 1.0;
+    // a constant pose (the origin tag, src/TagReconstructor.cpp:669-673, :494-497; vmm_ba_set_constant_poses) contributes
+    // no Jacobian columns.  Kept as flags and selected below: a flag costs no vector register where the pose is the
+    // wave's own
+    const bool cam_c = a.cam_const[cam_idx] != 0, tag_c = a.tag_const[tag_idx] != 0;
     // switched-off observations are selected out, never multiplied out (their poses are parked defaults)
     const bool on = valid && a.mask[a.caller[is]];
 
@@ -130,8 +132,9 @@ __device__ __forceinline__ void eval_body(const EvalArgs& a, const int wave)
         huber(a.robustify != 0, a.huber_a, s, rho0, wgt);
         wgt = on ? wgt : 0.0;
         cost += on ? 0.5 * rho0 : 0.0;
-        const double w_own = OWN_IS_CAM ? wgt : wgt * tag_on;
-        const double w_oth = OWN_IS_CAM ? wgt * tag_on : wgt;
+        const double w_cam = cam_c ? 0.0 : wgt, w_tag = tag_c ? 0.0 : wgt;
+        const double w_own = OWN_IS_CAM ? w_cam : w_tag;
+        const double w_oth = OWN_IS_CAM ? w_tag : w_cam;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const double res = (r == 0 ? e.ru : e.rv) * wgt;  // corrected residual
@@ -323,7 +326,8 @@ void k_eval_fused(const EvalArgs a, const FusedArgs fa)
         const Rigid& tag = E_IS_CAM ? kept : elim;
         const double* camq = E_IS_CAM ? elimq : keptq;
         const double hw = POINTS ? 0.0 : 0.5 * a.tag_wh[2 * tag_idx], hh = POINTS ? 0.0 : 0.5 * a.tag_wh[2 * tag_idx + 1];
-        const double tag_on = ((tag_idx >> a.fixed_shift) == a.fixed_tag) ? 0.0 : 1.0;
+        const int cam_idx = E_IS_CAM ? e : fs;
+        const bool cam_c = a.cam_const[cam_idx] != 0, tag_c = a.tag_const[tag_idx] != 0;
         AT H[21];
         double g[6], cost = 0.0;
         AT Wacc[36];
@@ -369,8 +373,9 @@ void k_eval_fused(const EvalArgs a, const FusedArgs fa)
             huber(a.robustify != 0, a.huber_a, s, rho0, wgt);
             wgt = on ? wgt : 0.0;
             cost += on ? 0.5 * rho0 : 0.0;
-            const double w_e = E_IS_CAM ? wgt : wgt * tag_on;   // weight of the eliminated family's columns
-            const double w_f = E_IS_CAM ? wgt * tag_on : wgt;   // ... of the kept family's
+            const double w_cam = cam_c ? 0.0 : wgt, w_tag = tag_c ? 0.0 : wgt;
+            const double w_e = E_IS_CAM ? w_cam : w_tag;   // weight of the eliminated family's columns
+            const double w_f = E_IS_CAM ? w_tag : w_cam;   // ... of the kept family's
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
                 const double res = (r == 0 ? ce.ru : ce.rv) * wgt;   // corrected residual
@@ -741,8 +746,8 @@ static EvalArgs make_eval_args(Engine& e, const ObsOrder& ord, bool own_is_cam, 
     a.own_pose = own_is_cam ? cam : tag;
     a.other_pose = own_is_cam ? tag : cam;
     a.tag_wh = e.tag_wh;
-    a.fixed_tag = e.fixed_tag;
-    a.fixed_shift = e.points ? 1 : 0;
+    a.cam_const = e.pose_const;
+    a.tag_const = e.pose_const + e.n_cams;
     a.robustify = 0;
     a.huber_a = 1.0;
     a.part = ord.part;

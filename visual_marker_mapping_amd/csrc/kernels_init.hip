@@ -300,7 +300,7 @@ struct InitArgs {
     const double* quad_qt;     // [14 * n_obs] caller order
     const double* quad_rms;    // [2 * n_obs]
     int sweep;                 // 0: place poses that are not placed yet; 1: redo every placed pose
-    int fixed;                 // pose of this family that is never touched (the origin tag), or -1
+    const uint8_t* own_const;  // [n_own] non-zero: the pose is constant -- placed from the start, never touched
     int min_obs;               // active observations a pose needs to be placed
     double cap2;               // score_cap_px^2
     int max_trials;            // LM trials of the refinement
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_init_score(const InitArgs a)
         a.todo[p] = 0;
     // everything up to the barrier depends on the pose alone: the whole workgroup leaves together or not at all
     const bool placed = a.own_placed[p] != 0;
-    if (p == a.fixed || (a.sweep ? !placed : placed))
+    if (a.own_const[p] != 0 || (a.sweep ? !placed : placed))
         return;
     const int b = a.start[p], e = a.start[p + 1];
     int n_act = 0, n_use = 0;
@@ -547,12 +547,12 @@ __global__ __launch_bounds__(256) void k_init_refine(const InitArgs a)
     }
 }
 
-// placed flags: cameras [0, n_cams), tags behind them; only the origin tag starts placed
-__global__ void k_init_begin(int32_t* placed, int n_pose, int origin)
+// placed flags: cameras [0, n_cams), tags behind them; the constant poses (the origin tag among them) start placed
+__global__ void k_init_begin(int32_t* placed, int n_pose, const uint8_t* __restrict__ pose_const)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_pose)
-        placed[i] = i == origin ? 1 : 0;
+        placed[i] = pose_const[i] != 0 ? 1 : 0;
 }
 
 // Mean corner reprojection distance (pixels) over the active observations whose camera and tag are both placed, and
@@ -635,7 +635,7 @@ InitArgs make_init_args(Engine& e, bool cam, const InitPass& s)
     a.quad_qt = e.init_quad_qt;
     a.quad_rms = e.init_quad_rms;
     a.sweep = s.sweep ? 1 : 0;
-    a.fixed = cam ? -1 : e.fixed_tag;
+    a.own_const = cam ? e.pose_const : e.pose_const + e.n_cams;
     a.min_obs = cam ? 1 : s.min_tag_observations;
     a.cap2 = s.score_cap_px * s.score_cap_px;
     a.max_trials = s.refine_iterations;
@@ -690,7 +690,7 @@ void launch_init_begin(Engine& e)
 {
     const int n_pose = e.n_cams + e.n_tags;
     hipLaunchKernelGGL(k_init_begin, dim3((unsigned)((n_pose + 255) / 256)), dim3(256), 0, e.stream, e.init_placed, n_pose,
-                       e.n_cams + e.fixed_tag);
+                       (const uint8_t*)e.pose_const);
 }
 
 // score + select + refine for one family

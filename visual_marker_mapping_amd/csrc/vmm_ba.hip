@@ -741,6 +741,25 @@ static void take_plan(Engine& e, const Plan& P)
     e.chol_nz_on = !P.chol_nz.empty();
 }
 
+// Engine::pose_const from the caller's flags (either may be null) and the problem's fixed tag; point landmarks: a tag
+// owns two landmark blocks.  Waits for the copy: the staging vector goes out of scope.
+static int upload_pose_const(Engine& e, const uint8_t* cam_const, const uint8_t* tag_const)
+{
+    std::vector<uint8_t> c((size_t)e.n_cams + (size_t)e.n_tags, 0);
+    const int rep = e.points ? 2 : 1;
+    if (cam_const)
+        for (int i = 0; i < e.n_cams; ++i)
+            c[(size_t)i] = cam_const[i] ? 1 : 0;
+    for (int t = 0; t < e.n_tags; ++t)
+        c[(size_t)e.n_cams + t] = ((tag_const && tag_const[t / rep]) || t / rep == e.fixed_tag) ? 1 : 0;
+    if (c.empty())
+        return VMM_BA_OK;
+    HIP_TRY(hipMemcpyAsync(e.pose_const, c.data(), c.size(), hipMemcpyHostToDevice, e.stream));
+    HIP_TRY(hipStreamSynchronize(e.stream));
+    e.any_const = std::find(c.begin(), c.end(), (uint8_t)1) != c.end();
+    return VMM_BA_OK;
+}
+
 // Device buffers of the engine, the plan's tables copied into them (the poses from the caller's problem `p`).
 static int allocate_and_upload(Engine& e, const Plan& P, const vmm_ba_problem& p)
 {
@@ -799,6 +818,8 @@ static int allocate_and_upload(Engine& e, const Plan& P, const vmm_ba_problem& p
         set_error("hipMemsetAsync(obs_mask) failed");
         return VMM_BA_ERR_HIP;
     }
+    if ((rc = dev_alloc(e, &e.pose_const, (size_t)n_pose))) return rc;
+    if ((rc = upload_pose_const(e, nullptr, nullptr))) return rc;
     const size_t n_stat = (size_t)e.ordE.n_tasks + (size_t)e.ordF.n_tasks + 1;
     if ((rc = dev_alloc(e, &e.stats_part, n_stat))) return rc;
     if ((rc = dev_alloc(e, &e.stats_cnt, n_stat))) return rc;
@@ -1326,6 +1347,17 @@ int vmm_ba_set_observation_mask(vmm_ba_handle h, const uint8_t* mask)
     return VMM_BA_OK;
 }
 
+int vmm_ba_set_constant_poses(vmm_ba_handle h, const uint8_t* cam_const, const uint8_t* tag_const)
+{
+    if (!h) {
+        set_error("null handle");
+        return VMM_BA_ERR_ARGUMENT;
+    }
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    HIP_TRY(hipSetDevice(e.device));
+    return upload_pose_const(e, cam_const, tag_const);
+}
+
 int vmm_ba_reprojection_stats(vmm_ba_handle h, double* per_cam_mean, double* per_tag_mean, double* avg,
                               double* per_corner)
 {
@@ -1600,8 +1632,8 @@ int vmm_ba_initialize(vmm_ba_handle h, const vmm_ba_init_options* opt, vmm_ba_in
         set_error("vmm_ba_initialize needs a single-GPU handle with tag-pose landmarks");
         return VMM_BA_ERR_STATE;
     }
-    if (e.fixed_tag < 0) {
-        set_error("vmm_ba_initialize needs a fixed (origin) tag: the map grows from its pose");
+    if (!e.any_const) {
+        set_error("vmm_ba_initialize needs a fixed (origin) tag or a constant pose: the map grows from there");
         return VMM_BA_ERR_ARGUMENT;
     }
     vmm_ba_init_options o;

@@ -70,6 +70,7 @@ class BundleAdjuster:
             co.n_structure_obs, co.structure_obs_cam, co.structure_obs_tag = len(s_cam), ip(s_cam), ip(s_tag)
         _lib.check(L.vmm_ba_create(C.byref(p), C.byref(co), C.byref(self._h)))
         self._allreduce_cb = None
+        self.constant_poses = (None, None)   # the flags of the last set_constant_poses call, as bytes
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -99,6 +100,24 @@ class BundleAdjuster:
         if len(m) != self.n_obs:
             raise ValueError("mask length differs from the number of observations")
         _lib.check(_lib.lib().vmm_ba_set_observation_mask(self._h, m.ctypes.data_as(C.c_void_p)))
+
+    def set_constant_poses(self, cam_const=None, tag_const=None):
+        """Holds poses constant (vmm_ba_set_constant_poses; Ceres' SetParameterBlockConstant): cam_const (n_cams,) and
+        tag_const (n_tags,), non-zero = constant, None = no pose of that family.  Replaces any earlier set; the
+        problem's fixed tag stays constant regardless.  Every rank of a multi-GPU run passes the same arrays."""
+        flags = []
+        for name, a, n in (("cam_const", cam_const, self.n_cams), ("tag_const", tag_const, self.n_tags)):
+            if a is None:
+                flags.append(None)
+                continue
+            a = np.asarray(a)
+            if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+                raise TypeError("%s must be a boolean or integer array, not %s" % (name, a.dtype))
+            if a.shape != (n,):
+                raise ValueError("%s must have shape (%d,), not %s" % (name, n, a.shape))
+            flags.append(np.ascontiguousarray(a != 0, np.uint8))
+        _lib.check(_lib.lib().vmm_ba_set_constant_poses(self._h, _ptr(flags[0]), _ptr(flags[1])))
+        self.constant_poses = tuple(None if f is None or not f.any() else f.tobytes() for f in flags)
 
     def get_state(self):
         cam, tag = np.zeros((self.n_cams, 7)), np.zeros((self.n_tags, 7))
@@ -154,9 +173,9 @@ class BundleAdjuster:
 
     def initialize(self, **options):
         """Initial poses from the detections alone (vmm_ba_initialize): overwrites the device state of every pose
-        reachable from the fixed tag, whose current pose is kept.  options: the fields of vmm_ba_init_options
-        (sweeps, min_tag_observations, score_cap_px, refine_iterations).  Returns (report dict, cam_reached,
-        tag_reached) with boolean masks; unreached poses keep their state."""
+        reachable from the constant poses (the fixed tag, set_constant_poses), whose current poses are kept.
+        options: the fields of vmm_ba_init_options (sweeps, min_tag_observations, score_cap_px, refine_iterations).
+        Returns (report dict, cam_reached, tag_reached) with boolean masks; unreached poses keep their state."""
         o = _lib.InitOptions()
         _lib.lib().vmm_ba_default_init_options(C.byref(o))
         for k, v in options.items():

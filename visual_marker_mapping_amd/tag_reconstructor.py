@@ -145,6 +145,8 @@ class TagReconstructor:
 
     def __init__(self, detection_result, device=0):
         self.originTagId = -1                                  # src/TagReconstructor.cpp:70
+        # not in the reference API: ids of tags every bundle adjustment holds constant, like the origin tag (:669-673)
+        self.constantTagIds = set()
         self.detectionResults_ = detection_result
         self.reconstructedTags = {}                            # tag id -> ReconstructedTag
         self.reconstructedCameras = {}                         # image id -> Camera
@@ -355,6 +357,83 @@ class TagReconstructor:
         self.removeBadCameras(2.0)
         self.doBundleAdjustment(1500, numThreads, False, True)
 
+    def extendReconstruction(self, numThreads=1, **init_options):
+        """Not in the reference API: grows a finished map with new images while every tag of the map stays where it
+        is, bit for bit.  Precondition: reconstructedTags holds the finished map (io.parseReconstructions),
+        detectionResults_ the NEW images.  ONE device handle over the new detection result: its cameras are the new
+        images, its tags the map tags the new detections observe plus every tag the detections name that the map lacks
+        -- a large map costs nothing beyond what the new images see.  All packed map tags are held constant
+        (vmm_ba_set_constant_poses), vmm_ba_initialize grows outward from them, the reached poses become the
+        reconstructed sets, and the reference's closing sequence (src/TagReconstructor.cpp:271-277) runs with the
+        constants held: BA(1500, robust), both prunings (a map tag is never pruned), BA(1500, plain, summary).
+        Afterwards reconstructedTags is the whole map (q, t, width and height untouched) plus the new tags, and
+        reconstructedCameras holds the new images' cameras only.  init_options: fields of vmm_ba_init_options; the
+        report of the initialisation is kept in lastInitReport."""
+        whole_map = dict(self.reconstructedTags)
+        observed = {int(ob.tagId) for ob in self.detectionResults_.tagObservations}
+        packed_map = {tid: tag for tid, tag in whole_map.items() if tid in observed}
+        if not packed_map:
+            raise RuntimeError("No reconstructed tags in image found. To reconstruct the image pose "
+                               "already reconstructed markers are needed. This should NOT happen.")
+        saved_const = set(self.constantTagIds)
+        saved_cameras = self.reconstructedCameras
+        self.reconstructedTags = dict(packed_map)
+        self.reconstructedCameras = {}
+        self.constantTagIds = saved_const | set(packed_map)
+        self._resident = True
+        done = False
+        try:
+            self._extend_reconstruction(numThreads, init_options)
+            done = True
+        finally:
+            self._resident = False
+            self._drop_cached()
+            self._full = None
+            self.constantTagIds = saved_const
+            if done:
+                # the map tags no new image sees were never packed
+                self.reconstructedTags = {**{t: v for t, v in whole_map.items() if t not in packed_map},
+                                          **self.reconstructedTags}
+            else:
+                # a failure part-way leaves the object as it was: the map, and whatever cameras it held
+                self.reconstructedTags = whole_map
+                self.reconstructedCameras = saved_cameras
+
+    def _extend_reconstruction(self, numThreads, init_options):
+        tagById = {t.tagId: t for t in self.detectionResults_.tags}
+        # the resident packing with the observed map tags reconstructed (and constant): every other pose is a placeholder
+        p = self._pack_resident(for_ba=True)
+        full = self._full
+        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
+        try:
+            ba.set_observation_mask(None)
+            report, cam_ok, tag_ok = ba.initialize(**init_options)
+            cam, tag = ba.get_state()
+        except Exception:
+            self._drop_cached()
+            raise
+        self.lastInitReport = report
+        print("Initialized %d of %d cameras and %d of %d tags in %d rounds, average reprojection error %g"
+              % (report["cams_reached"], len(cam_ok), report["tags_reached"], len(tag_ok), report["rounds"],
+                 report["avg_reprojection_px"]))
+        if not cam_ok.any():
+            raise RuntimeError("No reconstructed tags in image found. To reconstruct the image pose "
+                               "already reconstructed markers are needed. This should NOT happen.")
+        for r, cid in enumerate(full["cams"].tolist()):
+            if cam_ok[r]:
+                self.reconstructedCameras[cid] = Camera(cameraId=cid, q=cam[r, :4], t=cam[r, 4:])
+        for r, tid in enumerate(full["tags"].tolist()):
+            if tid in self.reconstructedTags or not tag_ok[r] or tid not in tagById:
+                continue
+            d = tagById[tid]
+            self.reconstructedTags[tid] = ReconstructedTag(id=tid, tagType=d.tagType, q=tag[r, :4], t=tag[r, 4:],
+                                                           tagWidth=d.width, tagHeight=d.height)
+        print("Starting final bundle adjustment")
+        self.doBundleAdjustment(1500, numThreads, True, False)
+        self.removeBadMarkers(2.0)
+        self.removeBadCameras(2.0)
+        self.doBundleAdjustment(1500, numThreads, False, True)
+
     def computeRelativeCameraPoseFromImg(self, imageId, intr, dist, observations=None):
         """src/TagReconstructor.cpp:280-312: (q, t) of the camera from every correspondence between this
         image's detected corners and the corners of already reconstructed tags, or None without any."""
@@ -476,8 +555,9 @@ class TagReconstructor:
                           np.float64).reshape(-1, 2)
         fixed = tag_ids.index(self.originTagId) if self.originTagId in self.reconstructedTags else -1   # :669-673
         intr = [self.camModel.fx, self.camModel.fy, self.camModel.cx, self.camModel.cy]
+        tag_const = np.isin(tag_arr, np.asarray(sorted(self.constantTagIds), np.int64)).astype(np.uint8)
         return dict(tag_ids=tag_ids, cam_ids=cam_ids, intr=intr, dist=self.camModel.distortionCoefficients,
-                    cam_qt=cam_qt, tag_qt=tag_qt, tag_wh=tag_wh, fixed=fixed,
+                    cam_qt=cam_qt, tag_qt=tag_qt, tag_wh=tag_wh, fixed=fixed, tag_const=tag_const,
                     obs_cam=obs_cam, obs_tag=obs_tag, obs_px=np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8),
                     cam_rows=list(range(len(cam_ids))), tag_rows=list(range(len(tag_ids))), mask=None, key=None,
                     n_active=int(len(obs_cam)))
@@ -524,9 +604,14 @@ class TagReconstructor:
         intr = [self.camModel.fx, self.camModel.fy, self.camModel.cx, self.camModel.cy]
         key = ("resident", id(full), fixed, tuple(float(v) for v in intr),
                tuple(float(v) for v in self.camModel.distortionCoefficients), tag_wh.tobytes())
+        # constant tags: rows of the full arrays; only reconstructed ones (the others have no active observation)
+        tag_const = np.zeros(len(full["tags"]), np.uint8)
+        for t, r in zip(tag_ids, tag_rows):
+            if t in self.constantTagIds:
+                tag_const[r] = 1
         return dict(tag_ids=tag_ids, cam_ids=cam_ids, cam_rows=cam_rows, tag_rows=tag_rows, intr=intr,
                     dist=self.camModel.distortionCoefficients, cam_qt=cam_qt, tag_qt=tag_qt, tag_wh=tag_wh,
-                    fixed=fixed, obs_cam=full["obs_cam"], obs_tag=full["obs_tag"], obs_px=full["obs_px"],
+                    fixed=fixed, tag_const=tag_const, obs_cam=full["obs_cam"], obs_tag=full["obs_tag"], obs_px=full["obs_px"],
                     mask=mask, key=key, n_active=int(mask.sum()))
 
     def _engine_for(self, p, **kw):
@@ -548,14 +633,24 @@ class TagReconstructor:
             ba = self._cached[1]
             ba.set_state(p["cam_qt"], p["tag_qt"])
             ba.set_observation_mask(p.get("mask"))
+            self._set_constants(ba, p)
             return ba
         self._drop_cached()
         ba = _engine.BundleAdjuster(p["intr"], p["dist"], p["cam_qt"], p["tag_qt"], p["tag_wh"], p["fixed"],
                                     p["obs_cam"], p["obs_tag"], p["obs_px"], device=self.device, **kw)
         if p.get("mask") is not None:
             ba.set_observation_mask(p["mask"])
+        self._set_constants(ba, p)
         self._cached = (key, ba)
         return ba
+
+    @staticmethod
+    def _set_constants(ba, p):
+        """The packed constant-tag flags go to the handle when they differ from what it holds (constantTagIds)."""
+        tc = p.get("tag_const")
+        want = tc.tobytes() if tc is not None and tc.any() else None
+        if ba.constant_poses != (None, want):
+            ba.set_constant_poses(None, tc if want is not None else None)
 
     def _drop_cached(self):
         if self._cached is not None:
@@ -632,7 +727,8 @@ class TagReconstructor:
         TagReconstructionCostFunction.h:9-84; 3x3 landmark blocks, SPARSE_SCHUR ordering :492,534-535), the origin
         tag's corners constant (:494-497), no loss (:556).  Cameras are written back as at :583-605, tag poses are
         rebuilt from the optimised corners as at :608-639 (with today's corner order, see vmm_ba.h); the corners
-        themselves are kept in self.lastPoints (tag id -> 4 x 3)."""
+        themselves are kept in self.lastPoints (tag id -> 4 x 3).  The corners of the tags in constantTagIds are
+        constant too, and those tags' q and t are left as they are, bit for bit."""
         p = self._pack(for_ba=True)
         if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
             print("Solution %d" % _engine.CONVERGENCE)
@@ -653,9 +749,11 @@ class TagReconstructor:
             self.reconstructedCameras[cid].t = cam[k, 4:].copy()
         self.lastPoints = {}
         for k, tid in zip(p["tag_rows"], p["tag_ids"]):
+            self.lastPoints[tid] = pts[k].copy()
+            if tid in self.constantTagIds:
+                continue    # its corners did not move: the pose keeps its bits instead of being rebuilt from them
             self.reconstructedTags[tid].q = tag[k, :4].copy()
             self.reconstructedTags[tid].t = tag[k, 4:].copy()
-            self.lastPoints[tid] = pts[k].copy()
         self.lastSummary = summary
         print("Solution %d" % summary["termination_type"])                                   # :579
         print("Cost: initial %.6e final %.6e; iterations %d; time in solver %.4f s" % (     # :580-581 (FullReport)
@@ -696,7 +794,7 @@ class TagReconstructor:
         """:786-802."""
         reperrors, _avg = self.computeReprojectionErrorPerTag()
         for tid in sorted(reperrors):
-            if reperrors[tid] > threshold and tid != self.originTagId:
+            if reperrors[tid] > threshold and tid != self.originTagId and tid not in self.constantTagIds:
                 print("Removing bad marker with id %d and reprojection error %g" % (tid, reperrors[tid]))
                 del self.reconstructedTags[tid]
 

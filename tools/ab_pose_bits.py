@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Bit comparison of two builds of libvmm_ba.so on the single-pose solver's three entries: vmm_ba_quad_poses,
+vmm_ba_initialize and vmm_ba_localize.
+
+    python tools/ab_pose_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--keep DIR]
+
+Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
+writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
+{"equal": ..., "outputs": {name: {"equal": ..., "sha256": [a, b]}}}; the exit status is 1 on any difference.  The
+scenes are the smallest that reach every loop trip and both variants of every kernel; all of
+them are generated here from fixed seeds.  The wall time in the initialisation report is the one field left out."""
+import argparse
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INTR = (8075.29, 8083.17, 3016.39, 1996.29)
+DIST = (-0.18618, 0.37018, -2.939e-4, 4.153e-4, 0.05704)
+
+
+def _quad_cases(eng, out):
+    """65 and 200 observations (one wave plus a lane; four workgroups), with and without distortion; observation 3 has
+    four equal corners (RMS = +inf)."""
+    from visual_marker_mapping_amd import pnp
+    w = 0.1285
+    quad = np.array([[-w / 2, -w / 2, 0], [w / 2, -w / 2, 0], [w / 2, w / 2, 0], [-w / 2, w / 2, 0]])
+    for n in (65, 200):
+        for name, dist in (("plain", (0.0,) * 5), ("dist", DIST)):
+            rng = np.random.default_rng(1000 + n)
+            px = np.zeros((n, 8))
+            for i in range(n):
+                R = pnp.rodrigues(rng.normal(size=3) * 0.4)
+                t = np.array([rng.normal() * 0.2, rng.normal() * 0.2, 3.0 + 3.0 * rng.random()])
+                px[i] = eng.project_points(INTR, dist, quad @ R.T + t).reshape(8) + rng.normal(size=8) * 0.3
+            px[3] = np.tile(px[3, :2], 4)
+            qt2, rms2 = eng.quad_poses(INTR, dist, np.full((n, 2), w), px)
+            out["quad_%d_%s_qt2" % (n, name)], out["quad_%d_%s_rms2" % (n, name)] = qt2, rms2
+
+
+def _init_cases(eng, make_scene, out):
+    """70 x 12: 70 > 64 observations per tag, the second trip of the lane-strided sums.  520 x 4: 1040 candidates per
+    tag, the second trip of k_init_score's candidate loop.  100 x 60 at visibility 0.3: several growth rounds."""
+    for name, kw in (("70x12", dict(n_cams=70, n_tags=12)), ("520x4", dict(n_cams=520, n_tags=4)),
+                     ("100x60_vis0.30", dict(n_cams=100, n_tags=60, visibility=0.30))):
+        s = make_scene(1, seed=4242, **kw)
+        cam = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 1.0]), (len(s.cam_gt), 1))
+        tag = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0.0]), (len(s.tag_gt), 1))
+        tag[s.fixed_tag] = s.tag_gt[s.fixed_tag]
+        with eng.BundleAdjuster(s.intr, s.dist, cam, tag, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag, s.obs_px) as ba:
+            report, cam_ok, tag_ok = ba.initialize(sweeps=1)
+            cam_qt, tag_qt = ba.get_state()
+        out["init_%s_cam_qt" % name], out["init_%s_tag_qt" % name] = cam_qt, tag_qt
+        out["init_%s_cam_reached" % name], out["init_%s_tag_reached" % name] = cam_ok, tag_ok
+        out["init_%s_counts" % name] = np.array([report["rounds"], report["cams_reached"], report["tags_reached"]], np.int64)
+        out["init_%s_avg_px" % name] = np.array([report["avg_reprojection_px"]])
+
+
+def _localize_cases(eng, make_scene, out):
+    """One batch of images with 1, 2, 64, 256 (the last staged size) and 257 (the first unstaged; second trip of the
+    256-thread stride) observations, a tenth of the 64-observation image's pixel coordinates displaced by up to 60 px; robust and plain,
+    with 0 and 2 reclassification passes."""
+    s = make_scene(1, seed=4243, n_cams=5, n_tags=260)
+    sizes, tags, pxs = (1, 2, 64, 256, 257), [], []
+    for c, m in enumerate(sizes):
+        idx = np.flatnonzero(s.obs_cam == c)[:m]
+        assert len(idx) == m, (c, len(idx))
+        tags.append(s.obs_tag[idx])
+        pxs.append(s.obs_px[idx].copy())
+    rng = np.random.default_rng(4244)
+    hit = rng.random(pxs[2].shape) < 0.1
+    pxs[2][hit] += rng.uniform(-60.0, 60.0, int(hit.sum()))
+    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    for robust in (1, 0):
+        for passes in (0, 2):
+            cam, cov, inl, res = eng.localize(s.intr, s.dist, s.tag_gt, s.tag_wh, start, np.concatenate(tags),
+                                              np.concatenate(pxs), robustify=robust, reclassify_passes=passes)
+            key = "loc_%s_p%d_" % ("robust" if robust else "plain", passes)
+            out[key + "cam_qt"], out[key + "cam_cov"], out[key + "inlier"] = cam, cov, inl
+            out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
+            out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
+
+
+def child(path):
+    sys.path.insert(0, ROOT)
+    from visual_marker_mapping_amd import engine as eng
+    from visual_marker_mapping_amd.synthetic import make_scene
+    out = {}
+    _quad_cases(eng, out)
+    _init_cases(eng, make_scene, out)
+    _localize_cases(eng, make_scene, out)
+    np.savez(path, **out)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--a", help="first library")
+    ap.add_argument("--b", help="second library")
+    ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args.child)
+    if not args.a or not args.b:
+        ap.error("--a and --b are required")
+    keep = args.keep or tempfile.mkdtemp(prefix="ab_pose_bits_")
+    os.makedirs(keep, exist_ok=True)
+    data = {}
+    for side, lib in (("a", args.a), ("b", args.b)):
+        path = os.path.join(keep, side + ".npz")
+        env = dict(os.environ, VMM_BA_LIB=os.path.abspath(lib), PYTHONPATH=ROOT)
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, timeout=600)
+        if run.returncode != 0:   # nothing more is started on the GPU after a child that failed
+            print(json.dumps({"equal": False, "error": "child %s exited with %d" % (side, run.returncode)}))
+            return 2
+        with np.load(path) as z:
+            data[side] = {k: (z[k].dtype.str, z[k].shape, z[k].tobytes()) for k in z.files}
+    outputs, equal = {}, sorted(data["a"]) == sorted(data["b"])
+    for k in sorted(set(data["a"]) | set(data["b"])):
+        same = k in data["a"] and k in data["b"] and data["a"][k] == data["b"][k]
+        equal = equal and same
+        outputs[k] = {"equal": same, "sha256": [hashlib.sha256(data[x][k][2]).hexdigest() if k in data[x] else None
+                                                for x in ("a", "b")]}
+    print(json.dumps({"equal": equal, "a": args.a, "b": args.b, "n_outputs": len(outputs), "outputs": outputs}))
+    return 0 if equal else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

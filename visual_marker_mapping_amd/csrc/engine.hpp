@@ -260,6 +260,51 @@ struct Engine {
 
 void set_error(const std::string& s);
 
+inline Intrinsics make_intrinsics(const double intr[4], const double dist[5])
+{
+    Intrinsics K;
+    K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3];
+    K.k1 = dist[0]; K.k2 = dist[1]; K.p1 = dist[2]; K.p2 = dist[3]; K.k3 = dist[4];
+    return K;
+}
+
+// The device memory of an entry point that works without a handle: one allocation, released on every way out, and the
+// first HIP error of the steps made through it -- after a failure the later copies are skipped.
+struct Arena {
+    char* base = nullptr;
+    size_t used = 0;
+    hipError_t err = hipSuccess;
+    Arena() = default;
+    Arena(const Arena&) = delete;
+    Arena& operator=(const Arena&) = delete;
+    ~Arena()
+    {
+        if (base)
+            (void)hipFree(base);
+    }
+    hipError_t alloc(size_t bytes)
+    {
+        err = hipMalloc((void**)&base, bytes);
+        if (err != hipSuccess)
+            base = nullptr;
+        return err;
+    }
+    static size_t round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    template <typename T>
+    T* take(size_t count)   // the next 256-byte aligned piece
+    {
+        T* p = reinterpret_cast<T*>(base + used);
+        used += round(count * sizeof(T));
+        return p;
+    }
+    // blocking, on the null stream: ordered with the kernels launched there
+    void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind)
+    {
+        if (err == hipSuccess)
+            err = hipMemcpy(dst, src, bytes, kind);
+    }
+};
+
 // one per .hip file: hipFuncGetAttributes on every kernel (returns the number of failures)
 int preload_eval_kernels();
 int preload_schur_kernels();

@@ -9,6 +9,12 @@
 //                  scored by the truncated squared reprojection error over ALL the pose's corners on placed
 //                  counterparts; the lowest sum wins
 //   k_init_refine  wave = pose: Levenberg-Marquardt on that pose alone against its fixed placed counterparts
+// The single-pose solver all three are built from lives in pose_lm.hpp and is shared with kernels_localize.hip: the
+// Levenberg-Marquardt trial loop (lm_refine: quad_refine and k_init_refine supply their sums as a lambda), the camera-side
+// projection with its Jacobian (project_camera_point: quad_corner forms the rotated point and calls it), the candidate
+// winner rule (better, wave_winner: k_init_score), the 21 + 6 sums (zero_normal, wave_sum_normal, accumulate_rows, solve6)
+// and the chaining of candidates (chain_camera, chain_tag, quat_from_R).  What is here is what differs: how a quad's
+// rotated point is formed (z = 0), which observations a pose sums over, and the bookkeeping of the growth rounds.
 // All f64, the projections of geom.hpp: k_quad_pose fits CameraModel::projectPoint (what vmm_ba_project_points computes,
 // aliased tangential term included), scoring and refinement use the functor the bundle adjustment minimises (the two
 // differ by up to 0.02 px with the README distortion, geom.hpp: distort).  Every loop is bounded by a
@@ -28,41 +34,14 @@ constexpr int kUndistortIters = 20;    // fixed-point iterations of the undistor
 
 // ---- k_quad_pose ---------------------------------------------------------------------------------------------------
 
-// One corner (X0, X1, 0) of the quad under the tag->camera pose T, projected like CameraModel::projectPoint
-// (src/CameraModel.cpp:6-26, distort(.., camera_model = true): what vmm_ba_project_points computes), with the 2 x 6
-// Jacobian over T's tangent (translation, half-angle rotation).  eval_corner has no Jacobian for that projection; this
-// is its camera-side Jacobian with the two entries of d(yd)/d(x, y) that the aliased term 2 p2 (xd - x) y adds.
+// One corner (X0, X1, 0) of the quad under the tag->camera pose T, projected like CameraModel::projectPoint, with the
+// 2 x 6 Jacobian over T's tangent (project_camera_point<true, .>, pose_lm.hpp).  z = 0: two columns of R form b.
 template <bool JAC>
 __device__ __forceinline__ void quad_corner(const Intrinsics& K, const Rigid& T, const double X0, const double X1,
                                             const double u_obs, const double v_obs, double& ru, double& rv, double (&j)[2][6])
 {
     const double b0 = T.R[0] * X0 + T.R[1] * X1, b1 = T.R[3] * X0 + T.R[4] * X1, b2 = T.R[6] * X0 + T.R[7] * X1;
-    const double iz = 1.0 / (b2 + T.t[2]);
-    const double x = (b0 + T.t[0]) * iz, y = (b1 + T.t[1]) * iz;
-    const double r2 = x * x + y * y;
-    const double rad = 1.0 + r2 * (K.k1 + r2 * (K.k2 + r2 * K.k3));
-    double xd, yd;
-    distort(K, true, x, y, r2, rad, xd, yd);
-    ru = K.fx * xd + K.cx - u_obs;
-    rv = K.fy * yd + K.cy - v_obs;
-    if (!JAC)
-        return;
-    const double dr = K.k1 + r2 * (2.0 * K.k2 + 3.0 * K.k3 * r2);
-    const double D00 = rad + 2.0 * x * x * dr + 2.0 * K.p1 * y + 6.0 * K.p2 * x;
-    const double D01 = 2.0 * x * y * dr + 2.0 * K.p1 * x + 2.0 * K.p2 * y;
-    const double D10 = D01 + 2.0 * K.p2 * y * (D00 - 1.0);
-    const double D11 = rad + 2.0 * y * y * dr + 2.0 * K.p2 * x + 6.0 * K.p1 * y + 2.0 * K.p2 * (xd - x) + 2.0 * K.p2 * y * D01;
-    const double g[2][3] = { { K.fx * D00 * iz, K.fx * D01 * iz, -K.fx * (D00 * x + D01 * y) * iz },
-                             { K.fy * D10 * iz, K.fy * D11 * iz, -K.fy * (D10 * x + D11 * y) * iz } };
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        j[r][0] = g[r][0];
-        j[r][1] = g[r][1];
-        j[r][2] = g[r][2];
-        j[r][3] = 2.0 * (b1 * g[r][2] - b2 * g[r][1]);
-        j[r][4] = 2.0 * (b2 * g[r][0] - b0 * g[r][2]);
-        j[r][5] = 2.0 * (b0 * g[r][1] - b1 * g[r][0]);
-    }
+    project_camera_point<true, JAC>(K, b0, b1, b2, T.t, u_obs, v_obs, ru, rv, j);
 }
 
 // Sum of the 8 squared pixel residuals of the quad under the tag->camera pose q; with JAC also J^T J and J^T r.
@@ -72,14 +51,8 @@ __device__ __forceinline__ double quad_cost(const Intrinsics& K, const double* q
 {
     Rigid cam;
     load_rigid<true>(q, cam);
-    if (JAC) {
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            A[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            g[k] = 0.0;
-    }
+    if (JAC)
+        zero_normal(A, g);
     double cost = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -92,38 +65,14 @@ __device__ __forceinline__ double quad_cost(const Intrinsics& K, const double* q
     return cost;
 }
 
-// Levenberg-Marquardt over the 6 tangent degrees of freedom of q (in place); returns the final cost.
+// Levenberg-Marquardt on the tag->camera pose q (in place) of one quad; returns the final cost.
 __device__ __forceinline__ double quad_refine(const Intrinsics& K, double* q, const double hw, const double hh,
                                               const double (&px)[8])
 {
-    double A[21], g[6], step[6], cand[7];
-    double lam = kLamInit;
-    double cost = quad_cost<true>(K, q, hw, hh, px, A, g);
-    for (int it = 0; it < kQuadTrials; ++it) {
-        if (!finite_d(cost) || lam > kLamMax)
-            break;
-        if (!solve6(A, g, lam, step)) {
-            lam *= 10.0;
-            continue;
-        }
-        const double sm = max_abs6(step);
-        if (sm < 1e-14)
-            break;
-        pose_plus(q, step, cand);
-        double A2[21], g2[6];
-        const double cc = quad_cost<false>(K, cand, hw, hh, px, A2, g2);
-        if (finite_d(cc) && cc < cost) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k)
-                q[k] = cand[k];
-            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
-            cost = quad_cost<true>(K, q, hw, hh, px, A, g);
-        } else {
-            if (sm < 1e-10 || cost_at_floor(cost, cc))
-                break;
-            lam *= 10.0;
-        }
-    }
+    double cost;
+    lm_refine<false, false>(q, kQuadTrials, [&](auto jac, const double* at, double (&A)[21], double (&g)[6]) {
+        return quad_cost<decltype(jac)::value>(K, at, hw, hh, px, A, g);
+    }, cost);
     return cost;
 }
 
@@ -409,15 +358,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_init_score(const InitArgs a)
             best_c = -1;
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double os = __shfl_xor(best, m, 64);
-        const int oc = __shfl_xor(best_c, m, 64);
-        if (os < best || (os == best && oc < best_c)) {
-            best = os;
-            best_c = oc;
-        }
-    }
+    wave_winner(best, best_c);
     if (lane == 0) {
         s_best[wave] = best;
         s_c[wave] = best_c;
@@ -426,7 +367,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_init_score(const InitArgs a)
     if (threadIdx.x != 0)
         return;
     for (int w = 1; w < kScoreThreads / 64; ++w)
-        if (s_best[w] < best || (s_best[w] == best && s_c[w] < best_c)) {
+        if (better(s_best[w], s_c[w], best, best_c)) {
             best = s_best[w];
             best_c = s_c[w];
         }
@@ -453,14 +394,8 @@ __device__ __forceinline__ double refine_sums(const InitArgs& a, const double* q
     Rigid own;
     load_rigid<true>(q, own);
     double cost = 0.0;
-    if (JAC) {
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            A[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            g[k] = 0.0;
-    }
+    if (JAC)
+        zero_normal(A, g);
     for (int d = b + lane; d < e; d += 64) {
         if (!obs_usable(a, d))
             continue;
@@ -480,14 +415,8 @@ __device__ __forceinline__ double refine_sums(const InitArgs& a, const double* q
         }
     }
     cost = wave_sum(cost);
-    if (JAC) {
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            A[k] = wave_sum(A[k]);
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            g[k] = wave_sum(g[k]);
-    }
+    if (JAC)
+        wave_sum_normal(A, g);
     return cost;
 }
 
@@ -499,40 +428,14 @@ __global__ __launch_bounds__(256) void k_init_refine(const InitArgs a)
     if (p >= a.n_own || a.todo[p] == 0)
         return;
     const int b = a.start[p], e = a.start[p + 1];
-    double q[7], cand[7], A[21], g[6], step[6];
+    double q[7], cost;
 #pragma unroll
     for (int k = 0; k < 7; ++k)
         q[k] = a.own_qt[7 * (int64_t)p + k];
-    // every lane holds the same sums, so the whole wave takes the same branches below
-    double lam = kLamInit;
-    double cost = refine_sums<CAM, true>(a, q, p, b, e, lane, A, g);
-    for (int it = 0; it < a.max_trials; ++it) {
-        if (!finite_d(cost) || lam > kLamMax)
-            break;
-        if (!solve6(A, g, lam, step)) {
-            lam *= 10.0;
-            continue;
-        }
-        const double sm = max_abs6(step);
-        if (sm < 1e-14)
-            break;
-        pose_plus(q, step, cand);
-        double A2[21], g2[6];
-        const double cc = refine_sums<CAM, false>(a, cand, p, b, e, lane, A2, g2);
-        if (finite_d(cc) && cc < cost) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k)
-                q[k] = cand[k];
-            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
-            if (sm < 1e-9)   // an initial guess for the bundle adjustment: no need to go further
-                break;
-            cost = refine_sums<CAM, true>(a, q, p, b, e, lane, A, g);
-        } else {
-            if (sm < 1e-10 || cost_at_floor(cost, cc))
-                break;
-            lam *= 10.0;
-        }
-    }
+    // refine_sums gives every lane the wave's totals: the wave runs lm_refine as one
+    lm_refine<false, true>(q, a.max_trials, [&](auto jac, const double* at, double (&A)[21], double (&g)[6]) {
+        return refine_sums<CAM, decltype(jac)::value>(a, at, p, b, e, lane, A, g);
+    }, cost);
     if (lane == 0) {
         const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
         double* out = a.own_qt + 7 * (int64_t)p;

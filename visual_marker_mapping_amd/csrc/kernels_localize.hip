@@ -8,11 +8,16 @@
 //   k_localize      workgroup = image, one launch from candidates to covariance:
 //                   scoring   thread = candidate (two per observation, chained through the map tag), truncated squared
 //                             reprojection error over all the image's corners; the waves' winners meet in LDS and are
-//                             taken in wave order (k_init_score's rules)
+//                             taken in wave order (better / wave_winner, pose_lm.hpp: the rule k_init_score uses)
 //                   passes    classify the observations at the pose, Levenberg-Marquardt over the inliers: threads
 //                             stride the observation list, 21 + 6 + 2 sums reduced by one butterfly per wave
 //                             (wave_sum32) and combined in LDS in wave order; every thread runs the same 6 x 6 solve
 //                   result    flags at the returned pose, (J^T J)^-1 by a 6 x 6 Cholesky in registers
+// The single-pose solver is pose_lm.hpp's, shared with kernels_init.hip: lm_refine (refine_image supplies image_sums as a
+// lambda; the sums hold barriers, so the workgroup runs the driver as one), project_camera_point (world_corner forms
+// the rotated point from three columns and calls it), better / wave_winner, zero_normal, accumulate_rows, solve6,
+// chain_camera, quat_from_R.  Here: the image view (LDS or global), the Huber-weighted sums and their workgroup
+// reduction, the classification passes and the covariance.
 // An image's pixels and world corners (20 doubles per observation) are staged in LDS when the image has at most
 // kStage observations (k_localize<true>); larger images read them from global memory (k_localize<false>).  Both run the
 // same arithmetic in the same order, and which one an image takes depends on its own length alone.
@@ -58,7 +63,8 @@ __global__ __launch_bounds__(256) void k_map_corners(int n_tags, const double* _
     }
 }
 
-// eval_corner's camera half (geom.hpp) on a world corner: residual and, with JAC, the 2 x 6 camera Jacobian.
+// A world corner under the world->camera pose `cam`, projected like the functor the bundle adjustment minimises
+// (project_camera_point<false, .>, pose_lm.hpp): residual and, with JAC, the 2 x 6 camera Jacobian.
 template <bool JAC>
 __device__ __forceinline__ void world_corner(const Intrinsics& K, const Rigid& cam, const double w0, const double w1,
                                              const double w2, const double u_obs, const double v_obs, double& ru, double& rv,
@@ -67,31 +73,7 @@ __device__ __forceinline__ void world_corner(const Intrinsics& K, const Rigid& c
     const double b0 = cam.R[0] * w0 + cam.R[1] * w1 + cam.R[2] * w2;
     const double b1 = cam.R[3] * w0 + cam.R[4] * w1 + cam.R[5] * w2;
     const double b2 = cam.R[6] * w0 + cam.R[7] * w1 + cam.R[8] * w2;
-    const double iz = 1.0 / (b2 + cam.t[2]);
-    const double x = (b0 + cam.t[0]) * iz, y = (b1 + cam.t[1]) * iz;
-    const double r2 = x * x + y * y;
-    const double rad = 1.0 + r2 * (K.k1 + r2 * (K.k2 + r2 * K.k3));
-    double xd, yd;
-    distort(K, false, x, y, r2, rad, xd, yd);
-    ru = K.fx * xd + K.cx - u_obs;
-    rv = K.fy * yd + K.cy - v_obs;
-    if (!JAC)
-        return;
-    const double dr = K.k1 + r2 * (2.0 * K.k2 + 3.0 * K.k3 * r2);
-    const double D00 = rad + 2.0 * x * x * dr + 2.0 * K.p1 * y + 6.0 * K.p2 * x;
-    const double D01 = 2.0 * x * y * dr + 2.0 * K.p1 * x + 2.0 * K.p2 * y;
-    const double D11 = rad + 2.0 * y * y * dr + 2.0 * K.p2 * x + 6.0 * K.p1 * y;
-    const double g[2][3] = { { K.fx * D00 * iz, K.fx * D01 * iz, -K.fx * (D00 * x + D01 * y) * iz },
-                             { K.fy * D01 * iz, K.fy * D11 * iz, -K.fy * (D01 * x + D11 * y) * iz } };
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        j[r][0] = g[r][0];
-        j[r][1] = g[r][1];
-        j[r][2] = g[r][2];
-        j[r][3] = 2.0 * (b1 * g[r][2] - b2 * g[r][1]);
-        j[r][4] = 2.0 * (b2 * g[r][0] - b0 * g[r][2]);
-        j[r][5] = 2.0 * (b0 * g[r][1] - b1 * g[r][0]);
-    }
+    project_camera_point<false, JAC>(K, b0, b1, b2, cam.t, u_obs, v_obs, ru, rv, j);
 }
 
 // One image's observations: element k (0..7 pixels, 8..19 world corners) of local observation d.
@@ -179,14 +161,8 @@ __device__ __forceinline__ double image_sums(const Intrinsics& K, const ImageVie
     load_rigid<true>(q, cam);
     double acc[32];   // 0..20 J^T J, 21..26 J^T r, 27 cost, 28 raw2
     double cost = 0.0, raw = 0.0;
-    if (JAC) {
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            A[k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            g[k] = 0.0;
-    }
+    if (JAC)
+        zero_normal(A, g);
     for (int d = threadIdx.x; d < v.m; d += kLocThreads) {
         if (flags && flags[d] == 0)
             continue;
@@ -254,43 +230,17 @@ __device__ __forceinline__ double image_sums(const Intrinsics& K, const ImageVie
     return t;
 }
 
-// Levenberg-Marquardt on q (in place) over the active observations; returns the trials spent.
+// Levenberg-Marquardt on q (in place) over the active observations; returns the trials spent.  image_sums gives every
+// thread the workgroup's totals (and holds the barriers): the workgroup runs lm_refine as one.
 template <bool STAGED>
 __device__ __forceinline__ int refine_image(const Intrinsics& K, const ImageView<STAGED>& v, double (&q)[7],
                                             const uint8_t* flags, const bool robust, const double huber_a,
                                             const int max_trials, double* s_red)
 {
-    double cand[7], A[21], g[6], step[6], raw2;
-    double lam = kLamInit;
-    // every thread holds the same sums, so the whole workgroup takes the same branches (and reaches the same barriers)
-    double cost = image_sums<STAGED, true>(K, v, q, flags, robust, huber_a, s_red, A, g, raw2);
-    int it = 0;
-    for (; it < max_trials; ++it) {
-        if (!finite_bits(cost) || lam > kLamMax)
-            break;
-        if (!solve6<true>(A, g, lam, step)) {
-            lam *= 10.0;
-            continue;
-        }
-        const double sm = max_abs6(step);
-        if (sm < 1e-14)
-            break;
-        pose_plus(q, step, cand);
-        double A2[21], g2[6];
-        const double cc = image_sums<STAGED, false>(K, v, cand, flags, robust, huber_a, s_red, A2, g2, raw2);
-        if (finite_bits(cc) && cc < cost) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k)
-                q[k] = cand[k];
-            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
-            cost = image_sums<STAGED, true>(K, v, q, flags, robust, huber_a, s_red, A, g, raw2);
-        } else {
-            if (sm < 1e-10 || cost_at_floor(cost, cc))
-                break;
-            lam *= 10.0;
-        }
-    }
-    return it;
+    double cost, raw2;
+    return lm_refine<true, false>(q, max_trials, [&](auto jac, const double* at, double (&A)[21], double (&g)[6]) {
+        return image_sums<STAGED, decltype(jac)::value>(K, v, at, flags, robust, huber_a, s_red, A, g, raw2);
+    }, cost);
 }
 
 // C = A^-1 for a packed lower 6 x 6 A by Cholesky, in registers; false: not positive definite (C is not valid).
@@ -433,15 +383,7 @@ __global__ __launch_bounds__(kLocThreads) void k_localize(const LocalizeArgs a)
             best_c = c;
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const double os = __shfl_xor(best, s, 64);
-        const int oc = __shfl_xor(best_c, s, 64);
-        if (os < best || (os == best && oc < best_c)) {
-            best = os;
-            best_c = oc;
-        }
-    }
+    wave_winner(best, best_c);
     if (lane == 0) {
         s_best[wave] = best;
         s_c[wave] = best_c;
@@ -451,7 +393,7 @@ __global__ __launch_bounds__(kLocThreads) void k_localize(const LocalizeArgs a)
     best_c = s_c[0];
 #pragma unroll
     for (int w = 1; w < kLocWaves; ++w)
-        if (s_best[w] < best || (s_best[w] == best && s_c[w] < best_c)) {
+        if (better(s_best[w], s_c[w], best, best_c)) {
             best = s_best[w];
             best_c = s_c[w];
         }

@@ -17,25 +17,6 @@ int bad_argument(const char* what)
     return VMM_BA_ERR_ARGUMENT;
 }
 
-// one device arena, released on every way out
-struct Arena {
-    char* base = nullptr;
-    size_t used = 0;
-    ~Arena()
-    {
-        if (base)
-            (void)hipFree(base);
-    }
-    static size_t round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    template <typename T>
-    T* take(size_t count)
-    {
-        T* p = reinterpret_cast<T*>(base + used);
-        used += round(count * sizeof(T));
-        return p;
-    }
-};
-
 } // namespace
 
 extern "C" {
@@ -142,9 +123,7 @@ int vmm_ba_localize(const double intr[4], const double dist[5], int32_t n_tags, 
     const size_t total = Arena::round(8 * 7 * nt) + Arena::round(8 * 2 * nt) + Arena::round(8 * 12 * nt) + Arena::round(8 * (ni + 1))
         + Arena::round(4 * no) + Arena::round(8 * 8 * no) + Arena::round(8 * 14 * no) + Arena::round(8 * 2 * no)
         + Arena::round(8 * 7 * ni) + Arena::round(8 * 36 * ni) + Arena::round(no) + Arena::round(sizeof(vmm_ba_localize_result) * ni);
-    err = hipMalloc((void**)&ar.base, total);
-    if (err != hipSuccess) {
-        ar.base = nullptr;
+    if ((err = ar.alloc(total)) != hipSuccess) {
         set_error(std::string("vmm_ba_localize: hipMalloc: ") + hipGetErrorString(err));
         return VMM_BA_ERR_HIP;
     }
@@ -162,8 +141,7 @@ int vmm_ba_localize(const double intr[4], const double dist[5], int32_t n_tags, 
     vmm_ba_localize_result* d_res = ar.take<vmm_ba_localize_result>(ni);
 
     LocalizeArgs a;
-    a.K.fx = intr[0]; a.K.fy = intr[1]; a.K.cx = intr[2]; a.K.cy = intr[3];
-    a.K.k1 = dist[0]; a.K.k2 = dist[1]; a.K.p1 = dist[2]; a.K.p2 = dist[3]; a.K.k3 = dist[4];
+    a.K = make_intrinsics(intr, dist);
     a.n_imgs = n_imgs;
     a.img_start = d_start;
     a.obs_tag = d_obs_tag;
@@ -185,31 +163,26 @@ int vmm_ba_localize(const double intr[4], const double dist[5], int32_t n_tags, 
     a.res = d_res;
 
     // everything on the null stream, in order; the blocking copies back wait for the kernels
-    err = hipMemcpy(d_tag_qt, tag_qt, 8 * 7 * nt, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = hipMemcpy(d_tag_wh, tag_wh, 8 * 2 * nt, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = hipMemcpy(d_start, img_start, 8 * (ni + 1), hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = hipMemcpy(d_obs_tag, obs_tag, 4 * no, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = hipMemcpy(d_px, obs_px, 8 * 8 * no, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
+    ar.copy(d_tag_qt, tag_qt, 8 * 7 * nt, hipMemcpyHostToDevice);
+    ar.copy(d_tag_wh, tag_wh, 8 * 2 * nt, hipMemcpyHostToDevice);
+    ar.copy(d_start, img_start, 8 * (ni + 1), hipMemcpyHostToDevice);
+    ar.copy(d_obs_tag, obs_tag, 4 * no, hipMemcpyHostToDevice);
+    ar.copy(d_px, obs_px, 8 * 8 * no, hipMemcpyHostToDevice);
+    if (ar.err == hipSuccess) {
         launch_quad_poses(nullptr, a.K, n_obs, d_tag_wh, d_px, d_quad_qt, d_quad_rms, d_obs_tag);
         launch_map_corners(nullptr, n_tags, d_tag_qt, d_tag_wh, d_corners);
         launch_localize(nullptr, a, any_staged, any_unstaged);
-        err = hipGetLastError();
+        ar.err = hipGetLastError();
     }
-    if (err == hipSuccess)
-        err = hipMemcpy(cam_qt, d_cam, 8 * 7 * ni, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && cam_cov)
-        err = hipMemcpy(cam_cov, d_cov, 8 * 36 * ni, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && obs_inlier)
-        err = hipMemcpy(obs_inlier, d_inl, no, hipMemcpyDeviceToHost);
-    if (err == hipSuccess && res)
-        err = hipMemcpy(res, d_res, sizeof(vmm_ba_localize_result) * ni, hipMemcpyDeviceToHost);
-    if (err != hipSuccess) {
-        set_error(std::string("vmm_ba_localize: ") + hipGetErrorString(err));
+    ar.copy(cam_qt, d_cam, 8 * 7 * ni, hipMemcpyDeviceToHost);
+    if (cam_cov)
+        ar.copy(cam_cov, d_cov, 8 * 36 * ni, hipMemcpyDeviceToHost);
+    if (obs_inlier)
+        ar.copy(obs_inlier, d_inl, no, hipMemcpyDeviceToHost);
+    if (res)
+        ar.copy(res, d_res, sizeof(vmm_ba_localize_result) * ni, hipMemcpyDeviceToHost);
+    if (ar.err != hipSuccess) {
+        set_error(std::string("vmm_ba_localize: ") + hipGetErrorString(ar.err));
         return VMM_BA_ERR_HIP;
     }
     return VMM_BA_OK;

@@ -1,6 +1,14 @@
-// One-pose Levenberg-Marquardt building blocks shared by kernels_init.hip (map initialisation) and
-// kernels_localize.hip (localisation against a finished map): everything is __forceinline__ and lives in registers.
+// The single-pose solver shared by kernels_init.hip (map initialisation) and kernels_localize.hip (localisation against
+// a finished map): fit one 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
+//   lm_refine               the Levenberg-Marquardt trial loop; the caller supplies the sums (cost, J^T J, J^T r)
+//   project_camera_point    camera-side projection of a rotated point with its 2 x 6 Jacobian over the pose's tangent
+//   better / wave_winner    the candidate winner rule and its wave butterfly
+//   zero_normal / wave_sum_normal, accumulate_rows, solve6   the 21 + 6 sums of the normal equations and their solve
+//   chain_camera / chain_tag, quat_from_R                    candidates chained through a placed pose
+// Everything is __forceinline__ and lives in registers.
 #pragma once
+#include <type_traits>
+
 #include "geom.hpp"
 
 namespace vmm {
@@ -16,6 +24,9 @@ __device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
 // (v = a * b + c: v - v becomes fma(a, b, c - v), the rounding error of v instead of zero), which reports a perfectly
 // finite v as non-finite; where that would be wrong rather than merely slow, ask this one.
 __device__ __forceinline__ bool finite_bits(double v) { return __builtin_isfinite(v); }
+
+template <bool BITS>
+__device__ __forceinline__ bool finite_v(double v) { return BITS ? finite_bits(v) : finite_d(v); }
 
 // Eigen::Quaterniond(R) (trace test), normalised; R row-major.
 __device__ __forceinline__ void quat_from_R(const double* R, double* q)
@@ -83,7 +94,7 @@ __device__ __forceinline__ void chain_tag(const Rigid& rel, const Rigid& cam, Ri
 
 // (A + lam diag(max(A_ii, 1e-12))) step = -g by Cholesky; A packed lower (tri6).  false: not positive definite.
 // BITS: test finiteness with finite_bits instead of finite_d.
-template <bool BITS = false>
+template <bool BITS>
 __device__ __forceinline__ bool solve6(const double (&A)[21], const double (&g)[6], const double lam, double (&step)[6])
 {
     double L[21];
@@ -102,7 +113,7 @@ __device__ __forceinline__ bool solve6(const double (&A)[21], const double (&g)[
 #pragma unroll
         for (int k = 0; k < j; ++k)
             d -= L[tri6(j, k)] * L[tri6(j, k)];
-        ok = ok && d > 0.0 && (BITS ? finite_bits(d) : finite_d(d));
+        ok = ok && d > 0.0 && finite_v<BITS>(d);
         const double s = sqrt(d);
         L[tri6(j, j)] = s;
         const double is = 1.0 / s;
@@ -134,7 +145,7 @@ __device__ __forceinline__ bool solve6(const double (&A)[21], const double (&g)[
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i)
-        ok = ok && (BITS ? finite_bits(step[i]) : finite_d(step[i]));
+        ok = ok && finite_v<BITS>(step[i]);
     return ok;
 }
 
@@ -148,6 +159,27 @@ __device__ __forceinline__ void accumulate_rows(const double (&j)[2][6], const d
         for (int b = 0; b <= a; ++b)
             A[tri6(a, b)] += j[0][a] * j[0][b] + j[1][a] * j[1][b];
     }
+}
+
+__device__ __forceinline__ void zero_normal(double (&A)[21], double (&g)[6])
+{
+#pragma unroll
+    for (int k = 0; k < 21; ++k)
+        A[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        g[k] = 0.0;
+}
+
+// every lane ends with the wave's totals (wave_sum's fixed butterfly)
+__device__ __forceinline__ void wave_sum_normal(double (&A)[21], double (&g)[6])
+{
+#pragma unroll
+    for (int k = 0; k < 21; ++k)
+        A[k] = wave_sum(A[k]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        g[k] = wave_sum(g[k]);
 }
 
 __device__ __forceinline__ double max_abs6(const double (&s)[6])
@@ -164,6 +196,113 @@ __device__ __forceinline__ double max_abs6(const double (&s)[6])
 __device__ __forceinline__ bool cost_at_floor(const double cost, const double cand)
 {
     return cand - cost <= 1e-10 * cost + 1e-20;
+}
+
+// Levenberg-Marquardt over the 6 tangent degrees of freedom of q (in place), at most max_trials trials (accepted +
+// rejected); returns the trials spent.  sums(jac, q, A, g) returns the cost at q and, when jac is std::true_type, fills
+// J^T J (packed lower) and J^T r.  cost receives the cost of the last evaluation with Jacobians: that of q, except
+// after the STOP_SMALL exit, where it is the cost before the last accepted step.
+// STOP_SMALL: also stop after an accepted step below 1e-9 (an initial guess for the bundle adjustment needs no more).
+// BITS: test finiteness with finite_bits instead of finite_d.
+// The invariant every caller keeps: all threads that run the driver together (a lane alone, a wave, or a workgroup when
+// sums contains __syncthreads) hold the same sums, so they take the same branches and reach the same barriers.
+template <bool BITS, bool STOP_SMALL, typename Sums>
+__device__ __forceinline__ int lm_refine(double* q, const int max_trials, Sums&& sums, double& cost)
+{
+    double cand[7], A[21], g[6], step[6];
+    double lam = kLamInit;
+    cost = sums(std::true_type{}, q, A, g);
+    int it = 0;
+    for (; it < max_trials; ++it) {
+        if (!finite_v<BITS>(cost) || lam > kLamMax)
+            break;
+        if (!solve6<BITS>(A, g, lam, step)) {
+            lam *= 10.0;
+            continue;
+        }
+        const double sm = max_abs6(step);
+        if (sm < 1e-14)
+            break;
+        pose_plus(q, step, cand);
+        double A2[21], g2[6];
+        const double cc = sums(std::false_type{}, cand, A2, g2);
+        if (finite_v<BITS>(cc) && cc < cost) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k)
+                q[k] = cand[k];
+            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
+            if (STOP_SMALL && sm < 1e-9)
+                break;
+            cost = sums(std::true_type{}, q, A, g);
+        } else {
+            if (sm < 1e-10 || cost_at_floor(cost, cc))
+                break;
+            lam *= 10.0;
+        }
+    }
+    return it;
+}
+
+// The camera half of eval_corner (geom.hpp) on a point already rotated into the camera frame, b = R P: residual of
+// the projection of b + t against the observed pixel and, with JAC, the 2 x 6 Jacobian over the pose's tangent
+// (translation, half-angle rotation).  CAMERA_MODEL: project like CameraModel::projectPoint (src/CameraModel.cpp:6-26,
+// what vmm_ba_project_points computes); eval_corner has no Jacobian for that projection -- it is the functor's with the
+// two entries of d(yd)/d(x, y) that the aliased term 2 p2 (xd - x) y adds.
+template <bool CAMERA_MODEL, bool JAC>
+__device__ __forceinline__ void project_camera_point(const Intrinsics& K, const double b0, const double b1, const double b2,
+                                                     const double (&t)[3], const double u_obs, const double v_obs, double& ru,
+                                                     double& rv, double (&j)[2][6])
+{
+    const double iz = 1.0 / (b2 + t[2]);
+    const double x = (b0 + t[0]) * iz, y = (b1 + t[1]) * iz;
+    const double r2 = x * x + y * y;
+    const double rad = 1.0 + r2 * (K.k1 + r2 * (K.k2 + r2 * K.k3));
+    double xd, yd;
+    distort(K, CAMERA_MODEL, x, y, r2, rad, xd, yd);
+    ru = K.fx * xd + K.cx - u_obs;
+    rv = K.fy * yd + K.cy - v_obs;
+    if (!JAC)
+        return;
+    const double dr = K.k1 + r2 * (2.0 * K.k2 + 3.0 * K.k3 * r2);
+    const double D00 = rad + 2.0 * x * x * dr + 2.0 * K.p1 * y + 6.0 * K.p2 * x;
+    const double D01 = 2.0 * x * y * dr + 2.0 * K.p1 * x + 2.0 * K.p2 * y;
+    double D10 = D01, D11 = rad + 2.0 * y * y * dr + 2.0 * K.p2 * x + 6.0 * K.p1 * y;
+    if (CAMERA_MODEL) {
+        D10 = D01 + 2.0 * K.p2 * y * (D00 - 1.0);
+        D11 = D11 + 2.0 * K.p2 * (xd - x) + 2.0 * K.p2 * y * D01;
+    }
+    const double g[2][3] = { { K.fx * D00 * iz, K.fx * D01 * iz, -K.fx * (D00 * x + D01 * y) * iz },
+                             { K.fy * D10 * iz, K.fy * D11 * iz, -K.fy * (D10 * x + D11 * y) * iz } };
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        j[r][0] = g[r][0];
+        j[r][1] = g[r][1];
+        j[r][2] = g[r][2];
+        j[r][3] = 2.0 * (b1 * g[r][2] - b2 * g[r][1]);
+        j[r][4] = 2.0 * (b2 * g[r][0] - b0 * g[r][2]);
+        j[r][5] = 2.0 * (b0 * g[r][1] - b1 * g[r][0]);
+    }
+}
+
+// The candidate winner rule: the lowest score wins, ties go to the lowest index, NaN and +inf lose (a thread that found
+// no candidate holds (kInf, INT_MAX)).  better: whether (score, index) beats (other_score, other_index).
+__device__ __forceinline__ bool better(const double score, const int index, const double other_score, const int other_index)
+{
+    return score < other_score || (score == other_score && index < other_index);
+}
+
+// the wave's winner in every lane; the waves of a workgroup then meet in LDS and are taken in wave order
+__device__ __forceinline__ void wave_winner(double& best, int& best_c)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double os = __shfl_xor(best, m, 64);
+        const int oc = __shfl_xor(best_c, m, 64);
+        if (better(os, oc, best, best_c)) {
+            best = os;
+            best_c = oc;
+        }
+    }
 }
 
 __device__ __forceinline__ double corner_sx(int k) { return (k == 1 || k == 2) ? 1.0 : -1.0; }   // LL, LR, UR, UL

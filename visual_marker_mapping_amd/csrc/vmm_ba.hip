@@ -1019,8 +1019,7 @@ int vmm_ba_create(const vmm_ba_problem* p, const vmm_ba_create_options* copt, vm
     e.f32_accum = co.precision == VMM_BA_PRECISION_F32_ACCUM;
     e.multi = e.world > 1 || e.sw.force_collectives;   // test hook: one rank, but staging buffers + eager launches + all-reduce callbacks
     e.rccl_graph = e.sw.rccl_graph;
-    e.K.fx = p->intr[0]; e.K.fy = p->intr[1]; e.K.cx = p->intr[2]; e.K.cy = p->intr[3];
-    e.K.k1 = p->dist[0]; e.K.k2 = p->dist[1]; e.K.p1 = p->dist[2]; e.K.p2 = p->dist[3]; e.K.k3 = p->dist[4];
+    e.K = make_intrinsics(p->intr, p->dist);
     e.n_cams = p->n_cams;
     e.n_tags = p->n_tags;
     e.fixed_tag = user->fixed_tag;
@@ -1512,9 +1511,7 @@ int vmm_ba_project_points(const double intr[4], const double dist[5], int64_t n,
     if (n == 0)
         return VMM_BA_OK;
     HIP_TRY(hipSetDevice(device));
-    Intrinsics K;
-    K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3];
-    K.k1 = dist[0]; K.k2 = dist[1]; K.p1 = dist[2]; K.p2 = dist[3]; K.k3 = dist[4];
+    const Intrinsics K = make_intrinsics(intr, dist);
     // CameraModel::projectPoint is called point by point by its users: the device buffer of small calls is kept per
     // device (grown on demand, up to 1 M points = 40 MB; larger calls allocate and free), calls are serialised
     static std::mutex mu;
@@ -1522,29 +1519,29 @@ int vmm_ba_project_points(const double intr[4], const double dist[5], int64_t n,
     static int64_t cache_cap[kMaxProjectDevices] = {};
     std::lock_guard<std::mutex> lock(mu);
     const bool cached = n <= (int64_t)1 << 20 && device >= 0 && device < kMaxProjectDevices;
+    Arena ar;   // owns the buffer of a call that is not cached
     double* buf = nullptr;
     if (cached && cache_cap[device] >= n) {
         buf = cache[device];
     } else {
         const int64_t cap = cached ? std::max<int64_t>(n, 1024) : n;
-        HIP_TRY(hipMalloc((void**)&buf, sizeof(double) * 5 * (size_t)cap));
+        HIP_TRY(ar.alloc(sizeof(double) * 5 * (size_t)cap));
+        buf = reinterpret_cast<double*>(ar.base);
         if (cached) {
             if (cache[device])
                 (void)hipFree(cache[device]);
             cache[device] = buf;
             cache_cap[device] = cap;
+            ar.base = nullptr;   // the cache owns it now
         }
     }
     double *d_p = buf, *d_uv = buf + 3 * n;
-    hipError_t err = hipMemcpy(d_p, points_cam, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
+    ar.copy(d_p, points_cam, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
+    if (ar.err == hipSuccess)
         launch_project(nullptr, K, n, d_p, d_uv);
-        err = hipMemcpy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
-    }
-    if (!cached)
-        (void)hipFree(buf);
-    if (err != hipSuccess) {
-        set_error(std::string("project_points: ") + hipGetErrorString(err));
+    ar.copy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
+    if (ar.err != hipSuccess) {
+        set_error(std::string("project_points: ") + hipGetErrorString(ar.err));
         return VMM_BA_ERR_HIP;
     }
     return VMM_BA_OK;
@@ -1559,18 +1556,16 @@ int vmm_ba_pose_plus(int64_t n, const double* qt, const double* delta, double* o
     if (n == 0)
         return VMM_BA_OK;
     HIP_TRY(hipSetDevice(device));
-    double* d = nullptr;   // qt | delta | out
-    HIP_TRY(hipMalloc((void**)&d, sizeof(double) * 20 * n));
-    hipError_t err = hipMemcpy(d, qt, sizeof(double) * 7 * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = hipMemcpy(d + 7 * n, delta, sizeof(double) * 6 * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
+    Arena ar;   // qt | delta | out
+    HIP_TRY(ar.alloc(sizeof(double) * 20 * n));
+    double* const d = reinterpret_cast<double*>(ar.base);
+    ar.copy(d, qt, sizeof(double) * 7 * n, hipMemcpyHostToDevice);
+    ar.copy(d + 7 * n, delta, sizeof(double) * 6 * n, hipMemcpyHostToDevice);
+    if (ar.err == hipSuccess)
         launch_pose_plus(nullptr, n, d, d + 7 * n, d + 13 * n);
-        err = hipMemcpy(out, d + 13 * n, sizeof(double) * 7 * n, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d);
-    if (err != hipSuccess) {
-        set_error(std::string("pose_plus: ") + hipGetErrorString(err));
+    ar.copy(out, d + 13 * n, sizeof(double) * 7 * n, hipMemcpyDeviceToHost);
+    if (ar.err != hipSuccess) {
+        set_error(std::string("pose_plus: ") + hipGetErrorString(ar.err));
         return VMM_BA_ERR_HIP;
     }
     return VMM_BA_OK;
@@ -1586,24 +1581,19 @@ int vmm_ba_quad_poses(const double intr[4], const double dist[5], int64_t n, con
     if (n == 0)
         return VMM_BA_OK;
     HIP_TRY(hipSetDevice(device));
-    Intrinsics K;
-    K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3];
-    K.k1 = dist[0]; K.k2 = dist[1]; K.p1 = dist[2]; K.p2 = dist[3]; K.k3 = dist[4];
-    double* d = nullptr;   // tag_wh | obs_px | qt2 | rms2
-    HIP_TRY(hipMalloc((void**)&d, sizeof(double) * 26 * n));
+    const Intrinsics K = make_intrinsics(intr, dist);
+    Arena ar;   // tag_wh | obs_px | qt2 | rms2
+    HIP_TRY(ar.alloc(sizeof(double) * 26 * n));
+    double* const d = reinterpret_cast<double*>(ar.base);
     double *d_wh = d, *d_px = d + 2 * n, *d_qt = d + 10 * n, *d_rms = d + 24 * n;
-    hipError_t err = hipMemcpy(d_wh, tag_wh, sizeof(double) * 2 * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-        err = hipMemcpy(d_px, obs_px, sizeof(double) * 8 * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
+    ar.copy(d_wh, tag_wh, sizeof(double) * 2 * n, hipMemcpyHostToDevice);
+    ar.copy(d_px, obs_px, sizeof(double) * 8 * n, hipMemcpyHostToDevice);
+    if (ar.err == hipSuccess)
         launch_quad_poses(nullptr, K, n, d_wh, d_px, d_qt, d_rms);
-        err = hipMemcpy(qt2, d_qt, sizeof(double) * 14 * n, hipMemcpyDeviceToHost);
-    }
-    if (err == hipSuccess)
-        err = hipMemcpy(rms2, d_rms, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (err != hipSuccess) {
-        set_error(std::string("quad_poses: ") + hipGetErrorString(err));
+    ar.copy(qt2, d_qt, sizeof(double) * 14 * n, hipMemcpyDeviceToHost);
+    ar.copy(rms2, d_rms, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
+    if (ar.err != hipSuccess) {
+        set_error(std::string("quad_poses: ") + hipGetErrorString(ar.err));
         return VMM_BA_ERR_HIP;
     }
     return VMM_BA_OK;

@@ -10,6 +10,7 @@ startReconstruction (the incremental driver) is ho
 path; its two PnP initialisations (OpenCV in the reference) live in pnp.py.  Callers may also provide
 initial poses through setReconstructedTags / setReconstructedCameras and call doBundleAdjustment directly.
 """
+import contextlib
 import math
 import os
 
@@ -208,13 +209,28 @@ class TagReconstructor:
         The bundle adjustments and the reprojection statistics run on the MI355X through libvmm_ba; the two
         PnP initialisations are host code in pnp.py (OpenCV's role in the reference)."""
         from . import pnp as _pnp
-        self._resident = bool(deviceResident)
-        try:
+        with self._resident_frame(deviceResident):
             self._start_reconstruction(numThreads, _pnp)
+
+    @contextlib.contextmanager
+    def _resident_frame(self, resident=True):
+        """The frame of a whole-run driver: the device-resident packing while it runs; afterwards, however it ends,
+        the cached handle is released and the full arrays are dropped."""
+        self._resident = bool(resident)
+        try:
+            yield
         finally:
             self._resident = False
             self._drop_cached()
             self._full = None
+
+    def _closing_sequence(self, numThreads):
+        """The reference's closing sequence (src/TagReconstructor.cpp:271-277)."""
+        print("Starting final bundle adjustment")
+        self.doBundleAdjustment(1500, numThreads, True, False)
+        self.removeBadMarkers(2.0)
+        self.removeBadCameras(2.0)
+        self.doBundleAdjustment(1500, numThreads, False, True)
 
     def _start_reconstruction(self, numThreads, _pnp):
         if self.originTagId == -1:
@@ -284,11 +300,7 @@ class TagReconstructor:
                 break
             print("----------------------------------------------------------")
 
-        print("Starting final bundle adjustment")
-        self.doBundleAdjustment(1500, numThreads, True, False)
-        self.removeBadMarkers(2.0)
-        self.removeBadCameras(2.0)
-        self.doBundleAdjustment(1500, numThreads, False, True)
+        self._closing_sequence(numThreads)
 
     def startReconstructionGlobal(self, numThreads=1, **init_options):
         """Not in the reference API: the same map as startReconstruction without its N + 2 dependent bundle
@@ -298,13 +310,8 @@ class TagReconstructor:
         DESIGN.md section 9) -- these become the reconstructed sets; then the reference's closing sequence
         (src/TagReconstructor.cpp:271-277): BA(1500, robust), both prunings, BA(1500, plain, summary).
         init_options: fields of vmm_ba_init_options.  The report of the initialisation is kept in lastInitReport."""
-        self._resident = True
-        try:
+        with self._resident_frame():
             self._start_reconstruction_global(numThreads, init_options)
-        finally:
-            self._resident = False
-            self._drop_cached()
-            self._full = None
 
     def _start_reconstruction_global(self, numThreads, init_options):
         if self.originTagId == -1:
@@ -318,6 +325,26 @@ class TagReconstructor:
             id=self.originTagId, tagType=o.tagType, tagWidth=o.width, tagHeight=o.height))
         # the resident packing with nothing but the origin tag reconstructed: every other pose is a placeholder that
         # still gives finite residuals (cameras 1 m in front of tags at identity)
+        reached = self._initialize_on_device(tagById, init_options)
+        imagesOfTag = {}
+        for ob in self.detectionResults_.tagObservations:
+            imagesOfTag.setdefault(ob.tagId, set()).add(ob.imageId)
+        for tid, recTag in reached:
+            if tid == self.originTagId:
+                continue
+            if recTag is not None:
+                self.reconstructedTags[tid] = recTag
+            elif len(imagesOfTag.get(tid, ())) == 1:
+                print("   Skipping reconstruction of tag %d: Only observed once!" % tid)
+
+        self._closing_sequence(numThreads)
+
+    def _initialize_on_device(self, tagById, init_options):
+        """The stage startReconstructionGlobal and extendReconstruction share: packs the whole detection result around
+        the tags reconstructed so far, runs vmm_ba_initialize on ONE handle, keeps and prints the report, and makes
+        every reached image a reconstructed camera.  Returns, in the order of the packed tags, (tag id, the
+        ReconstructedTag at its initialised pose -- None when the tag was not reached or is not in the detection
+        result's tag list); which of them join the map is the caller's rule."""
         p = self._pack_resident(for_ba=True)
         full = self._full
         ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
@@ -335,27 +362,18 @@ class TagReconstructor:
         if not cam_ok.any():
             raise RuntimeError("No reconstructed tags in image found. To reconstruct the image pose "
                                "already reconstructed markers are needed. This should NOT happen.")
-        imagesOfTag = {}
-        for ob in self.detectionResults_.tagObservations:
-            imagesOfTag.setdefault(ob.tagId, set()).add(ob.imageId)
         for r, cid in enumerate(full["cams"].tolist()):
             if cam_ok[r]:
                 self.reconstructedCameras[cid] = Camera(cameraId=cid, q=cam[r, :4], t=cam[r, 4:])
+        reached = []
         for r, tid in enumerate(full["tags"].tolist()):
-            if tid == self.originTagId:
-                continue
+            recTag = None
             if tag_ok[r] and tid in tagById:
                 d = tagById[tid]
-                self.reconstructedTags[tid] = ReconstructedTag(id=tid, tagType=d.tagType, q=tag[r, :4], t=tag[r, 4:],
-                                                               tagWidth=d.width, tagHeight=d.height)
-            elif len(imagesOfTag.get(tid, ())) == 1:
-                print("   Skipping reconstruction of tag %d: Only observed once!" % tid)
-
-        print("Starting final bundle adjustment")
-        self.doBundleAdjustment(1500, numThreads, True, False)
-        self.removeBadMarkers(2.0)
-        self.removeBadCameras(2.0)
-        self.doBundleAdjustment(1500, numThreads, False, True)
+                recTag = ReconstructedTag(id=tid, tagType=d.tagType, q=tag[r, :4], t=tag[r, 4:],
+                                          tagWidth=d.width, tagHeight=d.height)
+            reached.append((tid, recTag))
+        return reached
 
     def extendReconstruction(self, numThreads=1, **init_options):
         """Not in the reference API: grows a finished map with new images while every tag of the map stays where it
@@ -380,15 +398,12 @@ class TagReconstructor:
         self.reconstructedTags = dict(packed_map)
         self.reconstructedCameras = {}
         self.constantTagIds = saved_const | set(packed_map)
-        self._resident = True
         done = False
         try:
-            self._extend_reconstruction(numThreads, init_options)
+            with self._resident_frame():
+                self._extend_reconstruction(numThreads, init_options)
             done = True
         finally:
-            self._resident = False
-            self._drop_cached()
-            self._full = None
             self.constantTagIds = saved_const
             if done:
                 # the map tags no new image sees were never packed
@@ -402,37 +417,10 @@ class TagReconstructor:
     def _extend_reconstruction(self, numThreads, init_options):
         tagById = {t.tagId: t for t in self.detectionResults_.tags}
         # the resident packing with the observed map tags reconstructed (and constant): every other pose is a placeholder
-        p = self._pack_resident(for_ba=True)
-        full = self._full
-        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
-        try:
-            ba.set_observation_mask(None)
-            report, cam_ok, tag_ok = ba.initialize(**init_options)
-            cam, tag = ba.get_state()
-        except Exception:
-            self._drop_cached()
-            raise
-        self.lastInitReport = report
-        print("Initialized %d of %d cameras and %d of %d tags in %d rounds, average reprojection error %g"
-              % (report["cams_reached"], len(cam_ok), report["tags_reached"], len(tag_ok), report["rounds"],
-                 report["avg_reprojection_px"]))
-        if not cam_ok.any():
-            raise RuntimeError("No reconstructed tags in image found. To reconstruct the image pose "
-                               "already reconstructed markers are needed. This should NOT happen.")
-        for r, cid in enumerate(full["cams"].tolist()):
-            if cam_ok[r]:
-                self.reconstructedCameras[cid] = Camera(cameraId=cid, q=cam[r, :4], t=cam[r, 4:])
-        for r, tid in enumerate(full["tags"].tolist()):
-            if tid in self.reconstructedTags or not tag_ok[r] or tid not in tagById:
-                continue
-            d = tagById[tid]
-            self.reconstructedTags[tid] = ReconstructedTag(id=tid, tagType=d.tagType, q=tag[r, :4], t=tag[r, 4:],
-                                                           tagWidth=d.width, tagHeight=d.height)
-        print("Starting final bundle adjustment")
-        self.doBundleAdjustment(1500, numThreads, True, False)
-        self.removeBadMarkers(2.0)
-        self.removeBadCameras(2.0)
-        self.doBundleAdjustment(1500, numThreads, False, True)
+        for tid, recTag in self._initialize_on_device(tagById, init_options):
+            if recTag is not None and tid not in self.reconstructedTags:
+                self.reconstructedTags[tid] = recTag
+        self._closing_sequence(numThreads)
 
     def computeRelativeCameraPoseFromImg(self, imageId, intr, dist, observations=None):
         """src/TagReconstructor.cpp:280-312: (q, t) of the camera from every correspondence between this
@@ -668,14 +656,26 @@ class TagReconstructor:
             pass
 
     # -- the hot path --
+    def _pack_for_ba(self):
+        """The packed problem of a bundle adjustment, or None for an empty one -- Ceres solves that trivially:
+        CONVERGENCE, nothing changes."""
+        p = self._pack(for_ba=True)
+        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
+            print("Solution %d" % _engine.CONVERGENCE)
+            self.lastSummary = {"termination_type": _engine.CONVERGENCE, "iterations": 1}
+            return None
+        return p
+
+    def _write_back_cameras(self, p, cam):
+        for k, cid in zip(p["cam_rows"], p["cam_ids"]):
+            self.reconstructedCameras[cid].q = cam[k, :4].copy()
+            self.reconstructedCameras[cid].t = cam[k, 4:].copy()
+
     def doBundleAdjustment(self, maxNumIterations, ceresThreads=1, robustify=True, printSummary=False,
                            elimination=_engine.ELIM_AUTO):
         """src/TagReconstructor.cpp:646-743.  Poses are updated in place like the reference's map nodes."""
-        p = self._pack(for_ba=True)
-        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
-            # Ceres solves an empty problem trivially: CONVERGENCE, nothing changes
-            print("Solution %d" % _engine.CONVERGENCE)
-            self.lastSummary = {"termination_type": _engine.CONVERGENCE, "iterations": 1}
+        p = self._pack_for_ba()
+        if p is None:
             return
         ba = self._engine_for(p, elimination=elimination)
         try:
@@ -687,9 +687,7 @@ class TagReconstructor:
         except Exception:
             self._drop_cached()
             raise
-        for k, cid in zip(p["cam_rows"], p["cam_ids"]):
-            self.reconstructedCameras[cid].q = cam[k, :4].copy()
-            self.reconstructedCameras[cid].t = cam[k, 4:].copy()
+        self._write_back_cameras(p, cam)
         for k, tid in zip(p["tag_rows"], p["tag_ids"]):
             self.reconstructedTags[tid].q = tag[k, :4].copy()
             self.reconstructedTags[tid].t = tag[k, 4:].copy()
@@ -729,10 +727,8 @@ class TagReconstructor:
         rebuilt from the optimised corners as at :608-639 (with today's corner order, see vmm_ba.h); the corners
         themselves are kept in self.lastPoints (tag id -> 4 x 3).  The corners of the tags in constantTagIds are
         constant too, and those tags' q and t are left as they are, bit for bit."""
-        p = self._pack(for_ba=True)
-        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
-            print("Solution %d" % _engine.CONVERGENCE)
-            self.lastSummary = {"termination_type": _engine.CONVERGENCE, "iterations": 1}
+        p = self._pack_for_ba()
+        if p is None:
             return
         ba = self._engine_for(p, elimination=elimination, landmarks=_engine.LANDMARK_POINTS)
         try:
@@ -744,9 +740,7 @@ class TagReconstructor:
         except Exception:
             self._drop_cached()
             raise
-        for k, cid in zip(p["cam_rows"], p["cam_ids"]):
-            self.reconstructedCameras[cid].q = cam[k, :4].copy()
-            self.reconstructedCameras[cid].t = cam[k, 4:].copy()
+        self._write_back_cameras(p, cam)
         self.lastPoints = {}
         for k, tid in zip(p["tag_rows"], p["tag_ids"]):
             self.lastPoints[tid] = pts[k].copy()

@@ -1,7 +1,7 @@
 """A spin give-up is not an indefinite matrix.
 
-k_chol_dataflow and k_backsolve_chain (visual_marker_mapping_amd/csrc/kernels_chol.hip) hand data between workgroups
-inside one launch with bounded spins.  A spin that gives up -- a GPU time-sliced between rank processes, a profiler
+k_chol_dataflow and k_backsolve_chain (kernels_chol_dataflow.hip, kernels_backsolve.hip in visual_marker_mapping_amd/csrc)
+hand data between workgroups inside one launch with bounded spins.  A spin that gives up -- a GPU time-sliced between rank processes, a profiler
 serialising workgroups -- used to raise LmCtl::lin_fail, which the trust-region policy (Ceres' HandleInvalidStep:
 radius shrink, retry, FAILURE after five) takes for a failed linear solve: a scheduling event silently changed the LM
 trajectory.  Now it raises LmCtl::sync_timeout, pauses the pass, and the host redoes that pass's factorisation on the

@@ -155,7 +155,7 @@ def test_shard_bounds_cover_and_balance():
 
 
 def _replay_chol_schedule(n_blk, n_df, n_cu=256):
-    """Replays the launch schedule of the launch-per-column Cholesky (csrc/kernels_chol.hip, chol_step_schedule) on a
+    """Replays the launch schedule of the launch-per-column Cholesky (csrc/kernels_chol_step.hip, chol_step_schedule) on a
     model of the block matrix: which panels has every tile (block row i >= block column j; i == n_blk is the right-hand
     side row) received so far?"""
     import ctypes as C

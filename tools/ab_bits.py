@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Bit comparison of two builds of libvmm_ba.so on the single-pose solver's three entries: vmm_ba_quad_poses,
-vmm_ba_initialize and vmm_ba_localize.
+"""Bit comparison of two builds of libvmm_ba.so.  --cases pose (default): the single-pose solver's three entries,
+vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every Cholesky and back-substitution kernel
+(csrc/kernels_chol*.hip, kernels_backsolve.hip) through vmm_ba_dense_spd_solve and a tree-ordered bundle adjustment.
 
-    python tools/ab_pose_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
@@ -86,14 +87,82 @@ def _localize_cases(eng, make_scene, out):
             out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
 
 
-def child(path):
+class _Env:
+    """Switches of the engine for one case (a handle and vmm_ba_dense_spd_solve read them when they are created / called)."""
+
+    def __init__(self, **kw):
+        self.kw = {k: str(v) for k, v in kw.items()}
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kw}
+        os.environ.update(self.kw)
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def _chol_dense_cases(eng, out):
+    """vmm_ba_dense_spd_solve on seeded SPD systems, the smallest orders that reach every kernel and loop trip: 40 (one
+    block: the chain's single-block exit), 130 (3 blocks: one hop, one trip behind it), 300 (5: several trips with the
+    next tile requested ahead), 1200 (19: the benchmark's size), 3136 (49: launch-per-column steps with paired rank-128
+    updates, the hand-over launch, the dataflow tail, the chain over 49 blocks); 300 without the dataflow kernel
+    (k_chol_step all the way, rank-64 updates) and without the chain (k_backsolve_step); 1200 on the bulk kernel; an
+    indefinite 70 x 70 matrix (info on the failure path)."""
+    def system(n):
+        rng = np.random.default_rng(7000 + n)
+        M = rng.normal(size=(n, n))
+        return M @ M.T + n * np.eye(n), rng.normal(size=n)
+
+    cases = [("n40", 40, {}), ("n130", 130, {}), ("n300", 300, {}), ("n1200", 1200, {}), ("n3136", 3136, {}),
+             ("n300_no_dataflow", 300, dict(VMM_BA_NO_DATAFLOW=1)), ("n300_no_chain", 300, dict(VMM_BA_NO_CHAIN=1)),
+             ("n1200_df_bulk", 1200, dict(VMM_BA_DF_BULK=1))]
+    for name, n, env in cases:
+        A, b = system(n)
+        with _Env(**env):
+            x, info = eng.dense_spd_solve(A, b)
+        out["dense_%s_x" % name], out["dense_%s_info" % name] = x, np.array([info], np.int32)
+    A, b = system(70)
+    A[35, 35] = -1.0
+    x, info = eng.dense_spd_solve(A, b)
+    out["dense_indefinite70_x"], out["dense_indefinite70_info"] = x, np.array([info], np.int32)
+
+
+def _chol_tree_cases(eng, make_scene, out):
+    """A close-up scene whose kept family gets a tree ordering (tree_ordering >= 3): k_chol_dataflow_tree and
+    k_backsolve_chain_tree; the same with helper waves; the same with every chain giving up and its pass redone."""
+    s = make_scene(1, n_cams=60, n_tags=70, neighbors_min=3, neighbors_max=6)
+    base = dict(VMM_BA_ORDER="nd", VMM_BA_SCHUR="sparse")
+    for name, env in (("tree", {}), ("tree_help", dict(VMM_BA_DF_HELP=1)),
+                      ("tree_chain_redone", dict(VMM_BA_DEBUG_SPIN_LIMIT=1, VMM_BA_DEBUG_SPIN_KERNEL="chain",
+                                                 VMM_BA_DEBUG_SPIN_ONCE=0))):
+        with _Env(**base, **env):
+            with eng.BundleAdjuster(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag,
+                                    s.obs_px) as ba:
+                res = ba.solve(eng.default_options(max_num_iterations=6), trace_capacity=16)
+                cam_qt, tag_qt = ba.get_state()
+        assert res["tree_ordering"] >= 3, res["tree_ordering"]   # else the tree kernels did not run: pick another scene
+        out["%s_costs" % name] = np.array([it["cost"] for it in res["trace"]])
+        out["%s_cam_qt" % name], out["%s_tag_qt" % name] = cam_qt, tag_qt
+        out["%s_tree_ordering" % name] = np.array([res["tree_ordering"], res["block_sparse"]], np.int32)
+        out["%s_redone" % name] = np.array([res["num_sync_timeouts"] > 0], np.int32)
+
+
+def child(path, cases):
     sys.path.insert(0, ROOT)
     from visual_marker_mapping_amd import engine as eng
     from visual_marker_mapping_amd.synthetic import make_scene
     out = {}
-    _quad_cases(eng, out)
-    _init_cases(eng, make_scene, out)
-    _localize_cases(eng, make_scene, out)
+    if cases == "pose":
+        _quad_cases(eng, out)
+        _init_cases(eng, make_scene, out)
+        _localize_cases(eng, make_scene, out)
+    else:
+        _chol_dense_cases(eng, out)
+        _chol_tree_cases(eng, make_scene, out)
     np.savez(path, **out)
 
 
@@ -101,20 +170,21 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
+    ap.add_argument("--cases", choices=("pose", "chol"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        return child(args.child)
+        return child(args.child, args.cases)
     if not args.a or not args.b:
         ap.error("--a and --b are required")
-    keep = args.keep or tempfile.mkdtemp(prefix="ab_pose_bits_")
+    keep = args.keep or tempfile.mkdtemp(prefix="ab_bits_")
     os.makedirs(keep, exist_ok=True)
     data = {}
     for side, lib in (("a", args.a), ("b", args.b)):
         path = os.path.join(keep, side + ".npz")
         env = dict(os.environ, VMM_BA_LIB=os.path.abspath(lib), PYTHONPATH=ROOT)
-        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, timeout=600)
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path, "--cases", args.cases], env=env, timeout=600)
         if run.returncode != 0:   # nothing more is started on the GPU after a child that failed
             print(json.dumps({"equal": False, "error": "child %s exited with %d" % (side, run.returncode)}))
             return 2
@@ -126,7 +196,7 @@ def main():
         equal = equal and same
         outputs[k] = {"equal": same, "sha256": [hashlib.sha256(data[x][k][2]).hexdigest() if k in data[x] else None
                                                 for x in ("a", "b")]}
-    print(json.dumps({"equal": equal, "a": args.a, "b": args.b, "n_outputs": len(outputs), "outputs": outputs}))
+    print(json.dumps({"equal": equal, "cases": args.cases, "a": args.a, "b": args.b, "n_outputs": len(outputs), "outputs": outputs}))
     return 0 if equal else 1
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build-time audit of the hand-issued loads in k_chol_step (kernels_chol.hip, chol_update_wg).
+"""Build-time audit of the hand-issued loads in k_chol_step (kernels_chol_step.hip, chol_update_wg).
 
 The trailing-update loop requests its C values and the next tile's operands with `global_load_*` written as inline
 asm and waits for them with a separate `s_waitcnt vmcnt(0)` asm statement 16 MFMA steps later.  hipcc does not know
@@ -18,7 +18,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "visual_marker_mapping_amd", "csrc", "kernels_chol.hip")
+SRC = os.path.join(ROOT, "visual_marker_mapping_amd", "csrc", "kernels_chol_step.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNEL = "_ZN3vmm11k_chol_step"
 

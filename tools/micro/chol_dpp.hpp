@@ -1,6 +1,6 @@
 // Pivot-block Cholesky and row scaling with one matrix ROW per lane (gfx950).
 //
-// The pivot chain of the blocked Cholesky (kernels_chol.hip) used to factor its 8x8 pivot block redundantly in every
+// The pivot chain of the blocked Cholesky (csrc/kernels_chol_step.hip, csrc/kernels_chol_dataflow.hip) used to factor its 8x8 pivot block redundantly in every
 // lane: ~176 f64 instructions per block, and on this hardware that code is ISSUE-bound (a f64 VALU instruction occupies
 // the SIMD for ~6 cycles whether or not it depends on the previous one -- tools/micro/lat2.hip -- so the 1100 cycles of
 // the 8x8 block were its instruction count, not its dependent chain of ~400).  Here lane i of every 16-lane DPP row owns
@@ -36,7 +36,7 @@ __device__ __forceinline__ void fnma_bcast(double& acc, const double b, const do
 }
 
 // 1/sqrt(v): v_rsq_f64 seed + one third-order correction (~1 ulp), branch-free; a non-positive or non-finite pivot gives
-// NaN and clears ok (same contract as safe_rsqrt of potrf64.inc)
+// NaN and clears ok (same contract as safe_rsqrt of csrc/chol_common.hpp)
 __device__ __forceinline__ double rsqrt_refined(const double v, bool& ok)
 {
     ok = ok && (v > 0.0) && isfinite(v);

@@ -1,6 +1,6 @@
-// Checks and times the DPP pivot-block primitives of csrc/chol_dpp.hpp on one wave: W x W Cholesky with a matrix row per
+// Checks and times the DPP pivot-block primitives of chol_dpp.hpp on one wave: W x W Cholesky with a matrix row per
 // lane, then the scaling of a 64-row panel, against the same operations done on the host in the same order (fma).
-// build: hipcc -O3 --offload-arch=gfx950 -I visual_marker_mapping_amd/csrc tools/micro/dpp_chol.hip -o /tmp/dpp_chol
+// build: hipcc -O3 --offload-arch=gfx950 tools/micro/dpp_chol.hip -o /tmp/dpp_chol
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>

@@ -209,7 +209,7 @@ struct Engine {
     double* Linv = nullptr;         // [n_blk][64][64] their inverses (all but the last block)
     unsigned* flags = nullptr;      // [256] unused | epoch word | abort word | two tile counters of k_chol_step | agreement word
     unsigned long long* gran = nullptr;   // [2 * ld] {epoch, 32 value bits} granules of the chain's hand-offs
-    unsigned long long* df_gran = nullptr;   // published 64x8 slices of the dataflow factorisation (<= 21 blocks)
+    unsigned long long* df_gran = nullptr;   // published 64x8 slices of the dataflow factorisation: [slot][8][kDfSlice], DfArgs::G
     double* df_compact = nullptr;            // the same blocks once they are COMPLETE, as plain doubles [slot][column][row]
     unsigned* df_done = nullptr;             // [slot] == factorisation epoch: the block's compact copy is written
     double* yf = nullptr;           // [ldz] solution of the reduced system (scaled coordinates)
@@ -330,12 +330,14 @@ void launch_syrk_reduced(Engine& e);
 void launch_pack_lower(Engine& e, bool unpack);
 void launch_syrk_plan(hipStream_t st, const LmCtl* ctl, const double* Z, int ldz, const SyrkPlan& p);
 void launch_reduce_plan(hipStream_t st, const LmCtl* ctl, const SyrkPlan& p, int ld, int n_rows, double* S);
-// kernels_chol.hip
+// kernels_chol.hip: which path factors what
 // safe: the launch-per-block-column factorisation and the per-block back-substitution (no workgroup waits on another)
 void launch_cholesky_solve(Engine& e, double* S, int n_pad, int ld, double* y, LmCtl* ctl, bool safe = false);
-void launch_chol_inverse(Engine& e, int k);
+int dataflow_workgroups(int n_blk);   // workgroups of the dense one-launch factorisation of n_blk block columns
 int dataflow_max_workgroups(int n_cu, const Switches& sw);
-int dataflow_blocks(int n_blk, int n_cu, const Switches& sw);
+int dataflow_blocks(int n_blk, int n_cu, const Switches& sw);   // trailing block columns factored by k_chol_dataflow (n_blk: all; 0: none)
+// kernels_chol_step.hip
+void launch_chol_inverse(Engine& e, int k);
 struct CholLaunch {   // one k_chol_step launch of the launch-per-column factorisation
     int k;            // block column its panel workgroups factor; -1: the update-only hand-over launch
     int lazy[2];      // panels those workgroups first apply to their own column (older first; -1: none)
@@ -343,8 +345,16 @@ struct CholLaunch {   // one k_chol_step launch of the launch-per-column factori
     int c0, t0, t1;   // first block column of the update's tile list, and the range of that list this launch takes
 };
 std::vector<CholLaunch> chol_step_schedule(int n_blk, int n_df);
-void chol_schedule_tile(int n_blk, const CholLaunch& L, int t, int* bi, int* bj);   // trailing block columns factored by k_chol_dataflow (n_blk: all; 0: none)
-int dataflow_workgroups(int n_blk);   // workgroups of k_chol_dataflow (must all fit on the chip at one per CU)
+void chol_schedule_tile(int n_blk, const CholLaunch& L, int t, int* bi, int* bj);
+void launch_chol_steps(Engine& e, double* S, int n_pad, int ld, LmCtl* ctl, int n_df);   // the schedule's launches
+int preload_chol_step_kernels();
+// kernels_chol_dataflow.hip: block columns first_blk .. n_blk-1 (+ the right-hand side row) in one launch
+void launch_dataflow(Engine& e, double* S, int n_pad, int ld, LmCtl* ctl, int first_blk, int n_blk);
+int preload_chol_dataflow_kernels();
+// kernels_backsolve.hip
+void launch_backsolve_chain(Engine& e, double* S, int n_pad, int ld, double* y, LmCtl* ctl);   // one launch
+void launch_backsolve_steps(Engine& e, double* S, int n_pad, int ld, double* y, LmCtl* ctl);   // one launch per block
+int preload_backsolve_kernels();
 // kernels_cov.hip
 void launch_cov_prepare(Engine& e);
 void launch_cov_rhs(Engine& e, double* B, int ldb, bool identity_rhs);

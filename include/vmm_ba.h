@@ -308,6 +308,25 @@ int vmm_ba_reprojection_stats(vmm_ba_handle h, double* per_cam_mean, double* per
  * unscaled normal equations; VMM_BA_ERR_NUMERIC if they are not positive definite.  Single-GPU handles. */
 int vmm_ba_tag_translation_covariance(vmm_ba_handle h, int robustify, double huber_a, double* cov);
 
+/* ABI 6 (additive).  Any 6x6 marginal or cross block of the pose covariance.
+ * cov[36*p ..] = row-major 6x6 block (pose_a[p], pose_b[p]) of (J^T J)^-1 in tangent coordinates at the current
+ * state (translation, then half-angle rotation), J with the loss applied when robustify != 0.
+ * Pose index space: cameras 0 .. n_cams-1, then tags n_cams .. n_cams+n_tags-1 (the order of scale / D2 / active).
+ * Ceres: Covariance::Compute(covariance_blocks) + GetCovarianceBlockInTangentSpace.
+ *   - The call leaves the state alone and is idempotent; a handle on the block-sparse or tree-ordered path switches to
+ *     the dense, naturally ordered system for the call and back, like vmm_ba_tag_translation_covariance.
+ *   - Pairs may repeat and come in any order; a == b is the marginal (symmetric in its bits).
+ *   - A pair that names an inactive pose (constant, origin, or without an active observation) gets 36 zeros, the
+ *     cross block included.
+ *   - The bits of a block depend neither on what else is in the request nor on the call.
+ *   - n_obs == 0: zeros.  n_pairs == 0: VMM_BA_OK without a device call.
+ * VMM_BA_ERR_ARGUMENT (before any device call) for null pointers with n_pairs > 0 or an index outside
+ * [0, n_cams + n_tags); VMM_BA_ERR_STATE for world_size > 1 or VMM_BA_LANDMARK_POINTS handles; VMM_BA_ERR_NUMERIC if
+ * the normal equations are not positive definite; VMM_BA_ERR_HIP (with the byte count in the message) if the
+ * n_pad x 6 (distinct poses, rounded up to 64 columns) right-hand side cannot be allocated. */
+int vmm_ba_covariance_blocks(vmm_ba_handle h, int robustify, double huber_a, int64_t n_pairs,
+                             const int32_t* pose_a, const int32_t* pose_b, double* cov);
+
 /* Replaces CameraModel::projectPoint (src/CameraModel.cpp:6-26) for n camera-frame points. */
 int vmm_ba_project_points(const double intr[4], const double dist[5], int64_t n,
                           const double* points_cam, double* uv, int device);

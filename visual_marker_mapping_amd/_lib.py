@@ -26,7 +26,7 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_get_state", "vmm_ba_get_points", "vmm_ba_set_allreduce", "vmm_ba_rccl_available", "vmm_ba_rccl_unique_id",
            "vmm_ba_enable_rccl",
            "vmm_ba_set_observation_mask", "vmm_ba_solve", "vmm_ba_cost",
-           "vmm_ba_reprojection_stats", "vmm_ba_tag_translation_covariance", "vmm_ba_project_points", "vmm_ba_eval_blocks",
+           "vmm_ba_reprojection_stats", "vmm_ba_tag_translation_covariance", "vmm_ba_covariance_blocks", "vmm_ba_project_points", "vmm_ba_eval_blocks",
            "vmm_ba_dense_spd_solve", "vmm_ba_dense_syrk", "vmm_ba_time_kernels", "vmm_ba_pose_plus", "vmm_ba_debug_overlap",
            "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
            "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
@@ -150,6 +150,11 @@ def lib():
         L.vmm_ba_reprojection_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_double), C.c_void_p]
         L.vmm_ba_tag_translation_covariance.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        # additive within ABI 6: a library built before the entry (VMM_BA_LIB, tools/bench_covariance.py times the parent
+        # commit's build) still loads; calling the missing entry raises AttributeError
+        if hasattr(L, "vmm_ba_covariance_blocks"):
+            L.vmm_ba_covariance_blocks.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
         L.vmm_ba_project_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_int]
         L.vmm_ba_eval_blocks.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double),

@@ -360,6 +360,9 @@ void launch_cov_prepare(Engine& e);
 void launch_cov_rhs(Engine& e, double* B, int ldb, bool identity_rhs);
 void launch_cov_trsm(Engine& e, double* B, int ldb, int n_chunks, bool identity_rhs);
 void launch_cov_gram(Engine& e, const double* X, int ldb, double* cov_dev);
+void launch_cov_rhs_slots(Engine& e, const int32_t* slot_src, int n_slots, double* B, int ldb);
+void launch_cov_trsm_mfma(Engine& e, double* B, int ldb, const std::vector<int>& chunks_at);
+void launch_cov_pairs(Engine& e, const double* X, int ldb, const int32_t* pair, int64_t n_pairs, double* cov_dev);
 // kernels_init.hip
 struct InitPass {   // one score + select + refine pass over a family
     bool sweep = false;             // false: place what is not placed yet; true: redo every placed pose

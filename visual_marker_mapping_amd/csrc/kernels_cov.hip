@@ -222,6 +222,248 @@ __global__ __launch_bounds__(256) void k_cov_gram(const double* __restrict__ X, 
             out[3 * a + b] = G[a][b];
 }
 
+// ---- any 6x6 block of (J^T J)^{-1} (vmm_ba_covariance_blocks) ----------------------------------------
+//
+// [X | U] = L^{-1} [I | Z^T]; C(p) = the six columns of pose p (of X for a kept pose, of U for an eliminated one):
+//   kept f, kept g:              Cov = C(f)^T C(g)
+//   eliminated i, kept f:        Cov = -L_i^{-T} C(i)^T C(f)            (its transpose for the pair (f, i))
+//   eliminated i, eliminated j:  Cov = L_i^{-T} (delta_ij I + C(i)^T C(j)) L_j^{-1}
+// The right-hand side holds the six columns of every distinct pose of the request ("slot" s = columns 6 s .. 6 s + 5,
+// eliminated poses first, then the kept ones by ascending row), the substitution is the right-looking walk of
+// launch_cov_trsm on the f64 matrix cores, and one workgroup per pair forms its Gram block.
+//
+// Bits: an element of X is B - L_i0 X_0 - L_i1 X_1 ... with every 64-term product summed by 16 MFMAs in ascending k on
+// top of the running value, then Linv_k times the block row in ascending k from zero: per column the same chain
+// wherever the column sits in B.  A leading block row that is skipped for a chunk holds +0 in all of its columns and
+// would stay +0 if it were processed (0 + (+-0) = +0, x - (+-0) = x), so skipping leaves the bits alone.
+
+// slot_src[s] >= 0: kept pose whose first row of the reduced system is slot_src[s]; < 0: eliminated pose -1 - slot_src[s]
+__global__ __launch_bounds__(256) void k_cov_rhs_slots(const int32_t* __restrict__ slot_src, const double* __restrict__ Z,
+                                                        int ldz, int n_red, double* __restrict__ B, int ldb)
+{
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int v = slot_src[s];
+    if (v >= 0) {
+        if (tid < 6)
+            B[(int64_t)(v + tid) * ldb + 6 * s + tid] = 1.0;
+        return;
+    }
+    const double* Ze = Z + (int64_t)6 * (-1 - v) * ldz;
+    for (int r = tid; r < n_red; r += 256)
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+            B[(int64_t)r * ldb + 6 * s + a] = Ze[(int64_t)a * ldz + r];
+}
+
+typedef double cov_double4 __attribute__((ext_vector_type(4)));
+
+// v_mfma_f64_16x16x4_f64 operand maps (kernels_schur.hip): A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
+// result col = lane & 15, row = (lane >> 4) + 4 * reg.  Wave w of a workgroup owns rows 16 w .. 16 w + 15 of a block row.
+constexpr int kLdX = 80;   // LDS row stride: rows k and k + 1 of a 32-lane ds_read_b64 group fall into opposite bank halves
+
+// X_k = Linv_k B_k in place; one workgroup per 64-column chunk.  The block row is staged in LDS: every wave reads all
+// 64 rows of it and writes 16.
+__global__ __launch_bounds__(256) void k_trsm_diag_mfma(const double* __restrict__ Linv_k, double* __restrict__ B,
+                                                        int ldb, int k)
+{
+    __shared__ double Xs[64 * kLdX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fi = lane & 15, fk = lane >> 4;
+    double* Bk = B + (int64_t)k * 64 * ldb + (int64_t)blockIdx.x * 64;
+    for (int idx = tid; idx < 4096; idx += 256) {
+        const int r = idx >> 6, c = idx & 63;
+        Xs[r * kLdX + c] = Bk[(int64_t)r * ldb + c];
+    }
+    __syncthreads();
+    cov_double4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        acc[t] = (cov_double4){ 0.0, 0.0, 0.0, 0.0 };
+    const double* Arow = Linv_k + (16 * wave + fi) * 64 + fk;
+#pragma unroll 4
+    for (int ks = 0; ks < 16; ++ks) {
+        const double a = Arow[4 * ks];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Xs[(4 * ks + fk) * kLdX + 16 * t + fi], acc[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+            Bk[(int64_t)(16 * wave + fk + 4 * reg) * ldb + 16 * t + fi] = acc[t][reg];
+}
+
+// B_i -= L_ik X_k for the block rows i > k; grid (pairs of column chunks, block rows below k).  A wave keeps its 16 x 64
+// strip of -L_ik in registers for both chunks of the workgroup; the accumulators start from B_i.  No LDS, no barrier.
+__global__ __launch_bounds__(256) void k_trsm_update_mfma(const double* __restrict__ S, int ld, double* __restrict__ B,
+                                                          int ldb, int k, int n_chunks)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fi = lane & 15, fk = lane >> 4;
+    const int i = k + 1 + (int)blockIdx.y;
+    const double* Arow = S + (int64_t)(i * 64 + 16 * wave + fi) * ld + (int64_t)k * 64 + fk;
+    double a[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks)
+        a[ks] = -Arow[4 * ks];
+    for (int ch = 2 * (int)blockIdx.x; ch < n_chunks && ch < 2 * (int)blockIdx.x + 2; ++ch) {
+        const double* Xk = B + (int64_t)k * 64 * ldb + (int64_t)ch * 64 + fi;
+        double* Bi = B + (int64_t)(i * 64 + 16 * wave + fk) * ldb + (int64_t)ch * 64 + fi;
+        cov_double4 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg)
+                acc[t][reg] = Bi[(int64_t)(4 * reg) * ldb + 16 * t];
+#pragma unroll 4
+        for (int ks = 0; ks < 16; ++ks)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], Xk[(int64_t)(4 * ks + fk) * ldb + 16 * t], acc[t], 0, 0,
+                                                              0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg)
+                Bi[(int64_t)(4 * reg) * ldb + 16 * t] = acc[t][reg];
+    }
+}
+
+// T = L^{-1} of a lower-triangular 6x6 factor (k_cov_gram's substitution)
+__device__ void inv_lower6(const double* __restrict__ L, double (&T)[6][6])
+{
+    for (int c = 0; c < 6; ++c)
+        for (int r = 0; r < 6; ++r) {
+            if (r < c) {
+                T[r][c] = 0.0;
+                continue;
+            }
+            double s = (r == c) ? 1.0 : 0.0;
+            for (int m = c; m < r; ++m)
+                s -= L[6 * r + m] * T[m][c];
+            T[r][c] = s / L[6 * r + r];
+        }
+}
+
+// One workgroup per requested pair: G = C(a)^T C(b) over the n_rows rows of X in k_cov_gram's form (thread-private sums
+// in row order, LDS tree, no floating-point atomics; 21 sums and a mirror when both slots are the same), then thread 0
+// applies the sign, delta_ij and the L^{-T} .. L^{-1} transforms of the eliminated endpoints.  pair[4 p ..] = pose a,
+// pose b (cameras, then tags), slot a, slot b.  A pair that names an inactive pose gets zeros.
+__global__ __launch_bounds__(256) void k_cov_pair(const double* __restrict__ X, int ldb, int n_rows,
+                                                   const int32_t* __restrict__ pair, int n_cams, bool elim_cams,
+                                                   const double* __restrict__ Le, const int32_t* __restrict__ active,
+                                                   double* __restrict__ cov)
+{
+    __shared__ double sh[36][256 + 1];
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int pa = pair[4 * p], pb = pair[4 * p + 1], sa = pair[4 * p + 2], sb = pair[4 * p + 3];
+    double* out = cov + 36 * p;
+    if (!active[pa] || !active[pb]) {   // constant (origin) or residual-free pose: Ceres reports zero covariance
+        if (tid < 36)
+            out[tid] = 0.0;
+        return;
+    }
+    const bool same = sa == sb;
+    const int n_sum = same ? 21 : 36;
+    double g[36];
+#pragma unroll
+    for (int q = 0; q < 36; ++q)
+        g[q] = 0.0;
+    if (same) {
+        for (int r = tid; r < n_rows; r += 256) {
+            double x[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+                x[a] = X[(int64_t)r * ldb + 6 * sa + a];
+            int q = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b <= a; ++b)
+                    g[q++] += x[a] * x[b];
+        }
+    } else {
+        for (int r = tid; r < n_rows; r += 256) {
+            double x[6], y[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                x[a] = X[(int64_t)r * ldb + 6 * sa + a];
+                y[a] = X[(int64_t)r * ldb + 6 * sb + a];
+            }
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b < 6; ++b)
+                    g[6 * a + b] += x[a] * y[b];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 36; ++q)
+        if (q < n_sum)
+            sh[q][tid] = g[q];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int q = 0; q < n_sum; ++q)
+                sh[q][tid] += sh[q][tid + s];
+        __syncthreads();
+    }
+    if (tid != 0)
+        return;
+    double G[6][6];
+    if (same) {
+        int q = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b <= a; ++b) {
+                G[a][b] = sh[q][0];
+                G[b][a] = sh[q][0];
+                ++q;
+            }
+    } else {
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b < 6; ++b)
+                G[a][b] = sh[6 * a + b][0];
+    }
+    const bool ea = elim_cams ? pa < n_cams : pa >= n_cams;
+    const bool eb = elim_cams ? pb < n_cams : pb >= n_cams;
+    if (ea && eb && pa == pb)
+        for (int a = 0; a < 6; ++a)
+            G[a][a] += 1.0;
+    double T[6][6], M[6][6];
+    if (eb) {   // G <- G L_b^{-1}
+        inv_lower6(Le + 36 * (int64_t)(elim_cams ? pb : pb - n_cams), T);
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b < 6; ++b) {
+                double s = 0.0;
+                for (int m = 0; m < 6; ++m)
+                    s += G[a][m] * T[m][b];
+                M[a][b] = s;
+            }
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b < 6; ++b)
+                G[a][b] = M[a][b];
+    }
+    if (ea) {   // G <- L_a^{-T} G
+        inv_lower6(Le + 36 * (int64_t)(elim_cams ? pa : pa - n_cams), T);
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b < 6; ++b) {
+                double s = 0.0;
+                for (int m = 0; m < 6; ++m)
+                    s += T[m][a] * G[m][b];
+                M[a][b] = s;
+            }
+        for (int a = 0; a < 6; ++a)
+            for (int b = 0; b < 6; ++b)
+                G[a][b] = M[a][b];
+    }
+    const double sign = (ea != eb) ? -1.0 : 1.0;
+    for (int a = 0; a < 6; ++a)
+        for (int b = 0; b < 6; ++b)
+            out[6 * a + b] = sign * ((pa == pb && b > a) ? G[b][a] : G[a][b]);   // a marginal is symmetric in its bits
+}
+
 // ---- launchers -------------------------------------------------------------------------------------
 
 void launch_cov_prepare(Engine& e)
@@ -263,6 +505,34 @@ void launch_cov_gram(Engine& e, const double* X, int ldb, double* cov_dev)
                        (const double*)e.Le, (const int32_t*)(e.active + e.n_cams), cov_dev);
 }
 
+void launch_cov_rhs_slots(Engine& e, const int32_t* slot_src, int n_slots, double* B, int ldb)
+{
+    hipLaunchKernelGGL(k_cov_rhs_slots, dim3(n_slots), dim3(256), 0, e.stream, slot_src, (const double*)e.Z, e.ldz, e.n_red,
+                       B, ldb);
+}
+
+// Forward substitution L X = B on the matrix cores; chunks_at[k] = leading 64-column chunks that are non-zero in block
+// row k (the chunks are ordered by their first non-zero block row).  Two launches per block row.
+void launch_cov_trsm_mfma(Engine& e, double* B, int ldb, const std::vector<int>& chunks_at)
+{
+    for (int k = 0; k < e.n_blk; ++k) {
+        const int chunks = chunks_at[(size_t)k];
+        if (chunks == 0)
+            continue;
+        hipLaunchKernelGGL(k_trsm_diag_mfma, dim3(chunks), dim3(256), 0, e.stream,
+                           (const double*)(e.Linv + (size_t)k * 4096), B, ldb, k);
+        if (k + 1 < e.n_blk)
+            hipLaunchKernelGGL(k_trsm_update_mfma, dim3((chunks + 1) / 2, e.n_blk - 1 - k), dim3(256), 0, e.stream,
+                               (const double*)e.S, e.ldz, B, ldb, k, chunks);
+    }
+}
+
+void launch_cov_pairs(Engine& e, const double* X, int ldb, const int32_t* pair, int64_t n_pairs, double* cov_dev)
+{
+    hipLaunchKernelGGL(k_cov_pair, dim3((unsigned)n_pairs), dim3(256), 0, e.stream, X, ldb, e.n_pad, pair, e.n_cams,
+                       e.elim_cams, (const double*)e.Le, (const int32_t*)e.active, cov_dev);
+}
+
 // Touches every kernel of this file once (vmm_ba_create): the code object is loaded and the kernel's resources
 // are known before any launch is recorded into a hipGraph (nothing may be loaded lazily under stream capture).
 int preload_cov_kernels()
@@ -275,6 +545,10 @@ int preload_cov_kernels()
     bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trsm_diag)) != hipSuccess;
     bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trsm_update)) != hipSuccess;
     bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_cov_gram)) != hipSuccess;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_cov_rhs_slots)) != hipSuccess;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trsm_diag_mfma)) != hipSuccess;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trsm_update_mfma)) != hipSuccess;
+    bad += hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_cov_pair)) != hipSuccess;
     return bad;
 }
 

@@ -208,6 +208,26 @@ class BundleAdjuster:
                                                                _ptr(cov)))
         return cov
 
+    def covariance_blocks(self, pairs, robustify=False, huber_a=1.0):
+        """(n_pairs, 6, 6) blocks of (J^T J)^-1 in tangent coordinates (translation, then rotation) at the current state
+        for `pairs` = (n_pairs, 2) pose indices, cameras 0 .. n_cams - 1, then tags n_cams .. n_cams + n_tags - 1
+        (vmm_ba_covariance_blocks; Ceres' Covariance::Compute + GetCovarianceBlockInTangentSpace).  Equal indices give
+        the marginal; a pair that names a constant, origin or residual-free pose gives zeros."""
+        pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+        if len(pr) and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
+            raise ValueError("pose index out of the int32 range")
+        a, b = np.ascontiguousarray(pr[:, 0], np.int32), np.ascontiguousarray(pr[:, 1], np.int32)
+        cov = np.zeros((len(pr), 6, 6))
+        _lib.check(_lib.lib().vmm_ba_covariance_blocks(self._h, int(bool(robustify)), float(huber_a), len(pr), _ptr(a),
+                                                       _ptr(b), _ptr(cov)))
+        return cov
+
+    def pose_covariances(self, robustify=False, huber_a=1.0):
+        """(cam_cov (n_cams, 6, 6), tag_cov (n_tags, 6, 6)): the 6x6 marginal of every pose, one covariance_blocks call."""
+        idx = np.arange(self.n_cams + self.n_tags)
+        cov = self.covariance_blocks(np.stack([idx, idx], axis=1), robustify, huber_a)
+        return cov[:self.n_cams], cov[self.n_cams:]
+
     # ---- diagnostics ----
     def eval_blocks(self, robustify=True, huber_a=1.0, want_W=True):
         V, U = np.zeros((self.n_cams, 6, 6)), np.zeros((self.n_tags, 6, 6))
@@ -232,6 +252,12 @@ class BundleAdjuster:
         t = _lib.KernelTimes()
         _lib.check(_lib.lib().vmm_ba_time_kernels(self._h, C.byref(o), int(reps), C.byref(t)))
         return {k: getattr(t, k) for k, _ in _lib.KernelTimes._fields_}
+
+
+def joint_covariance(caa, cab, cbb):
+    """The 12x12 covariance [[Caa, Cab], [Cab^T, Cbb]] of two poses from their marginals and their cross block."""
+    caa, cab, cbb = (np.asarray(m, np.float64).reshape(6, 6) for m in (caa, cab, cbb))
+    return np.block([[caa, cab], [cab.T, cbb]])
 
 
 def rccl_available():

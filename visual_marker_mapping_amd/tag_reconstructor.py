@@ -155,6 +155,7 @@ class TagReconstructor:
         self.device = int(device)
         self.lastSummary = None                                # summary of the last doBundleAdjustment
         self.lastCovariances = None                            # tag id -> 3x3 (last printSummary call)
+        self.lastPoseCovariances = None                        # {"tags": {id: 6x6}, "cameras": {id: 6x6}} (computePoseCovariances)
         self.lastInitReport = None                             # report of vmm_ba_initialize (startReconstructionGlobal)
         self.lastLocalizationReport = None                     # image id -> report (computeRelativeCameraPosesFromImgs)
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
@@ -717,6 +718,26 @@ class TagReconstructor:
                 avg_diag += diag
             avg_diag /= len(p["tag_ids"])
             print("Marker Position RMS = %.6g" % np.linalg.norm(np.sqrt(avg_diag)))
+
+    def computePoseCovariances(self, robustify=False):
+        """The 6x6 covariance (tangent order: translation, then rotation) of every reconstructed tag and camera at the
+        current poses, no solve: the problem doBundleAdjustment builds (origin tag and constantTagIds constant), then
+        one vmm_ba_covariance_blocks call for all marginals.  Fills and returns self.lastPoseCovariances =
+        {"tags": {id: 6x6}, "cameras": {id: 6x6}}; the origin tag and the constant tags are zeros.  Not in the
+        reference, which asks Ceres for the tags' (t, t) blocks only (src/TagReconstructor.cpp:744-783)."""
+        self.lastPoseCovariances = {"tags": {}, "cameras": {}}
+        p = self._pack(for_ba=True)
+        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
+            return self.lastPoseCovariances
+        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
+        try:
+            cam_cov, tag_cov = ba.pose_covariances(robustify, _engine.default_options().huber_a)
+        except Exception:
+            self._drop_cached()
+            raise
+        self.lastPoseCovariances["tags"] = {t: tag_cov[k].copy() for k, t in zip(p["tag_rows"], p["tag_ids"])}
+        self.lastPoseCovariances["cameras"] = {c: cam_cov[k].copy() for k, c in zip(p["cam_rows"], p["cam_ids"])}
+        return self.lastPoseCovariances
 
     def doBundleAdjustment_points(self, maxNumIterations, ceresThreads=1, printSummary=False,
                                   elimination=_engine.ELIM_AUTO):

@@ -1,0 +1,82 @@
+"""Command-line uncertainty step: how well a finished map is known.
+
+    python -m visual_marker_mapping_amd.uncertainty --project_path DIR [--map FILE] [--output FILE]
+
+Reads <project>/camera_intrinsics.json, <project>/marker_detections.json and the map (default
+<project>/reconstruction.json), builds the bundle-adjustment problem of the map at its poses (no solve) and writes
+reconstruction_uncertainty.json: the 6x6 covariance of every reconstructed tag and camera in tangent order (translation,
+then rotation), conditional on the origin tag, from one vmm_ba_covariance_blocks call.  The reference reports the
+tags' translation blocks only (src/TagReconstructor.cpp:744-783).
+
+    {"origin_tag_id": .., "robustify": ..,
+     "reconstructed_tags":    [{"id", "sigma": [6 square roots of the diagonal],
+                                "covariance": {"rows": 6, "cols": 6, "coefficents": [36 row-major values]}}],
+     "reconstructed_cameras": [the same]}
+
+(the dynamic-matrix form of SURVEY.md Appendix B, spelling included, as localization.json uses it).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+
+def uncertainty_tree(origin_tag_id, robustify, tag_cov, cam_cov):
+    """The property tree of reconstruction_uncertainty.json from plain values: tag_cov and cam_cov map an id to its
+    6x6 covariance.  Entries are written by ascending id."""
+    def entries(cov):
+        out = []
+        for i in sorted(cov):
+            m = np.asarray(cov[i], np.float64).reshape(6, 6)
+            out.append({"id": int(i), "sigma": [float(v) for v in np.sqrt(np.diag(m))],
+                        "covariance": {"rows": 6, "cols": 6, "coefficents": [float(v) for v in m.reshape(-1)]}})
+        return out
+    return {"origin_tag_id": int(origin_tag_id), "robustify": bool(robustify),
+            "reconstructed_tags": entries(tag_cov), "reconstructed_cameras": entries(cam_cov)}
+
+
+def write_uncertainty(path, origin_tag_id, robustify, tag_cov, cam_cov):
+    """Writes reconstruction_uncertainty.json (every scalar a quoted string, like the reference's output files)."""
+    from . import io as _io
+    _io.write_json(path, uncertainty_tree(origin_tag_id, robustify, tag_cov, cam_cov))
+
+
+def main(argv=None):
+    from . import io as _io
+    from .tag_reconstructor import TagReconstructor
+    ap = argparse.ArgumentParser(description="6x6 covariance of every tag and camera of a finished map")
+    ap.add_argument("--project_path", required=True, help="Path to the project (holds camera_intrinsics.json, "
+                    "marker_detections.json and the map)")
+    ap.add_argument("--map", default=None, help="map file (default: <project>/reconstruction.json)")
+    ap.add_argument("--output", default=None, help="output file (default: <project>/reconstruction_uncertainty.json)")
+    ap.add_argument("--start_tag_id", type=int, default=-1,
+                    help="Id of the marker in the origin of the model (default: the lowest id of the map)")
+    ap.add_argument("--robustify", action="store_true", help="apply the Huber loss of the mapping step to J")
+    ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    a = ap.parse_args(argv)
+    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
+    out = a.output or os.path.join(a.project_path, "reconstruction_uncertainty.json")
+    for f in (recon, os.path.join(a.project_path, "camera_intrinsics.json"),
+              os.path.join(a.project_path, "marker_detections.json")):
+        if not os.path.isfile(f):
+            raise FileNotFoundError("'%s' does not exist" % f)
+    tags, cams, _ = _io.parseReconstructions(recon)
+    rec = TagReconstructor(_io.readDetectionResult(os.path.join(a.project_path, "marker_detections.json")),
+                           device=a.device)
+    rec.setCameraModel(_io.readCameraModel(os.path.join(a.project_path, "camera_intrinsics.json")))
+    rec.setReconstructedTags(tags)
+    rec.setReconstructedCameras(cams)
+    origin = a.start_tag_id if a.start_tag_id != -1 else min(tags)
+    if origin not in tags:
+        raise RuntimeError("Could not use tag with id %d as origin tag, because it is not in the map." % origin)
+    rec.setOriginTagId(origin)
+    cov = rec.computePoseCovariances(robustify=a.robustify)
+    rec.close()
+    write_uncertainty(out, origin, a.robustify, cov["tags"], cov["cameras"])
+    print("Covariance of %d tags and %d cameras; wrote %s!" % (len(cov["tags"]), len(cov["cameras"]), out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -424,6 +424,70 @@ int vmm_ba_localize(const double intr[4], const double dist[5],
                     vmm_ba_localize_result* res, /* [n_imgs] or NULL */
                     int device);
 
+/* ABI 6, additive.  Calibrates a camera against a finished map: the nine numbers of the camera model
+ * (fx, fy, cx, cy, k1, k2, p1, p2, k3) and one pose per image, the map held fixed.  Stateless like vmm_ba_localize.
+ *   objective   1/2 sum rho(|r_corner|^2) over the inlier observations of the images that take part, with the residual
+ *               the bundle adjustment and the localisation minimise (the cost functor's projection, not
+ *               CameraModel::projectPoint, which differs in the tangential y term).
+ *   start       vmm_ba_localize's own steps under intr0 / dist0 and o->loc.  An image that is not VMM_BA_LOC_OK, or has
+ *               fewer than min_inlier_tags inlier observations, takes no part: it keeps the pose, flags and result the
+ *               localisation gave it and gets a zero cam_cov.
+ *   refinement  Levenberg-Marquardt on all poses and the parameters in refine_mask at once, Marquardt damping
+ *               lam diag on the pose blocks and on the 9 x 9 block; every image's 6 x 6 block is eliminated and the 9 x 9
+ *               reduced system is solved Jacobi-scaled.  A trial with a strictly lower finite cost is accepted (lam x 0.1),
+ *               any other rejected (lam x 10).  The loop stops when a rejected trial's cost equals the current one to
+ *               rounding, when the step is negligible (every pose-tangent component and every |dk_j| / max(|k_j|, 1)
+ *               below 1e-10 on a rejected trial, 1e-14 on any), or when lam passes 1e12; VMM_BA_CAL_NO_CONVERGENCE when
+ *               max_trials (accepted + rejected) ran out first -- the best state is still returned.
+ *               reclassify_passes times afterwards: every observation of the localised images is classified again under
+ *               the current model and poses (inlier: largest corner distance at most inlier_px), who takes part is
+ *               decided again from the new counts, and the refinement runs again.  The status is the last refinement's.
+ *   mask        a parameter outside refine_mask has zero columns, a unit diagonal and a zero step: it comes back with
+ *               the bits it went in with, and its rows and columns of intr_cov are zero.
+ *   result      intr / dist; cam_qt; obs_inlier = the inlier set the last refinement minimised over; res = the
+ *               localisation's results with n_inlier_obs, rms_px and cost of the images that took part taken at the result.
+ *   covariance  at the result, from the undamped system with the loss applied (as the tag translation covariance above):
+ *               intr_cov = S^-1 with S = sum_i (C_i - B_i' A_i^-1 B_i); cam_cov_i = A_i^-1 + A_i^-1 B_i S^-1 B_i' A_i^-1,
+ *               the marginal of the JOINT problem (wider than vmm_ba_localize's, which takes the model as known).
+ *               VMM_BA_CAL_SINGULAR: S or an A_i is not positive definite (S: a Cholesky pivot at or below 1e-13 of
+ *               its entry of diag(sum C_i), the scale of S's rounding errors); both covariances are zeros, parameters
+ *               and poses are still returned.
+ * VMM_BA_CAL_NO_IMAGES: no image takes part; intr / dist are the start values, cam_cov and intr_cov zeros.
+ * No output is ever NaN.  Results are bit-identical from run to run for the same batch; the sum over the images has a
+ * fixed order, so the bits DO depend on the order of the images in the batch (unlike vmm_ba_localize).
+ * VMM_BA_ERR_ARGUMENT (before any device call): what vmm_ba_localize rejects, a refine_mask outside [0, 0x1FF], bad
+ * tolerances or counts, null intr / dist.  n_imgs == 0 returns VMM_BA_OK with intr / dist copied from the start
+ * values and status NO_IMAGES, without a device call. */
+enum { VMM_BA_CAL_OK = 0, VMM_BA_CAL_NO_IMAGES = 1, VMM_BA_CAL_SINGULAR = 2, VMM_BA_CAL_NO_CONVERGENCE = 3 };
+typedef struct vmm_ba_calibrate_options {
+    vmm_ba_localize_options loc; /* the initial localisation under the starting intrinsics, as vmm_ba_localize runs it */
+    int32_t max_trials;          /* 100: LM trials (accepted + rejected) of one joint refinement */
+    int32_t refine_mask;         /* 0x1FF: bit i set = parameter i of (fx,fy,cx,cy,k1,k2,p1,p2,k3) is refined */
+    int32_t robustify;           /* 1 */
+    int32_t reclassify_passes;   /* 2: after a joint refinement, reclassify every observation at inlier_px and refine again */
+    int32_t min_inlier_tags;     /* 2: an image with fewer inlier observations takes no part */
+    int32_t reserved;
+    double  huber_a;             /* 1.0 */
+    double  inlier_px;           /* 8.0 */
+} vmm_ba_calibrate_options;
+typedef struct vmm_ba_calibrate_report {
+    int32_t status, trials, accepted, passes, n_images_used, n_obs_used;
+    double initial_cost, final_cost, initial_rms_px, final_rms_px, time_s;
+} vmm_ba_calibrate_report;
+void vmm_ba_default_calibrate_options(vmm_ba_calibrate_options* o);
+int vmm_ba_calibrate(const double intr0[4], const double dist0[5],
+                     int32_t n_tags, const double* tag_qt, const double* tag_wh,
+                     int32_t n_imgs, const int64_t* img_start, const int32_t* obs_tag, const double* obs_px,
+                     const vmm_ba_calibrate_options* o,
+                     double intr[4], double dist[5],       /* result */
+                     double* intr_cov,                     /* [81] row-major 9x9, or NULL */
+                     double* cam_qt,                       /* [7*n_imgs] */
+                     double* cam_cov,                      /* [36*n_imgs] or NULL: the JOINT marginal */
+                     uint8_t* obs_inlier,                  /* [n_obs] or NULL */
+                     vmm_ba_localize_result* res,          /* [n_imgs] or NULL */
+                     vmm_ba_calibrate_report* rep,         /* or NULL */
+                     int device);
+
 /* Test/diagnostic: one residual+Jacobian evaluation at the current state; copies out the
  * accumulated normal-equation blocks in the caller's index space.  Any output may be NULL.
  *   V[36*n_cams], U[36*n_tags]  row-major 6x6 J^T J diagonal blocks (Huber-corrected, unscaled)

@@ -19,6 +19,9 @@ CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 # VMM_BA_LOC_*: status of one image of vmm_ba_localize
 LOC_OK, LOC_NO_OBSERVATIONS, LOC_NO_CANDIDATE, LOC_TOO_FEW_INLIERS, LOC_SINGULAR = 0, 1, 2, 3, 4
 LOC_STATUS_NAMES = ("ok", "no_observations", "no_candidate", "too_few_inliers", "singular")
+# VMM_BA_CAL_*: status of vmm_ba_calibrate
+CAL_OK, CAL_NO_IMAGES, CAL_SINGULAR, CAL_NO_CONVERGENCE = 0, 1, 2, 3
+CAL_STATUS_NAMES = ("ok", "no_images", "singular", "no_convergence")
 
 # every symbol include/vmm_ba.h declares
 EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
@@ -30,7 +33,8 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_dense_spd_solve", "vmm_ba_dense_syrk", "vmm_ba_time_kernels", "vmm_ba_pose_plus", "vmm_ba_debug_overlap",
            "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
            "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
-           "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses"]
+           "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses",
+           "vmm_ba_default_calibrate_options", "vmm_ba_calibrate"]
 
 
 class Problem(C.Structure):
@@ -108,6 +112,19 @@ class LocalizeResult(C.Structure):
                 ("rms_px", C.c_double), ("cost", C.c_double)]
 
 
+class CalibrateOptions(C.Structure):
+    _fields_ = [("loc", LocalizeOptions), ("max_trials", C.c_int32), ("refine_mask", C.c_int32),
+                ("robustify", C.c_int32), ("reclassify_passes", C.c_int32), ("min_inlier_tags", C.c_int32),
+                ("reserved", C.c_int32), ("huber_a", C.c_double), ("inlier_px", C.c_double)]
+
+
+class CalibrateReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("trials", C.c_int32), ("accepted", C.c_int32), ("passes", C.c_int32),
+                ("n_images_used", C.c_int32), ("n_obs_used", C.c_int32), ("initial_cost", C.c_double),
+                ("final_cost", C.c_double), ("initial_rms_px", C.c_double), ("final_rms_px", C.c_double),
+                ("time_s", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 _LIB = None
@@ -178,6 +195,13 @@ def lib():
         L.vmm_ba_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.POINTER(LocalizeOptions), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "vmm_ba_calibrate"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
+            L.vmm_ba_default_calibrate_options.restype = None
+            L.vmm_ba_default_calibrate_options.argtypes = [C.POINTER(CalibrateOptions)]
+            L.vmm_ba_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(CalibrateOptions), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(CalibrateReport), C.c_int]
         L.vmm_ba_debug_chol_tile.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB

@@ -395,6 +395,48 @@ void launch_map_corners(hipStream_t st, int n_tags, const double* tag_qt, const 
 void launch_localize(hipStream_t st, const LocalizeArgs& a, bool any_staged, bool any_unstaged);
 int localize_stage_capacity();   // observations of one image that k_localize stages in LDS
 int preload_localize_kernels();
+// kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
+constexpr int kCalRec = 68;    // doubles of an image's record: reduced 9 x 9 block (45, packed lower) | reduced gradient (9) |
+                               // diag(C) (9) | cost | sum |r|^2 | 1 if A + lam diag was not positive definite | inlier
+                               // observations | 1 (the image takes part); all zero for an image that takes no part
+constexpr int kCalElim = 84;   // doubles of an image's elimination: L (21, packed lower) | Y = L^-1 B (6 x 9) | y = L^-1 g (6)
+struct CalibCtl {              // control block of the LM loop: k_calib_solve and k_calib_control write it, the host polls it
+    double k[9], k_cand[9], dk[9];   // (fx, fy, cx, cy, k1, k2, p1, p2, k3): current, candidate, step
+    double lam, cost, raw2;          // damping; sum rho and sum |r|^2 over the inliers at the current state
+    double initial_cost, initial_raw2;
+    int32_t refine_mask, max_trials;
+    int32_t trials, accepted;
+    int32_t done, stop;              // done: every kernel returns at once; stop: 1 converged, 2 max_trials ran out
+    int32_t solve_ok, first;         // first: the next evaluation is the start of the whole call (initial_*)
+    int32_t n_used, n_obs_used;      // images that take part, their inlier observations
+    int32_t cov_ok, initial_n_obs;
+};
+struct CalibArgs {
+    int n_imgs;
+    const int64_t* img_start;
+    const int32_t* obs_tag;
+    const double* obs_px;
+    const double* corners;         // [12 * n_tags] world corners (k_map_corners)
+    uint8_t* flags;                // [n_obs] the inlier set of the refinement
+    vmm_ba_localize_result* res;   // [n_imgs] the localisation's results; k_calib_cov_pose updates the images that took part
+    double* cam_qt;                // [7 * n_imgs] current poses
+    double* cam_cand;              // [7 * n_imgs] candidates
+    int32_t* part;                 // [n_imgs] the image takes part
+    int32_t* n_in;                 // [n_imgs] its inlier observations
+    double* rec;                   // [kCalRec * n_imgs]
+    double* elim;                  // [kCalElim * n_imgs]
+    double* trial;                 // [2 * n_imgs] candidate cost | max |pose step|
+    CalibCtl* ctl;
+    int robustify, min_inliers;
+    double huber_a, inlier2;
+    double* intr_cov;              // [81]
+    double* cam_cov;               // [36 * n_imgs]
+};
+void launch_calib_begin(hipStream_t st, const CalibArgs& a);      // who takes part, from the localisation's results
+void launch_calib_classify(hipStream_t st, const CalibArgs& a);   // new inlier flags under the current camera model
+void launch_calib_trial(hipStream_t st, const CalibArgs& a);      // one LM trial: image sums -> solve -> try -> control
+void launch_calib_covariance(hipStream_t st, const CalibArgs& a); // undamped system at the result: intr_cov, cam_cov, res
+int preload_calibrate_kernels();
 void launch_init_quad(Engine& e);
 void launch_init_begin(Engine& e);
 void launch_init_pass(Engine& e, bool cam, const InitPass& s);

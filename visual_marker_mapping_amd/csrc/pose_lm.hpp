@@ -2,6 +2,7 @@
 // a finished map): fit one 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
 //   lm_refine               the Levenberg-Marquardt trial loop; the caller supplies the sums (cost, J^T J, J^T r)
 //   project_camera_point    camera-side projection of a rotated point with its 2 x 6 Jacobian over the pose's tangent
+//   project_camera_point_intrinsics   the same with the 2 x 9 Jacobian over the camera model (kernels_calibrate.hip)
 //   better / wave_winner    the candidate winner rule and its wave butterfly
 //   zero_normal / wave_sum_normal, accumulate_rows, solve6   the 21 + 6 sums of the normal equations and their solve
 //   chain_camera / chain_tag, quat_from_R                    candidates chained through a placed pose
@@ -282,6 +283,43 @@ __device__ __forceinline__ void project_camera_point(const Intrinsics& K, const 
         j[r][4] = 2.0 * (b2 * g[r][0] - b0 * g[r][2]);
         j[r][5] = 2.0 * (b0 * g[r][1] - b1 * g[r][0]);
     }
+}
+
+// project_camera_point<false, true> and, next to it, the 2 x 9 Jacobian of the same residual over the camera model in
+// the order of Intrinsics (fx, fy, cx, cy, k1, k2, p1, p2, k3).  The residual and the pose Jacobian are the existing
+// function's; the normalised point is formed again with the same expressions for the intrinsic columns.
+__device__ __forceinline__ void project_camera_point_intrinsics(const Intrinsics& K, const double b0, const double b1,
+                                                                const double b2, const double (&t)[3], const double u_obs,
+                                                                const double v_obs, double& ru, double& rv,
+                                                                double (&j)[2][6], double (&jk)[2][9])
+{
+    project_camera_point<false, true>(K, b0, b1, b2, t, u_obs, v_obs, ru, rv, j);
+    const double iz = 1.0 / (b2 + t[2]);
+    const double x = (b0 + t[0]) * iz, y = (b1 + t[1]) * iz;
+    const double r2 = x * x + y * y;
+    const double rad = 1.0 + r2 * (K.k1 + r2 * (K.k2 + r2 * K.k3));
+    double xd, yd;
+    distort(K, false, x, y, r2, rad, xd, yd);
+    const double r4 = r2 * r2, r6 = r4 * r2, xy2 = 2.0 * x * y;
+    const double fxx = K.fx * x, fyy = K.fy * y;
+    jk[0][0] = xd;
+    jk[1][0] = 0.0;
+    jk[0][1] = 0.0;
+    jk[1][1] = yd;
+    jk[0][2] = 1.0;
+    jk[1][2] = 0.0;
+    jk[0][3] = 0.0;
+    jk[1][3] = 1.0;
+    jk[0][4] = fxx * r2;
+    jk[1][4] = fyy * r2;
+    jk[0][5] = fxx * r4;
+    jk[1][5] = fyy * r4;
+    jk[0][6] = K.fx * xy2;
+    jk[1][6] = K.fy * (r2 + 2.0 * y * y);
+    jk[0][7] = K.fx * (r2 + 2.0 * x * x);
+    jk[1][7] = K.fy * xy2;
+    jk[0][8] = fxx * r6;
+    jk[1][8] = fyy * r6;
 }
 
 // The candidate winner rule: the lowest score wins, ties go to the lowest index, NaN and +inf lose (a thread that found

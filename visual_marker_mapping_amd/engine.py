@@ -342,6 +342,62 @@ def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, *
     return cam_qt, cam_cov, inl.astype(bool), results
 
 
+_LOC_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_obs", "<i4"), ("n_inlier_obs", "<i4"), ("trials", "<i4"),
+                              ("rms_px", "<f8"), ("cost", "<f8")])
+
+
+def default_calibrate_options(**kw):
+    """vmm_ba_calibrate_options with its defaults; keywords are its fields, `loc_<field>` sets a field of the initial
+    localisation's options (vmm_ba_calibrate_options.loc)."""
+    o = _lib.CalibrateOptions()
+    _lib.lib().vmm_ba_default_calibrate_options(C.byref(o))
+    for k, v in kw.items():
+        if k.startswith("loc_") and k[4:] in dict(_lib.LocalizeOptions._fields_):
+            setattr(o.loc, k[4:], v)
+        elif k not in ("loc", "reserved") and hasattr(o, k):
+            setattr(o, k, v)
+        else:
+            raise AttributeError("unknown calibration option %r" % k)
+    return o
+
+
+def calibrate(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
+    """The camera model (fx, fy, cx, cy | k1, k2, p1, p2, k3) and one pose per image from a batch of images of a finished
+    map, the map held fixed (vmm_ba_calibrate).  intr0 (4,), dist0 (5,): the starting model; the map and the
+    observations as engine.localize takes them.  options: the fields of vmm_ba_calibrate_options, `loc_<field>` for
+    those of the initial localisation.  Returns (intr (4,), dist (5,), intr_cov (9, 9), cam_qt (n_imgs, 7) world->camera,
+    cam_cov (n_imgs, 6, 6) the joint marginals, obs_inlier (n_obs,) bool, results: one dict per image as
+    engine.localize, report: dict of vmm_ba_calibrate_report)."""
+    intr0 = np.ascontiguousarray(intr0, np.float64).reshape(4)
+    dist0 = np.ascontiguousarray(dist0, np.float64).reshape(5)
+    tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
+    tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
+    img_start = np.ascontiguousarray(img_start, np.int64).reshape(-1)
+    obs_tag = np.ascontiguousarray(obs_tag, np.int32).reshape(-1)
+    obs_px = np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8)
+    if len(tag_wh) != len(tag_qt):
+        raise ValueError("tag_wh and tag_qt differ in length")
+    if len(obs_tag) != len(obs_px):
+        raise ValueError("observation arrays differ in length")
+    if len(img_start) < 1 or img_start[-1] != len(obs_tag):
+        raise ValueError("img_start must have n_imgs + 1 entries and end at the number of observations")
+    o = default_calibrate_options(**options)
+    n_imgs = len(img_start) - 1
+    intr, dist, intr_cov = np.zeros(4), np.zeros(5), np.zeros((9, 9))
+    cam_qt, cam_cov = np.zeros((n_imgs, 7)), np.zeros((n_imgs, 6, 6))
+    inl = np.zeros(len(obs_tag), np.uint8)
+    res = (_lib.LocalizeResult * max(n_imgs, 1))()
+    rep = _lib.CalibrateReport()
+    _lib.check(_lib.lib().vmm_ba_calibrate(_ptr(intr0), _ptr(dist0), len(tag_qt), _ptr(tag_qt), _ptr(tag_wh), n_imgs,
+                                           _ptr(img_start), _ptr(obs_tag), _ptr(obs_px), C.byref(o), _ptr(intr), _ptr(dist),
+                                           _ptr(intr_cov), _ptr(cam_qt), _ptr(cam_cov), _ptr(inl), C.cast(res, C.c_void_p),
+                                           C.byref(rep), device))
+    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_imgs)
+    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_imgs)]
+    report = {k: getattr(rep, k) for k, _ in _lib.CalibrateReport._fields_}
+    return intr, dist, intr_cov, cam_qt, cam_cov, inl.astype(bool), results, report
+
+
 def pose_plus(qt, delta, device=0):
     """Plus(qt, delta) for (n,7) poses and (n,6) tangent steps with the engine's device function
     (Ceres QuaternionParameterization::Plus on q, addition on t; tangent = translation then rotation)."""

@@ -442,14 +442,10 @@ class TagReconstructor:
         R, t = _pnp.solvePnPRansac(np.asarray(X), np.asarray(px), intr, dist, seed=int(imageId) & 0x7FFFFFFF)
         return _pnp.quat_from_R(R), t
 
-    def computeRelativeCameraPosesFromImgs(self, imageIds=None, detectionResult=None, **options):
-        """Batch form of computeRelativeCameraPoseFromImg on the device (vmm_ba_localize): every image of
-        `detectionResult` (default: the reconstructor's own; `imageIds` restricts it) is localised against the
-        reconstructed tags.  Observations of tags that are not reconstructed are dropped.  options: the fields of
-        vmm_ba_localize_options.  Returns {imageId: Camera} for the images with status OK; lastLocalizationReport holds
-        per image id the status, counts, rms_px, cost, the pose, the 6x6 covariance and the inlier flag of each used
-        observation (index into detectionResult.tagObservations)."""
-        det = self.detectionResults_ if detectionResult is None else detectionResult
+    def _pack_against_map(self, det, imageIds):
+        """The flat arrays engine.localize and engine.calibrate take: the reconstructed tags as the map and the
+        observations of those tags grouped by image.  Returns (ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px);
+        order[k] indexes det.tagObservations."""
         if imageIds is None:
             ids = sorted({int(im.imageId) for im in det.images} | {int(ob.imageId) for ob in det.tagObservations})
         else:
@@ -470,6 +466,17 @@ class TagReconstructor:
         obs_tag = np.array([dense[det.tagObservations[k].tagId] for k in order], np.int32)
         obs_px = (np.stack([np.asarray(det.tagObservations[k].corners, np.float64).reshape(8) for k in order])
                   if order else np.zeros((0, 8)))
+        return ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px
+
+    def computeRelativeCameraPosesFromImgs(self, imageIds=None, detectionResult=None, **options):
+        """Batch form of computeRelativeCameraPoseFromImg on the device (vmm_ba_localize): every image of
+        `detectionResult` (default: the reconstructor's own; `imageIds` restricts it) is localised against the
+        reconstructed tags.  Observations of tags that are not reconstructed are dropped.  options: the fields of
+        vmm_ba_localize_options.  Returns {imageId: Camera} for the images with status OK; lastLocalizationReport holds
+        per image id the status, counts, rms_px, cost, the pose, the 6x6 covariance and the inlier flag of each used
+        observation (index into detectionResult.tagObservations)."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_against_map(det, imageIds)
         m = self.camModel
         cam_qt, cam_cov, inl, res = _engine.localize([m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, tag_qt, tag_wh,
                                                      img_start, obs_tag, obs_px, device=self.device, **options)
@@ -482,6 +489,30 @@ class TagReconstructor:
                 cams[i] = Camera(i, cam_qt[n, :4], cam_qt[n, 4:])
         self.lastLocalizationReport = report
         return cams
+
+    def refineCameraModel(self, imageIds=None, detectionResult=None, **options):
+        """Calibrates the camera against the reconstructed tags (vmm_ba_calibrate): the nine numbers of the camera model
+        and one pose per image are refined together from the detections, the tags held fixed, starting at the current
+        camModel.  options: the fields of vmm_ba_calibrate_options (`loc_<field>` for the initial localisation's).
+        Sets camModel to the result when some image took part and returns the report: the fields of
+        vmm_ba_calibrate_report plus `intrinsics` (9,), `covariance` (9, 9), `std` (9,) and `cameras`
+        ({imageId: Camera} of the localised images; one that took no part in the refinement keeps the localisation's
+        pose).  The reference has no such member."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_against_map(det, imageIds)
+        m = self.camModel
+        intr, dist, intr_cov, cam_qt, cam_cov, inl, res, report = _engine.calibrate(
+            [m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, tag_qt, tag_wh, img_start, obs_tag, obs_px,
+            device=self.device, **options)
+        report = dict(report, intrinsics=np.concatenate([intr, dist]), covariance=intr_cov,
+                      std=np.sqrt(np.diag(intr_cov)),
+                      cameras={i: Camera(i, cam_qt[n, :4], cam_qt[n, 4:]) for n, i in enumerate(ids)
+                               if res[n]["status"] == _engine._lib.LOC_OK})
+        if report["status"] != _engine._lib.CAL_NO_IMAGES:
+            self.camModel = CameraModel(fx=float(intr[0]), fy=float(intr[1]), cx=float(intr[2]), cy=float(intr[3]),
+                                        distortionCoefficients=dist, verticalResolution=m.verticalResolution,
+                                        horizontalResolution=m.horizontalResolution)
+        return report
 
     def moveTagIntoOrigin(self, tagId):
         """src/TagReconstructor.cpp:314-338 (applies the same map to tags AND cameras, as the reference does)."""

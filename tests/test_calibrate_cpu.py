@@ -245,6 +245,66 @@ def test_calibrate_validates_arguments_before_touching_the_device():
     assert ei.value.status == _lib.ERR_ARGUMENT
 
 
+def _call_localize(intr, dist, tag_qt, tag_wh, n_imgs, img_start, obs_tag, obs_px, cam_qt, opt=None, n_tags=None):
+    from visual_marker_mapping_amd import _lib
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    return _lib.lib().vmm_ba_localize(p(intr), p(dist), len(tag_qt) if n_tags is None else n_tags, p(tag_qt), p(tag_wh),
+                                      n_imgs, p(img_start), p(obs_tag), p(obs_px), opt, p(cam_qt), None, None, None, 0)
+
+
+def test_calibrate_and_localize_reject_the_same_batches_maps_and_localisation_options_with_the_same_text():
+    """One host stage checks the batch, the map and the localisation options for both entry points: every such fault
+    is an argument error of both, with the same text behind the entry point's own name."""
+    from visual_marker_mapping_amd import _lib, engine
+    intr0, dist0 = np.array([1000.0, 1000.0, 500.0, 400.0]), np.array([0.01, -0.02, 1e-3, -1e-3, 0.005])
+    tag_qt = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0]), (3, 1))
+    tag_wh = np.full((3, 2), 0.1)
+    batch = dict(tag_qt=tag_qt, tag_wh=tag_wh, n_imgs=2, img_start=np.array([0, 2, 3], np.int64),
+                 obs_tag=np.array([0, 1, 2], np.int32), obs_px=np.ones((3, 8)), cam_qt=np.zeros((2, 7)))
+
+    def edited(a, row, col, v):
+        a = a.copy()
+        a[row, col] = v
+        return a
+
+    faults = [("img_start decreases", dict(img_start=np.array([0, 3, 2], np.int64))),
+              ("img_start[0] != 0", dict(img_start=np.array([1, 2, 3], np.int64))),
+              ("obs_tag too large", dict(obs_tag=np.array([0, 1, 3], np.int32))),
+              ("obs_tag negative", dict(obs_tag=np.array([0, -1, 2], np.int32))),
+              ("null tag_qt", dict(tag_qt=None, n_tags=3)), ("null tag_wh", dict(tag_wh=None, n_tags=3)),
+              ("zero quaternion", dict(tag_qt=edited(tag_qt, 2, 0, 0.0)))]
+    for v in (np.nan, np.inf, -np.inf):
+        faults += [("map quaternion %r" % v, dict(tag_qt=edited(tag_qt, 1, 0, v))),
+                   ("map translation %r" % v, dict(tag_qt=edited(tag_qt, 1, 5, v))),
+                   ("tag width %r" % v, dict(tag_wh=edited(tag_wh, 0, 0, v))),
+                   ("tag height %r" % v, dict(tag_wh=edited(tag_wh, 2, 1, v)))]
+    options = [dict(refine_iterations=-1), dict(reclassify_passes=-1), dict(min_inlier_tags=0)]
+    for field in ("huber_a", "score_cap_px", "inlier_px"):
+        options += [{field: v} for v in (0.0, -1.0, np.nan, np.inf)]
+    texts = set()
+    for name, kw in faults + [(repr(o), o) for o in options]:
+        is_option = name.startswith("{")
+        lo = C.byref(engine.default_localize_options(**kw)) if is_option else None
+        co = C.byref(engine.default_calibrate_options(**{"loc_" + k: v for k, v in kw.items()})) if is_option else None
+        args = batch if is_option else dict(batch, **kw)
+        assert _call_localize(intr=intr0, dist=dist0, opt=lo, **args) == _lib.ERR_ARGUMENT, name
+        loc_text = _lib.lib().vmm_ba_last_error().decode()
+        assert _call(intr0=intr0, dist0=dist0, intr=np.zeros(4), dist=np.zeros(5), opt=co, **args) == _lib.ERR_ARGUMENT, name
+        cal_text = _lib.lib().vmm_ba_last_error().decode()
+        assert loc_text.startswith("vmm_ba_localize: ") and cal_text.startswith("vmm_ba_calibrate: "), (name, loc_text, cal_text)
+        assert loc_text[len("vmm_ba_localize: "):] == cal_text[len("vmm_ba_calibrate: "):] != "", (name, loc_text, cal_text)
+        texts.add(cal_text)
+    assert len(texts) >= 8   # the faults are told apart
+    # each entry point keeps its own order: vmm_ba_calibrate looks at the options before the batch, vmm_ba_localize after
+    both = dict(batch, img_start=np.array([0, 3, 2], np.int64))
+    co = engine.default_calibrate_options(loc_inlier_px=-1.0)
+    assert _call(intr0=intr0, dist0=dist0, intr=np.zeros(4), dist=np.zeros(5), opt=C.byref(co), **both) == _lib.ERR_ARGUMENT
+    assert _lib.lib().vmm_ba_last_error().decode() == "vmm_ba_calibrate: bad localisation options"
+    lo = engine.default_localize_options(inlier_px=-1.0)
+    assert _call_localize(intr=intr0, dist=dist0, opt=C.byref(lo), **both) == _lib.ERR_ARGUMENT
+    assert _lib.lib().vmm_ba_last_error().decode() == "vmm_ba_localize: img_start decreases"
+
+
 def test_write_camera_model_round_trips(tmp_path):
     """The README's camera_intrinsics.json is laid out by hand ("%.16e", " : "); Boost's writer, whose layout the
     writers here produce, cannot emit that text.  What round-trips byte for byte: every value (bit for bit through

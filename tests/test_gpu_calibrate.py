@@ -245,6 +245,33 @@ def test_two_calls_give_identical_bytes(outliers):
     assert {k: v for k, v in d["report"].items() if k != "time_s"} == {k: v for k, v in again["report"].items() if k != "time_s"}
 
 
+def test_reclassification_without_a_trial_reproduces_the_localisations_flags():
+    """max_trials=0: the camera model never moves and the poses stay the localisation's, so the one reclassification
+    pass (k_calib_classify) must return byte for byte the flags k_localize ended with for the same model and options --
+    both run classify_image.  24 images: one of 257 observations (the second trip of the 256-thread stride, read from
+    global memory by both kernels), the others of 3 to 10; a tenth of all pixel coordinates displaced by up to 60 px,
+    far beyond inlier_px = 8."""
+    from visual_marker_mapping_amd import engine as eng
+    from visual_marker_mapping_amd.synthetic import make_scene
+    s = make_scene(5, seed=4247, n_cams=24, n_tags=260, visibility=1.0)
+    rng = np.random.default_rng(4248)
+    sizes = rng.integers(3, 11, len(s.cam_gt))
+    sizes[0] = 257
+    idx = np.concatenate([np.flatnonzero(s.obs_cam == c)[:m] for c, m in enumerate(sizes)])
+    assert len(idx) == sizes.sum()
+    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tag, px = s.obs_tag[idx].astype(np.int32), s.obs_px[idx].copy()
+    hit = rng.random(px.shape) < 0.1
+    px[hit] += rng.uniform(-60.0, 60.0, int(hit.sum()))
+    _, _, inl, _ = eng.localize(s.intr, s.dist, s.tag_gt, s.tag_wh, start, tag, px)
+    d = _calibrate(s, _truth(s), start, tag, px, max_trials=0, reclassify_passes=1)
+    print("flags: %d of %d observations inliers of the localisation, %d of the calibration; passes %d trials %d"
+          % (int(inl.sum()), len(inl), int(d["inl"].sum()), d["report"]["passes"], d["report"]["trials"]))
+    assert d["report"]["passes"] == 2 and d["report"]["trials"] == 0
+    assert 0 < inl.sum() < len(inl) and not inl[start[0]:start[1]].all()   # both kinds, also in the long image
+    assert d["inl"].tobytes() == inl.tobytes()
+
+
 # ---- 7. edges -------------------------------------------------------------------------------------------------------
 
 def test_edges_single_tag_empty_images_and_an_unusable_image():

@@ -109,6 +109,41 @@ def test_localize_validates_arguments_before_touching_the_device():
     assert ei.value.status == _lib.ERR_ARGUMENT
 
 
+def test_localize_checks_the_map_sizes_and_every_option_and_looks_at_no_option_of_an_empty_batch():
+    from visual_marker_mapping_amd import _lib, engine
+    intr, dist = np.array([1000.0, 1000.0, 500.0, 400.0]), np.zeros(5)
+    tag_qt = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0]), (3, 1))
+    tag_wh = np.full((3, 2), 0.1)
+    good = dict(intr=intr, dist=dist, tag_qt=tag_qt, tag_wh=tag_wh, n_imgs=2, img_start=np.array([0, 2, 3], np.int64),
+                obs_tag=np.array([0, 1, 2], np.int32), obs_px=np.ones((3, 8)), cam_qt=np.zeros((2, 7)))
+
+    def rejected(text, **kw):
+        assert _call(**dict(good, **kw)) == _lib.ERR_ARGUMENT, kw
+        assert _lib.lib().vmm_ba_last_error().decode() == "vmm_ba_localize: " + text, kw
+
+    zero_q = tag_qt.copy()
+    zero_q[2, :4] = 0.0
+    rejected("zero map quaternion", tag_qt=zero_q)
+    for v in (np.nan, np.inf):
+        for col in (0, 1):
+            bad_wh = tag_wh.copy()
+            bad_wh[1, col] = v
+            rejected("non-finite tag size", tag_wh=bad_wh)
+    rejected("null map", tag_qt=None, n_tags=3)
+    bad_options = [dict(refine_iterations=-1), dict(reclassify_passes=-1), dict(min_inlier_tags=0)]
+    for field in ("huber_a", "score_cap_px", "inlier_px"):
+        bad_options += [{field: v} for v in (0.0, -1.0, np.nan, np.inf)]
+    for kw in bad_options:
+        o = engine.default_localize_options(**kw)
+        rejected("bad localisation options", opt=C.byref(o))
+        # an empty batch is answered before the options are looked at
+        assert _call(**dict(good, n_imgs=0, opt=C.byref(o))) == _lib.OK, kw
+    # the camera model is checked behind the batch and in front of the map
+    nan_intr = np.array([1000.0, np.nan, 500.0, 400.0])
+    rejected("img_start decreases", intr=nan_intr, img_start=np.array([0, 3, 2], np.int64))
+    rejected("non-finite camera model", intr=nan_intr, tag_qt=zero_q)
+
+
 def test_localization_main_needs_a_reconstruction(tmp_path):
     from visual_marker_mapping_amd import localization
     with pytest.raises(FileNotFoundError) as ei:

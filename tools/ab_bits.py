@@ -2,14 +2,16 @@
 """Bit comparison of two builds of libvmm_ba.so.  --cases pose (default): the single-pose solver's three entries,
 vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every Cholesky and back-substitution kernel
 (csrc/kernels_chol*.hip, kernels_backsolve.hip) through vmm_ba_dense_spd_solve and a tree-ordered bundle adjustment.
+--cases calibrate: vmm_ba_calibrate (csrc/kernels_calibrate.hip behind the localisation's three kernels).
 
-    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol] [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
 {"equal": ..., "outputs": {name: {"equal": ..., "sha256": [a, b]}}}; the exit status is 1 on any difference.  The
 scenes are the smallest that reach every loop trip and both variants of every kernel; all of
-them are generated here from fixed seeds.  The wall time in the initialisation report is the one field left out."""
+them are generated here from fixed seeds.  The wall times in the initialisation and calibration reports are the fields
+left out."""
 import argparse
 import hashlib
 import json
@@ -87,6 +89,49 @@ def _localize_cases(eng, make_scene, out):
             out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
 
 
+def _calibrate_cases(eng, make_scene, out):
+    """258 images of a map of 260 tags, so that the 64-thread kernels (k_calib_begin, k_calib_cov_pose), k_calib_solve's
+    four chains and k_calib_control's 256-stride all wrap.  Image 0 has 257 observations (the second trip of the
+    256-thread stride, and the unstaged k_localize), image 1 none, image 2's detections are displaced so far that it
+    fails min_inlier_tags, a tenth of image 3's pixel coordinates are displaced by up to 60 px; the others have 4 to 12
+    observations.  The model starts off the truth.  Robust and plain, with 0 and 2 reclassification passes, all nine
+    parameters free and the distortion held; max_trials 8 keeps each call at a few dozen launches."""
+    s = make_scene(5, seed=4245, n_cams=258, n_tags=260, visibility=1.0)
+    rng = np.random.default_rng(4246)
+    sizes = rng.integers(4, 13, len(s.cam_gt))
+    sizes[0], sizes[1] = 257, 0
+    tags, pxs = [], []
+    for c, m in enumerate(sizes):
+        idx = np.flatnonzero(s.obs_cam == c)[:m]
+        assert len(idx) == m, (c, len(idx))
+        tags.append(s.obs_tag[idx])
+        pxs.append(s.obs_px[idx].copy())
+    pxs[2] += rng.uniform(-400.0, 400.0, pxs[2].shape)
+    hit = rng.random(pxs[3].shape) < 0.1
+    pxs[3][hit] += rng.uniform(-60.0, 60.0, int(hit.sum()))
+    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    k0 = np.concatenate([s.intr, s.dist]) + 0.25 * np.array([200.0, -150.0, 30.0, -25.0, 0.02, -0.05, 1e-3, -1e-3, 0.02])
+    names = ("intr", "dist", "intr_cov", "cam_qt", "cam_cov", "inlier")
+    for robust in (1, 0):
+        for passes in (0, 2):
+            for mask in (0x1FF, 0x00F):
+                got = eng.calibrate(k0[:4], k0[4:], s.tag_gt, s.tag_wh, start, np.concatenate(tags), np.concatenate(pxs),
+                                    robustify=robust, reclassify_passes=passes, refine_mask=mask, max_trials=8)
+                res, rep = got[6], got[7]
+                # else the scene does not do what the text above says: pick another one
+                assert rep["n_images_used"] == len(sizes) - 2 and not got[4][2].any() and got[4][3].any(), rep
+                key = "cal_%s_p%d_m%03x_" % ("robust" if robust else "plain", passes, mask)
+                for name, value in zip(names, got):
+                    out[key + name] = value
+                out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
+                out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
+                ints = ("status", "trials", "accepted", "passes", "n_images_used", "n_obs_used")
+                floats = ("initial_cost", "final_cost", "initial_rms_px", "final_rms_px")
+                assert sorted(ints + floats + ("time_s",)) == sorted(rep), sorted(rep)   # a new field belongs in one of them
+                out[key + "report_int"] = np.array([rep[k] for k in ints], np.int64)
+                out[key + "report_f64"] = np.array([rep[k] for k in floats], np.float64)
+
+
 class _Env:
     """Switches of the engine for one case (a handle and vmm_ba_dense_spd_solve read them when they are created / called)."""
 
@@ -160,6 +205,8 @@ def child(path, cases):
         _quad_cases(eng, out)
         _init_cases(eng, make_scene, out)
         _localize_cases(eng, make_scene, out)
+    elif cases == "calibrate":
+        _calibrate_cases(eng, make_scene, out)
     else:
         _chol_dense_cases(eng, out)
         _chol_tree_cases(eng, make_scene, out)
@@ -170,7 +217,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
-    ap.add_argument("--cases", choices=("pose", "chol"), default="pose", help="which set of cases (default: pose)")
+    ap.add_argument("--cases", choices=("pose", "chol", "calibrate"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()

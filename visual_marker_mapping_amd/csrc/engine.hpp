@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -260,16 +261,20 @@ struct Engine {
 
 void set_error(const std::string& s);
 
-inline Intrinsics make_intrinsics(const double intr[4], const double dist[5])
+__host__ __device__ inline Intrinsics make_intrinsics(const double intr[4], const double dist[5])
 {
     Intrinsics K;
     K.fx = intr[0]; K.fy = intr[1]; K.cx = intr[2]; K.cy = intr[3];
     K.k1 = dist[0]; K.k2 = dist[1]; K.p1 = dist[2]; K.p2 = dist[3]; K.k3 = dist[4];
     return K;
 }
+// the nine numbers in one array (fx, fy, cx, cy, k1, k2, p1, p2, k3), as CalibCtl holds them
+__host__ __device__ inline Intrinsics make_intrinsics(const double k[9]) { return make_intrinsics(k, k + 4); }
 
 // The device memory of an entry point that works without a handle: one allocation, released on every way out, and the
-// first HIP error of the steps made through it -- after a failure the later copies are skipped.
+// first HIP error of the steps made through it -- after a failure the later copies are skipped.  The pieces are
+// described once, by a function that takes them in order: layout() runs it without memory to learn the size, allocates,
+// and runs it again to hand out the pointers.
 struct Arena {
     char* base = nullptr;
     size_t used = 0;
@@ -291,11 +296,21 @@ struct Arena {
     }
     static size_t round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     template <typename T>
-    T* take(size_t count)   // the next 256-byte aligned piece
+    T* take(size_t count)   // the next 256-byte aligned piece (null while layout() is sizing)
     {
-        T* p = reinterpret_cast<T*>(base + used);
+        T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
         used += round(count * sizeof(T));
         return p;
+    }
+    template <typename Carve>
+    hipError_t layout(Carve&& carve)
+    {
+        carve(*this);
+        const size_t total = used;
+        used = 0;
+        if (alloc(total) == hipSuccess)
+            carve(*this);
+        return err;
     }
     // blocking, on the null stream: ordered with the kernels launched there
     void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind)
@@ -395,6 +410,55 @@ void launch_map_corners(hipStream_t st, int n_tags, const double* tag_qt, const 
 void launch_localize(hipStream_t st, const LocalizeArgs& a, bool any_staged, bool any_unstaged);
 int localize_stage_capacity();   // observations of one image that k_localize stages in LDS
 int preload_localize_kernels();
+// localize.hip: the host stage that vmm_ba_localize and vmm_ba_calibrate share -- a batch of images against a map, from
+// the argument checks to the localisation's results.  `who` is the entry point's name, for the error text; the checks
+// are separate functions because the two entry points make them in different orders.
+struct MapBatch {
+    // the caller's arrays (check_batch)
+    int32_t n_tags = 0, n_imgs = 0;
+    int64_t n_obs = 0;
+    const double *h_tag_qt = nullptr, *h_tag_wh = nullptr, *h_px = nullptr;
+    const int64_t* h_start = nullptr;
+    const int32_t* h_obs_tag = nullptr;
+    bool any_staged = false, any_unstaged = false;   // an image of at most / more than localize_stage_capacity() observations
+    // their device copies and what the three kernels write (carve)
+    double *tag_qt = nullptr, *tag_wh = nullptr, *corners = nullptr, *px = nullptr, *quad_qt = nullptr, *quad_rms = nullptr;
+    int64_t* start = nullptr;
+    int32_t* obs_tag = nullptr;
+    double *cam = nullptr, *cov = nullptr;
+    uint8_t* inl = nullptr;
+    vmm_ba_localize_result* res = nullptr;
+
+    void carve(Arena& ar);   // the twelve pieces, in this order; the caller's own go behind them
+    LocalizeArgs args(const double intr[4], const double dist[5], const vmm_ba_localize_options& o) const;
+    void upload(Arena& ar) const;   // the five copies to the device
+    // the uploads, then k_quad_pose -> k_map_corners -> k_localize and `then()` (the caller's further launches) on the
+    // null stream, in order, then one hipGetLastError; the blocking copies back wait for the kernels
+    template <typename Then>
+    void run(Arena& ar, const LocalizeArgs& a, Then&& then) const
+    {
+        upload(ar);
+        if (ar.err != hipSuccess)
+            return;
+        launch_quad_poses(nullptr, a.K, n_obs, tag_wh, px, quad_qt, quad_rms, obs_tag);
+        launch_map_corners(nullptr, n_tags, tag_qt, tag_wh, corners);
+        launch_localize(nullptr, a, any_staged, any_unstaged);
+        then();
+        ar.err = hipGetLastError();
+    }
+    void results(Arena& ar, double* cam_qt, double* cam_cov, uint8_t* obs_inlier, vmm_ba_localize_result* res_out) const;
+};
+int bad_argument(const char* who, const char* what);                 // VMM_BA_ERR_ARGUMENT, "<who>: <what>"
+int hip_failure(const char* who, const char* step, hipError_t err);  // VMM_BA_ERR_HIP, "<who>: <step><error string>"
+int check_camera_model(const char* who, const double intr[4], const double dist[5]);   // finite
+int check_batch(const char* who, MapBatch& mb, int32_t n_tags, const double* tag_qt, const double* tag_wh, int32_t n_imgs,
+                const int64_t* img_start, const int32_t* obs_tag, const double* obs_px, const double* cam_qt);
+int check_map(const char* who, const MapBatch& mb);
+int check_localize_options(const char* who, const vmm_ba_localize_options& o);
+// n_obs == 0: every image reports NO_OBSERVATIONS, the identity pose and a zero covariance
+void fill_no_observations(int32_t n_imgs, double* cam_qt, double* cam_cov, vmm_ba_localize_result* res);
+// hipSetDevice, and on an entry point's first call on a device every preload_* of `preload` (`done`: the caller's flags)
+int select_device(const char* who, int device, bool (&done)[64], std::initializer_list<int (*)()> preload);
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
 constexpr int kCalRec = 68;    // doubles of an image's record: reduced 9 x 9 block (45, packed lower) | reduced gradient (9) |
                                // diag(C) (9) | cost | sum |r|^2 | 1 if A + lam diag was not positive definite | inlier

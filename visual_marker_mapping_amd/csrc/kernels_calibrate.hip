@@ -22,12 +22,18 @@
 // cam_cov_i = L^-T (I + Y S^-1 Y') L^-1 = A_i^-1 + A_i^-1 B_i S^-1 B_i' A_i^-1.
 // Nothing but the selection of the image depends on blockIdx and every sum has a fixed order: the same batch gives the
 // same bits from run to run.  The sum over the images makes the bits depend on the order of the batch.
-// k_calib_image reads pixels and world corners from global memory (no LDS staging: one variant).
+// Every kernel reads pixels and world corners from global memory (ImageView<false>; no LDS staging: one variant).
+// Shared with kernels_localize.hip through image_sums.hpp: the image view, the rotation of a world corner, the
+// classification (k_calib_classify is classify_image under the current model) and the cost-only sum (k_calib_try's
+// candidate cost is image_sums<false, false>); from pose_lm.hpp: tri6, project_camera_point_intrinsics, the accept /
+// stop rules and lower_inverse / lower_gram (both covariances).  The camera model is loaded by engine.hpp's
+// make_intrinsics.  Calibration's own: the 15-wide sums (image_normal_sums) and the three small Cholesky loops, whose
+// pivot tests differ (damped in k_calib_image, weighted in chol9).
 //
 // Registers (hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S, the .s file's .vgpr_count / .vgpr_spill_count /
 // .private_segment_fixed_size): the table at k_calib_image below.
 #include "engine.hpp"
-#include "pose_lm.hpp"
+#include "image_sums.hpp"
 
 namespace vmm {
 
@@ -39,55 +45,19 @@ constexpr int kCalSums = 137;     // 120 (15 x 15 packed lower: pose 0..5, model
 constexpr int kCalChunks = 5;     // wave_sum32 calls that cover them
 constexpr int kSolveThreads = 512;
 
-__device__ constexpr int tri(int a, int b) { return a * (a + 1) / 2 + b; }   // a >= b
+static_assert(kCalThreads == kImageThreads, "classify_image and image_sums stride by kImageThreads");
 
-__device__ __forceinline__ Intrinsics load_model(const double* k)
+// image p's observations, read from global memory
+__device__ __forceinline__ ImageView<false> image_view(const CalibArgs& a, const int p)
 {
-    Intrinsics K;
-    K.fx = k[0]; K.fy = k[1]; K.cx = k[2]; K.cy = k[3];
-    K.k1 = k[4]; K.k2 = k[5]; K.p1 = k[6]; K.p2 = k[7]; K.k3 = k[8];
-    return K;
-}
-
-__device__ __forceinline__ void rotate_corner(const Rigid& cam, const double* w, double& b0, double& b1, double& b2)
-{
-    b0 = cam.R[0] * w[0] + cam.R[1] * w[1] + cam.R[2] * w[2];
-    b1 = cam.R[3] * w[0] + cam.R[4] * w[1] + cam.R[5] * w[2];
-    b2 = cam.R[6] * w[0] + cam.R[7] * w[1] + cam.R[8] * w[2];
-}
-
-// sum rho(|r_corner|^2) over the image's inlier observations at (K, q); every thread returns the total
-__device__ __forceinline__ double image_cost(const CalibArgs& a, const int64_t b, const int m, const Intrinsics& K,
-                                             const double* q, const bool robust, double* s_red)
-{
-    Rigid cam;
-    load_rigid<true>(q, cam);
-    double cost = 0.0;
-    for (int d = threadIdx.x; d < m; d += kCalThreads) {
-        if (a.flags[b + d] == 0)
-            continue;
-        const double* px = a.obs_px + 8 * (b + d);
-        const double* wc = a.corners + 12 * (int64_t)a.obs_tag[b + d];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double b0, b1, b2, ru, rv, j[2][6];
-            rotate_corner(cam, wc + 3 * c, b0, b1, b2);
-            project_camera_point<false, false>(K, b0, b1, b2, cam.t, px[2 * c], px[2 * c + 1], ru, rv, j);
-            double rho0, wgt;
-            huber(robust, a.huber_a, ru * ru + rv * rv, rho0, wgt);
-            cost += rho0;
-        }
-    }
-    cost = wave_sum(cost);
-    if ((threadIdx.x & 63) == 0)
-        s_red[threadIdx.x >> 6] = cost;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < kCalWaves; ++w)
-        t += s_red[w];
-    __syncthreads();
-    return t;
+    const int64_t b = a.img_start[p];
+    ImageView<false> v;
+    v.lds = nullptr;
+    v.m = (int)(a.img_start[p + 1] - b);
+    v.px = a.obs_px + 8 * b;
+    v.tag = a.obs_tag + b;
+    v.corners = a.corners;
+    return v;
 }
 
 // thread = image: who takes part in the first refinement, from the localisation's results and flags
@@ -101,45 +71,18 @@ __global__ __launch_bounds__(64) void k_calib_begin(const CalibArgs a)
     a.part[p] = r.status == VMM_BA_LOC_OK && r.n_inlier_obs >= a.min_inliers;
 }
 
-// workgroup = image: k_localize's classification rule (the largest corner distance of an observation at most
-// sqrt(inlier2), a non-finite distance is an outlier) under the current camera model, for the localised images
+// workgroup = image: k_localize's classification (classify_image, image_sums.hpp) under the current camera model, for
+// the localised images
 __global__ __launch_bounds__(kCalThreads) void k_calib_classify(const CalibArgs a)
 {
     __shared__ int s_cnt[kCalWaves];
     const int p = blockIdx.x;
     if (a.res[p].status != VMM_BA_LOC_OK)
         return;
-    const int64_t b = a.img_start[p];
-    const int m = (int)(a.img_start[p + 1] - b);
-    const Intrinsics K = load_model(a.ctl->k);
-    Rigid cam;
-    load_rigid<true>(a.cam_qt + 7 * (int64_t)p, cam);
-    int n = 0;
-    for (int d = threadIdx.x; d < m; d += kCalThreads) {
-        const double* px = a.obs_px + 8 * (b + d);
-        const double* wc = a.corners + 12 * (int64_t)a.obs_tag[b + d];
-        bool in = true;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            double b0, b1, b2, ru, rv, j[2][6];
-            rotate_corner(cam, wc + 3 * c, b0, b1, b2);
-            project_camera_point<false, false>(K, b0, b1, b2, cam.t, px[2 * c], px[2 * c + 1], ru, rv, j);
-            in = in && (ru * ru + rv * rv <= a.inlier2);
-        }
-        a.flags[b + d] = in ? 1 : 0;
-        n += in ? 1 : 0;
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
-        n += __shfl_xor(n, s, 64);
-    if ((threadIdx.x & 63) == 0)
-        s_cnt[threadIdx.x >> 6] = n;
-    __syncthreads();
+    const ImageView<false> v = image_view(a, p);
+    const int n = classify_image<false>(make_intrinsics(a.ctl->k), v, a.cam_qt + 7 * (int64_t)p, a.inlier2,
+                                        a.flags + a.img_start[p], s_cnt);
     if (threadIdx.x == 0) {
-        n = 0;
-#pragma unroll
-        for (int w = 0; w < kCalWaves; ++w)
-            n += s_cnt[w];
         a.n_in[p] = n;
         a.part[p] = n >= a.min_inliers;
     }
@@ -149,9 +92,9 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_classify(const CalibArgs 
 // C_i; entries 0..119), the gradient (120..134), the cost (135) and sum |r|^2 (136), the Huber corrector applied.
 // Each thread sums privately in list order, then one butterfly per wave (wave_sum32, five of them for the 137 sums),
 // then the waves in order through LDS.
-__device__ __forceinline__ void image_normal_sums(const CalibArgs& a, const int64_t b, const int m, const Intrinsics& K,
-                                                  const Rigid& cam, const int mask, const bool robust, double* s_red,
-                                                  double* s_tot)
+__device__ __forceinline__ void image_normal_sums(const ImageView<false>& v, const uint8_t* flags, const Intrinsics& K,
+                                                  const Rigid& cam, const int mask, const bool robust, const double huber_a,
+                                                  double* s_red, double* s_tot)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double acc[kCalChunks][32];
@@ -161,19 +104,17 @@ __device__ __forceinline__ void image_normal_sums(const CalibArgs& a, const int6
         for (int k = 0; k < 32; ++k)
             acc[c][k] = 0.0;
 #define VMM_ACC(i) acc[(i) >> 5][(i) & 31]
-    for (int d = tid; d < m; d += kCalThreads) {
-        if (a.flags[b + d] == 0)
+    for (int d = tid; d < v.m; d += kCalThreads) {
+        if (flags[d] == 0)
             continue;
-        const double* px = a.obs_px + 8 * (b + d);
-        const double* wc = a.corners + 12 * (int64_t)a.obs_tag[b + d];
 #pragma unroll 1
         for (int c = 0; c < 4; ++c) {   // not unrolled: four corners in flight at once cost registers the sums need
             double b0, b1, b2, ru, rv, jp[2][6], jk[2][9];
-            rotate_corner(cam, wc + 3 * c, b0, b1, b2);
-            project_camera_point_intrinsics(K, b0, b1, b2, cam.t, px[2 * c], px[2 * c + 1], ru, rv, jp, jk);
+            rotate_world(cam, v.world(d, 3 * c), v.world(d, 3 * c + 1), v.world(d, 3 * c + 2), b0, b1, b2);
+            project_camera_point_intrinsics(K, b0, b1, b2, cam.t, v.pixel(d, 2 * c), v.pixel(d, 2 * c + 1), ru, rv, jp, jk);
             const double s = ru * ru + rv * rv;
             double rho0, wgt;
-            huber(robust, a.huber_a, s, rho0, wgt);
+            huber(robust, huber_a, s, rho0, wgt);
             double J[2][15];
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
@@ -193,7 +134,7 @@ __device__ __forceinline__ void image_normal_sums(const CalibArgs& a, const int6
                 VMM_ACC(120 + i) += J[0][i] * ru + J[1][i] * rv;
 #pragma unroll
                 for (int k = 0; k <= i; ++k)
-                    VMM_ACC(tri(i, k)) += J[0][i] * J[0][k] + J[1][i] * J[1][k];
+                    VMM_ACC(tri6(i, k)) += J[0][i] * J[0][k] + J[1][i] * J[1][k];
             }
         }
     }
@@ -216,7 +157,7 @@ __device__ __forceinline__ void image_normal_sums(const CalibArgs& a, const int6
 
 // The image's sums and its elimination.
 //                         .vgpr_count  .vgpr_spill_count  .private_segment_fixed_size
-//   k_calib_image         388          0                  0
+//   k_calib_image         390          0                  0
 //   k_calib_try           120          0                  0
 // One 256-thread workgroup per CU = one wave per SIMD, 512 registers per lane: the 137 running sums (274 registers) stay
 // in registers next to one corner's 2 x 15 Jacobian, so one pass over the image is enough.  With the corner loop unrolled
@@ -241,14 +182,12 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_image(const CalibArgs a, 
             rec[tid] = 0.0;
         return;
     }
-    const int64_t b = a.img_start[p];
-    const int m = (int)(a.img_start[p + 1] - b);
-    const Intrinsics K = load_model(ctl->k);
+    const Intrinsics K = make_intrinsics(ctl->k);
     const int mask = ctl->refine_mask;
     const bool robust = a.robustify != 0;
     Rigid cam;
     load_rigid<true>(a.cam_qt + 7 * (int64_t)p, cam);
-    image_normal_sums(a, b, m, K, cam, mask, robust, s_red, s_tot);
+    image_normal_sums(image_view(a, p), a.flags + a.img_start[p], K, cam, mask, robust, a.huber_a, s_red, s_tot);
     // L = chol(A + lam diag(max(A_ii, 1e-12))), as solve6 damps
     if (tid == 0) {
         const double lam = cov_mode ? 0.0 : ctl->lam;
@@ -256,22 +195,22 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_image(const CalibArgs a, 
         bool ok = true;
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
-            const double ajj = s_tot[tri(j, j)];
+            const double ajj = s_tot[tri6(j, j)];
             double d = ajj + lam * (ajj > 1e-12 ? ajj : 1e-12);
 #pragma unroll
             for (int k = 0; k < j; ++k)
-                d -= L[tri(j, k)] * L[tri(j, k)];
+                d -= L[tri6(j, k)] * L[tri6(j, k)];
             ok = ok && d > 0.0 && finite_bits(d);
             const double sq = sqrt(d);
-            L[tri(j, j)] = sq;
+            L[tri6(j, j)] = sq;
             const double is = 1.0 / sq;
 #pragma unroll
             for (int i = j + 1; i < 6; ++i) {
-                double v = s_tot[tri(i, j)];
+                double v = s_tot[tri6(i, j)];
 #pragma unroll
                 for (int k = 0; k < j; ++k)
-                    v -= L[tri(i, k)] * L[tri(j, k)];
-                L[tri(i, j)] = v * is;
+                    v -= L[tri6(i, k)] * L[tri6(j, k)];
+                L[tri6(i, j)] = v * is;
             }
         }
 #pragma unroll
@@ -285,11 +224,11 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_image(const CalibArgs a, 
         double col[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            double v = tid < 9 ? s_tot[tri(6 + tid, i)] : s_tot[120 + i];
+            double v = tid < 9 ? s_tot[tri6(6 + tid, i)] : s_tot[120 + i];
 #pragma unroll
             for (int k = 0; k < i; ++k)
-                v -= s_L[tri(i, k)] * col[k];
-            col[i] = v / s_L[tri(i, i)];
+                v -= s_L[tri6(i, k)] * col[k];
+            col[i] = v / s_L[tri6(i, i)];
             s_Y[i][tid] = col[i];
         }
     }
@@ -298,10 +237,10 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_image(const CalibArgs a, 
         double v;
         if (tid < 45) {   // C_i - Y'Y, packed lower
             int r = 0;
-            while (tri(r + 1, 0) <= tid)
+            while (tri6(r + 1, 0) <= tid)
                 ++r;
-            const int c = tid - tri(r, 0);
-            v = s_tot[tri(6 + r, 6 + c)];
+            const int c = tid - tri6(r, 0);
+            v = s_tot[tri6(6 + r, 6 + c)];
 #pragma unroll
             for (int k = 0; k < 6; ++k)
                 v -= s_Y[k][r] * s_Y[k][c];
@@ -313,7 +252,7 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_image(const CalibArgs a, 
                 v -= s_Y[k][c] * s_Y[k][9];
         } else if (tid < 63) {
             const int c = tid - 54;
-            v = s_tot[tri(6 + c, 6 + c)];
+            v = s_tot[tri6(6 + c, 6 + c)];
         } else if (tid == 63) {
             v = s_tot[135];
         } else if (tid == 64) {
@@ -341,21 +280,21 @@ __device__ __forceinline__ bool chol9(double (&M)[45], const double (&weight)[9]
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
-        double d = M[tri(j, j)];
+        double d = M[tri6(j, j)];
 #pragma unroll
         for (int k = 0; k < j; ++k)
-            d -= M[tri(j, k)] * M[tri(j, k)];
+            d -= M[tri6(j, k)] * M[tri6(j, k)];
         ok = ok && d * weight[j] > min_pivot && finite_bits(d);
         const double sq = sqrt(d);
-        M[tri(j, j)] = sq;
+        M[tri6(j, j)] = sq;
         const double is = 1.0 / sq;
 #pragma unroll
         for (int i = j + 1; i < 9; ++i) {
-            double v = M[tri(i, j)];
+            double v = M[tri6(i, j)];
 #pragma unroll
             for (int k = 0; k < j; ++k)
-                v -= M[tri(i, k)] * M[tri(j, k)];
-            M[tri(i, j)] = v * is;
+                v -= M[tri6(i, k)] * M[tri6(j, k)];
+            M[tri6(i, j)] = v * is;
         }
     }
     return ok;
@@ -421,7 +360,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_calib_solve(const CalibArgs a
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
         const bool free_j = (mask >> j) & 1;
-        const double d = free_j ? s_tot[tri(j, j)] + lam * s_tot[54 + j] : 1.0;
+        const double d = free_j ? s_tot[tri6(j, j)] + lam * s_tot[54 + j] : 1.0;
         ok = ok && d > 0.0 && finite_bits(d);
         sc[j] = free_j ? 1.0 / sqrt(d) : 1.0;
         weight[j] = cov_mode && free_j ? d / s_tot[54 + j] : 1.0;   // S_jj / C_jj
@@ -431,37 +370,23 @@ __global__ __launch_bounds__(kSolveThreads) void k_calib_solve(const CalibArgs a
 #pragma unroll
         for (int j = 0; j <= i; ++j) {
             const bool both = ((mask >> i) & 1) && ((mask >> j) & 1);
-            M[tri(i, j)] = i == j ? 1.0 : (both ? s_tot[tri(i, j)] * sc[i] * sc[j] : 0.0);
+            M[tri6(i, j)] = i == j ? 1.0 : (both ? s_tot[tri6(i, j)] * sc[i] * sc[j] : 0.0);
         }
     ok = chol9(M, weight, cov_mode ? kCalMinPivot : 0.0) && ok;
     if (cov_mode) {
         // S^-1 = D (L L')^-1 D with the rows and columns of the fixed parameters zero
-        double W[45];   // L^-1, lower
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            W[tri(j, j)] = 1.0 / M[tri(j, j)];
-#pragma unroll
-            for (int i = j + 1; i < 9; ++i) {
-                double v = 0.0;
-#pragma unroll
-                for (int k = j; k < i; ++k)
-                    v -= M[tri(i, k)] * W[tri(k, j)];
-                W[tri(i, j)] = v / M[tri(i, i)];
-            }
-        }
+        double W[45], G[45];   // L^-1 (lower), its Gram matrix
+        lower_inverse<9>(M, W);
+        lower_gram<9>(W, G);
         double sum = 0.0;
 #pragma unroll
         for (int i = 0; i < 9; ++i)
 #pragma unroll
             for (int j = 0; j <= i; ++j) {
-                double v = 0.0;
-#pragma unroll
-                for (int k = i; k < 9; ++k)
-                    v += W[tri(k, i)] * W[tri(k, j)];
                 const bool both = ((mask >> i) & 1) && ((mask >> j) & 1);
-                v = both ? v * sc[i] * sc[j] : 0.0;
+                const double v = both ? G[tri6(i, j)] * sc[i] * sc[j] : 0.0;
                 sum += fabs(v);
-                M[tri(i, j)] = v;
+                M[tri6(i, j)] = v;
             }
         ok = ok && finite_bits(sum);
         ctl->cov_ok = ok ? 1 : 0;
@@ -469,7 +394,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_calib_solve(const CalibArgs a
         for (int i = 0; i < 9; ++i)
 #pragma unroll
             for (int j = 0; j < 9; ++j)
-                a.intr_cov[9 * i + j] = ok ? (i >= j ? M[tri(i, j)] : M[tri(j, i)]) : 0.0;
+                a.intr_cov[9 * i + j] = ok ? (i >= j ? M[tri6(i, j)] : M[tri6(j, i)]) : 0.0;
         return;
     }
     // (L L') z = -D g_k, dk = D z
@@ -479,16 +404,16 @@ __global__ __launch_bounds__(kSolveThreads) void k_calib_solve(const CalibArgs a
         double v = ((mask >> i) & 1) ? -s_tot[45 + i] * sc[i] : 0.0;
 #pragma unroll
         for (int k = 0; k < i; ++k)
-            v -= M[tri(i, k)] * z[k];
-        z[i] = v / M[tri(i, i)];
+            v -= M[tri6(i, k)] * z[k];
+        z[i] = v / M[tri6(i, i)];
     }
 #pragma unroll
     for (int i = 8; i >= 0; --i) {
         double v = z[i];
 #pragma unroll
         for (int k = i + 1; k < 9; ++k)
-            v -= M[tri(k, i)] * z[k];
-        z[i] = v / M[tri(i, i)];
+            v -= M[tri6(k, i)] * z[k];
+        z[i] = v / M[tri6(i, i)];
     }
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
@@ -529,15 +454,14 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_try(const CalibArgs a)
         double v = -w[i];
 #pragma unroll
         for (int k = i + 1; k < 6; ++k)
-            v -= el[tri(k, i)] * dp[k];
-        dp[i] = v / el[tri(i, i)];
+            v -= el[tri6(k, i)] * dp[k];
+        dp[i] = v / el[tri6(i, i)];
     }
     double cand[7];
     pose_plus(a.cam_qt + 7 * (int64_t)p, dp, cand);
-    const Intrinsics K = load_model(ctl->k_cand);
-    const int64_t b = a.img_start[p];
-    const int m = (int)(a.img_start[p + 1] - b);
-    const double cost = image_cost(a, b, m, K, cand, a.robustify != 0, s_red);
+    double A[21], g[6], raw2;   // not filled by the cost-only sum
+    const double cost = image_sums<false, false>(make_intrinsics(ctl->k_cand), image_view(a, p), cand, a.flags + a.img_start[p],
+                                                 a.robustify != 0, a.huber_a, s_red, A, g, raw2);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 7; ++k)
@@ -670,22 +594,11 @@ __global__ __launch_bounds__(64) void k_calib_cov_pose(const CalibArgs a)
 #pragma unroll
             for (int c = 0; c < 9; ++c)
                 v += T[c] * el[21 + 9 * j + c];
-            M[tri(i, j)] = v;
+            M[tri6(i, j)] = v;
         }
     }
     double W[21];   // L^-1, lower
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        W[tri(j, j)] = 1.0 / el[tri(j, j)];
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = j; k < i; ++k)
-                v -= el[tri(i, k)] * W[tri(k, j)];
-            W[tri(i, j)] = v / el[tri(i, i)];
-        }
-    }
+    lower_inverse<6>(el, W);
     // cov = W' M W: P = M W (full 6 x 6), cov[r][c] = sum_k W[k][r] P[k][c]
     double P[6][6];
 #pragma unroll
@@ -695,7 +608,7 @@ __global__ __launch_bounds__(64) void k_calib_cov_pose(const CalibArgs a)
             double v = 0.0;
 #pragma unroll
             for (int k = c; k < 6; ++k)
-                v += (i >= k ? M[tri(i, k)] : M[tri(k, i)]) * W[tri(k, c)];
+                v += (i >= k ? M[tri6(i, k)] : M[tri6(k, i)]) * W[tri6(k, c)];
             P[i][c] = v;
         }
     double sum = 0.0, C[21];
@@ -706,8 +619,8 @@ __global__ __launch_bounds__(64) void k_calib_cov_pose(const CalibArgs a)
             double v = 0.0;
 #pragma unroll
             for (int k = r; k < 6; ++k)
-                v += W[tri(k, r)] * P[k][c];
-            C[tri(r, c)] = v;
+                v += W[tri6(k, r)] * P[k][c];
+            C[tri6(r, c)] = v;
             sum += fabs(v);
         }
     const bool ok = finite_bits(sum);
@@ -715,7 +628,7 @@ __global__ __launch_bounds__(64) void k_calib_cov_pose(const CalibArgs a)
     for (int r = 0; r < 6; ++r)
 #pragma unroll
         for (int c = 0; c < 6; ++c)
-            out[6 * r + c] = ok ? (r >= c ? C[tri(r, c)] : C[tri(c, r)]) : 0.0;
+            out[6 * r + c] = ok ? (r >= c ? C[tri6(r, c)] : C[tri6(c, r)]) : 0.0;
 }
 
 } // namespace

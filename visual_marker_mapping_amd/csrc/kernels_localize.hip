@@ -14,10 +14,10 @@
 //                             (wave_sum32) and combined in LDS in wave order; every thread runs the same 6 x 6 solve
 //                   result    flags at the returned pose, (J^T J)^-1 by a 6 x 6 Cholesky in registers
 // The single-pose solver is pose_lm.hpp's, shared with kernels_init.hip: lm_refine (refine_image supplies image_sums as a
-// lambda; the sums hold barriers, so the workgroup runs the driver as one), project_camera_point (world_corner forms
-// the rotated point from three columns and calls it), better / wave_winner, zero_normal, accumulate_rows, solve6,
-// chain_camera, quat_from_R.  Here: the image view (LDS or global), the Huber-weighted sums and their workgroup
-// reduction, the classification passes and the covariance.
+// lambda; the sums hold barriers, so the workgroup runs the driver as one), better / wave_winner, solve6, chain_camera,
+// quat_from_R, lower_inverse / lower_gram (inverse6).  The image view (LDS or global), world_corner, classify_image and
+// image_sums with their workgroup reductions are image_sums.hpp's, shared with kernels_calibrate.hip.  Here: the
+// staging, the candidate scoring, the passes and the covariance.
 // An image's pixels and world corners (20 doubles per observation) are staged in LDS when the image has at most
 // kStage observations (k_localize<true>); larger images read them from global memory (k_localize<false>).  Both run the
 // same arithmetic in the same order, and which one an image takes depends on its own length alone.
@@ -34,14 +34,14 @@
 #include <limits.h>
 
 #include "engine.hpp"
-#include "pose_lm.hpp"
+#include "image_sums.hpp"
 
 namespace vmm {
 
 namespace {
 
-constexpr int kLocThreads = 256;
-constexpr int kLocWaves = kLocThreads / 64;
+constexpr int kLocThreads = kImageThreads;
+constexpr int kLocWaves = kImageWaves;
 constexpr int kStage = 256;   // observations staged in LDS: 20 x 8 B x 256 = 40 KiB per workgroup
 
 __global__ __launch_bounds__(256) void k_map_corners(int n_tags, const double* __restrict__ tag_qt,
@@ -63,37 +63,6 @@ __global__ __launch_bounds__(256) void k_map_corners(int n_tags, const double* _
     }
 }
 
-// A world corner under the world->camera pose `cam`, projected like the functor the bundle adjustment minimises
-// (project_camera_point<false, .>, pose_lm.hpp): residual and, with JAC, the 2 x 6 camera Jacobian.
-template <bool JAC>
-__device__ __forceinline__ void world_corner(const Intrinsics& K, const Rigid& cam, const double w0, const double w1,
-                                             const double w2, const double u_obs, const double v_obs, double& ru, double& rv,
-                                             double (&j)[2][6])
-{
-    const double b0 = cam.R[0] * w0 + cam.R[1] * w1 + cam.R[2] * w2;
-    const double b1 = cam.R[3] * w0 + cam.R[4] * w1 + cam.R[5] * w2;
-    const double b2 = cam.R[6] * w0 + cam.R[7] * w1 + cam.R[8] * w2;
-    project_camera_point<false, JAC>(K, b0, b1, b2, cam.t, u_obs, v_obs, ru, rv, j);
-}
-
-// One image's observations: element k (0..7 pixels, 8..19 world corners) of local observation d.
-template <bool STAGED>
-struct ImageView {
-    const double* lds;        // STAGED: [20][m]
-    int m;
-    const double* px;         // obs_px + 8 * first observation
-    const int32_t* tag;       // obs_tag + first observation
-    const double* corners;
-    __device__ __forceinline__ double pixel(const int d, const int k) const
-    {
-        return STAGED ? lds[k * m + d] : px[8 * (int64_t)d + k];
-    }
-    __device__ __forceinline__ double world(const int d, const int k) const
-    {
-        return STAGED ? lds[(8 + k) * m + d] : corners[12 * (int64_t)tag[d] + k];
-    }
-};
-
 // Truncated score of camera pose `cam` over all the image's corners.
 template <bool STAGED>
 __device__ __forceinline__ double score_image(const Intrinsics& K, const ImageView<STAGED>& v, const Rigid& cam,
@@ -111,123 +80,6 @@ __device__ __forceinline__ double score_image(const Intrinsics& K, const ImageVi
         }
     }
     return sum;
-}
-
-// Flags the observations whose largest corner distance under q is at most sqrt(inlier2); every thread returns their
-// number.  A non-finite distance is an outlier.
-template <bool STAGED>
-__device__ __forceinline__ int classify_image(const Intrinsics& K, const ImageView<STAGED>& v, const double* q,
-                                              const double inlier2, uint8_t* flags, int* s_cnt)
-{
-    Rigid cam;
-    load_rigid<true>(q, cam);
-    int n = 0;
-    for (int d = threadIdx.x; d < v.m; d += kLocThreads) {
-        bool in = true;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double ru, rv, j[2][6];
-            world_corner<false>(K, cam, v.world(d, 3 * k), v.world(d, 3 * k + 1), v.world(d, 3 * k + 2), v.pixel(d, 2 * k),
-                                v.pixel(d, 2 * k + 1), ru, rv, j);
-            in = in && (ru * ru + rv * rv <= inlier2);
-        }
-        flags[d] = in ? 1 : 0;
-        n += in ? 1 : 0;
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
-        n += __shfl_xor(n, s, 64);
-    if ((threadIdx.x & 63) == 0)
-        s_cnt[threadIdx.x >> 6] = n;
-    __syncthreads();   // also orders the flags (global memory, this workgroup only) before their readers
-    n = 0;
-#pragma unroll
-    for (int w = 0; w < kLocWaves; ++w)
-        n += s_cnt[w];
-    __syncthreads();
-    return n;
-}
-
-// Sums over the active observations (flags null: all) at pose q: returns 1/2-free cost sum rho(|r_corner|^2); with JAC
-// also J^T J (packed lower) and J^T r with the Huber corrector applied, and raw2 = sum |r|^2 without the loss.
-// Every thread returns the same totals.
-template <bool STAGED, bool JAC>
-__device__ __forceinline__ double image_sums(const Intrinsics& K, const ImageView<STAGED>& v, const double* q,
-                                             const uint8_t* flags, const bool robust, const double huber_a, double* s_red,
-                                             double (&A)[21], double (&g)[6], double& raw2)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    Rigid cam;
-    load_rigid<true>(q, cam);
-    double acc[32];   // 0..20 J^T J, 21..26 J^T r, 27 cost, 28 raw2
-    double cost = 0.0, raw = 0.0;
-    if (JAC)
-        zero_normal(A, g);
-    for (int d = threadIdx.x; d < v.m; d += kLocThreads) {
-        if (flags && flags[d] == 0)
-            continue;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            double ru, rv, j[2][6];
-            world_corner<JAC>(K, cam, v.world(d, 3 * k), v.world(d, 3 * k + 1), v.world(d, 3 * k + 2), v.pixel(d, 2 * k),
-                              v.pixel(d, 2 * k + 1), ru, rv, j);
-            const double s = ru * ru + rv * rv;
-            double rho0, wgt;
-            huber(robust, huber_a, s, rho0, wgt);
-            cost += rho0;
-            if (JAC) {
-                raw += s;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    j[0][c] *= wgt;
-                    j[1][c] *= wgt;
-                }
-                accumulate_rows(j, ru * wgt, rv * wgt, A, g);
-            }
-        }
-    }
-    if (JAC) {
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            acc[k] = A[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            acc[21 + k] = g[k];
-        acc[27] = cost;
-        acc[28] = raw;
-        acc[29] = acc[30] = acc[31] = 0.0;
-        const double tot = wave_sum32(acc, lane);
-        s_red[wave * 32 + wave_sum32_index(lane)] = tot;   // lanes 2 m and 2 m + 1 hold (and store) the same value
-        __syncthreads();
-        double r[29];
-#pragma unroll
-        for (int k = 0; k < 29; ++k) {
-            double t = s_red[k];
-#pragma unroll
-            for (int w = 1; w < kLocWaves; ++w)
-                t += s_red[w * 32 + k];
-            r[k] = t;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            A[k] = r[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            g[k] = r[21 + k];
-        raw2 = r[28];
-        return r[27];
-    }
-    cost = wave_sum(cost);
-    if (lane == 0)
-        s_red[wave] = cost;
-    __syncthreads();
-    double t = s_red[0];
-#pragma unroll
-    for (int w = 1; w < kLocWaves; ++w)
-        t += s_red[w];
-    __syncthreads();
-    return t;
 }
 
 // Levenberg-Marquardt on q (in place) over the active observations; returns the trials spent.  image_sums gives every
@@ -267,31 +119,8 @@ __device__ __forceinline__ bool inverse6(const double (&A)[21], double (&C)[21])
             L[tri6(i, j)] = v * is;
         }
     }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        M[tri6(j, j)] = 1.0 / L[tri6(j, j)];
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = j; k < i; ++k)
-                v -= L[tri6(i, k)] * M[tri6(k, j)];
-            M[tri6(i, j)] = v / L[tri6(i, i)];
-        }
-    }
-    double sum = 0.0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = 0; b <= a; ++b) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = a; k < 6; ++k)
-                v += M[tri6(k, a)] * M[tri6(k, b)];
-            C[tri6(a, b)] = v;
-            sum += fabs(v);
-        }
-    return finite_bits(sum);
+    lower_inverse<6>(L, M);
+    return finite_bits(lower_gram<6>(M, C));
 }
 
 // What thread 0 stores for image p; have_cov false: a zero covariance.

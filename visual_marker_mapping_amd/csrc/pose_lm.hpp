@@ -1,10 +1,13 @@
-// The single-pose solver shared by kernels_init.hip (map initialisation) and kernels_localize.hip (localisation against
-// a finished map): fit one 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
+// The single-pose solver shared by kernels_init.hip (map initialisation), kernels_localize.hip (localisation against
+// a finished map) and, through image_sums.hpp and the pieces named below, kernels_calibrate.hip: fit one
+// 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
 //   lm_refine               the Levenberg-Marquardt trial loop; the caller supplies the sums (cost, J^T J, J^T r)
 //   project_camera_point    camera-side projection of a rotated point with its 2 x 6 Jacobian over the pose's tangent
 //   project_camera_point_intrinsics   the same with the 2 x 9 Jacobian over the camera model (kernels_calibrate.hip)
 //   better / wave_winner    the candidate winner rule and its wave butterfly
 //   zero_normal / wave_sum_normal, accumulate_rows, solve6   the 21 + 6 sums of the normal equations and their solve
+//   lower_inverse / lower_gram   L^-1 and M^T M of packed lower matrices: the covariances of kernels_localize.hip (6 x 6)
+//                                and kernels_calibrate.hip (6 x 6 and 9 x 9)
 //   chain_camera / chain_tag, quat_from_R                    candidates chained through a placed pose
 // Everything is __forceinline__ and lives in registers.
 #pragma once
@@ -17,7 +20,7 @@ namespace vmm {
 constexpr double kInf = __builtin_huge_val();
 constexpr double kLamInit = 1e-3, kLamMin = 1e-12, kLamMax = 1e12;
 
-__device__ __forceinline__ int tri6(int a, int b) { return a * (a + 1) / 2 + b; }   // a >= b
+__device__ __forceinline__ int tri6(int a, int b) { return a * (a + 1) / 2 + b; }   // a >= b: packed lower, any order
 
 __device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
 
@@ -148,6 +151,44 @@ __device__ __forceinline__ bool solve6(const double (&A)[21], const double (&g)[
     for (int i = 0; i < 6; ++i)
         ok = ok && finite_v<BITS>(step[i]);
     return ok;
+}
+
+// M = L^-1 for a packed lower N x N factor L (tri6 indexing; L: anything indexable, registers or memory).
+template <int N, typename Lower>
+__device__ __forceinline__ void lower_inverse(const Lower& L, double (&M)[N * (N + 1) / 2])
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        M[tri6(j, j)] = 1.0 / L[tri6(j, j)];
+#pragma unroll
+        for (int i = j + 1; i < N; ++i) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = j; k < i; ++k)
+                v -= L[tri6(i, k)] * M[tri6(k, j)];
+            M[tri6(i, j)] = v / L[tri6(i, i)];
+        }
+    }
+}
+
+// C = M^T M (packed lower) for a packed lower N x N M; returns sum |C_ab| over the packed entries: finite exactly when
+// every entry is.
+template <int N>
+__device__ __forceinline__ double lower_gram(const double (&M)[N * (N + 1) / 2], double (&C)[N * (N + 1) / 2])
+{
+    double sum = 0.0;
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int b = 0; b <= a; ++b) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = a; k < N; ++k)
+                v += M[tri6(k, a)] * M[tri6(k, b)];
+            C[tri6(a, b)] = v;
+            sum += fabs(v);
+        }
+    return sum;
 }
 
 __device__ __forceinline__ void accumulate_rows(const double (&j)[2][6], const double ru, const double rv, double (&A)[21],

@@ -308,13 +308,14 @@ def default_localize_options(**kw):
     return o
 
 
-def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
-    """Poses of a batch of images against a finished map (vmm_ba_localize; the batch form of
-    TagReconstructor::computeRelativeCameraPoseFromImg, src/TagReconstructor.cpp:280-312 of the reference).
-    tag_qt (n_tags, 7) tag->world and tag_wh (n_tags, 2): the map.  img_start (n_imgs + 1,): image i owns the
-    observations [img_start[i], img_start[i + 1]) of obs_tag (n_obs,) and obs_px (n_obs, 8).  options: the fields of
-    vmm_ba_localize_options.  Returns (cam_qt (n_imgs, 7) world->camera, cam_cov (n_imgs, 6, 6), obs_inlier (n_obs,)
-    bool, results: one dict per image with status, n_obs, n_inlier_obs, trials, rms_px, cost)."""
+# vmm_ba_localize_result
+_LOC_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_obs", "<i4"), ("n_inlier_obs", "<i4"), ("trials", "<i4"),
+                              ("rms_px", "<f8"), ("cost", "<f8")])
+
+
+def _map_batch_arrays(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px):
+    """The camera model, the map and the batch of images as vmm_ba_localize and vmm_ba_calibrate take them: contiguous
+    arrays of the C types, refused when their lengths do not fit together."""
     intr = np.ascontiguousarray(intr, np.float64).reshape(4)
     dist = np.ascontiguousarray(dist, np.float64).reshape(5)
     tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
@@ -328,6 +329,18 @@ def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, *
         raise ValueError("observation arrays differ in length")
     if len(img_start) < 1 or img_start[-1] != len(obs_tag):
         raise ValueError("img_start must have n_imgs + 1 entries and end at the number of observations")
+    return intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px
+
+
+def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
+    """Poses of a batch of images against a finished map (vmm_ba_localize; the batch form of
+    TagReconstructor::computeRelativeCameraPoseFromImg, src/TagReconstructor.cpp:280-312 of the reference).
+    tag_qt (n_tags, 7) tag->world and tag_wh (n_tags, 2): the map.  img_start (n_imgs + 1,): image i owns the
+    observations [img_start[i], img_start[i + 1]) of obs_tag (n_obs,) and obs_px (n_obs, 8).  options: the fields of
+    vmm_ba_localize_options.  Returns (cam_qt (n_imgs, 7) world->camera, cam_cov (n_imgs, 6, 6), obs_inlier (n_obs,)
+    bool, results: one dict per image with status, n_obs, n_inlier_obs, trials, rms_px, cost)."""
+    intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr, dist, tag_qt, tag_wh, img_start, obs_tag,
+                                                                               obs_px)
     o = default_localize_options(**options)
     n_imgs = len(img_start) - 1
     cam_qt, cam_cov = np.zeros((n_imgs, 7)), np.zeros((n_imgs, 6, 6))
@@ -336,14 +349,9 @@ def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, *
     _lib.check(_lib.lib().vmm_ba_localize(_ptr(intr), _ptr(dist), len(tag_qt), _ptr(tag_qt), _ptr(tag_wh), n_imgs,
                                           _ptr(img_start), _ptr(obs_tag), _ptr(obs_px), C.byref(o), _ptr(cam_qt),
                                           _ptr(cam_cov), _ptr(inl), C.cast(res, C.c_void_p), device))
-    r = np.frombuffer(res, dtype=np.dtype([("status", "<i4"), ("n_obs", "<i4"), ("n_inlier_obs", "<i4"),
-                                           ("trials", "<i4"), ("rms_px", "<f8"), ("cost", "<f8")]), count=n_imgs)
+    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_imgs)
     results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_imgs)]
     return cam_qt, cam_cov, inl.astype(bool), results
-
-
-_LOC_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_obs", "<i4"), ("n_inlier_obs", "<i4"), ("trials", "<i4"),
-                              ("rms_px", "<f8"), ("cost", "<f8")])
 
 
 def default_calibrate_options(**kw):
@@ -368,19 +376,8 @@ def calibrate(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0
     those of the initial localisation.  Returns (intr (4,), dist (5,), intr_cov (9, 9), cam_qt (n_imgs, 7) world->camera,
     cam_cov (n_imgs, 6, 6) the joint marginals, obs_inlier (n_obs,) bool, results: one dict per image as
     engine.localize, report: dict of vmm_ba_calibrate_report)."""
-    intr0 = np.ascontiguousarray(intr0, np.float64).reshape(4)
-    dist0 = np.ascontiguousarray(dist0, np.float64).reshape(5)
-    tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
-    tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
-    img_start = np.ascontiguousarray(img_start, np.int64).reshape(-1)
-    obs_tag = np.ascontiguousarray(obs_tag, np.int32).reshape(-1)
-    obs_px = np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8)
-    if len(tag_wh) != len(tag_qt):
-        raise ValueError("tag_wh and tag_qt differ in length")
-    if len(obs_tag) != len(obs_px):
-        raise ValueError("observation arrays differ in length")
-    if len(img_start) < 1 or img_start[-1] != len(obs_tag):
-        raise ValueError("img_start must have n_imgs + 1 entries and end at the number of observations")
+    intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag,
+                                                                                  obs_px)
     o = default_calibrate_options(**options)
     n_imgs = len(img_start) - 1
     intr, dist, intr_cov = np.zeros(4), np.zeros(5), np.zeros((9, 9))

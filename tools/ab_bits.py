@@ -3,12 +3,14 @@
 vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every Cholesky and back-substitution kernel
 (csrc/kernels_chol*.hip, kernels_backsolve.hip) through vmm_ba_dense_spd_solve and a tree-ordered bundle adjustment.
 --cases calibrate: vmm_ba_calibrate (csrc/kernels_calibrate.hip behind the localisation's three kernels).
+--cases cov: vmm_ba_tag_translation_covariance (csrc/kernels_cov.hip) after a solve.
 
-    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate] [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|cov] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
-{"equal": ..., "outputs": {name: {"equal": ..., "sha256": [a, b]}}}; the exit status is 1 on any difference.  The
+{"equal": ..., "outputs": {name: {"equal": ..., "sha256": [a, b]}}}; the exit status is 1 on any difference.  A float
+output of 3 x 3 blocks that differs also gets "max_gap_3x3", the largest |a - b| over the largest |a| of its block.  The
 scenes are the smallest that reach every loop trip and both variants of every kernel; all of
 them are generated here from fixed seeds.  The wall times in the initialisation and calibration reports are the fields
 left out."""
@@ -196,6 +198,32 @@ def _chol_tree_cases(eng, make_scene, out):
         out["%s_redone" % name] = np.array([res["num_sync_timeouts"] > 0], np.int32)
 
 
+def _cov_cases(eng, make_scene, out):
+    """The scenes of tests/test_gpu_pose_covariance.py (each configuration's own fixed seed): 30 x 14 under both eliminations, plain and robust (a reduced
+    system of two or three blocks, a right-hand side of 84 columns: not a multiple of 64); 20 x 10 with the cameras
+    eliminated (one block: no update launch); 12 x 24 (tags eliminated by ELIM_AUTO); a 60 x 80 close-up handle on the
+    block-sparse path, which switches to the dense system for the call.  The state after the solve is an output too: a
+    difference there is not the covariance's."""
+    def run(name, s, robust, **kw):
+        with eng.BundleAdjuster(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag,
+                                s.obs_px, **kw) as ba:
+            res = ba.solve(eng.default_options(robustify=robust))
+            assert res["termination_type"] == eng.CONVERGENCE, (name, res["termination_type"])
+            out["cov_%s_cam_qt" % name], out["cov_%s_tag_qt" % name] = ba.get_state()
+            out["cov_%s_tag_translation" % name] = ba.tag_translation_covariance(robustify=bool(robust))
+        return res
+
+    for elim, mode in (("cams", eng.ELIM_CAMERAS), ("tags", eng.ELIM_TAGS)):
+        for robust in (0, 1):
+            s = make_scene(5 if robust else 1, n_cams=30, n_tags=14, visibility=0.7)
+            run("30x14_elim_%s_%s" % (elim, "robust" if robust else "plain"), s, robust, elimination=mode)
+    run("20x10_elim_cams", make_scene(1), 0, elimination=eng.ELIM_CAMERAS)
+    run("12x24_auto", make_scene(1, n_cams=12, n_tags=24, visibility=0.5), 0, elimination=eng.ELIM_AUTO)
+    with _Env(VMM_BA_SCHUR="sparse"):
+        res = run("60x80_block_sparse", make_scene(2, n_cams=60, n_tags=80, neighbors_min=6, neighbors_max=10), 0)
+    assert res["block_sparse"] == 1, res["block_sparse"]   # else the handle was dense all along: pick another scene
+
+
 def child(path, cases):
     sys.path.insert(0, ROOT)
     from visual_marker_mapping_amd import engine as eng
@@ -207,6 +235,8 @@ def child(path, cases):
         _localize_cases(eng, make_scene, out)
     elif cases == "calibrate":
         _calibrate_cases(eng, make_scene, out)
+    elif cases == "cov":
+        _cov_cases(eng, make_scene, out)
     else:
         _chol_dense_cases(eng, out)
         _chol_tree_cases(eng, make_scene, out)
@@ -217,7 +247,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
-    ap.add_argument("--cases", choices=("pose", "chol", "calibrate"), default="pose", help="which set of cases (default: pose)")
+    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "cov"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -243,6 +273,12 @@ def main():
         equal = equal and same
         outputs[k] = {"equal": same, "sha256": [hashlib.sha256(data[x][k][2]).hexdigest() if k in data[x] else None
                                                 for x in ("a", "b")]}
+        if not same and k in data["a"] and k in data["b"] and data["a"][k][:2] == data["b"][k][:2] \
+                and data["a"][k][0] == "<f8" and data["a"][k][1][-2:] == (3, 3):
+            a, b = (np.frombuffer(data[x][k][2]).reshape(-1, 9) for x in ("a", "b"))
+            scale = np.abs(a).max(axis=1)
+            outputs[k]["max_gap_3x3"] = float((np.abs(a - b).max(axis=1)[scale > 0] / scale[scale > 0]).max(initial=0.0))
+            outputs[k]["blocks_differing"] = int((a != b).any(axis=1).sum())
     print(json.dumps({"equal": equal, "cases": args.cases, "a": args.a, "b": args.b, "n_outputs": len(outputs), "outputs": outputs}))
     return 0 if equal else 1
 

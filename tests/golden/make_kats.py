@@ -12,6 +12,11 @@ Tangent Jacobians are d residual(Plus(x, d)) / d d at d = 0, differentiated nume
 at 50 digits (columns: translation(3) then half-angle rotation(3), camera block then tag block).
 The reference itself holds no golden vectors, so these are the committed fixtures.
 
+`huber_widths` (HuberLoss(a) at widths other than 1, around its threshold) and `obs_hard` (records of the `obs` layout on
+geometry those stay away from: grazing, close-up, wide field under a strong distortion, quaternion norms of 1e-3 and 1e3,
+translations of 1e3 m, behind the camera, an outlier of 1e5 px, an exact observation) come after the older sections
+and draw from their own seed, so the older sections keep their bytes.
+
 Run:  python tests/golden/make_kats.py   (needs mpmath; deterministic)
 """
 import json
@@ -131,6 +136,138 @@ def rand_quat(rng, small=False):
         v = [rng.gauss(0, 1) for _ in range(4)]
     n = sum(c * c for c in v) ** 0.5
     return [c / n for c in v]
+
+
+def huber_width_cases():
+    """rho, rho', rho'' of ceres::HuberLoss(a) for widths other than 1.  The threshold is the f64 product b = a * a, as
+    the loss's constructor stores it (it is not the real a^2 for a = 1e-3), so `s = a^2 exactly` means s = b: the
+    quadratic side.  The values are the exact functions of the f64 numbers a, b and s."""
+    import math
+    out = []
+    for a in (1e-3, 0.5, 2.5, 30.0):
+        b = a * a
+        for s in (0.0, b / 4, b, math.nextafter(b, math.inf), 4 * b, 1e6 * b):
+            am, bm, sm = mpf(a), mpf(b), mpf(s)
+            if sm > bm:
+                r = sqrt(sm)
+                rho = [2 * am * r - bm, am / r, -(am / r) / (2 * sm)]
+            else:
+                rho = [sm, mpf(1), mpf(0)]
+            out.append({"a": a, "b": b, "s": s, "rho": [float(v) for v in rho]})
+    return out
+
+
+def qmul(z, w):
+    return [z[0] * w[0] - z[1] * w[1] - z[2] * w[2] - z[3] * w[3],
+            z[0] * w[1] + z[1] * w[0] + z[2] * w[3] - z[3] * w[2],
+            z[0] * w[2] - z[1] * w[3] + z[2] * w[0] + z[3] * w[1],
+            z[0] * w[3] + z[1] * w[2] - z[2] * w[1] + z[3] * w[0]]
+
+
+def obs_record(intr, dist, cam, tag, w, h, px, what):
+    """One record of the `obs` layout (residual, tangent Jacobians, statistics-path error) for f64 inputs."""
+    camm, tagm = [mpf(c) for c in cam], [mpf(c) for c in tag]
+    intrm, distm = [mpf(c) for c in intr], [mpf(c) for c in dist]
+    cls = local_corners(mpf(w), mpf(h))
+    pxm = [mpf(c) for c in px]
+    res, Jc, Jt, rep = [], [], [], []
+    for k, cl in enumerate(cls):
+        uv = pxm[2 * k:2 * k + 2]
+        res += corner_residual(intrm, distm, camm, tagm, cl, uv)
+        for comp in range(2):
+            rowc, rowt = [], []
+            for a in range(6):
+                def fc(e, a=a, comp=comp):
+                    d = [mpf(0)] * 6
+                    d[a] = e
+                    return corner_residual(intrm, distm, plus(camm, d), tagm, cl, uv)[comp]
+
+                def ft(e, a=a, comp=comp):
+                    d = [mpf(0)] * 6
+                    d[a] = e
+                    return corner_residual(intrm, distm, camm, plus(tagm, d), cl, uv)[comp]
+                rowc.append(diff(fc, mpf(0)))
+                rowt.append(diff(ft, mpf(0)))
+            Jc.append(rowc)
+            Jt.append(rowt)
+        rep += corner_reprojection_error(intrm, distm, camm, tagm, cl, uv)
+    return {"what": what, "intr": list(intr), "dist": list(dist), "cam_qt": list(cam), "tag_qt": list(tag), "wh": [w, h],
+            "px": list(px),
+            "residual": [float(v) for v in res],
+            "reprojection_error_camera_model": [float(v) for v in rep],
+            "J_cam": [[float(v) for v in row] for row in Jc],
+            "J_tag": [[float(v) for v in row] for row in Jt]}
+
+
+def hard_cases(intr):
+    """Geometry the `obs` cases stay away from, each with no distortion and with a strong one whose radial polynomial
+    turns over inside the field that the wide cases reach.  A case is set up by the tag's pose in the CAMERA frame
+    (q_ct, t_ct) and the tag's pose in the world; the camera is then q_c = q_ct conj(q_t), t_c = t_ct - R_c t_t."""
+    import math
+    rng = random.Random(20261018)
+    strong = [-0.45, 0.30, 5e-3, -4e-3, -0.10]
+    side = 0.1285
+
+    def axis_angle(axis, deg):
+        h = math.radians(deg) / 2
+        n = math.sqrt(sum(c * c for c in axis))
+        return [math.cos(h)] + [math.sin(h) * c / n for c in axis]
+
+    def rotate(q, p):
+        return [float(v) for v in quat_rotate([mpf(c) for c in q], [mpf(c) for c in p])]
+
+    def scene(q_ct, t_ct, t_t=None, cam_norm=1.0, tag_norm=1.0):
+        q_t = rand_quat(rng, small=True)
+        if t_t is None:
+            t_t = [rng.uniform(-1, 1), rng.uniform(-0.6, 0.6), rng.gauss(0, 0.05)]
+        q_c = qmul(q_ct, [q_t[0], -q_t[1], -q_t[2], -q_t[3]])
+        rt = rotate(q_c, t_t)
+        t_c = [t_ct[i] - rt[i] for i in range(3)]
+        return [c * cam_norm for c in q_c] + t_c, [c * tag_norm for c in q_t] + list(t_t)
+
+    def wobble(q):
+        return qmul(rand_quat(rng, small=True), q)
+
+    frontal = [0.0, 1.0, 0.0, 0.0]   # the tag faces the camera (180 degrees about x, as in the `obs` cases)
+    setups = [
+        ("tag normal 85 degrees from the viewing ray",
+         lambda: scene(qmul(axis_angle([0.0, 1.0, 0.0], 85.0), frontal), [0.1, -0.05, 2.5]), "noise"),
+        ("camera 0.15 m from the tag", lambda: scene(wobble(frontal), [0.01, -0.005, 0.15]), "noise"),
+        ("a corner at normalised radius about 1.5", lambda: scene(wobble(frontal), [1.1, 0.95, 1.0]), "noise"),
+        ("quaternion norms 1e-3 (camera) and 1e3 (tag)",
+         lambda: scene(wobble(frontal), [0.3, -0.2, 3.0], cam_norm=1e-3, tag_norm=1e3), "noise"),
+        ("translations near 1e3 m, 3 m apart",
+         lambda: scene(wobble(frontal), [0.2, -0.1, 3.0], t_t=[1000.3, -998.7, 1001.9]), "noise"),
+        ("tag behind the camera", lambda: scene(wobble(frontal), [0.3, -0.2, -2.0]), "noise"),
+        ("observation 1e5 px off", lambda: scene(wobble(frontal), [-0.2, 0.15, 3.2]), "outlier"),
+        ("observation equal to the f64 projection", lambda: scene(wobble(frontal), [0.25, 0.1, 2.8]), "exact"),
+    ]
+    out = []
+    for what, make, obs_kind in setups:
+        for dist in ([0.0] * 5, strong):
+            cam, tag = make()
+            if what.startswith("quaternion norms") and dist is strong:   # the other way round
+                cam[:4] = [c * 1e6 for c in cam[:4]]
+                tag[:4] = [c * 1e-6 for c in tag[:4]]
+                what_d = "quaternion norms 1e3 (camera) and 1e-3 (tag)"
+            else:
+                what_d = what
+            camm, tagm = [mpf(c) for c in cam], [mpf(c) for c in tag]
+            intrm, distm = [mpf(c) for c in intr], [mpf(c) for c in dist]
+            px = []
+            for k, cl in enumerate(local_corners(mpf(side), mpf(side))):
+                r0 = corner_residual(intrm, distm, camm, tagm, cl, [mpf(0), mpf(0)])
+                for comp in range(2):
+                    if obs_kind == "exact":
+                        off = 0.0
+                    elif obs_kind == "outlier" and k in (0, 2):
+                        off = rng.choice((-1.0, 1.0)) * 1e5 + rng.gauss(0, 1.5)
+                    else:
+                        off = rng.gauss(0, 1.5)
+                    px.append(float(r0[comp]) + off)
+            out.append(obs_record(intr, dist, cam, tag, side, side, px,
+                                  what_d + (", strong distortion" if dist is strong else ", no distortion")))
+    return out
 
 
 def main():
@@ -286,9 +423,15 @@ def main():
                             "J_point": [[float(v) for v in row] for row in Jp]})
     out = {"generator": "tests/golden/make_kats.py (mpmath %d digits)" % mp.dps,
            "obs": cases, "plus": plus_cases, "huber": huber, "project_point": project, "point_obs": point_cases}
+    # the later sections: one record per line, after the older sections as they always were written
+    text = json.dumps(out, indent=1)
+    assert text.endswith("\n}")
+    text = text[:-2]
+    for name, records in (("huber_widths", huber_width_cases()), ("obs_hard", hard_cases(intr))):
+        text += ',\n "%s": [\n  %s\n ]' % (name, ",\n  ".join(json.dumps(r) for r in records))
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "kat_residual.json")
     with open(path, "w") as f:
-        json.dump(out, f, indent=1)
+        f.write(text + "\n}")
     print("wrote", path, len(cases), "observation cases")
 
 

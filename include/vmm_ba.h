@@ -488,6 +488,82 @@ int vmm_ba_calibrate(const double intr0[4], const double dist0[5],
                      vmm_ba_calibrate_report* rep,         /* or NULL */
                      int device);
 
+/* ABI 6, additive.  The camera model of a handle.  Every entry point takes it from vmm_ba_problem.intr / dist at create;
+ * vmm_ba_set_intrinsics replaces it, after which every entry (cost, eval_blocks, solve, initialize, reprojection_stats,
+ * the covariances) behaves as a handle created with the new numbers -- the captured iteration graph holds the model by
+ * value and is dropped, the next solve captures again.  intr = fx, fy, cx, cy; dist = k1, k2, p1, p2, k3.
+ * VMM_BA_ERR_ARGUMENT for null pointers or non-finite numbers; VMM_BA_ERR_STATE for world_size > 1 or
+ * VMM_BA_LANDMARK_POINTS handles (as vmm_ba_covariance_blocks), after the argument checks.  vmm_ba_get_intrinsics
+ * works on every handle and makes no device call. */
+int vmm_ba_set_intrinsics(vmm_ba_handle h, const double intr[4], const double dist[5]);
+int vmm_ba_get_intrinsics(vmm_ba_handle h, double intr[4], double dist[5]);
+
+/* ABI 6, additive.  The camera-model part of the joint problem "cameras + tags + camera model" at the current state and
+ * the handle's model, k = (fx, fy, cx, cy, k1, k2, p1, p2, k3), J_k the Jacobian of the residuals over k:
+ *   cost          1/2 sum rho(|r|^2) over the active observations
+ *   g_k[9], C[81] J_k^T r and J_k^T J_k (row-major) over the active observations
+ *   r_k[9]        g_k - B^T A^-1 g      with A the pose normal matrix (cameras and tags), g the pose gradient and B the
+ *   S_k[81]       C - B^T A^-1 B        stack of the 6 x 9 blocks sum J_pose^T J_k: the reduced system of the camera
+ *                                       model with every pose eliminated (row-major, symmetric in its bits)
+ * Undamped and unscaled, the loss applied when robustify != 0 as everywhere else (rows and residuals scaled by
+ * sqrt(rho')).  The observation mask and the constant-pose flags are honoured: a switched-off observation contributes
+ * nothing; a constant pose has a zero block of B, its observations still feed C, g_k and the other pose's block.
+ * S_k^-1 is the covariance of the camera model with the poses marginalised; -S_k^-1 r_k its Gauss-Newton step.
+ * The call leaves the state alone and is idempotent; a block-sparse or tree-ordered handle switches to the dense,
+ * naturally ordered system for the call, as vmm_ba_covariance_blocks.  Every sum has a fixed order: the results are
+ * bit-identical from run to run.  Any output may be NULL.
+ * n_obs == 0 or no active observation: zeros.  VMM_BA_ERR_ARGUMENT for a null handle, VMM_BA_ERR_STATE for
+ * world_size > 1 or VMM_BA_LANDMARK_POINTS handles, VMM_BA_ERR_NUMERIC if A is not positive definite. */
+int vmm_ba_intrinsics_system(vmm_ba_handle h, int robustify, double huber_a, double* cost, double g_k[9], double C[81],
+                             double r_k[9], double S_k[81]);
+
+/* ABI 6, additive.  Bundle adjustment with the camera model refined: cameras, tags and the parameters of refine_mask at
+ * one optimum of 1/2 sum rho(|r|^2), and the covariance of the model with the poses marginalised.
+ *   start       one vmm_ba_solve(h, inner).  refine_mask == 0: that is all -- poses and *last_inner are those of a plain
+ *               vmm_ba_solve, outer_iterations == 0.
+ *   iteration   vmm_ba_intrinsics_system at the current state; a parameter outside refine_mask gets a unit row and a zero
+ *               step (it comes back with the bits it went in with); (S_k + lam diag S_k) dk = -r_k is solved on the host,
+ *               Jacobi-scaled; the poses are saved, the model becomes k + dk, vmm_ba_solve(h, inner) runs from the current
+ *               poses.  A strictly lower finite cost: accepted, lam x 0.1 (from 1e-4).  Otherwise poses and model are
+ *               restored exactly and lam x 10.
+ *   stop        VMM_BA_CAL_OK: an accepted step with every |dk_j| / max(|k_j|, 1) below parameter_tolerance; an accepted
+ *               step whose relative cost decrease is below function_tolerance; a rejected step whose cost equals the
+ *               current one to rounding; lam past 1e12.  VMM_BA_CAL_NO_CONVERGENCE: max_outer_iterations (accepted +
+ *               rejected) ran out; the best state is kept.  VMM_BA_CAL_SINGULAR: S_k is not positive definite (a Cholesky
+ *               pivot of its unit-diagonal scaling at or below 1e-13 C_jj / S_jj, as vmm_ba_calibrate); poses and model
+ *               are those of the first solve, intr_cov is zeros.
+ *   result      the handle holds the returned poses (vmm_ba_get_state) and model (intr / dist, vmm_ba_get_intrinsics);
+ *               intr_cov = S_k^-1 at the result over the free parameters, rows and columns of the others zero;
+ *               *last_inner (optional) is the summary of the last vmm_ba_solve the call made, rejected trials included.
+ *   inner       the outer loop compares the costs of consecutive solves: `inner` should stop well below the outer
+ *               function_tolerance (the defaults of vmm_ba_default_options stop at a relative cost decrease of 1e-6,
+ *               which leaves the model accurate to about that; function_tolerance 1e-14 and parameter_tolerance 1e-12
+ *               are what TagReconstructor.doBundleAdjustment(refineCameraModel) passes).
+ * No output is ever NaN.  Two calls from the same start give identical bytes (time_s aside).
+ * The iteration graph is captured again after every change of the model: once per outer iteration.
+ * VMM_BA_ERR_ARGUMENT: null handle, report, intr or dist; refine_mask outside [0, 0x1FF]; negative counts or tolerances.
+ * VMM_BA_ERR_STATE: world_size > 1 or VMM_BA_LANDMARK_POINTS.  VMM_BA_ERR_NUMERIC: the pose system is not positive
+ * definite at an iterate.  Errors of the inner solve are passed on. */
+typedef struct vmm_ba_selfcal_options {
+    int32_t max_outer_iterations;   /* 30: trials (accepted + rejected) of the outer loop */
+    int32_t refine_mask;            /* 0x1FF: bit i set = parameter i of (fx,fy,cx,cy,k1,k2,p1,p2,k3) is refined */
+    double parameter_tolerance;     /* 1e-10 */
+    double function_tolerance;      /* 1e-12 */
+} vmm_ba_selfcal_options;
+typedef struct vmm_ba_selfcal_report {
+    int32_t status;                 /* VMM_BA_CAL_OK / _SINGULAR / _NO_CONVERGENCE */
+    int32_t outer_iterations;       /* trials of the outer loop */
+    int32_t accepted;
+    int32_t inner_lm_iterations;    /* num_lm_iterations summed over every vmm_ba_solve of the call */
+    double initial_cost;            /* final cost of the first solve: the optimum under the starting model */
+    double final_cost;
+    double time_s;                  /* host wall time of the call */
+} vmm_ba_selfcal_report;
+void vmm_ba_default_selfcal_options(vmm_ba_selfcal_options* o);
+int vmm_ba_solve_selfcal(vmm_ba_handle h, const vmm_ba_options* inner, const vmm_ba_selfcal_options* o,
+                         vmm_ba_summary* last_inner, vmm_ba_selfcal_report* report, double intr[4], double dist[5],
+                         double* intr_cov /* [81] row-major 9x9, or NULL */);
+
 /* Test/diagnostic: one residual+Jacobian evaluation at the current state; copies out the
  * accumulated normal-equation blocks in the caller's index space.  Any output may be NULL.
  *   V[36*n_cams], U[36*n_tags]  row-major 6x6 J^T J diagonal blocks (Huber-corrected, unscaled)

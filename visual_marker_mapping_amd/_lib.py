@@ -34,7 +34,9 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
            "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
            "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses",
-           "vmm_ba_default_calibrate_options", "vmm_ba_calibrate"]
+           "vmm_ba_default_calibrate_options", "vmm_ba_calibrate",
+           "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
+           "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"]
 
 
 class Problem(C.Structure):
@@ -125,6 +127,17 @@ class CalibrateReport(C.Structure):
                 ("time_s", C.c_double)]
 
 
+class SelfcalOptions(C.Structure):
+    _fields_ = [("max_outer_iterations", C.c_int32), ("refine_mask", C.c_int32), ("parameter_tolerance", C.c_double),
+                ("function_tolerance", C.c_double)]
+
+
+class SelfcalReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("outer_iterations", C.c_int32), ("accepted", C.c_int32),
+                ("inner_lm_iterations", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("time_s", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 _LIB = None
@@ -203,6 +216,16 @@ def lib():
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(CalibrateReport), C.c_int]
         L.vmm_ba_debug_chol_tile.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "vmm_ba_solve_selfcal"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
+            L.vmm_ba_set_intrinsics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.vmm_ba_get_intrinsics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.vmm_ba_intrinsics_system.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]
+            L.vmm_ba_default_selfcal_options.restype = None
+            L.vmm_ba_default_selfcal_options.argtypes = [C.POINTER(SelfcalOptions)]
+            L.vmm_ba_solve_selfcal.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(SelfcalOptions),
+                                               C.POINTER(Summary), C.POINTER(SelfcalReport), C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
         _LIB = L
     return _LIB
 

@@ -378,6 +378,11 @@ void launch_cov_gram(Engine& e, const double* X, int ldb, double* cov_dev);
 void launch_cov_rhs_slots(Engine& e, const int32_t* slot_src, int n_slots, double* B, int ldb);
 void launch_cov_trsm_mfma(Engine& e, double* B, int ldb, const std::vector<int>& chunks_at);
 void launch_cov_pairs(Engine& e, const double* X, int ldb, const int32_t* pair, int64_t n_pairs, double* cov_dev);
+// kernels_border.hip: the border of the joint system "poses + camera model" and its reduction to 9 x 9
+constexpr int kBorderOut = 181;   // cost | g_k[9] | C[81] | r_k[9] | S_k[81]
+size_t border_workspace_doubles(const Engine& e);
+double* launch_border(Engine& e, int robustify, double huber_a, double* ws);   // behind the covariance preamble
+int preload_border_kernels();
 // kernels_init.hip
 struct InitPass {   // one score + select + refine pass over a family
     bool sweep = false;             // false: place what is not placed yet; true: redo every placed pose

@@ -228,6 +228,57 @@ class BundleAdjuster:
         cov = self.covariance_blocks(np.stack([idx, idx], axis=1), robustify, huber_a)
         return cov[:self.n_cams], cov[self.n_cams:]
 
+    # ---- the camera model ----
+    def set_intrinsics(self, intr, dist):
+        """Replaces the handle's camera model (vmm_ba_set_intrinsics): every later call behaves as a handle created with
+        it; the next solve captures its iteration graph again."""
+        intr = np.ascontiguousarray(intr, np.float64).reshape(4)
+        dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+        _lib.check(_lib.lib().vmm_ba_set_intrinsics(self._h, _ptr(intr), _ptr(dist)))
+        self.intr, self.dist = intr.copy(), dist.copy()
+
+    def get_intrinsics(self):
+        intr, dist = np.zeros(4), np.zeros(5)
+        _lib.check(_lib.lib().vmm_ba_get_intrinsics(self._h, _ptr(intr), _ptr(dist)))
+        return intr, dist
+
+    def intrinsics_system(self, robustify=True, huber_a=1.0):
+        """The camera-model part of the joint problem at the current state (vmm_ba_intrinsics_system): cost, g_k = Jk' r
+        and C = Jk' Jk over the active observations, and the reduced system with every pose eliminated,
+        r_k = g_k - B' A^-1 g and S_k = C - B' A^-1 B.  inv(S_k) is the covariance of the nine parameters."""
+        c = C.c_double(0)
+        gk, Ck, rk, Sk = np.zeros(9), np.zeros((9, 9)), np.zeros(9), np.zeros((9, 9))
+        _lib.check(_lib.lib().vmm_ba_intrinsics_system(self._h, int(bool(robustify)), float(huber_a), C.byref(c),
+                                                       _ptr(gk), _ptr(Ck), _ptr(rk), _ptr(Sk)))
+        return {"cost": c.value, "g_k": gk, "C": Ck, "r_k": rk, "S_k": Sk}
+
+    def solve_selfcal(self, options=None, trace_capacity=0, max_outer_iterations=None, refine_mask=None,
+                      parameter_tolerance=None, function_tolerance=None, **kw):
+        """Bundle adjustment with the camera model refined (vmm_ba_solve_selfcal).  options / **kw: the inner solver's
+        options as solve() takes them; the four named arguments are the fields of vmm_ba_selfcal_options.
+        Returns (intr, dist, intr_cov (9, 9), report dict, summary of the last inner solve as solve() returns it)."""
+        o = options or default_options(**kw)
+        so = _lib.SelfcalOptions()
+        _lib.lib().vmm_ba_default_selfcal_options(C.byref(so))
+        for name, v in (("max_outer_iterations", max_outer_iterations), ("refine_mask", refine_mask),
+                        ("parameter_tolerance", parameter_tolerance), ("function_tolerance", function_tolerance)):
+            if v is not None:
+                setattr(so, name, v)
+        s, r = _lib.Summary(), _lib.SelfcalReport()
+        buf = None
+        if trace_capacity > 0:
+            buf = (_lib.Iteration * trace_capacity)()
+            s.trace, s.trace_capacity = buf, trace_capacity
+        intr, dist, cov = np.zeros(4), np.zeros(5), np.zeros((9, 9))
+        _lib.check(_lib.lib().vmm_ba_solve_selfcal(self._h, C.byref(o), C.byref(so), C.byref(s), C.byref(r), _ptr(intr),
+                                                   _ptr(dist), _ptr(cov)))
+        self.intr, self.dist = intr.copy(), dist.copy()
+        out = {k: getattr(s, k) for k, _ in _lib.Summary._fields_ if k not in ("trace", "trace_capacity", "reserved")}
+        out["trace"] = [{k: getattr(buf[i], k) for k, _ in _lib.Iteration._fields_ if k != "reserved"}
+                        for i in range(min(s.iterations, trace_capacity))] if buf is not None else []
+        report = {k: getattr(r, k) for k, _ in _lib.SelfcalReport._fields_}
+        return intr, dist, cov, report, out
+
     # ---- diagnostics ----
     def eval_blocks(self, robustify=True, huber_a=1.0, want_W=True):
         V, U = np.zeros((self.n_cams, 6, 6)), np.zeros((self.n_tags, 6, 6))

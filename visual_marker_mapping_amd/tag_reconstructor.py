@@ -158,6 +158,7 @@ class TagReconstructor:
         self.lastPoseCovariances = None                        # {"tags": {id: 6x6}, "cameras": {id: 6x6}} (computePoseCovariances)
         self.lastInitReport = None                             # report of vmm_ba_initialize (startReconstructionGlobal)
         self.lastLocalizationReport = None                     # image id -> report (computeRelativeCameraPosesFromImgs)
+        self.lastSelfCalibrationReport = None                  # report of doBundleAdjustment(refineCameraModel=True)
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
         self._obs_cache = None                                 # observation list as arrays (see _obs_arrays)
         self._resident = False                                 # device-resident packing (startReconstruction)
@@ -704,8 +705,15 @@ class TagReconstructor:
             self.reconstructedCameras[cid].t = cam[k, 4:].copy()
 
     def doBundleAdjustment(self, maxNumIterations, ceresThreads=1, robustify=True, printSummary=False,
-                           elimination=_engine.ELIM_AUTO):
-        """src/TagReconstructor.cpp:646-743.  Poses are updated in place like the reference's map nodes."""
+                           elimination=_engine.ELIM_AUTO, refineCameraModel=False, refine_mask=0x1FF):
+        """src/TagReconstructor.cpp:646-743.  Poses are updated in place like the reference's map nodes.
+
+        refineCameraModel (not in the reference, which takes the camera model as given): the parameters of refine_mask
+        (bit i = parameter i of fx, fy, cx, cy, k1, k2, p1, p2, k3) are refined together with the poses
+        (vmm_ba_solve_selfcal); camModel becomes the result and lastSelfCalibrationReport holds the fields of
+        vmm_ba_selfcal_report plus `intrinsics` (9,), `covariance` (9, 9) and `std` (9,).  lastSummary is then the
+        summary of the last inner solve.  The inner solves run with function_tolerance 1e-14 and parameter_tolerance
+        1e-12 instead of the defaults, which stop too early for the outer loop's cost comparisons."""
         p = self._pack_for_ba()
         if p is None:
             return
@@ -713,7 +721,15 @@ class TagReconstructor:
         try:
             opts = _engine.default_options(max_num_iterations=int(maxNumIterations), robustify=int(bool(robustify)),
                                            num_threads=int(ceresThreads))
-            summary = ba.solve(opts, trace_capacity=int(maxNumIterations) + 2 if printSummary else 0)
+            trace_capacity = int(maxNumIterations) + 2 if printSummary else 0
+            if refineCameraModel:
+                # the outer loop compares the costs of consecutive solves down to a relative 1e-12: every inner solve
+                # has to converge well below Ceres' default stopping rules (a relative cost decrease of 1e-6)
+                opts.function_tolerance, opts.parameter_tolerance = 1e-14, 1e-12
+                intr, dist, intr_cov, report, summary = ba.solve_selfcal(opts, trace_capacity=trace_capacity,
+                                                                         refine_mask=int(refine_mask))
+            else:
+                summary = ba.solve(opts, trace_capacity=trace_capacity)
             cam, tag = ba.get_state()
             cov = ba.tag_translation_covariance(robustify, opts.huber_a) if printSummary else None   # :744-760
         except Exception:
@@ -724,6 +740,17 @@ class TagReconstructor:
             self.reconstructedTags[tid].q = tag[k, :4].copy()
             self.reconstructedTags[tid].t = tag[k, 4:].copy()
         self.lastSummary = summary
+        if refineCameraModel:
+            m = self.camModel
+            self.camModel = CameraModel(fx=float(intr[0]), fy=float(intr[1]), cx=float(intr[2]), cy=float(intr[3]),
+                                        distortionCoefficients=dist, verticalResolution=m.verticalResolution,
+                                        horizontalResolution=m.horizontalResolution)
+            self.lastSelfCalibrationReport = dict(report, intrinsics=np.concatenate([intr, dist]), covariance=intr_cov,
+                                                  std=np.sqrt(np.diag(intr_cov)))
+            self._drop_cached()   # the cached handle is keyed by the model it was created with
+            print("Camera model refined: status %d, %d outer iterations (%d accepted), cost %.6e -> %.6e" % (
+                report["status"], report["outer_iterations"], report["accepted"], report["initial_cost"],
+                report["final_cost"]))
         print("Solution %d" % summary["termination_type"])                                   # :740
         if printSummary:                                                                     # :741-742
             print("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius")

@@ -4,16 +4,18 @@ vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every C
 (csrc/kernels_chol*.hip, kernels_backsolve.hip) through vmm_ba_dense_spd_solve and a tree-ordered bundle adjustment.
 --cases calibrate: vmm_ba_calibrate (csrc/kernels_calibrate.hip behind the localisation's three kernels).
 --cases cov: vmm_ba_tag_translation_covariance (csrc/kernels_cov.hip) after a solve.
+--cases handle: the other entries that work on a handle after a solve (csrc/covariance.hip, selfcal.hip, initialize.hip
+and the evaluation entries of vmm_ba.hip).
 
-    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|cov] [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|cov|handle] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
 {"equal": ..., "outputs": {name: {"equal": ..., "sha256": [a, b]}}}; the exit status is 1 on any difference.  A float
 output of 3 x 3 blocks that differs also gets "max_gap_3x3", the largest |a - b| over the largest |a| of its block.  The
 scenes are the smallest that reach every loop trip and both variants of every kernel; all of
-them are generated here from fixed seeds.  The wall times in the initialisation and calibration reports are the fields
-left out."""
+them are generated here from fixed seeds.  The wall times in the initialisation, calibration and self-calibration
+reports and in the solver's summary are the fields left out."""
 import argparse
 import hashlib
 import json
@@ -224,6 +226,65 @@ def _cov_cases(eng, make_scene, out):
     assert res["block_sparse"] == 1, res["block_sparse"]   # else the handle was dense all along: pick another scene
 
 
+def _handle_cases(eng, make_scene, out):
+    """The two smallest scenes of tests/test_gpu_selfcal.py with a non-zero distortion (12 x 8) and a k_dim above 64 (the
+    12 x 30 close-up), under both eliminations.  After a solve from the initial guess: vmm_ba_covariance_blocks for pairs
+    that mix eliminated and kept poses (6 distinct poses: a right-hand side of 36 columns, not a multiple of 64),
+    vmm_ba_intrinsics_system, vmm_ba_eval_blocks, vmm_ba_reprojection_stats and vmm_ba_cost, robust and plain; then
+    vmm_ba_solve_selfcal from the true poses and a camera model off the truth (that test file's start), with every
+    parameter free and with the distortion held, on a handle of its own each; vmm_ba_initialize from poses that say
+    nothing."""
+    scenes = (("distortion_12x8", 5, dict(n_cams=12, n_tags=8, visibility=0.6)),
+              ("closeup_12x30", 2, dict(n_cams=12, n_tags=30, neighbors_min=6, neighbors_max=10)))
+    perturb = np.array([200.0, -150.0, 30.0, -25.0, 0.02, -0.05, 1e-3, -1e-3, 0.02])
+    for name, cfg, kw in scenes:
+        s = make_scene(cfg, **kw)
+        nc, nt = len(s.cam_init), len(s.tag_init)
+        pairs = np.array([[0, 0], [0, nc], [nc + 1, 1], [nc + nt - 1, nc + nt - 1], [nc - 1, 0], [nc, nc + 1]])
+        assert len(np.unique(pairs)) == 6
+        for elim, mode in (("tags", eng.ELIM_TAGS), ("cams", eng.ELIM_CAMERAS)):
+            key = "handle_%s_elim_%s_" % (name, elim)
+            new = lambda intr, dist, cam, tag: eng.BundleAdjuster(intr, dist, cam, tag, s.tag_wh, s.fixed_tag, s.obs_cam,
+                                                                  s.obs_tag, s.obs_px, elimination=mode)
+            with new(s.intr, s.dist, s.cam_init, s.tag_init) as ba:
+                res = ba.solve(eng.default_options(robustify=1))
+                out[key + "solve"] = np.array([res["termination_type"], res["iterations"]], np.int64)
+                out[key + "cam_qt"], out[key + "tag_qt"] = ba.get_state()
+                for robust in (0, 1):
+                    r = key + ("robust_" if robust else "plain_")
+                    out[r + "covariance_blocks"] = ba.covariance_blocks(pairs, robustify=bool(robust))
+                    for k, v in ba.intrinsics_system(robustify=bool(robust)).items():
+                        out[r + "system_" + k] = np.asarray(v)
+                    for k, v in ba.eval_blocks(robustify=bool(robust)).items():
+                        out[r + "eval_" + k] = np.asarray(v)
+                    out[r + "cost"] = np.array([ba.cost(robustify=bool(robust))])
+                pc, pt, avg, corner = ba.reprojection_stats()
+                out[key + "stats_per_cam"], out[key + "stats_per_tag"], out[key + "stats_corner"] = pc, pt, corner
+                out[key + "stats_avg"] = np.array([avg])
+            k0 = np.concatenate([s.intr, s.dist]) + perturb
+            for mask in (0x1FF, 0x00F):
+                m = key + "selfcal_m%03x_" % mask
+                with new(k0[:4], k0[4:], s.cam_gt, s.tag_gt) as ba:
+                    intr, dist, cov, rep, summ = ba.solve_selfcal(eng.default_options(robustify=1), refine_mask=mask)
+                    out[m + "intr"], out[m + "dist"], out[m + "intr_cov"] = intr, dist, cov
+                    out[m + "cam_qt"], out[m + "tag_qt"] = ba.get_state()
+                ints, floats = ("status", "outer_iterations", "accepted", "inner_lm_iterations"), ("initial_cost", "final_cost")
+                assert sorted(ints + floats + ("time_s",)) == sorted(rep), sorted(rep)   # a new field belongs in one of them
+                out[m + "report_int"] = np.array([rep[k] for k in ints], np.int64)
+                out[m + "report_f64"] = np.array([rep[k] for k in floats])
+                out[m + "last_inner"] = np.array([summ[k] for k in ("termination_type", "iterations", "num_lm_iterations")], np.int64)
+                out[m + "last_inner_cost"] = np.array([summ["initial_cost"], summ["final_cost"]])
+            cam = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 1.0]), (nc, 1))
+            tag = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0.0]), (nt, 1))
+            tag[s.fixed_tag] = s.tag_gt[s.fixed_tag]
+            with new(s.intr, s.dist, cam, tag) as ba:
+                report, cam_ok, tag_ok = ba.initialize(sweeps=1)
+                out[key + "init_cam_qt"], out[key + "init_tag_qt"] = ba.get_state()
+            out[key + "init_cam_reached"], out[key + "init_tag_reached"] = cam_ok, tag_ok
+            out[key + "init_counts"] = np.array([report["rounds"], report["cams_reached"], report["tags_reached"]], np.int64)
+            out[key + "init_avg_px"] = np.array([report["avg_reprojection_px"]])
+
+
 def child(path, cases):
     sys.path.insert(0, ROOT)
     from visual_marker_mapping_amd import engine as eng
@@ -237,6 +298,8 @@ def child(path, cases):
         _calibrate_cases(eng, make_scene, out)
     elif cases == "cov":
         _cov_cases(eng, make_scene, out)
+    elif cases == "handle":
+        _handle_cases(eng, make_scene, out)
     else:
         _chol_dense_cases(eng, out)
         _chol_tree_cases(eng, make_scene, out)
@@ -247,7 +310,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
-    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "cov"), default="pose", help="which set of cases (default: pose)")
+    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "cov", "handle"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()

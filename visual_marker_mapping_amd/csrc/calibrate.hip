@@ -9,7 +9,7 @@
 #include <chrono>
 #include <string>
 
-#include "engine.hpp"
+#include "host.hpp"
 #include "pose_lm.hpp"
 
 using namespace vmm;

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -453,17 +452,6 @@ struct MapBatch {
     }
     void results(Arena& ar, double* cam_qt, double* cam_cov, uint8_t* obs_inlier, vmm_ba_localize_result* res_out) const;
 };
-int bad_argument(const char* who, const char* what);                 // VMM_BA_ERR_ARGUMENT, "<who>: <what>"
-int hip_failure(const char* who, const char* step, hipError_t err);  // VMM_BA_ERR_HIP, "<who>: <step><error string>"
-int check_camera_model(const char* who, const double intr[4], const double dist[5]);   // finite
-int check_batch(const char* who, MapBatch& mb, int32_t n_tags, const double* tag_qt, const double* tag_wh, int32_t n_imgs,
-                const int64_t* img_start, const int32_t* obs_tag, const double* obs_px, const double* cam_qt);
-int check_map(const char* who, const MapBatch& mb);
-int check_localize_options(const char* who, const vmm_ba_localize_options& o);
-// n_obs == 0: every image reports NO_OBSERVATIONS, the identity pose and a zero covariance
-void fill_no_observations(int32_t n_imgs, double* cam_qt, double* cam_cov, vmm_ba_localize_result* res);
-// hipSetDevice, and on an entry point's first call on a device every preload_* of `preload` (`done`: the caller's flags)
-int select_device(const char* who, int device, bool (&done)[64], std::initializer_list<int (*)()> preload);
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
 constexpr int kCalRec = 68;    // doubles of an image's record: reduced 9 x 9 block (45, packed lower) | reduced gradient (9) |
                                // diag(C) (9) | cost | sum |r|^2 | 1 if A + lam diag was not positive definite | inlier

@@ -7,7 +7,7 @@
 
 #include <string>
 
-#include "engine.hpp"
+#include "host.hpp"
 
 namespace vmm {
 

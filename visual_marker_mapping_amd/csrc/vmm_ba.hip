@@ -4,6 +4,11 @@
 // (/root/reference/src/TagReconstructor.cpp:646-743): vmm_ba_create() takes the place of the
 // ceres::Problem construction (:657-724), vmm_ba_solve() of ceres::Solve (:737-738).  No CPU
 // fallback exists: without a HIP device every entry point fails with VMM_BA_ERR_HIP.
+//
+// This file: the error text, the handle (create, destroy, collectives, state), the LM iteration with its graphs,
+// vmm_ba_solve and the evaluation entries.  The other entry families have host files of their own -- covariance.hip,
+// selfcal.hip, initialize.hip, standalone.hip, diagnostics.hip, localize.hip, calibrate.hip -- and take what they
+// need from here through host.hpp.
 #include <dlfcn.h>
 #include <math.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl.so is resolved with dlopen when a communicator is asked for
@@ -14,38 +19,16 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <mutex>
 #include <string>
 #include <functional>
 #include <vector>
 
-#include "engine.hpp"
+#include "host.hpp"
 
 namespace vmm {
 
 static thread_local std::string g_err;
 void set_error(const std::string& s) { g_err = s; }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                         \
-            return VMM_BA_ERR_HIP;                                                                 \
-        }                                                                                          \
-    } while (0)
-
-template <typename T>
-static int dev_alloc(Engine& e, T** p, size_t count, bool zero = true)
-{
-    *p = nullptr;
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    HIP_TRY(hipMalloc((void**)p, bytes));
-    e.allocs.push_back(*p);
-    if (zero)
-        HIP_TRY(hipMemsetAsync(*p, 0, bytes, e.stream));
-    return VMM_BA_OK;
-}
 
 template <typename T>
 static int upload(Engine& e, T* dst, const std::vector<T>& src)
@@ -77,18 +60,16 @@ static Roctx& roctx()
     static Roctx r;
     return r;
 }
-struct Range {
-    explicit Range(const char* name)
-    {
-        if (roctx().push)
-            roctx().push(name);
-    }
-    ~Range()
-    {
-        if (roctx().pop)
-            roctx().pop();
-    }
-};
+Range::Range(const char* name)
+{
+    if (roctx().push)
+        roctx().push(name);
+}
+Range::~Range()
+{
+    if (roctx().pop)
+        roctx().pop();
+}
 
 // RCCL (north_star: "RCCL all-reduce over xGMI of the reduced camera system")
 struct Rccl {
@@ -148,7 +129,7 @@ static int upload_order(Engine& e, ObsOrder& o, const OrderPlan& p)
 }
 
 // The rank-k schedule of plan_syrk on the device: a fresh plan every time, and one partial tile per segment.
-static int make_syrk_plan(Engine& e, SyrkPlan& p, int n_row_blk, int n_col_blk, int k_pad)
+int make_syrk_plan(Engine& e, SyrkPlan& p, int n_row_blk, int n_col_blk, int k_pad)
 {
     const SyrkSchedule s = plan_syrk(n_row_blk, n_col_blk, k_pad, e.n_cu, e.sw);
     p = SyrkPlan();
@@ -175,7 +156,7 @@ static int make_syrk_plan(Engine& e, SyrkPlan& p, int n_row_blk, int n_col_blk, 
     return VMM_BA_OK;
 }
 // the two alternating transposed-panel buffers of the look-ahead Cholesky; P must be allocated
-static int setup_lookahead(Engine& e, int n_blk_max, int ld)
+int setup_lookahead(Engine& e, int n_blk_max, int ld)
 {
     (void)n_blk_max;
     for (int i = 0; i < 4; ++i)
@@ -246,7 +227,7 @@ static void points_to_tag(const double* pts, double* qt)
 
 // Dense Z and the plan of its rank-k update (the default at high visibility; a handle on the block-sparse path
 // builds them the first time the covariance report asks for Z as a matrix).
-static int ensure_dense_schur(Engine& e)
+int ensure_dense_schur(Engine& e)
 {
     if (e.Z)
         return VMM_BA_OK;
@@ -380,7 +361,7 @@ static int allreduce_after(Engine& e, int seg)
     }
 }
 
-static int enqueue_iteration(Engine& e, const vmm_ba_options& o)
+int enqueue_iteration(Engine& e, const vmm_ba_options& o)
 {
     static const char* const names[kNumSeg] = { "vmm_ba evaluation at the candidate", "vmm_ba decide + eliminate + rank-k",
                                                 "vmm_ba factor + solve + step", "vmm_ba candidate" };
@@ -442,7 +423,7 @@ static bool capture_alive(Engine& e)
     return st == hipStreamCaptureStatusActive;
 }
 
-static void drop_graphs(Engine& e)
+void drop_graphs(Engine& e)
 {
     for (auto& g : e.iter_graph_seg)
         if (g) {
@@ -466,7 +447,7 @@ static const char* const kSegName[kNumSeg] = { "evaluation at the candidate", "d
 // No kernel is launched for the first time under capture: vmm_ba_create touches every kernel (preload_*_kernels).
 // Round 1 ran the first iteration of a handle eagerly because of an intermittent "operation failed due to a previous
 // error during capture" at 2000 x 1000; VMM_BA_EAGER_FIRST=1 brings that back.
-static int run_iteration(Engine& e, const vmm_ba_options& o)
+int run_iteration(Engine& e, const vmm_ba_options& o)
 {
     e.last_passes = 1;
     if (!e.sw.use_graph)
@@ -550,8 +531,6 @@ static int run_iteration(Engine& e, const vmm_ba_options& o)
     return VMM_BA_OK;
 }
 
-static void init_ctl(Engine& e, LmCtl& c, const vmm_ba_options& o, int trace_capacity);
-
 // The control block (already read back into e.ctl_host) says done == 2: a workgroup of k_chol_dataflow or
 // k_backsolve_chain gave up waiting for another one in the pass that paused.  That is a scheduling event (several
 // processes time-slicing one GPU, a profiler serialising workgroups), not a property of the matrix: the pass is
@@ -584,7 +563,7 @@ static int recover_sync_timeout(Engine& e, const vmm_ba_options& o)
 }
 
 // Control block and candidate buffers at the start of an LM loop: iteration zero evaluates "the candidate" = x.
-static int begin_lm_loop(Engine& e, const vmm_ba_options& o, int trace_capacity)
+int begin_lm_loop(Engine& e, const vmm_ba_options& o, int trace_capacity)
 {
     init_ctl(e, *e.ctl_host, o, trace_capacity);
     launch_begin_loop(e, *e.ctl_host);   // control block, staged poses -> state, state -> candidate: one launch
@@ -599,7 +578,7 @@ static int begin_lm_loop(Engine& e, const vmm_ba_options& o, int trace_capacity)
 
 // Poses staged by vmm_ba_set_state go to the device (every entry point that reads them there calls this first;
 // vmm_ba_solve does it inside k_begin_loop).
-static int flush_state(Engine& e)
+int flush_state(Engine& e)
 {
     if (!e.dirty_cam && !e.dirty_tag)
         return VMM_BA_OK;
@@ -614,7 +593,7 @@ static int flush_state(Engine& e)
     return VMM_BA_OK;
 }
 
-static void init_ctl(Engine& e, LmCtl& c, const vmm_ba_options& o, int trace_capacity)
+void init_ctl(Engine& e, LmCtl& c, const vmm_ba_options& o, int trace_capacity)
 {
     memset(&c, 0, sizeof(c));
     c.spin_limit_df = e.sw.spin_df;
@@ -1155,10 +1134,8 @@ int vmm_ba_get_points(vmm_ba_handle h, double* points)
         return VMM_BA_ERR_STATE;
     }
     HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
+    int rc;
+    if ((rc = flush_state(e))) return rc;
     std::vector<double> pairs((size_t)7 * e.n_tags);
     HIP_TRY(hipMemcpyAsync(pairs.data(), e.tag_qt, sizeof(double) * pairs.size(), hipMemcpyDeviceToHost, e.stream));
     HIP_TRY(hipStreamSynchronize(e.stream));
@@ -1178,16 +1155,13 @@ int vmm_ba_get_state(vmm_ba_handle h, double* cam_qt, double* tag_qt)
     }
     Engine& e = *reinterpret_cast<Engine*>(h);
     HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
+    int rc;
+    if ((rc = flush_state(e))) return rc;
     if (cam_qt)
         HIP_TRY(hipMemcpyAsync(cam_qt, e.cam_qt, sizeof(double) * 7 * e.n_cams, hipMemcpyDeviceToHost, e.stream));
     if (tag_qt && e.points) {   // tag poses rebuilt from the optimised corners (src/TagReconstructor.cpp:608-639)
         std::vector<double> pts((size_t)12 * e.n_tags_user);
         HIP_TRY(hipStreamSynchronize(e.stream));
-        int rc;
         if ((rc = vmm_ba_get_points(h, pts.data()))) return rc;
         for (int t = 0; t < e.n_tags_user; ++t)
             points_to_tag(pts.data() + (size_t)12 * t, tag_qt + (size_t)7 * t);
@@ -1226,8 +1200,8 @@ int vmm_ba_solve(vmm_ba_handle h, const vmm_ba_options* opt, vmm_ba_summary* s)
 
     // device trace buffer sized for this call
     const int need_cap = std::max(user_cap, 1);
+    int rc;
     if (need_cap > e.trace_capacity) {
-        int rc;
         drop_graphs(e);   // the captured k_control holds the old trace pointer
         if (e.trace) {
             HIP_TRY(hipStreamSynchronize(e.stream));
@@ -1239,16 +1213,12 @@ int vmm_ba_solve(vmm_ba_handle h, const vmm_ba_options* opt, vmm_ba_summary* s)
         if ((rc = dev_alloc(e, &e.trace, (size_t)need_cap, false))) return rc;
         e.trace_capacity = need_cap;
     }
-    {
-        int rc;
-        if ((rc = begin_lm_loop(e, o, user_cap))) return rc;
-    }
+    if ((rc = begin_lm_loop(e, o, user_cap))) return rc;
 
     const int poll = std::max(1, o.poll_interval);
     const int64_t max_steps = (int64_t)o.max_num_iterations + 2;
     int64_t enq = 0;
     for (;;) {
-        int rc;
         for (int k = 0; k < poll && enq < max_steps; ++k) {
             if ((rc = run_iteration(e, o))) return rc;
             enq += e.last_passes;
@@ -1312,12 +1282,9 @@ int vmm_ba_cost(vmm_ba_handle h, int robustify, double huber_a, double* cost)
     }
     Engine& e = *reinterpret_cast<Engine*>(h);
     HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
-    launch_cost(e, e.cam_qt, e.tag_qt, false, robustify, huber_a, e.cost_comm);
     int rc;
+    if ((rc = flush_state(e))) return rc;
+    launch_cost(e, e.cam_qt, e.tag_qt, false, robustify, huber_a, e.cost_comm);
     if ((rc = do_allreduce(e, e.cost_comm, 1))) return rc;
     HIP_TRY(hipMemcpyAsync(cost, e.cost_comm, sizeof(double), hipMemcpyDeviceToHost, e.stream));
     HIP_TRY(hipStreamSynchronize(e.stream));
@@ -1371,15 +1338,11 @@ int vmm_ba_reprojection_stats(vmm_ba_handle h, double* per_cam_mean, double* per
         return VMM_BA_ERR_STATE;
     }
     HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
+    int rc;
+    if ((rc = flush_state(e))) return rc;
     const int n_pose = e.n_cams + e.n_tags;
-    if (per_corner && e.n_obs > 0 && !e.stats_corner) {
-        int rc;
-        if ((rc = dev_alloc(e, &e.stats_corner, (size_t)8 * e.n_obs, false))) return rc;
-    }
+    if (per_corner && e.n_obs > 0 && !e.stats_corner && (rc = dev_alloc(e, &e.stats_corner, (size_t)8 * e.n_obs, false)))
+        return rc;
     launch_stats(e, (per_corner && e.n_obs > 0) ? e.stats_corner : nullptr);
     HIP_TRY(hipGetLastError());
     // per-pose sums and counts come back in one copy; the means and the average are formed here in the
@@ -1410,778 +1373,6 @@ int vmm_ba_reprojection_stats(vmm_ba_handle h, double* per_cam_mean, double* per
     return VMM_BA_OK;
 }
 
-// The dense, naturally ordered system for the length of a covariance call: a handle on the block-sparse or tree-ordered
-// path switches over (the covariance kernels read Z as a dense matrix) and back when the guard goes out of scope.
-struct CovDensePath {
-    Engine& e;
-    bool v, nz;
-    CovDensePath(Engine& e_) : e(e_), v(e_.sparse_schur), nz(e_.chol_nz_on) {}
-    int enter()
-    {
-        if (v) {
-            int drc;
-            if ((drc = ensure_dense_schur(e))) return drc;
-            e.sparse_schur = false;
-        }
-        e.chol_nz_on = false;   // the dense, naturally ordered system has no block structure to follow
-        return VMM_BA_OK;
-    }
-    ~CovDensePath()
-    {
-        e.sparse_schur = v;
-        e.chol_nz_on = nz;
-    }
-};
-
-// The preamble of both covariance entries: the iteration's kernels on the undamped, unscaled system (H blocks, Z,
-// S = L L^T + block inverses), then `tail` (the entry's own substitution, Gram kernels and copy of the result), the
-// control block back and a synchronisation.  A second attempt only after a spin give-up of the one-launch
-// factorisation: the same on the fallback path.
-static hipError_t cov_factor_and(Engine& e, int robustify, double huber_a, hipError_t err,
-                                 const std::function<hipError_t()>& tail)
-{
-    vmm_ba_options o;
-    vmm_ba_default_options(&o);
-    o.robustify = robustify;
-    o.huber_a = huber_a;
-    for (int attempt = 0; attempt < 2 && err == hipSuccess; ++attempt) {
-        init_ctl(e, *e.ctl_host, o, 0);
-        err = hipMemcpyAsync(e.ctl, e.ctl_host, sizeof(LmCtl), hipMemcpyHostToDevice, e.stream);
-        if (err != hipSuccess)
-            break;
-        launch_eval_passes(e, robustify, huber_a, false);
-        launch_cov_prepare(e);
-        launch_elim(e);
-        launch_syrk_reduced(e);
-        launch_cholesky_solve(e, e.S, e.n_pad, e.ldz, e.yf, e.ctl, attempt > 0);
-        launch_chol_inverse(e, e.n_blk - 1);
-        err = tail();
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(e.ctl_host, e.ctl, sizeof(LmCtl), hipMemcpyDeviceToHost, e.stream);
-        if (err == hipSuccess)
-            err = hipStreamSynchronize(e.stream);
-        if (err != hipSuccess || e.ctl_host->done != 2)
-            break;
-    }
-    return err;
-}
-
-int vmm_ba_tag_translation_covariance(vmm_ba_handle h, int robustify, double huber_a, double* cov)
-{
-    if (!h || !cov) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.multi || e.points) {
-        set_error("tag_translation_covariance needs a single-GPU handle with tag-pose landmarks");
-        return VMM_BA_ERR_STATE;
-    }
-    HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
-    if (e.n_obs == 0 || e.n_tags == 0) {
-        memset(cov, 0, sizeof(double) * 9 * (size_t)e.n_tags);
-        return VMM_BA_OK;
-    }
-    CovDensePath dense(e);
-    {
-        int drc;
-        if ((drc = dense.enter())) return drc;
-    }
-    // L X = B with B = I (tags kept) or Z^T (tags eliminated), then per-tag Gram blocks
-    const bool identity_rhs = e.elim_cams;
-    const int n_rhs = identity_rhs ? e.n_pad : e.k_dim;
-    const int ldb = round_up(n_rhs, 64);
-    double *B = nullptr, *cov_dev = nullptr;
-    hipError_t err = hipMalloc((void**)&B, sizeof(double) * (size_t)e.n_pad * ldb);
-    if (err == hipSuccess) err = hipMalloc((void**)&cov_dev, sizeof(double) * 9 * (size_t)e.n_tags);
-    err = cov_factor_and(e, robustify, huber_a, err, [&]() {
-        hipError_t er = hipMemsetAsync(B, 0, sizeof(double) * (size_t)e.n_pad * ldb, e.stream);
-        if (er == hipSuccess) {
-            launch_cov_rhs(e, B, ldb, identity_rhs);
-            launch_cov_trsm(e, B, ldb, ldb / 64, identity_rhs);
-            launch_cov_gram(e, B, ldb, cov_dev);
-            er = hipGetLastError();
-        }
-        if (er == hipSuccess)
-            er = hipMemcpyAsync(cov, cov_dev, sizeof(double) * 9 * (size_t)e.n_tags, hipMemcpyDeviceToHost, e.stream);
-        return er;
-    });
-    (void)hipFree(B);
-    (void)hipFree(cov_dev);
-    if (err != hipSuccess) {
-        set_error(std::string("tag_translation_covariance: ") + hipGetErrorString(err));
-        return VMM_BA_ERR_HIP;
-    }
-    if (e.ctl_host->lin_fail) {
-        set_error("tag_translation_covariance: J^T J is not positive definite (rank-deficient Jacobian)");
-        return VMM_BA_ERR_NUMERIC;
-    }
-    return VMM_BA_OK;
-}
-
-int vmm_ba_covariance_blocks(vmm_ba_handle h, int robustify, double huber_a, int64_t n_pairs, const int32_t* pose_a,
-                             const int32_t* pose_b, double* cov)
-{
-    if (!h || n_pairs < 0 || n_pairs > INT32_MAX / 4 || (n_pairs > 0 && (!pose_a || !pose_b || !cov))) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.multi || e.points) {
-        set_error("covariance_blocks needs a single-GPU handle with tag-pose landmarks");
-        return VMM_BA_ERR_STATE;
-    }
-    if (n_pairs == 0)
-        return VMM_BA_OK;
-    const int n_pose = e.n_cams + e.n_tags;
-    for (int64_t p = 0; p < n_pairs; ++p)
-        if (pose_a[p] < 0 || pose_a[p] >= n_pose || pose_b[p] < 0 || pose_b[p] >= n_pose) {
-            set_error("covariance_blocks: pair " + std::to_string(p) + " names a pose outside [0, n_cams + n_tags)");
-            return VMM_BA_ERR_ARGUMENT;
-        }
-    HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
-    if (e.n_obs == 0) {
-        memset(cov, 0, sizeof(double) * 36 * (size_t)n_pairs);
-        return VMM_BA_OK;
-    }
-    CovDensePath dense(e);
-    {
-        int drc;
-        if ((drc = dense.enter())) return drc;
-    }
-    // the distinct poses of the request, eliminated family first, then the kept poses by ascending row of the reduced
-    // system: slot s owns columns 6 s .. 6 s + 5 of the right-hand side, and the first non-zero block row of a 64-column
-    // chunk does not decrease from chunk to chunk
-    auto eliminated = [&](int p) { return e.elim_cams ? p < e.n_cams : p >= e.n_cams; };
-    auto family_index = [&](int p) { return p < e.n_cams ? p : p - e.n_cams; };
-    std::vector<int32_t> slot_of((size_t)n_pose, -1), poses;
-    for (int64_t p = 0; p < n_pairs; ++p)
-        for (int32_t q : { pose_a[p], pose_b[p] })
-            if (slot_of[(size_t)q] < 0) {
-                slot_of[(size_t)q] = 0;
-                poses.push_back(q);
-            }
-    std::sort(poses.begin(), poses.end(), [&](int32_t a, int32_t b) {
-        return eliminated(a) != eliminated(b) ? eliminated(a) : a < b;
-    });
-    const int n_slots = (int)poses.size();
-    const int ldb = round_up(6 * n_slots, 64), n_chunks = ldb / 64;
-    // device tables: slot_src[n_slots] | pair[n_pairs][4] = pose a, pose b, slot a, slot b
-    std::vector<int32_t> meta((size_t)n_slots + 4 * (size_t)n_pairs);
-    std::vector<int> first_row((size_t)n_chunks, e.n_blk), chunks_at((size_t)e.n_blk, 0);
-    for (int s = 0; s < n_slots; ++s) {
-        const int p = poses[(size_t)s];
-        slot_of[(size_t)p] = s;
-        const bool el = eliminated(p);
-        meta[(size_t)s] = el ? -1 - family_index(p) : 6 * family_index(p);
-        for (int c = 6 * s / 64; c <= (6 * s + 5) / 64; ++c)
-            first_row[(size_t)c] = std::min(first_row[(size_t)c], el ? 0 : 6 * family_index(p) / 64);
-    }
-    for (int k = 0; k < e.n_blk; ++k)
-        for (int c = 0; c < n_chunks && first_row[(size_t)c] <= k; ++c)
-            chunks_at[(size_t)k] = c + 1;
-    for (int64_t p = 0; p < n_pairs; ++p) {
-        int32_t* m = meta.data() + n_slots + 4 * p;
-        m[0] = pose_a[p];
-        m[1] = pose_b[p];
-        m[2] = slot_of[(size_t)pose_a[p]];
-        m[3] = slot_of[(size_t)pose_b[p]];
-    }
-    const size_t b_bytes = sizeof(double) * (size_t)e.n_pad * ldb;
-    double *B = nullptr, *cov_dev = nullptr;
-    int32_t* meta_dev = nullptr;
-    hipError_t err = hipMalloc((void**)&B, b_bytes);
-    if (err != hipSuccess) {
-        set_error("covariance_blocks: the right-hand side needs " + std::to_string(b_bytes) + " bytes: " +
-                  hipGetErrorString(err));
-        return VMM_BA_ERR_HIP;
-    }
-    err = hipMalloc((void**)&cov_dev, sizeof(double) * 36 * (size_t)n_pairs);
-    if (err == hipSuccess) err = hipMalloc((void**)&meta_dev, sizeof(int32_t) * meta.size());
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(meta_dev, meta.data(), sizeof(int32_t) * meta.size(), hipMemcpyHostToDevice, e.stream);
-    err = cov_factor_and(e, robustify, huber_a, err, [&]() {
-        hipError_t er = hipMemsetAsync(B, 0, b_bytes, e.stream);
-        if (er == hipSuccess) {
-            launch_cov_rhs_slots(e, meta_dev, n_slots, B, ldb);
-            launch_cov_trsm_mfma(e, B, ldb, chunks_at);
-            launch_cov_pairs(e, B, ldb, meta_dev + n_slots, n_pairs, cov_dev);
-            er = hipGetLastError();
-        }
-        if (er == hipSuccess)
-            er = hipMemcpyAsync(cov, cov_dev, sizeof(double) * 36 * (size_t)n_pairs, hipMemcpyDeviceToHost, e.stream);
-        return er;
-    });
-    (void)hipFree(B);
-    (void)hipFree(cov_dev);
-    (void)hipFree(meta_dev);
-    if (err != hipSuccess) {
-        set_error(std::string("covariance_blocks: ") + hipGetErrorString(err));
-        return VMM_BA_ERR_HIP;
-    }
-    if (e.ctl_host->lin_fail) {
-        set_error("covariance_blocks: J^T J is not positive definite (rank-deficient Jacobian)");
-        return VMM_BA_ERR_NUMERIC;
-    }
-    return VMM_BA_OK;
-}
-
-// ---- the camera model of a handle, and the bundle adjustment that refines it ----
-
-static int tag_pose_handle(const Engine& e, const char* who)
-{
-    if (e.multi || e.points) {
-        set_error(std::string(who) + " needs a single-GPU handle with tag-pose landmarks");
-        return VMM_BA_ERR_STATE;
-    }
-    return VMM_BA_OK;
-}
-
-int vmm_ba_set_intrinsics(vmm_ba_handle h, const double intr[4], const double dist[5])
-{
-    if (!h || !intr || !dist) {
-        set_error("set_intrinsics: null argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    for (int k = 0; k < 9; ++k)
-        if (!std::isfinite(k < 4 ? intr[k] : dist[k - 4])) {
-            set_error("set_intrinsics: the camera model is not finite");
-            return VMM_BA_ERR_ARGUMENT;
-        }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    int rc;
-    if ((rc = tag_pose_handle(e, "set_intrinsics"))) return rc;
-    HIP_TRY(hipSetDevice(e.device));
-    e.K = make_intrinsics(intr, dist);
-    drop_graphs(e);   // the captured kernels hold the model by value: the next solve captures again
-    return VMM_BA_OK;
-}
-
-int vmm_ba_get_intrinsics(vmm_ba_handle h, double intr[4], double dist[5])
-{
-    if (!h || !intr || !dist) {
-        set_error("get_intrinsics: null argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    const Intrinsics& K = reinterpret_cast<Engine*>(h)->K;
-    intr[0] = K.fx; intr[1] = K.fy; intr[2] = K.cx; intr[3] = K.cy;
-    dist[0] = K.k1; dist[1] = K.k2; dist[2] = K.p1; dist[3] = K.p2; dist[4] = K.k3;
-    return VMM_BA_OK;
-}
-
-int vmm_ba_intrinsics_system(vmm_ba_handle h, int robustify, double huber_a, double* cost, double* g_k, double* C,
-                             double* r_k, double* S_k)
-{
-    if (!h) {
-        set_error("intrinsics_system: null handle");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    int rc;
-    if ((rc = tag_pose_handle(e, "intrinsics_system"))) return rc;
-    HIP_TRY(hipSetDevice(e.device));
-    if ((rc = flush_state(e))) return rc;
-    double out[kBorderOut] = {};
-    if (e.n_obs > 0) {
-        CovDensePath dense(e);
-        if ((rc = dense.enter())) return rc;
-        double* ws = nullptr;
-        hipError_t err = hipMalloc((void**)&ws, sizeof(double) * border_workspace_doubles(e));
-        err = cov_factor_and(e, robustify, huber_a, err, [&]() {
-            const double* res = launch_border(e, robustify, huber_a, ws);
-            hipError_t er = hipGetLastError();
-            if (er == hipSuccess)
-                er = hipMemcpyAsync(out, res, sizeof(out), hipMemcpyDeviceToHost, e.stream);
-            return er;
-        });
-        (void)hipFree(ws);
-        if (err != hipSuccess) {
-            set_error(std::string("intrinsics_system: ") + hipGetErrorString(err));
-            return VMM_BA_ERR_HIP;
-        }
-        if (e.ctl_host->lin_fail) {
-            set_error("intrinsics_system: the pose system J^T J is not positive definite (rank-deficient Jacobian)");
-            return VMM_BA_ERR_NUMERIC;
-        }
-    }
-    if (cost) *cost = out[0];
-    if (g_k) memcpy(g_k, out + 1, sizeof(double) * 9);
-    if (C) memcpy(C, out + 10, sizeof(double) * 81);
-    if (r_k) memcpy(r_k, out + 91, sizeof(double) * 9);
-    if (S_k) memcpy(S_k, out + 100, sizeof(double) * 81);
-    return VMM_BA_OK;
-}
-
-void vmm_ba_default_selfcal_options(vmm_ba_selfcal_options* o)
-{
-    if (!o)
-        return;
-    o->max_outer_iterations = 30;
-    o->refine_mask = 0x1FF;
-    o->parameter_tolerance = 1e-10;
-    o->function_tolerance = 1e-12;
-}
-
-// The 9 x 9 system of the camera model on the host, as k_calib_solve (kernels_calibrate.hip) treats its own: the fixed
-// parameters get unit rows, the rest is damped by lam diag(S), scaled to a unit diagonal and factored; a pivot times its
-// weight must exceed min_pivot.  M receives the factor (lower), sc the scaling.
-static bool selfcal_factor(const double* S, const double* C, int mask, double lam, bool weighted, double (&M)[9][9],
-                           double (&sc)[9])
-{
-    bool ok = true;
-    double weight[9];
-    for (int j = 0; j < 9; ++j) {
-        const bool free_j = (mask >> j) & 1;
-        const double d = free_j ? S[10 * j] + lam * S[10 * j] : 1.0;
-        ok = ok && d > 0.0 && std::isfinite(d);
-        sc[j] = free_j && d > 0.0 ? 1.0 / sqrt(d) : 1.0;
-        weight[j] = weighted && free_j ? d / C[10 * j] : 1.0;   // S_jj / C_jj
-    }
-    for (int i = 0; i < 9; ++i)
-        for (int j = 0; j < 9; ++j) {
-            const bool both = ((mask >> i) & 1) && ((mask >> j) & 1);
-            M[i][j] = i == j ? 1.0 : (both && j < i ? S[9 * i + j] * sc[i] * sc[j] : 0.0);
-        }
-    for (int j = 0; j < 9 && ok; ++j) {
-        double d = M[j][j];
-        for (int k = 0; k < j; ++k)
-            d -= M[j][k] * M[j][k];
-        ok = d * weight[j] > (weighted ? 1e-13 : 0.0) && std::isfinite(d);
-        if (!ok)
-            break;
-        const double sq = sqrt(d);
-        M[j][j] = sq;
-        for (int i = j + 1; i < 9; ++i) {
-            double v = M[i][j];
-            for (int k = 0; k < j; ++k)
-                v -= M[i][k] * M[j][k];
-            M[i][j] = v / sq;
-        }
-    }
-    return ok;
-}
-
-// x = D (L L')^-1 D b
-static void selfcal_apply(const double (&M)[9][9], const double (&sc)[9], const double* b, double* x)
-{
-    double z[9];
-    for (int i = 0; i < 9; ++i) {
-        double v = b[i] * sc[i];
-        for (int k = 0; k < i; ++k)
-            v -= M[i][k] * z[k];
-        z[i] = v / M[i][i];
-    }
-    for (int i = 8; i >= 0; --i) {
-        double v = z[i];
-        for (int k = i + 1; k < 9; ++k)
-            v -= M[k][i] * z[k];
-        z[i] = v / M[i][i];
-    }
-    for (int i = 0; i < 9; ++i)
-        x[i] = z[i] * sc[i];
-}
-
-// cov = S^-1 over the free parameters (zeros elsewhere), symmetric in its bits; false (and zeros): S fails the pivot test
-static bool selfcal_covariance(const double* S, const double* C, int mask, double* cov)
-{
-    double M[9][9], sc[9];
-    memset(cov, 0, sizeof(double) * 81);
-    if (!selfcal_factor(S, C, mask, 0.0, true, M, sc))
-        return false;
-    double col[9][9];
-    bool finite = true;
-    for (int j = 0; j < 9; ++j) {
-        double unit[9] = {};
-        unit[j] = 1.0;
-        selfcal_apply(M, sc, unit, col[j]);
-        for (int i = 0; i < 9; ++i)
-            finite = finite && std::isfinite(col[j][i]);
-    }
-    if (!finite)
-        return false;
-    for (int i = 0; i < 9; ++i)
-        for (int j = 0; j <= i; ++j)
-            if (((mask >> i) & 1) && ((mask >> j) & 1))
-                cov[9 * i + j] = cov[9 * j + i] = col[j][i];
-    return true;
-}
-
-int vmm_ba_solve_selfcal(vmm_ba_handle h, const vmm_ba_options* inner, const vmm_ba_selfcal_options* so,
-                         vmm_ba_summary* last_inner, vmm_ba_selfcal_report* rep, double intr[4], double dist[5],
-                         double* intr_cov)
-{
-    if (!h || !rep || !intr || !dist) {
-        set_error("solve_selfcal: null argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    vmm_ba_selfcal_options o;
-    if (so)
-        o = *so;
-    else
-        vmm_ba_default_selfcal_options(&o);
-    if (o.max_outer_iterations < 0 || o.refine_mask < 0 || o.refine_mask > 0x1FF || !(o.parameter_tolerance >= 0.0)
-        || !(o.function_tolerance >= 0.0)) {
-        set_error("solve_selfcal: bad options");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    int rc;
-    if ((rc = tag_pose_handle(e, "solve_selfcal"))) return rc;
-    vmm_ba_options in;
-    if (inner)
-        in = *inner;
-    else
-        vmm_ba_default_options(&in);
-    const auto t0 = std::chrono::steady_clock::now();
-    memset(rep, 0, sizeof(*rep));
-    vmm_ba_summary local;
-    memset(&local, 0, sizeof(local));
-    vmm_ba_summary* const s = last_inner ? last_inner : &local;
-    const int mask = o.refine_mask;
-    double k[9], cov[81] = {};
-    vmm_ba_get_intrinsics(h, k, k + 4);
-    auto solve = [&]() {
-        const int r = vmm_ba_solve(h, &in, s);
-        if (r == VMM_BA_OK)
-            rep->inner_lm_iterations += s->num_lm_iterations;
-        return r;
-    };
-    auto finish = [&](int status, double cost) {
-        rep->status = status;
-        rep->final_cost = cost;
-        memcpy(intr, k, sizeof(double) * 4);
-        memcpy(dist, k + 4, sizeof(double) * 5);
-        if (intr_cov)
-            memcpy(intr_cov, cov, sizeof(cov));
-        rep->time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return VMM_BA_OK;
-    };
-    if ((rc = solve())) return rc;
-    double cost = s->final_cost;
-    rep->initial_cost = cost;
-    if (mask == 0)
-        return finish(VMM_BA_CAL_OK, cost);
-    if (!std::isfinite(cost)) {
-        rep->initial_cost = HUGE_VAL;
-        return finish(VMM_BA_CAL_NO_CONVERGENCE, HUGE_VAL);
-    }
-
-    const size_t nc = (size_t)7 * e.n_cams, nt = (size_t)7 * e.n_tags;
-    std::vector<double> first(nc + nt), cur(nc + nt);   // the state of the first solve; the state a trial starts from
-    if ((rc = vmm_ba_get_state(h, first.data(), first.data() + nc))) return rc;
-    cur = first;
-    double k0[9];
-    memcpy(k0, k, sizeof(k));
-    const double cost0 = cost;
-    auto restore = [&](const std::vector<double>& x, const double* model) {
-        int r = vmm_ba_set_state(h, x.data(), x.data() + nc);
-        return r ? r : vmm_ba_set_intrinsics(h, model, model + 4);
-    };
-    // S_k fails the pivot test: the state of the first solve, no covariance
-    auto singular = [&]() {
-        memset(cov, 0, sizeof(cov));
-        memcpy(k, k0, sizeof(k));
-        const int r = restore(first, k0);
-        return r ? r : finish(VMM_BA_CAL_SINGULAR, cost0);
-    };
-
-    double gk[9], C[81], rk[9], Sk[81], dk[9], M[9][9], sc[9];
-    double lam = 1e-4;
-    bool have_system = false;   // C, r_k, S_k and cov belong to the current state
-    int status = VMM_BA_CAL_NO_CONVERGENCE;
-    for (;;) {
-        if (!have_system) {
-            if ((rc = vmm_ba_intrinsics_system(h, in.robustify, in.huber_a, nullptr, gk, C, rk, Sk))) return rc;
-            have_system = true;
-            double cmax = 0.0;
-            for (int j = 0; j < 81; ++j)
-                cmax = std::max(cmax, fabs(C[j]));
-            if (cmax == 0.0) {   // no active observation: nothing to refine
-                memset(cov, 0, sizeof(cov));
-                status = VMM_BA_CAL_OK;
-                break;
-            }
-            if (!selfcal_covariance(Sk, C, mask, cov))
-                return singular();
-        }
-        if (lam > 1e12) {
-            status = VMM_BA_CAL_OK;
-            break;
-        }
-        if (rep->outer_iterations >= o.max_outer_iterations)
-            break;
-        rep->outer_iterations += 1;
-        bool step_ok = selfcal_factor(Sk, C, mask, lam, false, M, sc);
-        if (step_ok) {
-            double b[9];
-            for (int j = 0; j < 9; ++j)
-                b[j] = ((mask >> j) & 1) ? -rk[j] : 0.0;
-            selfcal_apply(M, sc, b, dk);
-            for (int j = 0; j < 9; ++j) {
-                if (!((mask >> j) & 1))
-                    dk[j] = 0.0;
-                step_ok = step_ok && std::isfinite(dk[j]);
-            }
-        }
-        if (!step_ok) {
-            lam *= 10.0;
-            continue;
-        }
-        double kc[9];
-        for (int j = 0; j < 9; ++j)
-            kc[j] = ((mask >> j) & 1) ? k[j] + dk[j] : k[j];   // a fixed parameter keeps its bits
-        if ((rc = vmm_ba_set_intrinsics(h, kc, kc + 4))) return rc;
-        if ((rc = solve())) return rc;
-        const double cand = s->final_cost;
-        if (std::isfinite(cand) && cand < cost) {
-            bool small = true;
-            for (int j = 0; j < 9; ++j)
-                small = small && fabs(dk[j]) / std::max(fabs(k[j]), 1.0) < o.parameter_tolerance;
-            const double rel = (cost - cand) / cost;
-            memcpy(k, kc, sizeof(k));
-            cost = cand;
-            lam *= 0.1;
-            rep->accepted += 1;
-            have_system = false;
-            if ((rc = vmm_ba_get_state(h, cur.data(), cur.data() + nc))) return rc;
-            if (small || rel < o.function_tolerance) {
-                status = VMM_BA_CAL_OK;
-                break;
-            }
-        } else {
-            if ((rc = restore(cur, k))) return rc;
-            if (cand - cost <= 1e-10 * cost + 1e-20) {   // equal to rounding (cost_at_floor, pose_lm.hpp): the minimum
-                status = VMM_BA_CAL_OK;
-                break;
-            }
-            lam *= 10.0;
-        }
-    }
-    if (!have_system) {   // stopped on an accepted step: the covariance at the result
-        if ((rc = vmm_ba_intrinsics_system(h, in.robustify, in.huber_a, nullptr, gk, C, rk, Sk))) return rc;
-        if (!selfcal_covariance(Sk, C, mask, cov))
-            return singular();
-    }
-    return finish(status, cost);
-}
-
-constexpr int kMaxProjectDevices = 64;
-
-int vmm_ba_project_points(const double intr[4], const double dist[5], int64_t n, const double* points_cam,
-                          double* uv, int device)
-{
-    if (!intr || !dist || n < 0 || (n > 0 && (!points_cam || !uv))) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (n == 0)
-        return VMM_BA_OK;
-    HIP_TRY(hipSetDevice(device));
-    const Intrinsics K = make_intrinsics(intr, dist);
-    // CameraModel::projectPoint is called point by point by its users: the device buffer of small calls is kept per
-    // device (grown on demand, up to 1 M points = 40 MB; larger calls allocate and free), calls are serialised
-    static std::mutex mu;
-    static double* cache[kMaxProjectDevices] = {};
-    static int64_t cache_cap[kMaxProjectDevices] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    const bool cached = n <= (int64_t)1 << 20 && device >= 0 && device < kMaxProjectDevices;
-    Arena ar;   // owns the buffer of a call that is not cached
-    double* buf = nullptr;
-    if (cached && cache_cap[device] >= n) {
-        buf = cache[device];
-    } else {
-        const int64_t cap = cached ? std::max<int64_t>(n, 1024) : n;
-        HIP_TRY(ar.alloc(sizeof(double) * 5 * (size_t)cap));
-        buf = reinterpret_cast<double*>(ar.base);
-        if (cached) {
-            if (cache[device])
-                (void)hipFree(cache[device]);
-            cache[device] = buf;
-            cache_cap[device] = cap;
-            ar.base = nullptr;   // the cache owns it now
-        }
-    }
-    double *d_p = buf, *d_uv = buf + 3 * n;
-    ar.copy(d_p, points_cam, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
-    if (ar.err == hipSuccess)
-        launch_project(nullptr, K, n, d_p, d_uv);
-    ar.copy(uv, d_uv, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
-    if (ar.err != hipSuccess) {
-        set_error(std::string("project_points: ") + hipGetErrorString(ar.err));
-        return VMM_BA_ERR_HIP;
-    }
-    return VMM_BA_OK;
-}
-
-int vmm_ba_pose_plus(int64_t n, const double* qt, const double* delta, double* out, int device)
-{
-    if (n < 0 || (n > 0 && (!qt || !delta || !out))) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (n == 0)
-        return VMM_BA_OK;
-    HIP_TRY(hipSetDevice(device));
-    Arena ar;   // qt | delta | out
-    HIP_TRY(ar.alloc(sizeof(double) * 20 * n));
-    double* const d = reinterpret_cast<double*>(ar.base);
-    ar.copy(d, qt, sizeof(double) * 7 * n, hipMemcpyHostToDevice);
-    ar.copy(d + 7 * n, delta, sizeof(double) * 6 * n, hipMemcpyHostToDevice);
-    if (ar.err == hipSuccess)
-        launch_pose_plus(nullptr, n, d, d + 7 * n, d + 13 * n);
-    ar.copy(out, d + 13 * n, sizeof(double) * 7 * n, hipMemcpyDeviceToHost);
-    if (ar.err != hipSuccess) {
-        set_error(std::string("pose_plus: ") + hipGetErrorString(ar.err));
-        return VMM_BA_ERR_HIP;
-    }
-    return VMM_BA_OK;
-}
-
-int vmm_ba_quad_poses(const double intr[4], const double dist[5], int64_t n, const double* tag_wh, const double* obs_px,
-                      double* qt2, double* rms2, int device)
-{
-    if (!intr || !dist || n < 0 || (n > 0 && (!tag_wh || !obs_px || !qt2 || !rms2))) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (n == 0)
-        return VMM_BA_OK;
-    HIP_TRY(hipSetDevice(device));
-    const Intrinsics K = make_intrinsics(intr, dist);
-    Arena ar;   // tag_wh | obs_px | qt2 | rms2
-    HIP_TRY(ar.alloc(sizeof(double) * 26 * n));
-    double* const d = reinterpret_cast<double*>(ar.base);
-    double *d_wh = d, *d_px = d + 2 * n, *d_qt = d + 10 * n, *d_rms = d + 24 * n;
-    ar.copy(d_wh, tag_wh, sizeof(double) * 2 * n, hipMemcpyHostToDevice);
-    ar.copy(d_px, obs_px, sizeof(double) * 8 * n, hipMemcpyHostToDevice);
-    if (ar.err == hipSuccess)
-        launch_quad_poses(nullptr, K, n, d_wh, d_px, d_qt, d_rms);
-    ar.copy(qt2, d_qt, sizeof(double) * 14 * n, hipMemcpyDeviceToHost);
-    ar.copy(rms2, d_rms, sizeof(double) * 2 * n, hipMemcpyDeviceToHost);
-    if (ar.err != hipSuccess) {
-        set_error(std::string("quad_poses: ") + hipGetErrorString(ar.err));
-        return VMM_BA_ERR_HIP;
-    }
-    return VMM_BA_OK;
-}
-
-void vmm_ba_default_init_options(vmm_ba_init_options* o)
-{
-    if (!o)
-        return;
-    memset(o, 0, sizeof(*o));
-    o->sweeps = 1;
-    o->min_tag_observations = 2;
-    o->score_cap_px = 100.0;
-    o->refine_iterations = 30;
-}
-
-int vmm_ba_initialize(vmm_ba_handle h, const vmm_ba_init_options* opt, vmm_ba_init_report* r, uint8_t* cam_reached,
-                      uint8_t* tag_reached)
-{
-    if (!h) {
-        set_error("null handle");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.world > 1 || e.points) {
-        set_error("vmm_ba_initialize needs a single-GPU handle with tag-pose landmarks");
-        return VMM_BA_ERR_STATE;
-    }
-    if (!e.any_const) {
-        set_error("vmm_ba_initialize needs a fixed (origin) tag or a constant pose: the map grows from there");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    vmm_ba_init_options o;
-    if (opt)
-        o = *opt;
-    else
-        vmm_ba_default_init_options(&o);
-    if (o.sweeps < 0 || o.min_tag_observations < 1 || !(o.score_cap_px > 0.0) || o.refine_iterations < 0) {
-        set_error("bad initialisation options");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    HIP_TRY(hipSetDevice(e.device));
-    Range range("vmm_ba_initialize");
-    const auto t0 = std::chrono::steady_clock::now();
-    const int n_pose = e.n_cams + e.n_tags;
-    int rc;
-    if (!e.init_placed) {
-        const size_t n_obs = (size_t)std::max<int64_t>(e.n_obs, 1);
-        if ((rc = dev_alloc(e, &e.init_quad_qt, 14 * n_obs, false))) return rc;
-        if ((rc = dev_alloc(e, &e.init_quad_rms, 2 * n_obs, false))) return rc;
-        if ((rc = dev_alloc(e, &e.init_todo, (size_t)n_pose))) return rc;
-        if ((rc = dev_alloc(e, &e.init_counter, 1))) return rc;
-        if ((rc = dev_alloc(e, &e.init_stats, 2 + 2 * (size_t)e.n_cams))) return rc;
-        if (hipHostMalloc((void**)&e.init_host, sizeof(double) * 4) != hipSuccess) {
-            set_error("hipHostMalloc failed");
-            e.init_host = nullptr;
-            return VMM_BA_ERR_HIP;
-        }
-        if ((rc = dev_alloc(e, &e.init_placed, (size_t)n_pose))) return rc;
-    }
-    if ((rc = flush_state(e))) return rc;
-    launch_init_begin(e);
-    launch_init_quad(e);
-    InitPass pass;
-    pass.min_tag_observations = o.min_tag_observations;
-    pass.score_cap_px = o.score_cap_px;
-    pass.refine_iterations = o.refine_iterations;
-    int32_t* const placed_now = reinterpret_cast<int32_t*>(e.init_host);
-    int rounds = 0;
-    // every round but the last places at least one pose, so n_pose rounds are the most there can be
-    for (int round = 0; round < n_pose; ++round) {
-        HIP_TRY(hipMemsetAsync(e.init_counter, 0, sizeof(int32_t), e.stream));
-        launch_init_pass(e, true, pass);
-        launch_init_pass(e, false, pass);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(placed_now, e.init_counter, sizeof(int32_t), hipMemcpyDeviceToHost, e.stream));
-        HIP_TRY(hipStreamSynchronize(e.stream));
-        ++rounds;
-        if (*placed_now == 0)
-            break;
-    }
-    pass.sweep = true;
-    for (int s = 0; s < o.sweeps; ++s) {
-        launch_init_pass(e, true, pass);
-        launch_init_pass(e, false, pass);
-    }
-    launch_init_stats(e, e.init_stats);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> placed((size_t)n_pose);
-    HIP_TRY(hipMemcpyAsync(e.init_host + 2, e.init_stats, sizeof(double) * 2, hipMemcpyDeviceToHost, e.stream));
-    HIP_TRY(hipMemcpyAsync(placed.data(), e.init_placed, sizeof(int32_t) * n_pose, hipMemcpyDeviceToHost, e.stream));
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    int n_c = 0, n_t = 0;
-    for (int c = 0; c < e.n_cams; ++c) {
-        n_c += placed[(size_t)c] != 0;
-        if (cam_reached)
-            cam_reached[c] = placed[(size_t)c] != 0;
-    }
-    for (int t = 0; t < e.n_tags; ++t) {
-        n_t += placed[(size_t)e.n_cams + t] != 0;
-        if (tag_reached)
-            tag_reached[t] = placed[(size_t)e.n_cams + t] != 0;
-    }
-    if (r) {
-        memset(r, 0, sizeof(*r));
-        r->rounds = rounds;
-        r->cams_reached = n_c;
-        r->tags_reached = n_t;
-        r->avg_reprojection_px = e.init_host[3] > 0.0 ? e.init_host[2] / e.init_host[3] : 0.0;
-        r->time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return VMM_BA_OK;
-}
-
 int vmm_ba_eval_blocks(vmm_ba_handle h, int robustify, double huber_a, double* cost, double* V, double* U,
                        double* W, double* g_cam, double* g_tag)
 {
@@ -2195,10 +1386,8 @@ int vmm_ba_eval_blocks(vmm_ba_handle h, int robustify, double huber_a, double* c
         return VMM_BA_ERR_STATE;
     }
     HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
+    int rc;
+    if ((rc = flush_state(e))) return rc;
     launch_eval_passes(e, robustify, huber_a, false);
     HIP_TRY(hipGetLastError());
     if (cost) HIP_TRY(hipMemcpyAsync(cost, e.cost_slot, sizeof(double), hipMemcpyDeviceToHost, e.stream));
@@ -2228,439 +1417,6 @@ int vmm_ba_eval_blocks(vmm_ba_handle h, int robustify, double huber_a, double* c
                     W[(size_t)36 * caller[i] + 6 * ca + tb] = v;
                 }
     }
-    return VMM_BA_OK;
-}
-
-// Minimal engine for the dense test entry points: stream + panel buffer + a control block.
-static int make_scratch(Engine& e, int device, int ld)
-{
-    e.device = device;
-    e.sw = read_switches();
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking));
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            e.n_cu = prop.multiProcessorCount;
-    }
-    int rc;
-    if ((rc = dev_alloc(e, &e.P, (size_t)4 * kNB * ld))) return rc;
-    if ((rc = setup_lookahead(e, ld / kNB, ld))) return rc;
-    if ((rc = dev_alloc(e, &e.dinv, (size_t)ld + kNB))) return rc;
-    if ((rc = dev_alloc(e, &e.Ldiag, (size_t)(ld / kNB + 1) * 4096))) return rc;
-    if ((rc = dev_alloc(e, &e.Linv, (size_t)(ld / kNB + 1) * 4096))) return rc;
-    if ((rc = dev_alloc(e, &e.flags, 264))) return rc;
-    if ((rc = dev_alloc(e, &e.gran, (size_t)2 * ld))) return rc;
-    {
-        const int nb = ld / kNB - 1;   // ld = n_pad + 64
-        const size_t nd = e.sw.no_dataflow ? 0 : (size_t)dataflow_blocks(nb, e.n_cu, e.sw);
-        if (nd > 0 && (rc = dev_alloc(e, &e.df_gran, nd * (nd + 1) / 2 * 8 * 1024)))
-            return rc;
-        if (nd > 0 && (rc = dev_alloc(e, &e.df_compact, nd * (nd + 1) / 2 * 4096, false)))
-            return rc;
-        if (nd > 0 && (rc = dev_alloc(e, &e.df_done, nd * (nd + 1) / 2)))
-            return rc;
-    }
-    if ((rc = dev_alloc(e, &e.ctl, 1))) return rc;
-    return VMM_BA_OK;
-}
-
-static void free_scratch(Engine& e)
-{
-    if (e.stream)
-        (void)hipStreamSynchronize(e.stream);
-    for (void* p : e.allocs)
-        (void)hipFree(p);
-    if (e.stream)
-        (void)hipStreamDestroy(e.stream);
-    e.allocs.clear();
-    e.stream = nullptr;
-}
-
-int vmm_ba_dense_spd_solve(int device, int n, const double* A, const double* b, double* x, int* info)
-{
-    if (n <= 0 || !A || !b || !x) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    const int n_pad = round_up(n, kNB), ld = n_pad + kNB;
-    Engine e;
-    int rc = make_scratch(e, device, ld);
-    double *S = nullptr, *y = nullptr;
-    if (!rc) rc = dev_alloc(e, &S, (size_t)ld * ld);
-    if (!rc) rc = dev_alloc(e, &y, (size_t)ld);
-    if (rc) {
-        free_scratch(e);
-        return rc;
-    }
-    std::vector<double> hs((size_t)ld * ld, 0.0);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j <= i; ++j)
-            hs[(size_t)i * ld + j] = A[(size_t)i * n + j];
-    for (int i = n; i < n_pad; ++i)
-        hs[(size_t)i * ld + i] = 1.0;
-    for (int j = 0; j < n; ++j)
-        hs[(size_t)n_pad * ld + j] = b[j];
-    LmCtl c;
-    hipError_t err = hipSuccess;
-    // second attempt only after a spin give-up of the one-launch kernels: the same system on the fallback path
-    for (int attempt = 0; attempt < 2 && err == hipSuccess; ++attempt) {
-        memset(&c, 0, sizeof(c));
-        if (attempt == 0) {
-            c.spin_limit_df = e.sw.spin_df;
-            c.spin_limit_chain = e.sw.spin_chain;
-            c.spin_wg = e.sw.spin_wg;
-        }
-        err = hipMemcpyAsync(e.ctl, &c, sizeof(LmCtl), hipMemcpyHostToDevice, e.stream);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(S, hs.data(), sizeof(double) * hs.size(), hipMemcpyHostToDevice, e.stream);
-        if (err == hipSuccess) {
-            launch_cholesky_solve(e, S, n_pad, ld, y, e.ctl, attempt > 0);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) err = hipMemcpyAsync(x, y, sizeof(double) * n, hipMemcpyDeviceToHost, e.stream);
-        if (err == hipSuccess) err = hipMemcpyAsync(&c, e.ctl, sizeof(LmCtl), hipMemcpyDeviceToHost, e.stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(e.stream);
-        if (c.done != 2)
-            break;
-    }
-    free_scratch(e);
-    if (err != hipSuccess) {
-        set_error(std::string("dense_spd_solve: ") + hipGetErrorString(err));
-        return VMM_BA_ERR_HIP;
-    }
-    if (info)
-        *info = c.lin_fail;
-    return VMM_BA_OK;
-}
-
-int vmm_ba_dense_syrk(int device, int k, int n, const double* Zh, double* C)
-{
-    if (k <= 0 || n <= 0 || !Zh || !C) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    const int n_pad = round_up(n, kST), ld = n_pad;
-    const int n_blk = n_pad / kST;
-    const int k_pad = round_up(k, kKT);
-    Engine e;
-    int rc = make_scratch(e, device, ld);
-    double *Z = nullptr, *S = nullptr;
-    SyrkPlan plan;
-    if (!rc) rc = dev_alloc(e, &Z, (size_t)k_pad * ld);
-    if (!rc) rc = dev_alloc(e, &S, (size_t)ld * ld);
-    if (!rc) rc = make_syrk_plan(e, plan, n_blk, n_blk, k_pad);
-    if (rc) {
-        free_scratch(e);
-        return rc;
-    }
-    std::vector<double> hz((size_t)k_pad * ld, 0.0);
-    for (int r = 0; r < k; ++r)
-        for (int c = 0; c < n; ++c)
-            hz[(size_t)r * ld + c] = Zh[(size_t)r * n + c];
-    hipError_t err = hipMemcpyAsync(Z, hz.data(), sizeof(double) * hz.size(), hipMemcpyHostToDevice, e.stream);
-    std::vector<double> hs((size_t)ld * ld, 0.0);
-    if (err == hipSuccess) {
-        launch_syrk_plan(e.stream, nullptr, Z, ld, plan);
-        launch_reduce_plan(e.stream, nullptr, plan, ld, n_pad, S);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipMemcpyAsync(hs.data(), S, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, e.stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e.stream);
-    free_scratch(e);
-    if (err != hipSuccess) {
-        set_error(std::string("dense_syrk: ") + hipGetErrorString(err));
-        return VMM_BA_ERR_HIP;
-    }
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j)
-            C[(size_t)i * n + j] = (j <= i) ? -hs[(size_t)i * ld + j] : -hs[(size_t)j * ld + i];
-    return VMM_BA_OK;
-}
-
-int vmm_ba_time_kernels(vmm_ba_handle h, const vmm_ba_options* opt, int reps, vmm_ba_kernel_times* out)
-{
-    if (!h || !out || reps <= 0) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.multi) {
-        set_error("time_kernels is a single-GPU diagnostic");
-        return VMM_BA_ERR_STATE;
-    }
-    vmm_ba_options o;
-    if (opt)
-        o = *opt;
-    else
-        vmm_ba_default_options(&o);
-    HIP_TRY(hipSetDevice(e.device));
-    {
-        int frc;
-        if ((frc = flush_state(e))) return frc;
-    }
-    memset(out, 0, sizeof(*out));
-    out->n_obs = e.n_obs;
-    out->reduced_dim = e.n_red;
-    out->elim_dim = e.k_dim;
-    out->schur_sparse = e.sparse_schur ? 1 : 0;
-    out->syrk_wide = (!e.sparse_schur && e.syrk.wide) ? 1 : 0;
-    out->schur_flops = e.schur_flops;
-    out->chol_flops = e.chol_nz_on ? e.chol_flops : 0.0;
-    // keep the caller's state: timing runs real iterations.  The RAW device buffers are saved and restored: through
-    // vmm_ba_get_state / vmm_ba_set_state a point-landmark handle would get its tags back as exact rectangles rebuilt
-    // from re-orthogonalised poses, not the optimised free corners it held.
-    std::vector<double> cam0((size_t)7 * e.n_cams), tag0((size_t)7 * e.n_tags);
-    int rc;
-    HIP_TRY(hipMemcpyAsync(cam0.data(), e.cam_qt, sizeof(double) * cam0.size(), hipMemcpyDeviceToHost, e.stream));
-    HIP_TRY(hipMemcpyAsync(tag0.data(), e.tag_qt, sizeof(double) * tag0.size(), hipMemcpyDeviceToHost, e.stream));
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    auto restore_raw = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(e.cam_qt, cam0.data(), sizeof(double) * cam0.size(), hipMemcpyHostToDevice, e.stream));
-        HIP_TRY(hipMemcpyAsync(e.tag_qt, tag0.data(), sizeof(double) * tag0.size(), hipMemcpyHostToDevice, e.stream));
-        HIP_TRY(hipStreamSynchronize(e.stream));
-        e.dirty_cam = e.dirty_tag = false;
-        return VMM_BA_OK;
-    };
-    if (e.trace_capacity < 1) {
-        if ((rc = dev_alloc(e, &e.trace, 1, false))) return rc;
-        e.trace_capacity = 1;
-        drop_graphs(e);
-    }
-    vmm_ba_options ot = o;
-    ot.max_num_iterations = 1 << 30;
-    ot.function_tolerance = 0.0;
-    ot.parameter_tolerance = 0.0;
-    ot.gradient_tolerance = 0.0;
-    if ((rc = begin_lm_loop(e, ot, 0))) return rc;
-    if ((rc = enqueue_iteration(e, ot))) return rc;   // populates every buffer of an iteration
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    // the priming step was accepted and moved x; go back so that the W recomputed by the timed
-    // evaluation passes stays consistent with the H blocks of the priming evaluation
-    if ((rc = restore_raw())) return rc;   // the timed pieces read the poses on the device
-    hipEvent_t ev0, ev1;
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    // each timed piece is captured into a hipGraph once and replayed, so that the gaps between its
-    // launches are the ones the production iteration graph sees
-    // `inner` > 1 (idempotent pieces only): the piece is captured that many times back to back and the
-    // graph time divided by it, which takes the ~9 us of graph-launch overhead out of a 5-30 us kernel
-    // (rocprofv3's per-kernel durations are the reference the bench line must agree with).
-    auto timed = [&](auto&& fn, auto&& prep, double* ms_out, int inner = 1) -> int {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge = nullptr;
-        HIP_TRY(hipStreamBeginCapture(e.stream, hipStreamCaptureModeThreadLocal));
-        for (int q = 0; q < inner; ++q)
-            fn();
-        HIP_TRY(hipStreamEndCapture(e.stream, &g));
-        HIP_TRY(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        double total = 0.0;
-        for (int r = 0; r < reps + 1; ++r) {   // replay 0 is untimed
-            prep();
-            HIP_TRY(hipEventRecord(ev0, e.stream));
-            HIP_TRY(hipGraphLaunch(ge, e.stream));
-            HIP_TRY(hipEventRecord(ev1, e.stream));
-            HIP_TRY(hipEventSynchronize(ev1));
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            if (r > 0) total += ms;
-        }
-        (void)hipGraphExecDestroy(ge);
-        *ms_out = total / reps / inner;
-        return VMM_BA_OK;
-    };
-    auto nop = [] {};
-    // the guards read ctl->done / lin_fail only; both are 0 after the priming iteration unless it failed
-    HIP_TRY(hipMemcpy(e.ctl_host, e.ctl, sizeof(LmCtl), hipMemcpyDeviceToHost));
-    e.ctl_host->done = 0;
-    e.ctl_host->lin_fail = 0;
-    HIP_TRY(hipMemcpy(e.ctl, e.ctl_host, sizeof(LmCtl), hipMemcpyHostToDevice));
-    if ((rc = timed([&] { launch_eval_passes(e, o.robustify, o.huber_a, false); }, nop, &out->eval_elim_ms, 8))) return rc;
-    out->eval_keep_ms = 0.0;
-    if ((rc = timed([&] { launch_cost_kernel(e, e.cam_qt, e.tag_qt, false, o.robustify, o.huber_a); }, nop, &out->cost_ms, 8))) return rc;
-    if ((rc = timed([&] { launch_elim(e); }, nop, &out->form_z_ms, 8))) return rc;
-    if ((rc = timed([&] { launch_syrk_only(e); }, nop, &out->syrk_ms, 4))) return rc;
-    if ((rc = timed([&] { launch_cholesky_solve(e, e.S, e.n_pad, e.ldz, e.yf, e.ctl); },
-                    [&] {
-                        launch_syrk_reduced(e);
-                        launch_pack_lower(e, false);   // world > 1: this rank's share alone (no all-reduce here)
-                        launch_pack_lower(e, true);
-                    },
-                    &out->cholesky_ms)))
-        return rc;
-    if ((rc = timed([&] { launch_backsub(e); }, nop, &out->backsub_ms, 8))) return rc;
-    if (e.sw.debug) {
-        HIP_TRY(hipMemcpy(e.ctl_host, e.ctl, sizeof(LmCtl), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[vmm_ba debug] after kernel timing: done=%d lin_fail=%d termination=%d iteration=%d\n",
-                e.ctl_host->done, e.ctl_host->lin_fail, e.ctl_host->termination, e.ctl_host->iteration);
-    }
-    // whole iterations from the caller's state
-    if ((rc = restore_raw())) return rc;
-    if ((rc = begin_lm_loop(e, ot, 0))) return rc;
-    HIP_TRY(hipEventRecord(ev0, e.stream));
-    int passes = 0;
-    for (int r = 0; r < reps; ++r) {
-        if ((rc = run_iteration(e, ot))) return rc;
-        passes += e.last_passes;
-    }
-    HIP_TRY(hipEventRecord(ev1, e.stream));
-    HIP_TRY(hipEventSynchronize(ev1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    out->lm_iteration_ms = ms / passes;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    return restore_raw();
-}
-
-// Diagnostic behind DESIGN.md's question "can the reduced-system assembly hide behind the factorisation?": times, with
-// HIP events, (0) rank-k update + partial-tile sum alone, (1) factorisation + triangular solves alone, (2) both back to
-// back on one stream (today's order), (3) both at once on two streams -- the factorisation on a valid S, the rank-k
-// update of the same Z writing its sum into a scratch matrix, so that only the sharing of the chip is measured, not a
-// dependency; (4) the factorisation's own duration inside (3).  Dense elimination, one GPU.  ms[5] averages over reps.
-int vmm_ba_debug_chol_schedule(int n_blk, int n_df, int n_cu, int32_t* launches, int cap, int* n_launches, int* n_df_used)
-{
-    if (n_blk < 1 || n_cu < 1 || cap < 0 || (cap > 0 && !launches) || !n_launches || (n_df > 0 && n_df > n_blk - 2)) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    if (n_df < 0) {
-        n_df = dataflow_blocks(n_blk, n_cu, read_switches());
-        if (n_df == n_blk)
-            n_df = 0;   // the one-launch kernel takes the whole system: what is returned is the fallback schedule
-    }
-    const std::vector<CholLaunch> sched = chol_step_schedule(n_blk, n_df);
-    for (size_t i = 0; i < sched.size() && (int)i < cap; ++i) {
-        const CholLaunch& L = sched[i];
-        const int32_t row[8] = { L.k, L.lazy[0], L.lazy[1], L.upd[0], L.upd[1], L.c0, L.t0, L.t1 };
-        memcpy(launches + 8 * i, row, sizeof(row));
-    }
-    *n_launches = (int)sched.size();
-    if (n_df_used)
-        *n_df_used = n_df;
-    return VMM_BA_OK;
-}
-
-int vmm_ba_debug_chol_tile(int n_blk, const int32_t* launch, int t, int* bi, int* bj)
-{
-    if (!launch || !bi || !bj || t < 0 || t >= launch[7]) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    const CholLaunch L = { launch[0], { launch[1], launch[2] }, { launch[3], launch[4] }, launch[5], launch[6], launch[7] };
-    chol_schedule_tile(n_blk, L, t, bi, bj);
-    return VMM_BA_OK;
-}
-
-int vmm_ba_debug_overlap(vmm_ba_handle h, int reps, double* ms)
-{
-    if (!h || !ms || reps <= 0) {
-        set_error("bad argument");
-        return VMM_BA_ERR_ARGUMENT;
-    }
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.multi || e.sparse_schur || !e.Z) {
-        set_error("debug_overlap needs a single-GPU handle on the dense elimination path");
-        return VMM_BA_ERR_STATE;
-    }
-    HIP_TRY(hipSetDevice(e.device));
-    int rc;
-    if ((rc = flush_state(e))) return rc;
-    vmm_ba_options o;
-    vmm_ba_default_options(&o);
-    o.max_num_iterations = 1 << 30;
-    o.function_tolerance = o.parameter_tolerance = o.gradient_tolerance = 0.0;
-    if (e.trace_capacity < 1) {
-        if ((rc = dev_alloc(e, &e.trace, 1, false))) return rc;
-        e.trace_capacity = 1;
-        drop_graphs(e);
-    }
-    if ((rc = begin_lm_loop(e, o, 0))) return rc;
-    if ((rc = enqueue_iteration(e, o))) return rc;   // populates Z, the small blocks and the control block
-    HIP_TRY(hipStreamSynchronize(e.stream));
-    double* S2 = nullptr;
-    hipStream_t sb = nullptr;
-    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    hipError_t err = hipMalloc((void**)&S2, sizeof(double) * (size_t)e.ldz * e.ldz);
-    if (err == hipSuccess) err = hipStreamCreateWithFlags(&sb, hipStreamNonBlocking);
-    for (int i = 0; i < 5 && err == hipSuccess; ++i)
-        err = hipEventCreate(&ev[i]);
-    auto reset_flags = [&]() -> hipError_t {
-        hipError_t r = hipMemcpy(e.ctl_host, e.ctl, sizeof(LmCtl), hipMemcpyDeviceToHost);
-        if (r != hipSuccess) return r;
-        e.ctl_host->done = 0;
-        e.ctl_host->lin_fail = 0;
-        e.ctl_host->sync_timeout = 0;
-        return hipMemcpy(e.ctl, e.ctl_host, sizeof(LmCtl), hipMemcpyHostToDevice);
-    };
-    double acc[8] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-    for (int r = 0; r < reps + 1 && err == hipSuccess; ++r) {   // repetition 0 is untimed
-        float t[8] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-        // (0) rank-k update + sum (leaves a valid S), (1) factorisation + solves
-        if ((err = reset_flags()) != hipSuccess) break;
-        (void)hipEventRecord(ev[0], e.stream);
-        launch_syrk_reduced(e);
-        (void)hipEventRecord(ev[1], e.stream);
-        launch_cholesky_solve(e, e.S, e.n_pad, e.ldz, e.yf, e.ctl);
-        (void)hipEventRecord(ev[2], e.stream);
-        if ((err = hipEventSynchronize(ev[2])) != hipSuccess) break;
-        (void)hipEventElapsedTime(&t[0], ev[0], ev[1]);
-        (void)hipEventElapsedTime(&t[1], ev[1], ev[2]);
-        (void)hipEventElapsedTime(&t[2], ev[0], ev[2]);
-        // (3) both at once: S rebuilt first (untimed), then the factorisation beside a second rank-k update into S2
-        if ((err = reset_flags()) != hipSuccess) break;
-        launch_syrk_reduced(e);
-        if ((err = hipStreamSynchronize(e.stream)) != hipSuccess) break;
-        // the factorisation is enqueued first: its workgroups (84 KB of LDS, one per CU) take their CUs, the rank-k
-        // update's (72 KB) fill what is left beside them
-        (void)hipEventRecord(ev[0], e.stream);
-        (void)hipStreamWaitEvent(sb, ev[0], 0);
-        launch_cholesky_solve(e, e.S, e.n_pad, e.ldz, e.yf, e.ctl);
-        (void)hipEventRecord(ev[3], e.stream);
-        launch_syrk_plan(sb, e.ctl, e.Z, e.ldz, e.syrk);
-        launch_reduce_plan(sb, e.ctl, e.syrk, e.ldz, e.n_pad + 1, S2);
-        (void)hipEventRecord(ev[1], sb);
-        (void)hipStreamWaitEvent(e.stream, ev[1], 0);
-        (void)hipEventRecord(ev[2], e.stream);
-        if ((err = hipEventSynchronize(ev[2])) != hipSuccess) break;
-        (void)hipEventElapsedTime(&t[3], ev[0], ev[2]);
-        (void)hipEventElapsedTime(&t[4], ev[0], ev[3]);
-        (void)hipEventElapsedTime(&t[5], ev[0], ev[1]);
-        // (6) the same with the rank-k update enqueued FIRST (its 495 workgroups take their slots, the factorisation's
-        // workgroups follow as slots fall free)
-        if ((err = reset_flags()) != hipSuccess) break;
-        launch_syrk_reduced(e);
-        if ((err = hipStreamSynchronize(e.stream)) != hipSuccess) break;
-        (void)hipEventRecord(ev[0], e.stream);
-        (void)hipStreamWaitEvent(sb, ev[0], 0);
-        launch_syrk_plan(sb, e.ctl, e.Z, e.ldz, e.syrk);
-        launch_reduce_plan(sb, e.ctl, e.syrk, e.ldz, e.n_pad + 1, S2);
-        (void)hipEventRecord(ev[1], sb);
-        (void)hipEventRecord(ev[4], e.stream);
-        launch_cholesky_solve(e, e.S, e.n_pad, e.ldz, e.yf, e.ctl);
-        (void)hipEventRecord(ev[3], e.stream);
-        (void)hipStreamWaitEvent(e.stream, ev[1], 0);
-        (void)hipEventRecord(ev[2], e.stream);
-        if ((err = hipEventSynchronize(ev[2])) != hipSuccess) break;
-        (void)hipEventElapsedTime(&t[6], ev[0], ev[2]);
-        (void)hipEventElapsedTime(&t[7], ev[4], ev[3]);
-        if (r > 0)
-            for (int i = 0; i < 8; ++i)
-                acc[i] += t[i];
-    }
-    if (err == hipSuccess)
-        err = hipGetLastError();
-    for (auto& x : ev)
-        if (x) (void)hipEventDestroy(x);
-    if (sb) (void)hipStreamDestroy(sb);
-    (void)hipFree(S2);
-    if (err != hipSuccess) {
-        set_error(std::string("debug_overlap: ") + hipGetErrorString(err));
-        return VMM_BA_ERR_HIP;
-    }
-    for (int i = 0; i < 8; ++i)
-        ms[i] = acc[i] / reps;
     return VMM_BA_OK;
 }
 

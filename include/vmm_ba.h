@@ -424,6 +424,82 @@ int vmm_ba_localize(const double intr[4], const double dist[5],
                     vmm_ba_localize_result* res, /* [n_imgs] or NULL */
                     int device);
 
+/* ABI 6, additive.  Triangulates n_pts free points (anything that is not a tag: a drill hole, an LED, a clicked feature,
+ * or a tag's own corners taken one by one) from the cameras of a finished map or of a localisation; the dual of
+ * vmm_ba_localize and stateless like it, every point independent of the others in the batch.  Point p owns the
+ * observations [pt_start[p], pt_start[p + 1]): obs_cam names the camera (strictly increasing within a point, so one
+ * image appears at most once in a track and the caller's ordering cannot change a result), obs_uv the pixel.
+ *   residual    the cost functor's projection of R X + t (q / |q| first) against the pixel: what the bundle adjustment
+ *               and the localisation minimise, not CameraModel::projectPoint.  An observation whose point is not in front
+ *               of its camera (Z <= 0) is never an inlier, adds score_cap_px^2 to a score, and makes the cost of a
+ *               refinement trial +inf (the trial is rejected).
+ *   rays        every pixel undistorted (20 fixed-point iterations of the functor's distortion) and turned into the world
+ *               ray through the camera centre c = -R^T t.
+ *   candidates  candidate 0: the least-squares point of all rays, sum (I - d d^T) X = sum (I - d d^T) c; candidates 1..:
+ *               the same solve on the two rays (a, b), a < b < min(n_obs, max_pair_views), in lexicographic order.  A
+ *               system that is not positive definite (parallel rays) gives no candidate.
+ *   winner      most observations within inlier_px (and Z > 0); ties to the lowest sum min(e^2, score_cap_px^2) over ALL
+ *               the point's observations; then to the lowest candidate index.  (The count comes first, unlike the
+ *               localisation's rule: at low parallax a pair that contains a gross outlier can put the point at a depth
+ *               where the clean views miss by only tens of pixels, and the truncated sum alone then prefers it.)
+ *   passes      reclassify_passes times: an observation is an inlier when its distance is at most inlier_px and Z > 0;
+ *               then Levenberg-Marquardt on the 3 coordinates over the inliers, minimising 1/2 sum rho(|r|^2), until the
+ *               cost is at its rounding floor or refine_iterations trials are spent.  A pass that finds fewer than
+ *               min_inlier_views inliers ends the passes.  reclassify_passes == 0: one refinement over all observations
+ *               in front of their camera.
+ *   result      obs_inlier = the classification at the returned point; rms_px and cost over those inliers;
+ *               xyz_cov = H^-1 (row-major 3x3), H = sum rho'_i Jp_i^T Jp_i over the inliers, the loss applied when
+ *               robustify != 0 (as the tag translation covariance above): the part the pixel noise (unit variance)
+ *               causes, the cameras taken as exact.
+ *               xyz_cov_cams = H^-1 (sum_i G_i C_i G_i^T) H^-1, G_i = rho'_i Jp_i^T Jc_i (3x6), Jc_i the 2x6 Jacobian over
+ *               camera i's tangent (translation, then half-angle rotation) and C_i = cam_cov[36 i ..], camera i's 6x6
+ *               marginal in that order (vmm_ba_covariance_blocks' or vmm_ba_localize's): first-order propagation of
+ *               each camera's own uncertainty.  It IGNORES THE CORRELATIONS BETWEEN CAMERAS (the cross blocks of the
+ *               map's covariance), which a bundle adjustment leaves positive between neighbours: treat it as the
+ *               independent-cameras figure.  Zeros when cam_cov is NULL.  The total is the sum of the two parts.
+ * Status per point: TOO_FEW_VIEWS (fewer than 2 observations): xyz = 0, zero covariances, zero flags.  NO_CANDIDATE
+ * (every candidate non-finite): the same.  TOO_FEW_INLIERS (fewer than min_inlier_views at the returned point): the
+ * best-effort point and its flags, zero covariances.  SINGULAR: H is not positive definite; point and flags are
+ * returned, both covariances are zeros.  No output is ever NaN; results are bit-identical from run to run and do not
+ * depend on what else is in the batch or on where the point sits in it.
+ * VMM_BA_ERR_ARGUMENT (before any device call): null intr, dist, pt_start or xyz; negative sizes; pt_start not starting
+ * at 0 or decreasing; null observations while n_obs > 0; obs_cam outside [0, n_cams) or not strictly increasing within
+ * a point; a non-finite camera model, pose, pixel or cam_cov; a zero quaternion; bad options.  n_pts == 0 returns
+ * VMM_BA_OK without a device call, and so does a batch in which no point has two observations. */
+enum { VMM_BA_TRI_OK = 0, VMM_BA_TRI_TOO_FEW_VIEWS = 1, VMM_BA_TRI_NO_CANDIDATE = 2,
+       VMM_BA_TRI_TOO_FEW_INLIERS = 3, VMM_BA_TRI_SINGULAR = 4 };
+
+typedef struct vmm_ba_triangulate_options {
+    int32_t refine_iterations;   /* 30: LM trials (accepted + rejected) of one refinement */
+    int32_t robustify;           /* 1: HuberLoss(huber_a) per observation */
+    double  huber_a;             /* 1.0 */
+    double  score_cap_px;        /* 100 */
+    double  inlier_px;           /* 8.0 */
+    int32_t reclassify_passes;   /* 2 */
+    int32_t min_inlier_views;    /* 2 */
+    int32_t max_pair_views;      /* 16, in [2, 64]: two-ray candidates are formed among the first this-many observations */
+    int32_t reserved;
+} vmm_ba_triangulate_options;
+
+typedef struct vmm_ba_triangulate_result {   /* one per point */
+    int32_t status, n_obs, n_inlier_obs, trials;
+    double  rms_px, cost;
+} vmm_ba_triangulate_result;
+
+void vmm_ba_default_triangulate_options(vmm_ba_triangulate_options* o);
+int vmm_ba_triangulate(const double intr[4], const double dist[5],
+                       int32_t n_cams, const double* cam_qt,      /* [7*n_cams] world->camera: the map's or the localisation's */
+                       const double* cam_cov,                     /* [36*n_cams] 6x6 per camera, tangent order, or NULL */
+                       int32_t n_pts, const int64_t* pt_start,    /* [n_pts+1], CSR */
+                       const int32_t* obs_cam, const double* obs_uv,   /* [n_obs], [2*n_obs] */
+                       const vmm_ba_triangulate_options* o,
+                       double* xyz,                 /* [3*n_pts] */
+                       double* xyz_cov,             /* [9*n_pts] or NULL: measurement part */
+                       double* xyz_cov_cams,        /* [9*n_pts] or NULL: part propagated from cam_cov (zeros when cam_cov is NULL) */
+                       uint8_t* obs_inlier,         /* [n_obs] or NULL */
+                       vmm_ba_triangulate_result* res, /* [n_pts] or NULL */
+                       int device);
+
 /* ABI 6, additive.  Calibrates a camera against a finished map: the nine numbers of the camera model
  * (fx, fy, cx, cy, k1, k2, p1, p2, k3) and one pose per image, the map held fixed.  Stateless like vmm_ba_localize.
  *   objective   1/2 sum rho(|r_corner|^2) over the inlier observations of the images that take part, with the residual

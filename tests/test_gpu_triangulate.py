@@ -1,0 +1,461 @@
+"""GPU tests of the triangulation of free points against a finished map (vmm_ba_triangulate, engine.triangulate, the
+members of TagReconstructor and the command line).
+
+Yardstick throughout: oracle/oracle.py -- point_eval gives the residual, the 2 x 6 camera Jacobian and the 2 x 3 point
+Jacobian of one observation, huber gives rho; the small Levenberg-Marquardt below is written around them and never calls
+the code under test.  Scenes come from synthetic.make_scene, the cameras are cam_gt, the free points are the four world
+corners of every tag; the track of corner k of tag t is the images that observe t, sorted by camera, with the pixels
+obs_px[:, 2k:2k+2].  Tolerances: 1e-9 on exact data (the localisation's exact-data gate), 1e-6 x max(|X|, 1) between two
+optima, 1e-9 relative on the cost, covariances to 1e-6 x max|ref| as the existing covariance tests.
+"""
+import json
+import os
+import shutil
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+INLIER_PX = 8.0   # the default of vmm_ba_triangulate_options
+
+EXACT = {
+    "config1_20x10": (1, dict()),
+    "100x60_vis0.30": (1, dict(n_cams=100, n_tags=60, visibility=0.30)),
+    "closeup_60x80": (2, dict(n_cams=60, n_tags=80, neighbors_min=6, neighbors_max=10)),
+    "distortion_30x40": (5, dict(n_cams=30, n_tags=40, visibility=0.5)),
+}
+
+
+# ---- helpers --------------------------------------------------------------------------------------------------------
+
+def _rotation(q):
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _tag_corners(qt, wh, scale=(1.0, 1.0)):
+    """World corners LL, LR, UR, UL of a tag of size wh * scale at pose qt."""
+    hw, hh = 0.5 * wh[0] * scale[0], 0.5 * wh[1] * scale[1]
+    local = np.array([[-hw, -hh, 0.0], [hw, -hh, 0.0], [hw, hh, 0.0], [-hw, hh, 0.0]])
+    return local @ _rotation(qt[:4]).T + qt[4:]
+
+
+def _tracks(s):
+    """The four world corners of every tag as free points: (pt_start, obs_cam, obs_uv, truth (n_pts, 3)); point 4 t + k
+    is corner k of tag t, its track sorted by camera."""
+    order = np.lexsort((s.obs_cam, s.obs_tag))
+    counts = np.bincount(s.obs_tag, minlength=len(s.tag_gt))
+    start, cam, uv = [0], [], []
+    b = 0
+    for t in range(len(s.tag_gt)):
+        idx = order[b:b + counts[t]]
+        b += counts[t]
+        assert (np.diff(s.obs_cam[idx]) > 0).all()
+        for k in range(4):
+            cam.append(s.obs_cam[idx])
+            uv.append(s.obs_px[idx, 2 * k:2 * k + 2])
+            start.append(start[-1] + len(idx))
+    truth = np.concatenate([_tag_corners(s.tag_gt[t], s.tag_wh[t]) for t in range(len(s.tag_gt))])
+    return np.array(start, np.int64), np.concatenate(cam).astype(np.int32), np.concatenate(uv).copy(), truth
+
+
+def _tri(eng, s, start, cam, uv, **kw):
+    return eng.triangulate(s.intr, s.dist, s.cam_gt, start, cam, uv, **kw)
+
+
+def _assert_clean(xyz, cov, cov_cams, res):
+    assert np.isfinite(xyz).all() and np.isfinite(cov).all() and np.isfinite(cov_cams).all()
+    for r in res:
+        assert np.isfinite(r["rms_px"]) and np.isfinite(r["cost"]), r
+
+
+def _normal_equations(O, s, X, cams, uvs, robust, a=1.0):
+    """cost = 1/2 sum rho(|r|^2), sum rho' Jp^T Jp and sum rho' Jp^T r of one point at X."""
+    A, g, cost = np.zeros((3, 3)), np.zeros(3), 0.0
+    for c, uv in zip(cams, uvs):
+        r, _, Jp = O.point_eval(s.intr, s.dist, s.cam_gt[c], X, uv)
+        sq = float(r @ r)
+        rho = O.huber(a, sq) if robust else (sq, 1.0, 0.0)
+        cost += 0.5 * rho[0]
+        A += rho[1] * (Jp.T @ Jp)
+        g += rho[1] * (Jp.T @ r)
+    return cost, A, g
+
+
+def _host_optimum(O, s, X0, cams, uvs, robust):
+    """Levenberg-Marquardt on the same objective from X0, run until the step is at the rounding floor of the point."""
+    X = np.array(X0, np.float64)
+    cost, A, g = _normal_equations(O, s, X, cams, uvs, robust)
+    lam = 1e-4
+    for _ in range(200):
+        try:
+            step = np.linalg.solve(A + lam * np.diag(np.maximum(np.diag(A), 1e-12)), -g)
+        except np.linalg.LinAlgError:
+            lam *= 10.0
+            continue
+        if np.abs(step).max() < 1e-14:
+            break
+        c2, A2, g2 = _normal_equations(O, s, X + step, cams, uvs, robust)
+        if c2 < cost:
+            X, cost, A, g = X + step, c2, A2, g2
+            lam = max(lam * 0.1, 1e-15)
+        else:
+            if lam > 1e8:
+                break
+            lam *= 10.0
+    return X, cost
+
+
+def _check_exact(_lib, start, truth, xyz, cov, cov_cams, inl, res, label):
+    err = np.linalg.norm(xyz - truth, axis=1)
+    print("%s: %d points %d observations, tracks %d..%d, max |X - truth| %.3g, max rms %.3g px, trials %d..%d"
+          % (label, len(xyz), len(inl), np.diff(start).min(), np.diff(start).max(), err.max(),
+             max(r["rms_px"] for r in res), min(r["trials"] for r in res), max(r["trials"] for r in res)))
+    assert [r["status"] for r in res] == [_lib.TRI_OK] * len(xyz)
+    assert inl.all()
+    assert [r["n_inlier_obs"] for r in res] == [r["n_obs"] for r in res] == list(np.diff(start))
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert err.max() <= 1e-9, err.max()
+
+
+# ---- 1. exact data -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(EXACT))
+def test_exact_data_recovers_the_ground_truth(name):
+    from visual_marker_mapping_amd import _lib, engine as eng
+    from visual_marker_mapping_amd.synthetic import make_scene
+    cfg, kw = EXACT[name]
+    s = make_scene(cfg, noise_px=0.0, outlier_frac=0.0, **kw)
+    start, cam, uv, truth = _tracks(s)
+    assert np.diff(start).min() >= 2
+    _check_exact(_lib, start, truth, *_tri(eng, s, start, cam, uv), name)
+
+
+# ---- 2. long tracks ------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("max_pair_views", [2, 16, 64])   # the candidate loop runs one, two and 32 strides of 64
+def test_long_tracks_cross_the_lane_strides(max_pair_views):
+    from visual_marker_mapping_amd import _lib, engine as eng
+    from visual_marker_mapping_amd.synthetic import make_scene
+    s = make_scene(1, n_cams=130, n_tags=3, visibility=1.0, noise_px=0.0, outlier_frac=0.0)
+    start, cam, uv, truth = _tracks(s)
+    assert (np.diff(start) == 130).all()   # two full strides of 64 lanes and a partial third
+    _check_exact(_lib, start, truth, *_tri(eng, s, start, cam, uv, max_pair_views=max_pair_views),
+                 "130 views, max_pair_views=%d" % max_pair_views)
+
+
+# ---- 3. gross outliers on exact data ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,max_left_out", [("100x60_vis0.30", 0), ("closeup_60x80", 60)])
+def test_gross_outliers_are_flagged_exactly_and_do_not_move_the_point(name, max_left_out):
+    from visual_marker_mapping_amd import _lib, engine as eng
+    from visual_marker_mapping_amd.synthetic import make_scene
+    cfg, kw = EXACT[name]
+    s = make_scene(cfg, noise_px=0.0, outlier_frac=0.0, **kw)
+    start, cam, uv, truth = _tracks(s)
+    rng = np.random.default_rng(11)
+    clean = np.ones(len(cam), bool)
+    for p in range(len(truth)):
+        for d in range(int(start[p]) + 1, int(start[p + 1]), 4):   # positions 1, 5, 9, ... of the track
+            ang, amp = rng.uniform(0, 2 * np.pi), rng.uniform(30.0, 400.0)
+            uv[d] += [amp * np.cos(ang), amp * np.sin(ang)]
+            clean[d] = False
+    n_clean = np.array([int(clean[start[p]:start[p + 1]].sum()) for p in range(len(truth))])
+    checked = np.flatnonzero(n_clean >= 3)
+    left_out = len(truth) - len(checked)
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, start, cam, uv)
+    _assert_clean(xyz, cov, cov_cams, res)
+    wrong, worst = 0, 0.0
+    for p in checked:
+        b, e = int(start[p]), int(start[p + 1])
+        wrong += int((inl[b:e] != clean[b:e]).sum())
+        worst = max(worst, float(np.linalg.norm(xyz[p] - truth[p])))
+    print("%s: %d of %d observations displaced, %d of %d points left out (fewer than 3 clean views), flags differing "
+          "from the clean mask %d, max |X - truth| %.3g" % (name, int((~clean).sum()), len(cam), left_out, len(truth), wrong,
+                                                            worst))
+    assert left_out <= max_left_out
+    if name == "closeup_60x80":
+        assert len(truth) == 320
+    for p in checked:
+        b, e = int(start[p]), int(start[p + 1])
+        assert res[p]["status"] == _lib.TRI_OK, (p, res[p])
+        assert (inl[b:e] == clean[b:e]).all(), (p, inl[b:e], clean[b:e])
+        assert np.linalg.norm(xyz[p] - truth[p]) <= 1e-9, (p, xyz[p], truth[p])
+
+
+# ---- 4. noisy data with outliers -------------------------------------------------------------------------------------
+
+def _noisy_scene():
+    from visual_marker_mapping_amd.synthetic import make_scene
+    s = make_scene(5, n_cams=30, n_tags=40)   # as generated: the generator's own noise and outliers
+    assert s.noise_px > 0 and s.robustify
+    return s
+
+
+def test_noisy_data_reaches_the_host_optimum(oracle):
+    from visual_marker_mapping_amd import _lib, engine as eng
+    s = _noisy_scene()
+    start, cam, uv, truth = _tracks(s)
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, start, cam, uv)
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert [r["status"] for r in res] == [_lib.TRI_OK] * len(xyz)
+    worst_x = worst_c = 0.0
+    for p in range(len(xyz)):
+        b, e = int(start[p]), int(start[p + 1])
+        keep = inl[b:e]
+        ref, cost = _host_optimum(oracle, s, truth[p], cam[b:e][keep], uv[b:e][keep], True)
+        gap = np.abs(xyz[p] - ref).max() / max(np.abs(ref).max(), 1.0)
+        cgap = abs(res[p]["cost"] - cost) / cost
+        worst_x, worst_c = max(worst_x, gap), max(worst_c, cgap)
+        assert gap <= 1e-6, (p, xyz[p], ref)
+        assert cgap <= 1e-9, (p, res[p]["cost"], cost)
+    print("noisy: %d points, %d of %d observations inliers, worst |dX| %.3g relative cost gap %.3g, max |X - truth| %.3g, "
+          "trials %s" % (len(xyz), int(inl.sum()), len(inl), worst_x, worst_c,
+                         np.linalg.norm(xyz - truth, axis=1).max(), sorted({r["trials"] for r in res})))
+
+
+# ---- 5. covariances --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("robustify", [0, 1])
+def test_covariances_match_the_formulas(oracle, robustify):
+    from visual_marker_mapping_amd import _lib, engine as eng
+    s = _noisy_scene()
+    start, cam, uv, _ = _tracks(s)
+    rng = np.random.default_rng(5)
+    cam_cov = np.zeros((len(s.cam_gt), 6, 6))
+    for i in range(len(cam_cov)):
+        m = rng.normal(size=(6, 6)) * np.array([1e-3, 1e-3, 1e-3, 2e-4, 2e-4, 2e-4])[:, None]
+        cam_cov[i] = m @ m.T + 1e-8 * np.eye(6)
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, start, cam, uv, cam_cov=cam_cov, robustify=robustify)
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert [r["status"] for r in res] == [_lib.TRI_OK] * len(xyz)
+    worst = [0.0, 0.0]
+    for p in range(len(xyz)):
+        H, S = np.zeros((3, 3)), np.zeros((3, 3))
+        for d in range(int(start[p]), int(start[p + 1])):
+            if not inl[d]:
+                continue
+            r, Jc, Jp = oracle.point_eval(s.intr, s.dist, s.cam_gt[cam[d]], xyz[p], uv[d])
+            w = oracle.huber(1.0, float(r @ r))[1] if robustify else 1.0
+            H += w * (Jp.T @ Jp)
+            G = w * (Jp.T @ Jc)
+            S += G @ cam_cov[cam[d]] @ G.T
+        ref = np.linalg.inv(H)
+        ref_cams = ref @ S @ ref
+        e0 = np.abs(cov[p] - ref).max() / np.abs(ref).max()
+        e1 = np.abs(cov_cams[p] - ref_cams).max() / np.abs(ref_cams).max()
+        worst = [max(worst[0], e0), max(worst[1], e1)]
+        assert e0 <= 1e-6 and e1 <= 1e-6, (p, e0, e1)
+        assert (cov[p] == cov[p].T).all() and (cov_cams[p] == cov_cams[p].T).all()
+        assert np.linalg.eigvalsh(cov[p]).min() > 0
+    print("robustify=%d: worst error of xyz_cov %.3g, of xyz_cov_cams %.3g of max|ref|" % (robustify, *worst))
+    x2, c2, cc2, i2, r2 = _tri(eng, s, start, cam, uv, robustify=robustify)   # cam_cov=None
+    assert (cc2 == 0).all()
+    assert x2.tobytes() == xyz.tobytes() and c2.tobytes() == cov.tobytes() and i2.tobytes() == inl.tobytes() and r2 == res
+
+
+# ---- 6. determinism and independence -----------------------------------------------------------------------------------
+
+def _bits(xyz, cov, cov_cams, inl, res):
+    return (xyz.tobytes(), cov.tobytes(), cov_cams.tobytes(), inl.tobytes(), json.dumps(res, sort_keys=True))
+
+
+def test_results_are_bit_identical_alone_in_a_batch_and_reversed():
+    from visual_marker_mapping_amd import engine as eng
+    s = _noisy_scene()
+    start, cam, uv, _ = _tracks(s)
+    cam_cov = np.tile(np.diag([1e-6, 2e-6, 3e-6, 1e-7, 2e-7, 3e-7]), (len(s.cam_gt), 1, 1))
+    first = _tri(eng, s, start, cam, uv, cam_cov=cam_cov)
+    again = _tri(eng, s, start, cam, uv, cam_cov=cam_cov)
+    assert _bits(*first) == _bits(*again)
+    xyz, cov, cov_cams, inl, res = first
+    n = len(xyz)
+    for p in (0, 1, 6, 77, n - 1):
+        b, e = int(start[p]), int(start[p + 1])
+        x1, c1, cc1, f1, r1 = _tri(eng, s, np.array([0, e - b], np.int64), cam[b:e], uv[b:e], cam_cov=cam_cov)
+        assert x1.tobytes() == xyz[p:p + 1].tobytes() and c1.tobytes() == cov[p:p + 1].tobytes()
+        assert cc1.tobytes() == cov_cams[p:p + 1].tobytes() and f1.tobytes() == inl[b:e].tobytes() and r1[0] == res[p]
+    rev = np.arange(n)[::-1]
+    r_start = np.zeros_like(start)
+    r_start[1:] = np.cumsum(np.diff(start)[rev])
+    idx = np.concatenate([np.arange(start[p], start[p + 1]) for p in rev]).astype(np.int64)
+    x2, c2, cc2, f2, r2 = _tri(eng, s, r_start, cam[idx], uv[idx], cam_cov=cam_cov)
+    assert x2.tobytes() == xyz[rev].tobytes() and c2.tobytes() == cov[rev].tobytes()
+    assert cc2.tobytes() == cov_cams[rev].tobytes() and f2.tobytes() == inl[idx].tobytes() and r2 == [res[p] for p in rev]
+
+
+# ---- 7. edges ----------------------------------------------------------------------------------------------------------
+
+def test_edges_never_produce_a_nan(oracle):
+    from visual_marker_mapping_amd import _lib, engine as eng
+    from visual_marker_mapping_amd.synthetic import make_scene
+    s = make_scene(1, noise_px=0.0, outlier_frac=0.0)
+    start, cam, uv, truth = _tracks(s)
+    lens = np.diff(start)
+    assert lens[0] >= 2 and lens[1] >= 2
+    b0, e0, b1, e1 = int(start[0]), int(start[1]), int(start[1]), int(start[2])
+    # a point without observations and one with a single view between two normal ones
+    e_start = np.array([0, e0 - b0, e0 - b0, e0 - b0 + 1, e0 - b0 + 1 + (e1 - b1)], np.int64)
+    e_cam = np.concatenate([cam[b0:e0], cam[b1:b1 + 1], cam[b1:e1]])
+    e_uv = np.concatenate([uv[b0:e0], uv[b1:b1 + 1], uv[b1:e1]])
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, e_start, e_cam, e_uv)
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert [r["status"] for r in res] == [_lib.TRI_OK, _lib.TRI_TOO_FEW_VIEWS, _lib.TRI_TOO_FEW_VIEWS, _lib.TRI_OK]
+    assert [r["n_obs"] for r in res] == [e0 - b0, 0, 1, e1 - b1]
+    for p in (1, 2):
+        assert (xyz[p] == 0).all() and (cov[p] == 0).all() and (cov_cams[p] == 0).all() and res[p]["n_inlier_obs"] == 0
+    assert not inl[e0 - b0] and inl[:e0 - b0].all() and inl[e0 - b0 + 1:].all()
+    assert np.linalg.norm(xyz[0] - truth[0]) <= 1e-9 and np.linalg.norm(xyz[3] - truth[1]) <= 1e-9
+    # two cameras with identical poses and identical pixels: the rays coincide, no candidate
+    twin = np.stack([s.cam_gt[cam[b0]], s.cam_gt[cam[b0]]])
+    xyz, cov, cov_cams, inl, res = eng.triangulate(s.intr, s.dist, twin, [0, 2], [0, 1], np.stack([uv[b0], uv[b0]]),
+                                                   cam_cov=np.tile(np.eye(6) * 1e-6, (2, 1, 1)))
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert res[0]["status"] == _lib.TRI_NO_CANDIDATE and not inl.any()
+    assert (xyz == 0).all() and (cov == 0).all() and (cov_cams == 0).all()
+    # a 2-view track with both views displaced so that no point comes within inlier_px of both.  The condition on the
+    # input is checked with the yardstick: of four displacement patterns the one whose ray midpoint is farthest from
+    # the two pixels is taken, and it must miss both by more than 3 x inlier_px.
+    two_cam, two_uv = cam[b0:b0 + 2], uv[b0:b0 + 2]
+
+    def midpoint_miss(pix):
+        c, d = [], []
+        for i in range(2):
+            q = s.cam_gt[two_cam[i]]
+            R = _rotation(q[:4])
+            ray = R.T @ np.array([(pix[i, 0] - s.intr[2]) / s.intr[0], (pix[i, 1] - s.intr[3]) / s.intr[1], 1.0])
+            c.append(-R.T @ q[4:])
+            d.append(ray / np.linalg.norm(ray))
+        A = sum(np.eye(3) - np.outer(v, v) for v in d)
+        X = np.linalg.solve(A, sum((np.eye(3) - np.outer(v, v)) @ o for v, o in zip(d, c)))
+        return min(np.linalg.norm(oracle.point_eval(s.intr, s.dist, s.cam_gt[two_cam[i]], X, pix[i], jac=False))
+                   for i in range(2))
+
+    assert not s.dist.any()   # the rays above take no distortion
+    patterns = [np.array([[dx, dy], [-dx, -dy]], np.float64) for dx, dy in ((150, 0), (0, 150), (150, 150), (150, -150))]
+    miss, shift = max(((midpoint_miss(two_uv + m), k) for k, m in enumerate(patterns)))
+    print("displaced pair: the ray midpoint misses the nearer pixel by %.3g px" % miss)
+    assert miss > 3 * INLIER_PX
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, np.array([0, 2], np.int64), two_cam, two_uv + patterns[shift])
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert res[0]["status"] == _lib.TRI_TOO_FEW_INLIERS and res[0]["n_inlier_obs"] == 0 and not inl.any()
+    assert (cov == 0).all() and (cov_cams == 0).all() and np.abs(xyz).max() > 0
+    # reclassify_passes == 0: one refinement over all observations
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, start, cam, uv, reclassify_passes=0)
+    _check_exact(_lib, start, truth, xyz, cov, cov_cams, inl, res, "reclassify_passes=0")
+    # min_inlier_views above what the track has: the best-effort point, flagged
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, np.array([0, 2], np.int64), two_cam, two_uv, min_inlier_views=3)
+    _assert_clean(xyz, cov, cov_cams, res)
+    assert res[0]["status"] == _lib.TRI_TOO_FEW_INLIERS and res[0]["n_inlier_obs"] == 2 and inl.all()
+    assert (cov == 0).all() and (cov_cams == 0).all()
+    assert np.linalg.norm(xyz[0] - truth[0]) <= 1e-9
+
+
+# ---- 8. tag geometry ---------------------------------------------------------------------------------------------------
+
+def _reconstructor(s, obs_px):
+    from visual_marker_mapping_amd.tag_reconstructor import (Camera, CameraModel, ReconstructedTag, TagReconstructor,
+                                                             detection_result_from_arrays)
+    det = detection_result_from_arrays(s.obs_cam, s.obs_tag, obs_px, s.tag_wh, len(s.cam_gt))
+    rec = TagReconstructor(det)
+    rec.setCameraModel(CameraModel(*[float(v) for v in s.intr], distortionCoefficients=s.dist))
+    rec.setReconstructedTags({t: ReconstructedTag(t, "apriltag_36h11", s.tag_gt[t, :4], s.tag_gt[t, 4:], s.tag_wh[t, 0],
+                                                  s.tag_wh[t, 1]) for t in range(len(s.tag_gt))})
+    rec.setReconstructedCameras({c: Camera(c, s.cam_gt[c, :4], s.cam_gt[c, 4:]) for c in range(len(s.cam_gt))})
+    return rec
+
+
+def test_tag_geometry_measures_a_tag_of_another_size(oracle):
+    from visual_marker_mapping_amd import _lib
+    from visual_marker_mapping_amd.synthetic import make_scene
+    cfg, kw = EXACT["distortion_30x40"]
+    s = make_scene(cfg, noise_px=0.0, outlier_frac=0.0, **kw)
+    odd = 7
+    px = s.obs_px.copy()
+    corners = _tag_corners(s.tag_gt[odd], s.tag_wh[odd], scale=(1.05, 0.97))
+    seen = np.flatnonzero(s.obs_tag == odd)
+    assert len(seen) >= 2
+    for d in seen:
+        for k in range(4):   # the residual against the pixel (0, 0) is the projection
+            px[d, 2 * k:2 * k + 2] = oracle.point_eval(s.intr, s.dist, s.cam_gt[s.obs_cam[d]], corners[k], np.zeros(2),
+                                                       jac=False)
+    geo = _reconstructor(s, px).triangulateTagCorners()
+    assert sorted(geo) == list(range(len(s.tag_gt)))
+    g = geo[odd]
+    print("tag %d seen %d times: width_ratio - 1.05 = %.3g, height_ratio - 0.97 = %.3g, out_of_plane %.3g, model_gap %.3g"
+          % (odd, len(seen), g["width_ratio"] - 1.05, g["height_ratio"] - 0.97, g["out_of_plane"], g["model_gap"]))
+    assert g["status"] == _lib.TRI_OK and g["corners"].shape == (4, 3)
+    assert abs(g["width_ratio"] - 1.05) <= 1e-9 and abs(g["height_ratio"] - 0.97) <= 1e-9
+    assert g["out_of_plane"] <= 1e-9
+    assert abs(g["width"] - 1.05 * s.tag_wh[odd, 0]) <= 1e-9 and abs(g["height"] - 0.97 * s.tag_wh[odd, 1]) <= 1e-9
+    assert np.abs(g["corners"] - corners).max() <= 1e-9
+    worst = 0.0
+    for t, g in geo.items():
+        if t == odd:
+            continue
+        worst = max(worst, abs(g["width_ratio"] - 1), abs(g["height_ratio"] - 1), g["model_gap"], g["out_of_plane"])
+        assert g["status"] == _lib.TRI_OK, t
+        assert abs(g["width_ratio"] - 1) <= 1e-9 and abs(g["height_ratio"] - 1) <= 1e-9 and g["model_gap"] <= 1e-9, (t, g)
+    print("other tags: worst deviation of a ratio from 1, model_gap or out_of_plane %.3g" % worst)
+
+
+# ---- 9. command line and reconstructor members ---------------------------------------------------------------------------
+
+def test_command_line_and_reconstructor_member_match_the_engine(tmp_path):
+    from visual_marker_mapping_amd import _lib, engine as eng, io as vio, triangulation
+    from visual_marker_mapping_amd.synthetic import make_scene, write_project
+    s = make_scene(1, noise_px=0.0, outlier_frac=0.0)
+    proj = str(tmp_path / "proj")
+    write_project(s, proj)
+    shutil.copy(os.path.join(proj, "ground_truth.json"), os.path.join(proj, "reconstruction.json"))
+    start, cam, uv, truth = _tracks(s)
+    # the tracks in the file: unsorted (reversed), and every point also seen in an image the map does not know
+    tracks = {p: [(int(cam[d]), (float(uv[d, 0]), float(uv[d, 1]))) for d in range(int(start[p + 1]) - 1, int(start[p]) - 1, -1)]
+              + [(1000 + p, (1.0, 2.0))] for p in range(len(truth))}
+    vio.writePointDetections(tracks, os.path.join(proj, "point_detections.json"))
+    # camera covariances in the layout of reconstruction_uncertainty.json
+    cam_cov = np.tile(np.diag([1e-6, 2e-6, 3e-6, 1e-7, 2e-7, 3e-7]), (len(s.cam_gt), 1, 1))
+    from visual_marker_mapping_amd.uncertainty import write_uncertainty
+    unc = os.path.join(proj, "reconstruction_uncertainty.json")
+    write_uncertainty(unc, 0, False, {}, {i: cam_cov[i] for i in range(len(cam_cov))})
+    assert triangulation.main(["--project_path", proj, "--camera_covariances", unc]) == 0
+    out = vio.read_json(os.path.join(proj, "triangulation.json"))["points"]
+    xyz, cov, cov_cams, inl, res = _tri(eng, s, start, cam, uv, cam_cov=cam_cov)
+    assert [int(p["id"]) for p in out] == list(range(len(truth)))
+    for n, p in enumerate(out):
+        assert np.array([float(v) for v in p["position"]]).tobytes() == xyz[n].tobytes(), n
+        assert p["status"] == "ok" and int(p["num_observations"]) == res[n]["n_obs"] == start[n + 1] - start[n]
+        assert int(p["num_inlier_observations"]) == res[n]["n_inlier_obs"] and float(p["rms_px"]) == res[n]["rms_px"]
+        for key, ref in (("covariance", cov[n]), ("covariance_cameras", cov_cams[n])):
+            assert (int(p[key]["rows"]), int(p[key]["cols"])) == (3, 3)
+            assert np.array([float(v) for v in p[key]["coefficents"]]).tobytes() == ref.tobytes()
+        assert np.allclose([float(v) for v in p["sigma"]], np.sqrt(np.diag(cov[n] + cov_cams[n])), rtol=1e-15, atol=0)
+        assert np.linalg.norm(xyz[n] - truth[n]) <= 1e-9
+    assert (cov_cams != 0).any()
+    # --cameras: a localization.json whose entry 3 failed is triangulated without image 3
+    loc = vio.read_json(os.path.join(proj, "reconstruction.json"))
+    cams = [dict(c, status="ok" if int(c["id"]) != 3 else "no_candidate") for c in loc["reconstructed_cameras"]]
+    loc_file, other = str(tmp_path / "localization.json"), str(tmp_path / "other.json")
+    vio.write_json(loc_file, {"reconstructed_cameras": cams})
+    assert triangulation.main(["--project_path", proj, "--cameras", loc_file, "--output", other]) == 0
+    got = vio.read_json(other)["points"]
+    for n, p in enumerate(got):
+        assert int(p["num_observations"]) == int(((cam[start[n]:start[n + 1]]) != 3).sum())
+    # --tag_corners
+    assert triangulation.main(["--project_path", proj, "--tag_corners"]) == 0
+    geo = vio.read_json(os.path.join(proj, "tag_geometry.json"))["tags"]
+    assert [int(g["id"]) for g in geo] == list(range(len(s.tag_gt)))
+    for g in geo:
+        assert g["status"] == "ok" and abs(float(g["width_ratio"]) - 1) <= 1e-9 and abs(float(g["height_ratio"]) - 1) <= 1e-9
+        assert float(g["model_gap"]) <= 1e-9 and float(g["out_of_plane"]) <= 1e-9
+    # the member of the reconstructor: the same bits as the engine, per image flags, dropped observations counted
+    rec = _reconstructor(s, s.obs_px)
+    pts = rec.triangulatePoints(tracks)
+    assert rec.lastTriangulationDropped == len(truth)
+    for n in range(len(truth)):
+        assert pts[n]["point"].tobytes() == xyz[n].tobytes() and pts[n]["covariance"].tobytes() == cov[n].tobytes()
+        assert pts[n]["status"] == _lib.TRI_OK and (pts[n]["covariance_cameras"] == 0).all()
+        assert pts[n]["inliers"] == {int(c): True for c in cam[start[n]:start[n + 1]]}

@@ -19,6 +19,9 @@ CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 # VMM_BA_LOC_*: status of one image of vmm_ba_localize
 LOC_OK, LOC_NO_OBSERVATIONS, LOC_NO_CANDIDATE, LOC_TOO_FEW_INLIERS, LOC_SINGULAR = 0, 1, 2, 3, 4
 LOC_STATUS_NAMES = ("ok", "no_observations", "no_candidate", "too_few_inliers", "singular")
+# VMM_BA_TRI_*: status of one point of vmm_ba_triangulate
+TRI_OK, TRI_TOO_FEW_VIEWS, TRI_NO_CANDIDATE, TRI_TOO_FEW_INLIERS, TRI_SINGULAR = 0, 1, 2, 3, 4
+TRI_STATUS_NAMES = ("ok", "too_few_views", "no_candidate", "too_few_inliers", "singular")
 # VMM_BA_CAL_*: status of vmm_ba_calibrate
 CAL_OK, CAL_NO_IMAGES, CAL_SINGULAR, CAL_NO_CONVERGENCE = 0, 1, 2, 3
 CAL_STATUS_NAMES = ("ok", "no_images", "singular", "no_convergence")
@@ -35,6 +38,7 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
            "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses",
            "vmm_ba_default_calibrate_options", "vmm_ba_calibrate",
+           "vmm_ba_default_triangulate_options", "vmm_ba_triangulate",
            "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
            "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"]
 
@@ -110,6 +114,17 @@ class LocalizeOptions(C.Structure):
 
 
 class LocalizeResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_obs", C.c_int32), ("n_inlier_obs", C.c_int32), ("trials", C.c_int32),
+                ("rms_px", C.c_double), ("cost", C.c_double)]
+
+
+class TriangulateOptions(C.Structure):
+    _fields_ = [("refine_iterations", C.c_int32), ("robustify", C.c_int32), ("huber_a", C.c_double),
+                ("score_cap_px", C.c_double), ("inlier_px", C.c_double), ("reclassify_passes", C.c_int32),
+                ("min_inlier_views", C.c_int32), ("max_pair_views", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TriangulateResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_obs", C.c_int32), ("n_inlier_obs", C.c_int32), ("trials", C.c_int32),
                 ("rms_px", C.c_double), ("cost", C.c_double)]
 
@@ -215,6 +230,12 @@ def lib():
                                            C.c_void_p, C.c_void_p, C.POINTER(CalibrateOptions), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(CalibrateReport), C.c_int]
+        if hasattr(L, "vmm_ba_triangulate"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
+            L.vmm_ba_default_triangulate_options.restype = None
+            L.vmm_ba_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
+            L.vmm_ba_triangulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.vmm_ba_debug_chol_tile.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "vmm_ba_solve_selfcal"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
             L.vmm_ba_set_intrinsics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

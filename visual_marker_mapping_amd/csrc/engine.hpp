@@ -452,6 +452,27 @@ struct MapBatch {
     }
     void results(Arena& ar, double* cam_qt, double* cam_cov, uint8_t* obs_inlier, vmm_ba_localize_result* res_out) const;
 };
+// kernels_triangulate.hip: free points from known cameras (vmm_ba_triangulate)
+constexpr int kCamFrame = 15;   // doubles of a camera's frame: R (9, row-major, of q / |q|) | t (3) | c = -R^T t (3)
+struct TriangulateArgs {
+    Intrinsics K;
+    int n_pts;
+    const double* frames;      // [kCamFrame * n_cams] (k_cam_frames)
+    const double* cam_cov;     // [36 * n_cams] or null
+    const int64_t* pt_start;   // [n_pts + 1]
+    const int32_t* obs_cam;    // [n_obs]
+    const double* obs_uv;      // [2 * n_obs]
+    int max_trials, robustify, passes, min_inliers, max_pair;
+    double huber_a, cap2, inlier2;
+    double* xyz;               // [3 * n_pts]
+    double* cov;               // [9 * n_pts]
+    double* cov_cams;          // [9 * n_pts]
+    uint8_t* obs_inlier;       // [n_obs]: the active set of every pass, the final flags at the end
+    vmm_ba_triangulate_result* res;
+};
+void launch_cam_frames(hipStream_t st, int n_cams, const double* cam_qt, double* frames);
+void launch_triangulate(hipStream_t st, const TriangulateArgs& a);
+int preload_triangulate_kernels();
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
 constexpr int kCalRec = 68;    // doubles of an image's record: reduced 9 x 9 block (45, packed lower) | reduced gradient (9) |
                                // diag(C) (9) | cost | sum |r|^2 | 1 if A + lam diag was not positive definite | inlier

@@ -446,6 +446,53 @@ def calibrate(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0
     return intr, dist, intr_cov, cam_qt, cam_cov, inl.astype(bool), results, report
 
 
+def default_triangulate_options(**kw):
+    o = _lib.TriangulateOptions()
+    _lib.lib().vmm_ba_default_triangulate_options(C.byref(o))
+    for k, v in kw.items():
+        if k == "reserved" or not hasattr(o, k):
+            raise AttributeError("unknown triangulation option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, device=0, **options):
+    """Free points (anything that is not a tag) from the cameras of a finished map or of a localisation
+    (vmm_ba_triangulate).  cam_qt (n_cams, 7) world->camera.  pt_start (n_pts + 1,): point p owns the observations
+    [pt_start[p], pt_start[p + 1]) of obs_cam (n_obs,), strictly increasing within a point, and obs_uv (n_obs, 2).
+    cam_cov (n_cams, 6, 6), optional: the cameras' marginal covariances in tangent order.  options: the fields of
+    vmm_ba_triangulate_options.  Returns (xyz (n_pts, 3), xyz_cov (n_pts, 3, 3) the part the pixel noise causes,
+    xyz_cov_cams (n_pts, 3, 3) the part propagated from cam_cov, camera by camera without their correlations (zeros
+    without cam_cov), obs_inlier (n_obs,) bool, results: one dict per point with status, n_obs, n_inlier_obs, trials,
+    rms_px, cost)."""
+    intr = np.ascontiguousarray(intr, np.float64).reshape(4)
+    dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
+    pt_start = np.ascontiguousarray(pt_start, np.int64).reshape(-1)
+    obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
+    obs_uv = np.ascontiguousarray(obs_uv, np.float64).reshape(-1, 2)
+    if len(obs_cam) != len(obs_uv):
+        raise ValueError("observation arrays differ in length")
+    if len(pt_start) < 1 or pt_start[-1] != len(obs_cam):
+        raise ValueError("pt_start must have n_pts + 1 entries and end at the number of observations")
+    if cam_cov is not None:
+        cam_cov = np.ascontiguousarray(cam_cov, np.float64).reshape(-1, 6, 6)
+        if len(cam_cov) != len(cam_qt):
+            raise ValueError("cam_cov and cam_qt differ in length")
+    o = default_triangulate_options(**options)
+    n_pts = len(pt_start) - 1
+    xyz, cov, cov_cams = np.zeros((n_pts, 3)), np.zeros((n_pts, 3, 3)), np.zeros((n_pts, 3, 3))
+    inl = np.zeros(len(obs_cam), np.uint8)
+    res = (_lib.TriangulateResult * max(n_pts, 1))()
+    _lib.check(_lib.lib().vmm_ba_triangulate(_ptr(intr), _ptr(dist), len(cam_qt), _ptr(cam_qt),
+                                             None if cam_cov is None else _ptr(cam_cov), n_pts, _ptr(pt_start),
+                                             _ptr(obs_cam), _ptr(obs_uv), C.byref(o), _ptr(xyz), _ptr(cov), _ptr(cov_cams),
+                                             _ptr(inl), C.cast(res, C.c_void_p), device))
+    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_pts)   # vmm_ba_triangulate_result has the same layout
+    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_pts)]
+    return xyz, cov, cov_cams, inl.astype(bool), results
+
+
 def pose_plus(qt, delta, device=0):
     """Plus(qt, delta) for (n,7) poses and (n,6) tangent steps with the engine's device function
     (Ceres QuaternionParameterization::Plus on q, addition on t; tangent = translation then rotation)."""

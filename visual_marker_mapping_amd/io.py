@@ -217,3 +217,28 @@ def parseReconstructions(path):
         cams[i] = Camera(cameraId=i, q=_vector(_children(pt, "rotation"), 4),
                          t=_vector(_children(pt, "translation"), 3))
     return tags, cams, propertyTreeToCameraModel(_children(t, "camera_model"))
+
+
+# ---- point_detections.json -------------------------------------------------------------------------------
+# Pixels of free points (anything that is not a tag) for the triangulation step; not a file of the reference.
+#   {"points": [{"id": 7, "observations": [{"image_id": 12, "uv": [u, v]}, ...]}, ...]}
+
+
+def writePointDetections(tracks, path):
+    """tracks: {pointId: [(imageId, (u, v)), ...]}, written in the order given."""
+    points = [{"id": int(pid), "observations": [{"image_id": int(i), "uv": [float(uv[0]), float(uv[1])]} for i, uv in obs]}
+              for pid, obs in tracks.items()]
+    write_json(path, {"points": points})
+    return True
+
+
+def readPointDetections(path):
+    """Returns {pointId: [(imageId, (u, v)), ...]} as TagReconstructor.triangulatePoints takes it."""
+    tracks = {}
+    for pt in _children(read_json(path), "points"):
+        obs = []
+        for ob in _children(pt, "observations"):
+            uv = _vector(_children(ob, "uv"), 2)
+            obs.append((_get(ob, "image_id", int), (float(uv[0]), float(uv[1]))))
+        tracks[_get(pt, "id", int)] = obs
+    return tracks

@@ -159,6 +159,7 @@ class TagReconstructor:
         self.lastInitReport = None                             # report of vmm_ba_initialize (startReconstructionGlobal)
         self.lastLocalizationReport = None                     # image id -> report (computeRelativeCameraPosesFromImgs)
         self.lastSelfCalibrationReport = None                  # report of doBundleAdjustment(refineCameraModel=True)
+        self.lastTriangulationDropped = 0                      # observations triangulatePoints dropped (image without a pose)
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
         self._obs_cache = None                                 # observation list as arrays (see _obs_arrays)
         self._resident = False                                 # device-resident packing (startReconstruction)
@@ -514,6 +515,95 @@ class TagReconstructor:
                                         distortionCoefficients=dist, verticalResolution=m.verticalResolution,
                                         horizontalResolution=m.horizontalResolution)
         return report
+
+    @staticmethod
+    def _pack_tracks(tracks, camera_ids):
+        """The flat arrays engine.triangulate takes from {pointId: [(imageId, (u, v)), ...]}: every track sorted by image
+        id, observations of images outside `camera_ids` (ascending; position = the camera's index) dropped.  Returns
+        (point_ids, pt_start, obs_cam, obs_uv, obs_image, n_dropped); an image that appears twice in a track is refused."""
+        dense = {int(c): k for k, c in enumerate(camera_ids)}
+        point_ids = list(tracks)
+        pt_start, obs_cam, obs_uv, obs_image, dropped = [0], [], [], [], 0
+        for pid in point_ids:
+            kept = sorted(((int(i), uv) for i, uv in tracks[pid]), key=lambda e: e[0])
+            seen = [i for i, _ in kept]
+            if len(set(seen)) != len(seen):
+                raise ValueError("point %r is observed twice in one image" % (pid,))
+            for i, uv in kept:
+                if i not in dense:
+                    dropped += 1
+                    continue
+                obs_cam.append(dense[i])
+                obs_image.append(i)
+                obs_uv.append(np.asarray(uv, np.float64).reshape(2))
+            pt_start.append(len(obs_cam))
+        obs_uv = np.stack(obs_uv) if obs_uv else np.zeros((0, 2))
+        return (point_ids, np.array(pt_start, np.int64), np.array(obs_cam, np.int32), obs_uv, obs_image, dropped)
+
+    def triangulatePoints(self, tracks, cameras=None, cameraCovariances=None, **options):
+        """Free points (anything that is not a tag) in the map's frame from pixels in images with a known pose
+        (vmm_ba_triangulate): the dual of computeRelativeCameraPosesFromImgs.  tracks: {pointId: [(imageId, (u, v)), ...]}.
+        cameras: {imageId: Camera}, default reconstructedCameras (a localisation's result works as well).
+        cameraCovariances: {imageId: 6x6} in tangent order (computePoseCovariances()["cameras"], or the covariances of
+        lastLocalizationReport); a camera without an entry counts as exact.  options: the fields of
+        vmm_ba_triangulate_options.  Observations of images without a pose are dropped (lastTriangulationDropped counts
+        them).  Returns {pointId: {"point" (3,), "covariance" (3, 3) from the pixel noise, "covariance_cameras" (3, 3)
+        propagated from cameraCovariances camera by camera, "status", "n_obs", "n_inlier_obs", "rms_px",
+        "inliers": {imageId: bool}}}.  The reference has no such member."""
+        cams = self.reconstructedCameras if cameras is None else {int(k): v for k, v in dict(cameras).items()}
+        cam_ids = sorted(cams)
+        point_ids, pt_start, obs_cam, obs_uv, obs_image, dropped = self._pack_tracks(tracks, cam_ids)
+        self.lastTriangulationDropped = dropped
+        cam_qt = np.array([np.concatenate([cams[i].q, cams[i].t]) for i in cam_ids], np.float64).reshape(-1, 7)
+        cam_cov = None
+        if cameraCovariances is not None:
+            cam_cov = np.zeros((len(cam_ids), 6, 6))
+            for k, i in enumerate(cam_ids):
+                if i in cameraCovariances:
+                    cam_cov[k] = np.asarray(cameraCovariances[i], np.float64).reshape(6, 6)
+        m = self.camModel
+        xyz, cov, cov_cams, inl, res = _engine.triangulate([m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, cam_qt,
+                                                           pt_start, obs_cam, obs_uv, cam_cov=cam_cov, device=self.device,
+                                                           **options)
+        out = {}
+        for n, pid in enumerate(point_ids):
+            b, e = int(pt_start[n]), int(pt_start[n + 1])
+            out[pid] = {"point": xyz[n].copy(), "covariance": cov[n].copy(), "covariance_cameras": cov_cams[n].copy(),
+                        "status": res[n]["status"], "n_obs": res[n]["n_obs"], "n_inlier_obs": res[n]["n_inlier_obs"],
+                        "rms_px": res[n]["rms_px"], "inliers": {obs_image[k]: bool(inl[k]) for k in range(b, e)}}
+        return out
+
+    def triangulateTagCorners(self, tagIds=None, **options):
+        """Measures the true shape of the reconstructed tags: the four corners of every tag (default: all; `tagIds`
+        restricts them) are triangulated as four free points from the corner pixels of the tag's detections in images
+        with a pose, without the rigid rectangle of the declared size that the bundle adjustment assumes.  options: as
+        triangulatePoints.  Returns {tagId: {"corners" (4, 3) LL, LR, UR, UL, "width" / "height" (the mean of the two
+        opposite sides), "width_ratio" / "height_ratio" (against the declared size), "out_of_plane" (distance of UR from
+        the plane through the other three), "model_gap" (largest distance between a triangulated corner and the map's
+        computeMarkerCorners3D()), "status" (the worst of the four VMM_BA_TRI_* statuses)}}."""
+        ids = sorted(self.reconstructedTags) if tagIds is None else [int(t) for t in tagIds]
+        wanted = set(ids)
+        tracks = {(t, k): [] for t in ids for k in range(4)}
+        for ob in self.detectionResults_.tagObservations:
+            if ob.tagId in wanted and ob.imageId in self.reconstructedCameras:
+                for k in range(4):
+                    tracks[(ob.tagId, k)].append((ob.imageId, ob.corners[k]))
+        pts = self.triangulatePoints(tracks, **options)
+        out = {}
+        for t in ids:
+            tag = self.reconstructedTags[t]
+            c = np.stack([pts[(t, k)]["point"] for k in range(4)])
+            width = 0.5 * (np.linalg.norm(c[1] - c[0]) + np.linalg.norm(c[2] - c[3]))
+            height = 0.5 * (np.linalg.norm(c[3] - c[0]) + np.linalg.norm(c[2] - c[1]))
+            normal = np.cross(c[1] - c[0], c[3] - c[0])
+            nn = np.linalg.norm(normal)
+            gap = max(np.linalg.norm(c[k] - m) for k, m in enumerate(tag.computeMarkerCorners3D()))
+            out[t] = {"corners": c, "width": float(width), "height": float(height),
+                      "width_ratio": float(width / tag.tagWidth) if tag.tagWidth > 0 else 0.0,
+                      "height_ratio": float(height / tag.tagHeight) if tag.tagHeight > 0 else 0.0,
+                      "out_of_plane": float(abs(np.dot(c[2] - c[0], normal)) / nn) if nn > 0 else 0.0,
+                      "model_gap": float(gap), "status": max(pts[(t, k)]["status"] for k in range(4))}
+        return out
 
     def moveTagIntoOrigin(self, tagId):
         """src/TagReconstructor.cpp:314-338 (applies the same map to tags AND cameras, as the reference does)."""

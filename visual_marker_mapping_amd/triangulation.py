@@ -1,0 +1,134 @@
+"""Command-line triangulation step: free points, or the tags' own corners, from the cameras of a finished map.
+
+    python -m visual_marker_mapping_amd.triangulation --project_path DIR [--map FILE] [--cameras FILE] \\
+        [--points FILE] [--camera_covariances FILE] [--tag_corners] [--output FILE] [--device N]
+
+The reference has no such executable.  The camera model comes from the map (default <project>/reconstruction.json); the
+camera poses from `--cameras`, any file with a `reconstructed_cameras` list (default: the map; in a localization.json
+the entries whose status is not "ok" are skipped); the pixels from `--points` (default <project>/point_detections.json,
+layout in io.py).  `--camera_covariances` names a reconstruction_uncertainty.json or a localization.json: both carry 6x6
+`covariance` entries per camera in the same tangent order, and the part of a point's covariance they cause is
+propagated camera by camera (vmm_ba_triangulate, include/vmm_ba.h).  Every point goes through one device call.
+
+triangulation.json:
+    {"points": [{"id", "position": [x, y, z], "status", "num_observations", "num_inlier_observations", "rms_px",
+                 "sigma": [3 square roots of the diagonal of the sum of the two covariances],
+                 "covariance": {rows, cols, coefficents}, "covariance_cameras": {...}}]}
+
+With --tag_corners the points are the four corners of every tag of the map, observed in <project>/marker_detections.json,
+and tag_geometry.json holds per tag the fields of TagReconstructor.triangulateTagCorners.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from . import _lib
+from . import io as _io
+from .tag_reconstructor import Camera, DetectionResult, TagReconstructor
+
+
+def _matrix(m):
+    m = np.asarray(m, np.float64)
+    return {"rows": int(m.shape[0]), "cols": int(m.shape[1]), "coefficents": [float(v) for v in m.reshape(-1)]}
+
+
+def triangulation_tree(points):
+    """The property tree of triangulation.json from the result of TagReconstructor.triangulatePoints, by ascending id."""
+    out = []
+    for pid in sorted(points):
+        r = points[pid]
+        total = np.asarray(r["covariance"], np.float64) + np.asarray(r["covariance_cameras"], np.float64)
+        out.append({"id": int(pid), "position": [float(v) for v in r["point"]],
+                    "status": _lib.TRI_STATUS_NAMES[r["status"]],
+                    "num_observations": int(r["n_obs"]), "num_inlier_observations": int(r["n_inlier_obs"]),
+                    "rms_px": float(r["rms_px"]), "sigma": [float(v) for v in np.sqrt(np.diag(total))],
+                    "covariance": _matrix(r["covariance"]), "covariance_cameras": _matrix(r["covariance_cameras"])})
+    return {"points": out}
+
+
+def tag_geometry_tree(geometry):
+    """The property tree of tag_geometry.json from the result of TagReconstructor.triangulateTagCorners."""
+    out = []
+    for t in sorted(geometry):
+        g = geometry[t]
+        out.append({"id": int(t), "status": _lib.TRI_STATUS_NAMES[g["status"]],
+                    "corners": [[float(v) for v in c] for c in np.asarray(g["corners"], np.float64)],
+                    "width": float(g["width"]), "height": float(g["height"]), "width_ratio": float(g["width_ratio"]),
+                    "height_ratio": float(g["height_ratio"]), "out_of_plane": float(g["out_of_plane"]),
+                    "model_gap": float(g["model_gap"])})
+    return {"tags": out}
+
+
+def read_cameras(path):
+    """{imageId: Camera} from any file with a `reconstructed_cameras` list; an entry with a `status` other than "ok"
+    (localization.json) is skipped."""
+    cams = {}
+    for pt in _io._children(_io.read_json(path), "reconstructed_cameras"):
+        if "status" in pt and pt["status"] != "ok":
+            continue
+        i = _io._get(pt, "id", int)
+        cams[i] = Camera(cameraId=i, q=_io._vector(_io._children(pt, "rotation"), 4),
+                         t=_io._vector(_io._children(pt, "translation"), 3))
+    return cams
+
+
+def read_camera_covariances(path):
+    """{imageId: 6x6} from the `reconstructed_cameras` of a reconstruction_uncertainty.json or a localization.json."""
+    cov = {}
+    for pt in _io._children(_io.read_json(path), "reconstructed_cameras"):
+        if "covariance" not in pt or ("status" in pt and pt["status"] != "ok"):
+            continue
+        cov[_io._get(pt, "id", int)] = _io._vector(_io._children(pt["covariance"], "coefficents"), 36).reshape(6, 6)
+    return cov
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Triangulates free points, or the tags' corners, against a finished map")
+    ap.add_argument("--project_path", required=True, help="Path to the project (holds reconstruction.json)")
+    ap.add_argument("--map", default=None, help="map file (default: <project>/reconstruction.json)")
+    ap.add_argument("--cameras", default=None, help="file with a reconstructed_cameras list (default: the map)")
+    ap.add_argument("--points", default=None, help="pixel file (default: <project>/point_detections.json)")
+    ap.add_argument("--camera_covariances", default=None,
+                    help="reconstruction_uncertainty.json or localization.json with the cameras' 6x6 covariances")
+    ap.add_argument("--tag_corners", action="store_true",
+                    help="triangulate the corners of the map's tags from marker_detections.json; writes tag_geometry.json")
+    ap.add_argument("--output", default=None, help="output file (default: <project>/triangulation.json or tag_geometry.json)")
+    ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
+    a = ap.parse_args(argv)
+    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
+    detections = os.path.join(a.project_path, "marker_detections.json")
+    points = a.points or os.path.join(a.project_path, "point_detections.json")
+    out = a.output or os.path.join(a.project_path, "tag_geometry.json" if a.tag_corners else "triangulation.json")
+    if not os.path.isfile(recon):
+        raise FileNotFoundError("no map to triangulate against: '%s' does not exist (run the mapping step first: "
+                                "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (recon, a.project_path))
+    needed = [(a.cameras, "camera file"), (a.camera_covariances, "camera covariance file"),
+              (detections, "detection file") if a.tag_corners else (points, "point detection file")]
+    for f, what in needed:
+        if f is not None and not os.path.isfile(f):
+            raise FileNotFoundError("%s '%s' does not exist" % (what, f))
+    tags, cams, model = _io.parseReconstructions(recon)
+    if a.cameras:
+        cams = read_cameras(a.cameras)
+    cov = read_camera_covariances(a.camera_covariances) if a.camera_covariances else None
+    rec = TagReconstructor(_io.readDetectionResult(detections) if a.tag_corners else DetectionResult(), device=a.device)
+    rec.setCameraModel(model)
+    rec.setReconstructedTags(tags)
+    rec.setReconstructedCameras(cams)
+    if a.tag_corners:
+        geometry = rec.triangulateTagCorners()
+        _io.write_json(out, tag_geometry_tree(geometry))
+        print("Triangulated the corners of %d tags; wrote %s!" % (len(geometry), out))
+        return 0
+    result = rec.triangulatePoints(_io.readPointDetections(points), cameraCovariances=cov)
+    ok = sum(1 for r in result.values() if r["status"] == _lib.TRI_OK)
+    _io.write_json(out, triangulation_tree(result))
+    print("Triangulated %d of %d points (%d observations of images without a pose dropped); wrote %s!"
+          % (ok, len(result), rec.lastTriangulationDropped, out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -424,6 +424,97 @@ int vmm_ba_localize(const double intr[4], const double dist[5],
                     vmm_ba_localize_result* res, /* [n_imgs] or NULL */
                     int device);
 
+/* ABI 6, additive.  Localises n_frames frames of a rig of n_rig_cams rigidly mounted cameras against a finished map:
+ * vmm_ba_localize with one pose per frame instead of one per image.  Stateless like it, every frame independent of the
+ * others in the batch.
+ *   rig         camera c has its own model intr[4c .. 4c+3] / dist[5c .. 5c+4] and stands at ext_qt[7c .. 7c+6]
+ *               (rig->camera) in the rig.  rig_qt[7f .. 7f+6] is world->rig of frame f, so camera c of frame f is
+ *               ext_c o rig_f: R = R_c R_f, t = R_c t_f + t_c.  The rig pose moves in its own tangent (translation, then
+ *               the half-angle rotation of vmm_ba_pose_plus), as every pose of this library.
+ *   batch       image (f, c) is slot f * n_rig_cams + c of img_start[n_frames * n_rig_cams + 1]; a camera that saw
+ *               nothing in a frame has an empty range.  obs_tag / obs_px as vmm_ba_localize.
+ *   candidates  both planar solutions of every observation of the frame, computed under the observing camera's model and
+ *               chained to the rig, T_c^-1 o T_rel o T_tag^-1; each scored by sum min(e^2, score_cap_px^2) over ALL the
+ *               frame's corners in all cameras, the residual being the one the bundle adjustment minimises under the
+ *               observing camera's model; lowest wins, ties to the lowest observation of the frame (camera-major) then
+ *               solution 0, non-finite loses
+ *   passes      as vmm_ba_localize, on the 6 degrees of freedom of the rig over the frame's inliers; min_inlier_tags
+ *               counts over the frame
+ *   result      obs_inlier = the classification at the returned pose; rig_cov = row-major 6x6 (J^T J)^-1 in the rig's
+ *               tangent over those inliers, the loss applied when robustify != 0; res[f]: the VMM_BA_LOC_* statuses with
+ *               the meanings and outputs vmm_ba_localize gives them, per frame.
+ * No output is ever NaN; a frame gives the same bits alone, in any batch, at any position and from run to run.
+ * VMM_BA_ERR_ARGUMENT (before any device call): what vmm_ba_localize rejects, n_rig_cams outside
+ * [1, VMM_BA_RIG_MAX_CAMS], a non-finite or zero-quaternion extrinsic, a non-finite camera model.  n_frames == 0
+ * returns VMM_BA_OK without a device call. */
+#define VMM_BA_RIG_MAX_CAMS 8
+int vmm_ba_rig_localize(int32_t n_rig_cams, const double* intr, const double* dist,   /* [4*K], [5*K] */
+                        const double* ext_qt,                                         /* [7*K] rig->camera */
+                        int32_t n_tags, const double* tag_qt, const double* tag_wh,   /* the map */
+                        int32_t n_frames, const int64_t* img_start,                   /* [n_frames*K+1], CSR */
+                        const int32_t* obs_tag, const double* obs_px,                 /* [n_obs], [8*n_obs] */
+                        const vmm_ba_localize_options* o,
+                        double* rig_qt,              /* [7*n_frames] world->rig */
+                        double* rig_cov,             /* [36*n_frames] or NULL */
+                        uint8_t* obs_inlier,         /* [n_obs] or NULL */
+                        vmm_ba_localize_result* res, /* [n_frames] or NULL */
+                        int device);
+
+/* ABI 6, additive.  Calibrates a rig against a finished map: the extrinsics of its cameras and one rig pose per frame
+ * are refined together, the map and the camera models held fixed.  The map of tags of known size is the calibration
+ * target.  Stateless; the rig, the map and the batch exactly as vmm_ba_rig_localize takes them.  The semantics are
+ * vmm_ba_calibrate's, with the 6 n_rig_cams extrinsic parameters (per camera: translation, then half-angle rotation, each
+ * extrinsic moving in its own tangent as vmm_ba_pose_plus moves a pose) in the place of the nine numbers:
+ *   start       vmm_ba_rig_localize's own steps under ext_qt0 and o->loc.  A frame that is not VMM_BA_LOC_OK, or has fewer
+ *               than min_inlier_tags inliers, takes no part: it keeps what the localisation gave it and gets a zero rig_cov.
+ *   refinement  Levenberg-Marquardt on 1/2 sum rho(|r_corner|^2) over the inlier observations, Marquardt damping on the
+ *               frame blocks and on the extrinsic block; every frame eliminates its own 6 x 6 block, the reduced
+ *               6K x 6K system is Jacobi-scaled.  An extrinsic outside refine_mask, or without an inlier observation in
+ *               this refinement, has zero columns, a unit diagonal and a zero step: it comes back with the bits it went
+ *               in with, and its rows and columns of ext_cov are zero.  Accept / reject, the stop rules,
+ *               VMM_BA_CAL_NO_CONVERGENCE, the reclassify passes (classification at inlier_px under the current
+ *               extrinsics, then a new refinement) and VMM_BA_CAL_SINGULAR (a pivot of the undamped reduced system at or
+ *               below 1e-13 C_jj / S_jj) are vmm_ba_calibrate's.
+ *   gauge       at least one camera must be held: a refine_mask with all n_rig_cams bits set, or with bits at or above
+ *               n_rig_cams, is VMM_BA_ERR_ARGUMENT.  The default (a null o, or the value
+ *               vmm_ba_default_rig_calibrate_options sets) is every camera of the rig but camera 0.
+ *   result      ext_qt; ext_cov = S^-1, row-major 6K x 6K in the order of the cameras, cross blocks between cameras
+ *               included; rig_cov_f = A_f^-1 + A_f^-1 B_f S^-1 B_f' A_f^-1, the marginal of the JOINT problem; both from
+ *               the undamped system at the result with the loss applied.  rep->cams_refined: bit c = extrinsic c moved.
+ * Results are bit-identical from run to run; the sum over the frames has a fixed order, so the bits DO depend on the
+ * order of the frames in the batch.  n_frames == 0 returns VMM_BA_OK, ext_qt = ext_qt0 and VMM_BA_CAL_NO_IMAGES without a
+ * device call. */
+typedef struct vmm_ba_rig_calibrate_options {
+    vmm_ba_localize_options loc; /* the initial localisation under the starting extrinsics */
+    int32_t max_trials;          /* 100: LM trials (accepted + rejected) of one refinement */
+    int32_t refine_mask;         /* bit c = extrinsic c is refined; default: every camera but 0 */
+    int32_t robustify;           /* 1 */
+    int32_t reclassify_passes;   /* 2 */
+    int32_t min_inlier_tags;     /* 2: a frame with fewer inliers takes no part */
+    int32_t reserved;
+    double  huber_a;             /* 1.0 */
+    double  inlier_px;           /* 8.0 */
+} vmm_ba_rig_calibrate_options;
+typedef struct vmm_ba_rig_calibrate_report {
+    int32_t status;              /* VMM_BA_CAL_* */
+    int32_t trials, accepted, passes, n_frames_used, n_obs_used, cams_refined, reserved;
+    double  initial_cost, final_cost, initial_rms_px, final_rms_px, time_s;
+} vmm_ba_rig_calibrate_report;
+void vmm_ba_default_rig_calibrate_options(vmm_ba_rig_calibrate_options* o);
+int vmm_ba_rig_calibrate(int32_t n_rig_cams, const double* intr, const double* dist, const double* ext_qt0,
+                         int32_t n_tags, const double* tag_qt, const double* tag_wh,
+                         int32_t n_frames, const int64_t* img_start,
+                         const int32_t* obs_tag, const double* obs_px,
+                         const vmm_ba_rig_calibrate_options* o,
+                         double* ext_qt,               /* [7*K] */
+                         double* ext_cov,              /* [(6K)*(6K)] or NULL */
+                         double* rig_qt,               /* [7*n_frames] */
+                         double* rig_cov,              /* [36*n_frames] or NULL: the joint marginals */
+                         uint8_t* obs_inlier,          /* [n_obs] or NULL */
+                         vmm_ba_localize_result* res,  /* [n_frames] or NULL */
+                         vmm_ba_rig_calibrate_report* rep, /* or NULL */
+                         int device);
+
 /* ABI 6, additive.  Triangulates n_pts free points (anything that is not a tag: a drill hole, an LED, a clicked feature,
  * or a tag's own corners taken one by one) from the cameras of a finished map or of a localisation; the dual of
  * vmm_ba_localize and stateless like it, every point independent of the others in the batch.  Point p owns the

@@ -13,6 +13,7 @@ ABI_VERSION = 6          # VMM_BA_ABI_VERSION of include/vmm_ba.h
 RCCL_ID_BYTES = 128      # VMM_BA_RCCL_ID_BYTES
 PRECISION_F64, PRECISION_F32_ACCUM = 0, 1
 LANDMARK_TAG_POSES, LANDMARK_POINTS = 0, 1
+RIG_MAX_CAMS = 8         # VMM_BA_RIG_MAX_CAMS
 OK, ERR_ARGUMENT, ERR_HIP, ERR_COLLECTIVE, ERR_STATE, ERR_NUMERIC = 0, 1, 2, 3, 4, 5
 ELIM_AUTO, ELIM_TAGS, ELIM_CAMERAS = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
@@ -37,6 +38,7 @@ EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
            "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
            "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
            "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses",
+           "vmm_ba_rig_localize", "vmm_ba_default_rig_calibrate_options", "vmm_ba_rig_calibrate",
            "vmm_ba_default_calibrate_options", "vmm_ba_calibrate",
            "vmm_ba_default_triangulate_options", "vmm_ba_triangulate",
            "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
@@ -142,6 +144,19 @@ class CalibrateReport(C.Structure):
                 ("time_s", C.c_double)]
 
 
+class RigCalibrateOptions(C.Structure):
+    _fields_ = [("loc", LocalizeOptions), ("max_trials", C.c_int32), ("refine_mask", C.c_int32),
+                ("robustify", C.c_int32), ("reclassify_passes", C.c_int32), ("min_inlier_tags", C.c_int32),
+                ("reserved", C.c_int32), ("huber_a", C.c_double), ("inlier_px", C.c_double)]
+
+
+class RigCalibrateReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("trials", C.c_int32), ("accepted", C.c_int32), ("passes", C.c_int32),
+                ("n_frames_used", C.c_int32), ("n_obs_used", C.c_int32), ("cams_refined", C.c_int32),
+                ("reserved", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("initial_rms_px", C.c_double), ("final_rms_px", C.c_double), ("time_s", C.c_double)]
+
+
 class SelfcalOptions(C.Structure):
     _fields_ = [("max_outer_iterations", C.c_int32), ("refine_mask", C.c_int32), ("parameter_tolerance", C.c_double),
                 ("function_tolerance", C.c_double)]
@@ -223,6 +238,17 @@ def lib():
         L.vmm_ba_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.POINTER(LocalizeOptions), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "vmm_ba_rig_localize"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
+            L.vmm_ba_rig_localize.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(LocalizeOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int]
+            L.vmm_ba_default_rig_calibrate_options.restype = None
+            L.vmm_ba_default_rig_calibrate_options.argtypes = [C.POINTER(RigCalibrateOptions)]
+            L.vmm_ba_rig_calibrate.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(RigCalibrateOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RigCalibrateReport), C.c_int]
         if hasattr(L, "vmm_ba_calibrate"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
             L.vmm_ba_default_calibrate_options.restype = None
             L.vmm_ba_default_calibrate_options.argtypes = [C.POINTER(CalibrateOptions)]

@@ -389,9 +389,10 @@ struct InitPass {   // one score + select + refine pass over a family
     double score_cap_px = 100.0;
     int refine_iterations = 30;
 };
-// wh_index: row of tag_wh that holds observation i's size (null: row i)
+// wh_index: row of tag_wh that holds observation i's size (null: row i); out_index: where in qt2 / rms2 observation i's
+// results go (null: i)
 void launch_quad_poses(hipStream_t st, const Intrinsics& K, int64_t n, const double* tag_wh, const double* obs_px, double* qt2,
-                       double* rms2, const int32_t* wh_index = nullptr);
+                       double* rms2, const int32_t* wh_index = nullptr, const int32_t* out_index = nullptr);
 // kernels_localize.hip
 struct LocalizeArgs {
     Intrinsics K;
@@ -414,7 +415,8 @@ void launch_map_corners(hipStream_t st, int n_tags, const double* tag_qt, const 
 void launch_localize(hipStream_t st, const LocalizeArgs& a, bool any_staged, bool any_unstaged);
 int localize_stage_capacity();   // observations of one image that k_localize stages in LDS
 int preload_localize_kernels();
-// localize.hip: the host stage that vmm_ba_localize and vmm_ba_calibrate share -- a batch of images against a map, from
+// localize.hip: the host stage that vmm_ba_localize and vmm_ba_calibrate share (vmm_ba_rig_localize takes its checks,
+// memory and uploads) -- a batch of images against a map, from
 // the argument checks to the localisation's results.  `who` is the entry point's name, for the error text; the checks
 // are separate functions because the two entry points make them in different orders.
 struct MapBatch {
@@ -452,6 +454,53 @@ struct MapBatch {
     }
     void results(Arena& ar, double* cam_qt, double* cam_cov, uint8_t* obs_inlier, vmm_ba_localize_result* res_out) const;
 };
+// kernels_rig.hip: a rig of rigidly mounted cameras against a fixed map (vmm_ba_rig_localize)
+struct RigArgs {
+    LocalizeArgs loc;          // per frame what it holds per image: n_imgs frames, img_start [n_rig_cams * n_imgs + 1] (image
+                               // (f, c) is slot f * n_rig_cams + c), cam_qt / cam_cov / res per frame; K is not used
+    int n_rig_cams;
+    const double* intr;        // [4 * n_rig_cams]
+    const double* dist;        // [5 * n_rig_cams]
+    const double* ext_qt;      // [7 * n_rig_cams] rig->camera
+};
+void launch_rig_localize(hipStream_t st, const RigArgs& a);
+// the joint refinement of the extrinsics and one rig pose per frame (vmm_ba_rig_calibrate); P = 6 n_rig_cams
+constexpr int kRigDof = 6 * VMM_BA_RIG_MAX_CAMS;
+__host__ __device__ constexpr int rig_rec_doubles(int P) { return P * (P + 1) / 2 + 2 * P + 5; }   // a frame's record: reduced P x P block (packed
+                               // lower) | reduced gradient (P) | diag(C) (P) | cost | sum |r|^2 | 1 if A + lam diag was not
+                               // positive definite | inlier observations | 1 (the frame takes part); zero for one that does not
+__host__ __device__ constexpr int rig_elim_doubles(int P) { return 27 + 6 * P; }   // a frame's elimination: L (21) | Y = L^-1 B (6 x P) | y = L^-1 g (6)
+struct RigCalCtl {             // control block of the LM loop, as CalibCtl
+    double ext[7 * VMM_BA_RIG_MAX_CAMS], ext_cand[7 * VMM_BA_RIG_MAX_CAMS], dext[kRigDof];
+    double lam, cost, raw2;
+    double initial_cost, initial_raw2;
+    int32_t refine_mask, max_trials;
+    int32_t trials, accepted;
+    int32_t done, stop;              // done: every kernel returns at once; stop: 1 converged, 2 max_trials ran out
+    int32_t solve_ok, first;
+    int32_t n_used, n_obs_used;
+    int32_t cov_ok, initial_n_obs;
+};
+struct RigCalArgs {
+    RigArgs rig;                   // the batch; loc.cam_qt: current rig poses, loc.obs_inlier: the inlier set of the refinement,
+                                   // loc.res: the localisation's results, loc.cam_cov: the joint marginals; ext_qt is not used
+                                   // (the extrinsics are RigCalCtl's)
+    double* rig_cand;              // [7 * n_frames]
+    int32_t* part;                 // [n_frames] the frame takes part
+    int32_t* n_in;                 // [n_frames] its inlier observations
+    double* rec;                   // [rig_rec_doubles(P) * n_frames]
+    double* elim;                  // [rig_elim_doubles(P) * n_frames]
+    double* trial;                 // [2 * n_frames] candidate cost | max |rig step|
+    RigCalCtl* ctl;
+    int robustify, min_inliers;
+    double huber_a, inlier2;
+    double* ext_cov;               // [P * P]
+};
+void launch_rigcal_begin(hipStream_t st, const RigCalArgs& a);
+void launch_rigcal_classify(hipStream_t st, const RigCalArgs& a);
+void launch_rigcal_trial(hipStream_t st, const RigCalArgs& a);
+void launch_rigcal_covariance(hipStream_t st, const RigCalArgs& a);
+int preload_rig_kernels();
 // kernels_triangulate.hip: free points from known cameras (vmm_ba_triangulate)
 constexpr int kCamFrame = 15;   // doubles of a camera's frame: R (9, row-major, of q / |q|) | t (3) | c = -R^T t (3)
 struct TriangulateArgs {

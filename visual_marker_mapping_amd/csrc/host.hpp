@@ -1,5 +1,5 @@
 // What the host files of libvmm_ba.so share (vmm_ba.hip, covariance.hip, selfcal.hip, initialize.hip, standalone.hip,
-// diagnostics.hip, localize.hip, calibrate.hip, triangulate.hip).  No device code; no kernels_*.hip includes this.
+// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip).  No device code; no kernels_*.hip includes this.
 #pragma once
 
 #include <algorithm>

@@ -549,7 +549,7 @@ InitArgs make_init_args(Engine& e, bool cam, const InitPass& s)
 } // namespace
 
 void launch_quad_poses(hipStream_t st, const Intrinsics& K, int64_t n, const double* tag_wh, const double* obs_px, double* qt2,
-                       double* rms2, const int32_t* wh_index)
+                       double* rms2, const int32_t* wh_index, const int32_t* out_index)
 {
     if (n <= 0)
         return;
@@ -561,7 +561,7 @@ void launch_quad_poses(hipStream_t st, const Intrinsics& K, int64_t n, const dou
     a.stride_i = 8;
     a.tag_wh = tag_wh;
     a.wh_index = wh_index;
-    a.out_index = nullptr;
+    a.out_index = out_index;
     a.mask = nullptr;
     a.qt2 = qt2;
     a.rms2 = rms2;

@@ -15,9 +15,9 @@
 //                   result    flags at the returned pose, (J^T J)^-1 by a 6 x 6 Cholesky in registers
 // The single-pose solver is pose_lm.hpp's, shared with kernels_init.hip: lm_refine (refine_image supplies image_sums as a
 // lambda; the sums hold barriers, so the workgroup runs the driver as one), better / wave_winner, solve6, chain_camera,
-// quat_from_R, lower_inverse / lower_gram (inverse6).  The image view (LDS or global), world_corner, classify_image and
-// image_sums with their workgroup reductions are image_sums.hpp's, shared with kernels_calibrate.hip.  Here: the
-// staging, the candidate scoring, the passes and the covariance.
+// quat_from_R, inverse6.  The image view (LDS or global), world_corner, classify_image and image_sums with their
+// workgroup reductions and the stores of an image's result are image_sums.hpp's, shared with kernels_calibrate.hip and
+// kernels_rig.hip.  Here: the staging, the candidate scoring and the passes.
 // An image's pixels and world corners (20 doubles per observation) are staged in LDS when the image has at most
 // kStage observations (k_localize<true>); larger images read them from global memory (k_localize<false>).  Both run the
 // same arithmetic in the same order, and which one an image takes depends on its own length alone.
@@ -93,66 +93,6 @@ __device__ __forceinline__ int refine_image(const Intrinsics& K, const ImageView
     return lm_refine<true, false>(q, max_trials, [&](auto jac, const double* at, double (&A)[21], double (&g)[6]) {
         return image_sums<STAGED, decltype(jac)::value>(K, v, at, flags, robust, huber_a, s_red, A, g, raw2);
     }, cost);
-}
-
-// C = A^-1 for a packed lower 6 x 6 A by Cholesky, in registers; false: not positive definite (C is not valid).
-// One test at the end covers every pivot: a negative pivot makes its square root a NaN and a zero pivot its reciprocal
-// an infinity, and either reaches the last entry of every later row of L^-1 and from there C.
-__device__ __forceinline__ bool inverse6(const double (&A)[21], double (&C)[21])
-{
-    double L[21], M[21];   // A = L L^T, M = L^-1 (lower)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = A[tri6(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= L[tri6(j, k)] * L[tri6(j, k)];
-        const double s = sqrt(d);
-        L[tri6(j, j)] = s;
-        const double is = 1.0 / s;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[tri6(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= L[tri6(i, k)] * L[tri6(j, k)];
-            L[tri6(i, j)] = v * is;
-        }
-    }
-    lower_inverse<6>(L, M);
-    return finite_bits(lower_gram<6>(M, C));
-}
-
-// What thread 0 stores for image p; have_cov false: a zero covariance.
-__device__ __forceinline__ void store_result(const LocalizeArgs& a, const int p, const double (&q)[7], const double (&C)[21],
-                                             const bool have_cov, const vmm_ba_localize_result& res)
-{
-    double* const out_q = a.cam_qt + 7 * (int64_t)p;
-    double* const out_cov = a.cam_cov + 36 * (int64_t)p;
-#pragma unroll
-    for (int k = 0; k < 7; ++k)
-        out_q[k] = q[k];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-            out_cov[6 * r + c] = have_cov ? (r >= c ? C[tri6(r, c)] : C[tri6(c, r)]) : 0.0;
-    a.res[p] = res;
-}
-
-// NO_OBSERVATIONS / NO_CANDIDATE: the identity pose, a zero covariance (the flags are zero already)
-__device__ __forceinline__ void store_failure(const LocalizeArgs& a, const int p, const int m, const int status, const int trials)
-{
-    const double q[7] = { 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-    vmm_ba_localize_result res;
-    res.status = status;
-    res.n_obs = m;
-    res.n_inlier_obs = 0;
-    res.trials = trials;
-    res.rms_px = 0.0;
-    res.cost = 0.0;
-    const double C[21] = {};
-    store_result(a, p, q, C, false, res);
 }
 
 template <bool STAGED>

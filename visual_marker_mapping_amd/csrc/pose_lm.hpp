@@ -8,6 +8,7 @@
 //   zero_normal / wave_sum_normal, accumulate_rows, solve6   the 21 + 6 sums of the normal equations and their solve
 //   lower_inverse / lower_gram   L^-1 and M^T M of packed lower matrices: the covariances of kernels_localize.hip (6 x 6)
 //                                and kernels_calibrate.hip (6 x 6 and 9 x 9)
+//   inverse6                the 6 x 6 covariance of one pose (kernels_localize.hip, kernels_rig.hip)
 //   chain_camera / chain_tag, quat_from_R                    candidates chained through a placed pose
 // Everything is __forceinline__ and lives in registers.
 #pragma once
@@ -189,6 +190,34 @@ __device__ __forceinline__ double lower_gram(const double (&M)[N * (N + 1) / 2],
             sum += fabs(v);
         }
     return sum;
+}
+
+// C = A^-1 for a packed lower 6 x 6 A by Cholesky, in registers; false: not positive definite (C is not valid).
+// One test at the end covers every pivot: a negative pivot makes its square root a NaN and a zero pivot its reciprocal
+// an infinity, and either reaches the last entry of every later row of L^-1 and from there C.
+__device__ __forceinline__ bool inverse6(const double (&A)[21], double (&C)[21])
+{
+    double L[21], M[21];   // A = L L^T, M = L^-1 (lower)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = A[tri6(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k)
+            d -= L[tri6(j, k)] * L[tri6(j, k)];
+        const double s = sqrt(d);
+        L[tri6(j, j)] = s;
+        const double is = 1.0 / s;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[tri6(i, j)];
+#pragma unroll
+            for (int k = 0; k < j; ++k)
+                v -= L[tri6(i, k)] * L[tri6(j, k)];
+            L[tri6(i, j)] = v * is;
+        }
+    }
+    lower_inverse<6>(L, M);
+    return finite_bits(lower_gram<6>(M, C));
 }
 
 __device__ __forceinline__ void accumulate_rows(const double (&j)[2][6], const double ru, const double rv, double (&A)[21],

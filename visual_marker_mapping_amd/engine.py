@@ -405,6 +405,126 @@ def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, *
     return cam_qt, cam_cov, inl.astype(bool), results
 
 
+def _rig_arrays(intr, dist, ext_qt):
+    """The models and extrinsics of a rig's cameras as vmm_ba_rig_localize takes them; returns them and the number of
+    cameras."""
+    intr = np.ascontiguousarray(intr, np.float64).reshape(-1, 4)
+    dist = np.ascontiguousarray(dist, np.float64).reshape(-1, 5)
+    ext_qt = np.ascontiguousarray(ext_qt, np.float64).reshape(-1, 7)
+    if not len(intr) == len(dist) == len(ext_qt):
+        raise ValueError("intr, dist and ext_qt must have one row per camera of the rig")
+    return intr, dist, ext_qt, len(ext_qt)
+
+
+def rig_localize(intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
+    """Poses of a rig of K rigidly mounted cameras, one per frame, against a finished map (vmm_ba_rig_localize).
+    intr (K, 4), dist (K, 5): one model per camera; ext_qt (K, 7): rig->camera.  The map and the observations as
+    engine.localize takes them, image (f, c) being slot f * K + c of img_start (n_frames * K + 1,); a missing image is an
+    empty range.  options: the fields of vmm_ba_localize_options.  Returns (rig_qt (n_frames, 7) world->rig, rig_cov
+    (n_frames, 6, 6), obs_inlier (n_obs,) bool, results: one dict per frame as engine.localize gives per image)."""
+    intr, dist, ext_qt, n_rig_cams = _rig_arrays(intr, dist, ext_qt)
+    _, _, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr[:1], dist[:1], tag_qt, tag_wh, img_start,
+                                                                         obs_tag, obs_px)
+    if n_rig_cams < 1 or (len(img_start) - 1) % n_rig_cams:
+        raise ValueError("img_start must have n_frames * K + 1 entries for the K >= 1 cameras of the rig")
+    o = default_localize_options(**options)
+    n_frames = (len(img_start) - 1) // n_rig_cams
+    rig_qt, rig_cov = np.zeros((n_frames, 7)), np.zeros((n_frames, 6, 6))
+    inl = np.zeros(len(obs_tag), np.uint8)
+    res = (_lib.LocalizeResult * max(n_frames, 1))()
+    _lib.check(_lib.lib().vmm_ba_rig_localize(n_rig_cams, _ptr(intr), _ptr(dist), _ptr(ext_qt), len(tag_qt), _ptr(tag_qt),
+                                              _ptr(tag_wh), n_frames, _ptr(img_start), _ptr(obs_tag), _ptr(obs_px),
+                                              C.byref(o), _ptr(rig_qt), _ptr(rig_cov), _ptr(inl), C.cast(res, C.c_void_p),
+                                              device))
+    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_frames)
+    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_frames)]
+    return rig_qt, rig_cov, inl.astype(bool), results
+
+
+def default_rig_calibrate_options(**kw):
+    """vmm_ba_rig_calibrate_options with its defaults; keywords are its fields, `loc_<field>` sets a field of the initial
+    localisation's options."""
+    o = _lib.RigCalibrateOptions()
+    _lib.lib().vmm_ba_default_rig_calibrate_options(C.byref(o))
+    for k, v in kw.items():
+        if k.startswith("loc_") and k[4:] in dict(_lib.LocalizeOptions._fields_):
+            setattr(o.loc, k[4:], v)
+        elif k not in ("loc", "reserved") and hasattr(o, k):
+            setattr(o, k, v)
+        else:
+            raise AttributeError("unknown rig calibration option %r" % k)
+    return o
+
+
+def rig_calibrate(intr, dist, ext_qt0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
+    """The extrinsics of a rig's cameras and one rig pose per frame from a batch of frames of a finished map, the map and
+    the camera models held fixed (vmm_ba_rig_calibrate).  Arguments as engine.rig_localize, ext_qt0 (K, 7) the starting
+    extrinsics; options: the fields of vmm_ba_rig_calibrate_options (`refine_mask`: bit c = extrinsic c is refined,
+    default every camera but 0), `loc_<field>` for those of the initial localisation.  Returns (ext_qt (K, 7), ext_cov
+    (6 K, 6 K), rig_qt (n_frames, 7), rig_cov (n_frames, 6, 6) the joint marginals, obs_inlier (n_obs,) bool, results:
+    one dict per frame, report: dict of vmm_ba_rig_calibrate_report)."""
+    intr, dist, ext_qt0, n_rig_cams = _rig_arrays(intr, dist, ext_qt0)
+    _, _, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr[:1], dist[:1], tag_qt, tag_wh, img_start,
+                                                                         obs_tag, obs_px)
+    if n_rig_cams < 1 or (len(img_start) - 1) % n_rig_cams:
+        raise ValueError("img_start must have n_frames * K + 1 entries for the K >= 1 cameras of the rig")
+    o = default_rig_calibrate_options(**options)
+    n_frames = (len(img_start) - 1) // n_rig_cams
+    ext_qt, ext_cov = np.zeros((n_rig_cams, 7)), np.zeros((6 * n_rig_cams, 6 * n_rig_cams))
+    rig_qt, rig_cov = np.zeros((n_frames, 7)), np.zeros((n_frames, 6, 6))
+    inl = np.zeros(len(obs_tag), np.uint8)
+    res = (_lib.LocalizeResult * max(n_frames, 1))()
+    rep = _lib.RigCalibrateReport()
+    _lib.check(_lib.lib().vmm_ba_rig_calibrate(n_rig_cams, _ptr(intr), _ptr(dist), _ptr(ext_qt0), len(tag_qt), _ptr(tag_qt),
+                                               _ptr(tag_wh), n_frames, _ptr(img_start), _ptr(obs_tag), _ptr(obs_px),
+                                               C.byref(o), _ptr(ext_qt), _ptr(ext_cov), _ptr(rig_qt), _ptr(rig_cov),
+                                               _ptr(inl), C.cast(res, C.c_void_p), C.byref(rep), device))
+    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_frames)
+    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_frames)]
+    report = {k: getattr(rep, k) for k, _ in _lib.RigCalibrateReport._fields_}
+    return ext_qt, ext_cov, rig_qt, rig_cov, inl.astype(bool), results, report
+
+
+def _pose_matrix(qt):
+    w, x, y, z = qt[:4] / np.linalg.norm(qt[:4])
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    return R, np.asarray(qt[4:], np.float64)
+
+
+def rig_extrinsics_start(n_rig_cams, n_frames, cam_qt, results):
+    """Starting extrinsics of a rig from the poses of its images, each localised on its own (host numpy, no device call).
+    cam_qt (n_frames * K, 7) and results: what engine.localize returned for the images in slot order f * K + c, each
+    camera under its own model.  Camera 0 is the rig.  For each camera c > 0, of the frames in which images (f, 0) and
+    (f, c) are both LOC_OK the one with the most inlier observations over the two images (ties: the lowest frame) gives
+    ext_c = cam(f, c) o cam(f, 0)^-1.  Returns ext_qt (K, 7); raises ValueError naming the camera that never shares a
+    localised frame with camera 0."""
+    from .pnp import quat_from_R
+    cam_qt = np.asarray(cam_qt, np.float64).reshape(n_frames * n_rig_cams, 7)
+    if len(results) != n_frames * n_rig_cams:
+        raise ValueError("results must have one entry per image, n_frames * K")
+    ext_qt = np.zeros((n_rig_cams, 7))
+    ext_qt[:, 0] = 1.0
+    for c in range(1, n_rig_cams):
+        best, best_f = -1, -1
+        for f in range(n_frames):
+            r0, rc = results[f * n_rig_cams], results[f * n_rig_cams + c]
+            if r0["status"] != _lib.LOC_OK or rc["status"] != _lib.LOC_OK:
+                continue
+            n = r0["n_inlier_obs"] + rc["n_inlier_obs"]
+            if n > best:
+                best, best_f = n, f
+        if best_f < 0:
+            raise ValueError("camera %d of the rig shares no localised frame with camera 0: no starting extrinsic" % c)
+        R0, t0 = _pose_matrix(cam_qt[best_f * n_rig_cams])
+        Rc, tc = _pose_matrix(cam_qt[best_f * n_rig_cams + c])
+        R = Rc @ R0.T
+        ext_qt[c, :4] = quat_from_R(R)
+        ext_qt[c, 4:] = tc - R @ t0
+    return ext_qt
+
+
 def default_calibrate_options(**kw):
     """vmm_ba_calibrate_options with its defaults; keywords are its fields, `loc_<field>` sets a field of the initial
     localisation's options (vmm_ba_calibrate_options.loc)."""

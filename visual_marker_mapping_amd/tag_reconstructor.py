@@ -492,6 +492,86 @@ class TagReconstructor:
         self.lastLocalizationReport = report
         return cams
 
+    def _pack_rig(self, det, frames, cameraModels, extrinsics, loc_options):
+        """The flat arrays engine.rig_localize and engine.rig_calibrate take for `frames` (one list of K image ids per
+        frame, None where a camera has no image) against the reconstructed tags.  extrinsics None: every image is
+        localised on its own under its camera's model (vmm_ba_localize) and engine.rig_extrinsics_start takes the
+        extrinsics from the best frame each camera shares with camera 0.  Returns (order, intr, dist, extrinsics,
+        tag_qt, tag_wh, img_start, obs_tag, obs_px); order[k] indexes det.tagObservations."""
+        K = len(cameraModels)
+        if K < 1 or any(len(frame) != K for frame in frames):
+            raise ValueError("every frame lists one image id (or None) per camera of the rig")
+        slots = [i for frame in frames for i in frame]
+        _, order, tag_qt, tag_wh, real_start, obs_tag, obs_px = self._pack_against_map(det, [i for i in slots if i is not None])
+        counts = iter(np.diff(real_start))
+        img_start = np.zeros(len(slots) + 1, np.int64)
+        img_start[1:] = np.cumsum([0 if i is None else next(counts) for i in slots])
+        intr = np.array([[m.fx, m.fy, m.cx, m.cy] for m in cameraModels], np.float64)
+        dist = np.array([m.distortionCoefficients for m in cameraModels], np.float64).reshape(K, 5)
+        n_frames = len(frames)
+        if extrinsics is None:
+            cam_qt, res = np.zeros((len(slots), 7)), [None] * len(slots)
+            for c in range(K):
+                own = np.arange(n_frames) * K + c
+                idx = np.concatenate([np.arange(img_start[i], img_start[i + 1]) for i in own]
+                                     + [np.zeros(0, np.int64)]).astype(np.int64)
+                start = np.zeros(n_frames + 1, np.int64)
+                start[1:] = np.cumsum(np.diff(img_start)[own])
+                q, _, _, r = _engine.localize(intr[c], dist[c], tag_qt, tag_wh, start, obs_tag[idx], obs_px[idx],
+                                              device=self.device, **loc_options)
+                cam_qt[own] = q
+                for f in range(n_frames):
+                    res[f * K + c] = r[f]
+            extrinsics = _engine.rig_extrinsics_start(K, n_frames, cam_qt, res)
+        extrinsics = np.array(extrinsics, np.float64).reshape(K, 7)
+        return order, intr, dist, extrinsics, tag_qt, tag_wh, img_start, obs_tag, obs_px
+
+    @staticmethod
+    def _rig_frames_report(K, order, img_start, rig_qt, rig_cov, inl, res):
+        rigs, report = {}, []
+        for f in range(len(res)):
+            b, e = int(img_start[f * K]), int(img_start[f * K + K])
+            report.append(dict(res[f], pose=rig_qt[f].copy(), covariance=rig_cov[f].copy(), observations=list(order[b:e]),
+                               inliers=inl[b:e].copy()))
+            if res[f]["status"] == _engine._lib.LOC_OK:
+                rigs[f] = Camera(f, rig_qt[f, :4], rig_qt[f, 4:])
+        return rigs, report
+
+    def computeRigPosesFromFrames(self, frames, cameraModels, extrinsics=None, detectionResult=None, **options):
+        """Localises a rig of K rigidly mounted cameras against the reconstructed tags, one pose per frame
+        (vmm_ba_rig_localize).  frames: one list of K image ids per frame, None where a camera has no image;
+        cameraModels: the K CameraModels; extrinsics (K, 7) rig->camera as (qw, qx, qy, qz, tx, ty, tz), or None: taken
+        from the per-image localisation (engine.rig_extrinsics_start; camera 0 is the rig).  options: the fields of
+        vmm_ba_localize_options.  Returns {frame index: Camera} (world->rig) for the frames with status OK;
+        lastRigLocalizationReport holds `extrinsics` (K, 7) and `frames`: per frame the status, counts, rms_px, cost, the
+        pose, the 6x6 covariance and, per used observation (index into detectionResult.tagObservations), the inlier
+        flag.  The reference has no such member."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        order, intr, dist, extrinsics, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_rig(
+            det, frames, cameraModels, extrinsics, options)
+        rig_qt, rig_cov, inl, res = _engine.rig_localize(intr, dist, extrinsics, tag_qt, tag_wh, img_start, obs_tag, obs_px,
+                                                         device=self.device, **options)
+        rigs, report = self._rig_frames_report(len(cameraModels), order, img_start, rig_qt, rig_cov, inl, res)
+        self.lastRigLocalizationReport = dict(extrinsics=extrinsics, frames=report)
+        return rigs
+
+    def calibrateRig(self, frames, cameraModels, extrinsics=None, detectionResult=None, **options):
+        """Calibrates the rig against the reconstructed tags (vmm_ba_rig_calibrate): the extrinsics of the cameras and one
+        rig pose per frame are refined together from the detections, the tags and the camera models held fixed.
+        frames, cameraModels and extrinsics (the start; None: from the per-image localisation) as
+        computeRigPosesFromFrames; options: the fields of vmm_ba_rig_calibrate_options (`loc_<field>` for the initial
+        localisation's).  Returns the report: the fields of vmm_ba_rig_calibrate_report plus `extrinsics` (K, 7),
+        `covariance` (6 K, 6 K), `rigs` ({frame index: Camera} of the localised frames) and `frames` (per frame as
+        lastRigLocalizationReport's, the covariance being the joint marginal).  The reference has no such member."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        loc = {k[4:]: v for k, v in options.items() if k.startswith("loc_")}
+        order, intr, dist, extrinsics, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_rig(
+            det, frames, cameraModels, extrinsics, loc)
+        ext, ext_cov, rig_qt, rig_cov, inl, res, report = _engine.rig_calibrate(
+            intr, dist, extrinsics, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=self.device, **options)
+        rigs, per_frame = self._rig_frames_report(len(cameraModels), order, img_start, rig_qt, rig_cov, inl, res)
+        return dict(report, extrinsics=ext, covariance=ext_cov, rigs=rigs, frames=per_frame)
+
     def refineCameraModel(self, imageIds=None, detectionResult=None, **options):
         """Calibrates the camera against the reconstructed tags (vmm_ba_calibrate): the nine numbers of the camera model
         and one pose per image are refined together from the detections, the tags held fixed, starting at the current

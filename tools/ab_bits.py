@@ -3,11 +3,12 @@
 vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every Cholesky and back-substitution kernel
 (csrc/kernels_chol*.hip, kernels_backsolve.hip) through vmm_ba_dense_spd_solve and a tree-ordered bundle adjustment.
 --cases calibrate: vmm_ba_calibrate (csrc/kernels_calibrate.hip behind the localisation's three kernels).
+--cases rig: vmm_ba_rig_localize and vmm_ba_rig_calibrate (csrc/kernels_rig.hip, rig.hip) at 3 and 8 cameras.
 --cases cov: vmm_ba_tag_translation_covariance (csrc/kernels_cov.hip) after a solve.
 --cases handle: the other entries that work on a handle after a solve (csrc/covariance.hip, selfcal.hip, initialize.hip
 and the evaluation entries of vmm_ba.hip).
 
-    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|cov|handle] [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|rig|cov|handle] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
@@ -134,6 +135,96 @@ def _calibrate_cases(eng, make_scene, out):
                 assert sorted(ints + floats + ("time_s",)) == sorted(rep), sorted(rep)   # a new field belongs in one of them
                 out[key + "report_int"] = np.array([rep[k] for k in ints], np.int64)
                 out[key + "report_f64"] = np.array([rep[k] for k in floats], np.float64)
+
+
+def _rig_cases(eng, make_rig_scene, out):
+    """258 frames of a rig of K = 3 (120 tags) and K = 8 cameras (50 tags), so that the 64-thread k_rigcal_begin,
+    k_rigcal_solve's four chains and k_rigcal_control's 256-stride all wrap; at K = 8 a record has 1277 doubles and every
+    256-strided loop over a record or the 48 x 48 system takes several trips, at K = 3 one.  Frame 0 has 257 observations
+    spread over its cameras (the second trip of the 256-thread stride), frame 1 none, frame 2 no image of camera 0, frame
+    3's detections are displaced so far that it fails min_inlier_tags, a tenth of frame 4's pixel coordinates (12
+    observations per image) are displaced by up to 60 px; the other images have 2 to 6 observations, the first m of their
+    slot.  The extrinsics start off the truth.  vmm_ba_rig_localize robust and plain, with 0 and 2 passes;
+    vmm_ba_rig_calibrate robust and plain, with 0 and 2 reclassification passes, under the default mask and with a
+    middle camera held, and once (K = 3) with the default mask on a batch in which camera 2 has no observation in any
+    frame (its unit rows); max_trials 8 keeps each call at a few dozen launches."""
+    def yaw(deg, t):
+        a = np.radians(deg) / 2
+        return [np.cos(a), 0.0, np.sin(a), 0.0, t[0], t[1], t[2]]
+
+    def batch(s, sizes, rng):
+        K = s.n_rig_cams
+        tags, pxs = [], []
+        for slot, m in enumerate(sizes.reshape(-1)):
+            idx = np.arange(s.img_start[slot], s.img_start[slot + 1])[:m]
+            assert len(idx) == m, (slot, len(idx))
+            tags.append(s.obs_tag[idx])
+            px = s.obs_px[idx].copy()
+            if slot // K == 3:
+                px += rng.uniform(-400.0, 400.0, px.shape)
+            if slot // K == 4:
+                hit = rng.random(px.shape) < 0.1
+                px[hit] += rng.uniform(-60.0, 60.0, int(hit.sum()))
+            pxs.append(px)
+        start = np.concatenate([[0], np.cumsum(sizes.reshape(-1))]).astype(np.int64)
+        return start, np.concatenate(tags), np.concatenate(pxs)
+
+    for K, n_tags in ((3, 120), (8, 50)):
+        ext = np.array([yaw(a, (0.1 * (k - (K - 1) / 2), 0.02 * (k % 3), 0.0)) for k, a in enumerate(np.linspace(-15.0, 15.0, K))])
+        s = make_rig_scene(5, ext, seed=4247 + K, n_cams=258, n_tags=n_tags, visibility=1.0)
+        F = s.n_frames
+        rng = np.random.default_rng(4250 + K)
+        avail = np.diff(s.img_start).reshape(F, K)
+        sizes = rng.integers(2, 7, (F, K))
+        sizes[0] = avail[0]
+        while sizes[0].sum() > 257:
+            sizes[0, sizes[0].argmax()] -= 1
+        assert sizes[0].sum() == 257 and (sizes[0] > 0).all(), sizes[0]
+        sizes[1] = 0
+        sizes[2, 0] = 0
+        sizes[4] = 12
+        ext0 = ext.copy()   # off the truth: a few pixels, so that the default inlier_px still localises the frames
+        ext0[1:, :4] += 2e-4 * np.array([0.0, 1.0, -1.0, 0.5]) * (1 + np.arange(1, K))[:, None] / K
+        ext0[1:, :4] /= np.linalg.norm(ext0[1:, :4], axis=1)[:, None]
+        ext0[1:, 4:] += 1e-3 * np.array([1.0, -0.5, 0.5])
+        start, tags, pxs = batch(s, sizes, np.random.default_rng(4260 + K))
+        for robust in (1, 0):
+            for passes in (0, 2):
+                rig, cov, inl, res = eng.rig_localize(s.intr, s.dist, ext0, s.tag_gt, s.tag_wh, start, tags, pxs,
+                                                      robustify=robust, reclassify_passes=passes)
+                key = "rigloc_k%d_%s_p%d_" % (K, "robust" if robust else "plain", passes)
+                out[key + "rig_qt"], out[key + "rig_cov"], out[key + "inlier"] = rig, cov, inl
+                out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
+                out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
+        held = 1 << (K // 2)
+        default = (1 << K) - 2
+        runs = [(name, mask, start, tags, pxs, 2) for name, mask in (("default", default), ("held", default & ~held))]
+        if K == 3:
+            blind = sizes.copy()
+            blind[:, 2] = 0
+            runs.append(("blind", default) + batch(s, blind, np.random.default_rng(4260 + K)) + (2,))
+        names = ("ext_qt", "ext_cov", "rig_qt", "rig_cov", "inlier")
+        for name, mask, st, tg, px, lost in runs:
+            for robust in (1, 0):
+                for passes in (0, 2):
+                    got = eng.rig_calibrate(s.intr, s.dist, ext0, s.tag_gt, s.tag_wh, st, tg, px, robustify=robust,
+                                            reclassify_passes=passes, refine_mask=mask, max_trials=8)
+                    res, rep = got[5], got[6]
+                    flags = lambda f: got[4][st[f * K]:st[(f + 1) * K]]
+                    # else the scene does not do what the text above says: pick another one
+                    assert rep["n_frames_used"] == F - lost and not flags(3).any() and flags(4).any(), rep
+                    if name == "blind":
+                        assert got[0][2].tobytes() == ext0[2].tobytes() and not rep["cams_refined"] & 4, rep
+                    key = "rigcal_k%d_%s_%s_p%d_" % (K, name, "robust" if robust else "plain", passes)
+                    for n, value in zip(names, got):
+                        out[key + n] = value
+                    out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
+                    out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
+                    ints = ("status", "trials", "accepted", "passes", "n_frames_used", "n_obs_used", "cams_refined", "reserved")
+                    floats = ("initial_cost", "final_cost", "initial_rms_px", "final_rms_px")
+                    assert sorted(ints + floats + ("time_s",)) == sorted(rep), sorted(rep)   # a new field belongs in one of them
+                    out[key + "report_int"] = np.array([rep[k] for k in ints], np.int64)
+                    out[key + "report_f64"] = np.array([rep[k] for k in floats], np.float64)
 
 
 class _Env:
@@ -296,6 +387,9 @@ def child(path, cases):
         _localize_cases(eng, make_scene, out)
     elif cases == "calibrate":
         _calibrate_cases(eng, make_scene, out)
+    elif cases == "rig":
+        from visual_marker_mapping_amd.synthetic import make_rig_scene
+        _rig_cases(eng, make_rig_scene, out)
     elif cases == "cov":
         _cov_cases(eng, make_scene, out)
     elif cases == "handle":
@@ -310,7 +404,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
-    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "cov", "handle"), default="pose", help="which set of cases (default: pose)")
+    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "rig", "cov", "handle"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()

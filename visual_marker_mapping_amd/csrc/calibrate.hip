@@ -1,8 +1,10 @@
 // vmm_ba_calibrate (include/vmm_ba.h): host side.  The checks, the device memory of the common buffers, the uploads,
 // the localisation under the starting camera model and the copies back are the stage it shares with vmm_ba_localize
-// (MapBatch, engine.hpp; defined in localize.hip).  Its own: the result arguments and the calibration options, seven
-// more buffers behind the common ones, CalibArgs, the trial loop, which drives the joint Levenberg-Marquardt refinement
-// of kernels_calibrate.hip one trial at a time and reads the small control block back after each, and the report.
+// (MapBatch, engine.hpp; defined in localize.hip).  The trial loop, which drives the joint Levenberg-Marquardt refinement
+// of kernels_calibrate.hip one trial at a time and reads the small control block back after each, the check of the
+// calibration options and the report are host.hpp's (run_arrow, check_arrow_options, fill_arrow_report), shared with
+// rig.hip.  Its own: the arguments, the mask rule, seven more buffers behind the common ones, CalibArgs, the start
+// values and writing back the camera model.
 #include <math.h>
 #include <string.h>
 
@@ -13,21 +15,6 @@
 #include "pose_lm.hpp"
 
 using namespace vmm;
-
-namespace {
-
-void empty_report(vmm_ba_calibrate_report* rep, int status, double time_s)
-{
-    if (!rep)
-        return;
-    memset(rep, 0, sizeof(*rep));
-    rep->status = status;
-    rep->time_s = time_s;
-}
-
-double finite_or_zero(double v) { return isfinite(v) ? v : 0.0; }
-
-} // namespace
 
 extern "C" {
 
@@ -70,9 +57,8 @@ int vmm_ba_calibrate(const double intr0[4], const double dist0[5], int32_t n_tag
         return rc;
     if (o.refine_mask < 0 || o.refine_mask > 0x1FF)
         return bad_argument(who, "refine_mask outside [0, 0x1FF]");
-    if (o.max_trials < 0 || o.reclassify_passes < 0 || o.min_inlier_tags < 1 || !(o.huber_a > 0.0) || !(o.inlier_px > 0.0)
-        || !isfinite(o.huber_a) || !isfinite(o.inlier_px))
-        return bad_argument(who, "bad options");
+    if ((rc = check_arrow_options(who, o)) != VMM_BA_OK)
+        return rc;
     const auto start_values = [&]() {   // what comes back unless the refinement moves it
         memcpy(intr, intr0, 4 * sizeof(double));
         memcpy(dist, dist0, 5 * sizeof(double));
@@ -128,17 +114,14 @@ int vmm_ba_calibrate(const double intr0[4], const double dist0[5], int32_t n_tag
     ca.flags = mb.inl;
     ca.res = mb.res;
     ca.cam_qt = mb.cam;
-    ca.cam_cand = d_cand;
-    ca.part = d_part;
-    ca.n_in = d_n_in;
-    ca.rec = d_rec;
-    ca.elim = d_elim;
-    ca.trial = d_trial;
+    ca.w.cand = d_cand;
+    ca.w.part = d_part;
+    ca.w.n_in = d_n_in;
+    ca.w.rec = d_rec;
+    ca.w.elim = d_elim;
+    ca.w.trial = d_trial;
+    set_arrow_options(ca.w, o);
     ca.ctl = d_ctl;
-    ca.robustify = o.robustify != 0;
-    ca.min_inliers = o.min_inlier_tags;
-    ca.huber_a = o.huber_a;
-    ca.inlier2 = o.inlier_px * o.inlier_px;
     ca.intr_cov = d_intr_cov;
     ca.cam_cov = mb.cov;
 
@@ -146,50 +129,25 @@ int vmm_ba_calibrate(const double intr0[4], const double dist0[5], int32_t n_tag
     memset(&ctl, 0, sizeof(ctl));
     for (int i = 0; i < 9; ++i)
         ctl.k[i] = ctl.k_cand[i] = i < 4 ? intr0[i] : dist0[i - 4];
-    ctl.refine_mask = o.refine_mask;
-    ctl.max_trials = o.max_trials;
-    ctl.first = 1;
+    ctl.lm.refine_mask = o.refine_mask;
+    ctl.lm.max_trials = o.max_trials;
+    ctl.lm.first = 1;
 
-    // everything on the null stream, in order; the blocking copies wait for the kernels
     mb.run(ar, la, [&] { launch_calib_begin(nullptr, ca); });
-    int passes = 0, trials = 0, accepted = 0;
-    for (int pass = 0; pass <= o.reclassify_passes && ar.err == hipSuccess; ++pass) {
-        ctl.lam = kLamInit;
-        ctl.trials = ctl.accepted = ctl.done = ctl.stop = ctl.solve_ok = 0;
-        ar.copy(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
-        if (pass > 0 && ar.err == hipSuccess)
-            launch_calib_classify(nullptr, ca);
-        // every trial either counts (k_calib_solve stops at max_trials) or sets done
-        for (int64_t t = 0; t <= (int64_t)o.max_trials + 1 && ar.err == hipSuccess; ++t) {
-            launch_calib_trial(nullptr, ca);
-            ar.err = hipGetLastError();
-            ar.copy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost);
-            if (ctl.done)
-                break;
-        }
-        ++passes;
-        trials += ctl.trials;
-        accepted += ctl.accepted;
-        if (ctl.n_used == 0)
-            break;
-    }
-    const int stop = ctl.stop;
-    if (ar.err == hipSuccess && ctl.n_used > 0) {
-        launch_calib_covariance(nullptr, ca);
-        ar.err = hipGetLastError();
-        ar.copy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost);
-    }
+    const ArrowRun run = run_arrow(ar, ctl, d_ctl, o.reclassify_passes, [&] { launch_calib_classify(nullptr, ca); },
+                                   [&] { launch_calib_trial(nullptr, ca); }, [&] { launch_calib_covariance(nullptr, ca); });
+    const int n_used = ctl.lm.n_used;
     mb.results(ar, cam_qt, cam_cov, obs_inlier, res);
-    if (intr_cov && ctl.n_used > 0)
+    if (intr_cov && n_used > 0)
         ar.copy(intr_cov, d_intr_cov, 8 * 81, hipMemcpyDeviceToHost);
     if (ar.err != hipSuccess)
         return hip_failure(who, "", ar.err);
-    if (ctl.n_used == 0) {   // no image was localised well enough to take part: cam_cov holds the localisation's
+    if (n_used == 0) {   // no image was localised well enough to take part: cam_cov holds the localisation's
         if (cam_cov)
             memset(cam_cov, 0, sizeof(double) * 36 * ni);
         empty_report(rep, VMM_BA_CAL_NO_IMAGES, elapsed());
         if (rep)
-            rep->passes = passes;
+            rep->passes = run.passes;
         return VMM_BA_OK;
     }
     bool finite = true;
@@ -199,18 +157,8 @@ int vmm_ba_calibrate(const double intr0[4], const double dist0[5], int32_t n_tag
         for (int i = 0; i < 9; ++i)
             (i < 4 ? intr[i] : dist[i - 4]) = ctl.k[i];
     if (rep) {
-        memset(rep, 0, sizeof(*rep));
-        rep->status = !ctl.cov_ok ? VMM_BA_CAL_SINGULAR : (stop == 2 || !finite ? VMM_BA_CAL_NO_CONVERGENCE : VMM_BA_CAL_OK);
-        rep->trials = trials;
-        rep->accepted = accepted;
-        rep->passes = passes;
-        rep->n_images_used = ctl.n_used;
-        rep->n_obs_used = ctl.n_obs_used;
-        rep->initial_cost = finite_or_zero(0.5 * ctl.initial_cost);
-        rep->final_cost = finite_or_zero(0.5 * ctl.cost);
-        rep->initial_rms_px = ctl.initial_n_obs > 0 ? finite_or_zero(sqrt(ctl.initial_raw2 / (4.0 * ctl.initial_n_obs))) : 0.0;
-        rep->final_rms_px = ctl.n_obs_used > 0 ? finite_or_zero(sqrt(ctl.raw2 / (4.0 * ctl.n_obs_used))) : 0.0;
-        rep->time_s = elapsed();
+        fill_arrow_report(rep, ctl.lm, run, finite, elapsed());
+        rep->n_images_used = n_used;
     }
     return VMM_BA_OK;
 }

@@ -454,6 +454,34 @@ struct MapBatch {
     }
     void results(Arena& ar, double* cam_qt, double* cam_cov, uint8_t* obs_inlier, vmm_ba_localize_result* res_out) const;
 };
+// arrowhead.hpp: what the two joint refinements against a fixed map share (vmm_ba_calibrate: the camera model and one pose
+// per image; vmm_ba_rig_calibrate: the extrinsics and one rig pose per frame).  An item is an image or a frame, P the
+// number of shared unknowns (9; 6 n_rig_cams).
+// An item's record: reduced P x P block (packed lower) | reduced gradient (P) | diag(C) (P) | cost | sum |r|^2 | 1 if
+// A + lam diag was not positive definite | inlier observations | 1 (the item takes part); all zero for one that does not
+__host__ __device__ constexpr int arrow_rec_doubles(int P) { return P * (P + 1) / 2 + 2 * P + 5; }
+// An item's elimination: L (21, packed lower) | Y = L^-1 B (6 x P) | y = L^-1 g (6)
+__host__ __device__ constexpr int arrow_elim_doubles(int P) { return 27 + 6 * P; }
+struct ArrowCtl {                    // the control block of the LM loop behind the shared unknowns' current, candidate, step
+    double lam, cost, raw2;          // damping; sum rho and sum |r|^2 over the inliers at the current state
+    double initial_cost, initial_raw2;
+    int32_t refine_mask, max_trials;
+    int32_t trials, accepted;
+    int32_t done, stop;              // done: every kernel returns at once; stop: 1 converged, 2 max_trials ran out
+    int32_t solve_ok, first;         // first: the next evaluation is the start of the whole call (initial_*)
+    int32_t n_used, n_obs_used;      // items that take part, their inlier observations
+    int32_t cov_ok, initial_n_obs;
+};
+struct ArrowArgs {                   // n: the number of items
+    double* cand;                    // [7 * n] candidate poses
+    int32_t* part;                   // [n] the item takes part
+    int32_t* n_in;                   // [n] its inlier observations
+    double* rec;                     // [arrow_rec_doubles(P) * n]
+    double* elim;                    // [arrow_elim_doubles(P) * n]
+    double* trial;                   // [2 * n] candidate cost | max |pose step|
+    int robustify, min_inliers;
+    double huber_a, inlier2;
+};
 // kernels_rig.hip: a rig of rigidly mounted cameras against a fixed map (vmm_ba_rig_localize)
 struct RigArgs {
     LocalizeArgs loc;          // per frame what it holds per image: n_imgs frames, img_start [n_rig_cams * n_imgs + 1] (image
@@ -464,36 +492,19 @@ struct RigArgs {
     const double* ext_qt;      // [7 * n_rig_cams] rig->camera
 };
 void launch_rig_localize(hipStream_t st, const RigArgs& a);
-// the joint refinement of the extrinsics and one rig pose per frame (vmm_ba_rig_calibrate); P = 6 n_rig_cams
+// the joint refinement of the extrinsics and one rig pose per frame (vmm_ba_rig_calibrate); P = 6 n_rig_cams.  The
+// control block's common part, the per-frame buffers and the record layouts are the arrowhead's (above)
 constexpr int kRigDof = 6 * VMM_BA_RIG_MAX_CAMS;
-__host__ __device__ constexpr int rig_rec_doubles(int P) { return P * (P + 1) / 2 + 2 * P + 5; }   // a frame's record: reduced P x P block (packed
-                               // lower) | reduced gradient (P) | diag(C) (P) | cost | sum |r|^2 | 1 if A + lam diag was not
-                               // positive definite | inlier observations | 1 (the frame takes part); zero for one that does not
-__host__ __device__ constexpr int rig_elim_doubles(int P) { return 27 + 6 * P; }   // a frame's elimination: L (21) | Y = L^-1 B (6 x P) | y = L^-1 g (6)
-struct RigCalCtl {             // control block of the LM loop, as CalibCtl
-    double ext[7 * VMM_BA_RIG_MAX_CAMS], ext_cand[7 * VMM_BA_RIG_MAX_CAMS], dext[kRigDof];
-    double lam, cost, raw2;
-    double initial_cost, initial_raw2;
-    int32_t refine_mask, max_trials;
-    int32_t trials, accepted;
-    int32_t done, stop;              // done: every kernel returns at once; stop: 1 converged, 2 max_trials ran out
-    int32_t solve_ok, first;
-    int32_t n_used, n_obs_used;
-    int32_t cov_ok, initial_n_obs;
+struct RigCalCtl {
+    double ext[7 * VMM_BA_RIG_MAX_CAMS], ext_cand[7 * VMM_BA_RIG_MAX_CAMS], dext[kRigDof];   // current, candidate, step
+    ArrowCtl lm;
 };
 struct RigCalArgs {
     RigArgs rig;                   // the batch; loc.cam_qt: current rig poses, loc.obs_inlier: the inlier set of the refinement,
                                    // loc.res: the localisation's results, loc.cam_cov: the joint marginals; ext_qt is not used
                                    // (the extrinsics are RigCalCtl's)
-    double* rig_cand;              // [7 * n_frames]
-    int32_t* part;                 // [n_frames] the frame takes part
-    int32_t* n_in;                 // [n_frames] its inlier observations
-    double* rec;                   // [rig_rec_doubles(P) * n_frames]
-    double* elim;                  // [rig_elim_doubles(P) * n_frames]
-    double* trial;                 // [2 * n_frames] candidate cost | max |rig step|
+    ArrowArgs w;                   // per frame; P = 6 n_rig_cams
     RigCalCtl* ctl;
-    int robustify, min_inliers;
-    double huber_a, inlier2;
     double* ext_cov;               // [P * P]
 };
 void launch_rigcal_begin(hipStream_t st, const RigCalArgs& a);
@@ -523,20 +534,11 @@ void launch_cam_frames(hipStream_t st, int n_cams, const double* cam_qt, double*
 void launch_triangulate(hipStream_t st, const TriangulateArgs& a);
 int preload_triangulate_kernels();
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
-constexpr int kCalRec = 68;    // doubles of an image's record: reduced 9 x 9 block (45, packed lower) | reduced gradient (9) |
-                               // diag(C) (9) | cost | sum |r|^2 | 1 if A + lam diag was not positive definite | inlier
-                               // observations | 1 (the image takes part); all zero for an image that takes no part
-constexpr int kCalElim = 84;   // doubles of an image's elimination: L (21, packed lower) | Y = L^-1 B (6 x 9) | y = L^-1 g (6)
+constexpr int kCalRec = arrow_rec_doubles(9);     // 68
+constexpr int kCalElim = 84;                        // the stride of an image's elimination: arrow_elim_doubles(9) = 81 of it are used
 struct CalibCtl {              // control block of the LM loop: k_calib_solve and k_calib_control write it, the host polls it
     double k[9], k_cand[9], dk[9];   // (fx, fy, cx, cy, k1, k2, p1, p2, k3): current, candidate, step
-    double lam, cost, raw2;          // damping; sum rho and sum |r|^2 over the inliers at the current state
-    double initial_cost, initial_raw2;
-    int32_t refine_mask, max_trials;
-    int32_t trials, accepted;
-    int32_t done, stop;              // done: every kernel returns at once; stop: 1 converged, 2 max_trials ran out
-    int32_t solve_ok, first;         // first: the next evaluation is the start of the whole call (initial_*)
-    int32_t n_used, n_obs_used;      // images that take part, their inlier observations
-    int32_t cov_ok, initial_n_obs;
+    ArrowCtl lm;
 };
 struct CalibArgs {
     int n_imgs;
@@ -547,15 +549,8 @@ struct CalibArgs {
     uint8_t* flags;                // [n_obs] the inlier set of the refinement
     vmm_ba_localize_result* res;   // [n_imgs] the localisation's results; k_calib_cov_pose updates the images that took part
     double* cam_qt;                // [7 * n_imgs] current poses
-    double* cam_cand;              // [7 * n_imgs] candidates
-    int32_t* part;                 // [n_imgs] the image takes part
-    int32_t* n_in;                 // [n_imgs] its inlier observations
-    double* rec;                   // [kCalRec * n_imgs]
-    double* elim;                  // [kCalElim * n_imgs]
-    double* trial;                 // [2 * n_imgs] candidate cost | max |pose step|
+    ArrowArgs w;                   // per image; P = 9
     CalibCtl* ctl;
-    int robustify, min_inliers;
-    double huber_a, inlier2;
     double* intr_cov;              // [81]
     double* cam_cov;               // [36 * n_imgs]
 };

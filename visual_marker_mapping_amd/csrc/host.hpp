@@ -1,12 +1,16 @@
 // What the host files of libvmm_ba.so share (vmm_ba.hip, covariance.hip, selfcal.hip, initialize.hip, standalone.hip,
-// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip).  No device code; no kernels_*.hip includes this.
+// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip).  No kernel; no kernels_*.hip includes this.
 #pragma once
 
 #include <algorithm>
 #include <initializer_list>
 #include <string>
 
+#include <math.h>
+#include <string.h>
+
 #include "engine.hpp"
+#include "pose_lm.hpp"
 
 namespace vmm {
 
@@ -61,5 +65,94 @@ int check_localize_options(const char* who, const vmm_ba_localize_options& o);
 void fill_no_observations(int32_t n_imgs, double* cam_qt, double* cam_cov, vmm_ba_localize_result* res);
 // hipSetDevice, and on an entry point's first call on a device every preload_* of `preload` (`done`: the caller's flags)
 int select_device(const char* who, int device, bool (&done)[64], std::initializer_list<int (*)()> preload);
+
+// ---- the host side of an arrowhead refinement (arrowhead.hpp), shared by calibrate.hip and rig.hip ----
+// the options both calibrations have; `who` as above
+template <typename Options>
+int check_arrow_options(const char* who, const Options& o)
+{
+    if (o.max_trials < 0 || o.reclassify_passes < 0 || o.min_inlier_tags < 1 || !(o.huber_a > 0.0) || !(o.inlier_px > 0.0)
+        || !isfinite(o.huber_a) || !isfinite(o.inlier_px))
+        return bad_argument(who, "bad options");
+    return VMM_BA_OK;
+}
+// the options' part of ArrowArgs; the buffers are the caller's
+template <typename Options>
+void set_arrow_options(ArrowArgs& w, const Options& o)
+{
+    w.robustify = o.robustify != 0;
+    w.min_inliers = o.min_inlier_tags;
+    w.huber_a = o.huber_a;
+    w.inlier2 = o.inlier_px * o.inlier_px;
+}
+struct ArrowRun {
+    int passes = 0, trials = 0, accepted = 0, stop = 0;
+};
+// The refinement from the first trial to the covariances, on the null stream, in order; the blocking copies wait for the
+// kernels.  Per pass: the control block (ctl: the shared unknowns and refine_mask, max_trials, first set by the caller)
+// goes up, from the second pass on classify() flags the observations anew, and trial() runs until the block comes back
+// done.  Then covariance(), unless no item takes part.  ctl holds the device's last block at the end; errors go to ar.err.
+template <typename Ctl, typename Classify, typename Trial, typename Covariance>
+ArrowRun run_arrow(Arena& ar, Ctl& ctl, Ctl* d_ctl, int reclassify_passes, Classify&& classify, Trial&& trial,
+                   Covariance&& covariance)
+{
+    ArrowRun r;
+    ArrowCtl& c = ctl.lm;
+    for (int pass = 0; pass <= reclassify_passes && ar.err == hipSuccess; ++pass) {
+        c.lam = kLamInit;
+        c.trials = c.accepted = c.done = c.stop = c.solve_ok = 0;
+        ar.copy(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
+        if (pass > 0 && ar.err == hipSuccess)
+            classify();
+        // every trial either counts (the solve kernel stops at max_trials) or sets done
+        for (int64_t t = 0; t <= (int64_t)c.max_trials + 1 && ar.err == hipSuccess; ++t) {
+            trial();
+            ar.err = hipGetLastError();
+            ar.copy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost);
+            if (c.done)
+                break;
+        }
+        ++r.passes;
+        r.trials += c.trials;
+        r.accepted += c.accepted;
+        if (c.n_used == 0)
+            break;
+    }
+    r.stop = c.stop;
+    if (ar.err == hipSuccess && c.n_used > 0) {
+        covariance();
+        ar.err = hipGetLastError();
+        ar.copy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost);
+    }
+    return r;
+}
+// a report that says `status` and nothing else (rep may be null)
+template <typename Report>
+void empty_report(Report* rep, int status, double time_s)
+{
+    if (!rep)
+        return;
+    memset(rep, 0, sizeof(*rep));
+    rep->status = status;
+    rep->time_s = time_s;
+}
+inline double finite_or_zero(double v) { return isfinite(v) ? v : 0.0; }
+// The report of a refinement in which items took part, but for the number of them (n_images_used / n_frames_used) and
+// what else is the entry's own.  finite: the shared unknowns came back finite.
+template <typename Report>
+void fill_arrow_report(Report* rep, const ArrowCtl& c, const ArrowRun& r, bool finite, double time_s)
+{
+    memset(rep, 0, sizeof(*rep));
+    rep->status = !c.cov_ok ? VMM_BA_CAL_SINGULAR : (r.stop == 2 || !finite ? VMM_BA_CAL_NO_CONVERGENCE : VMM_BA_CAL_OK);
+    rep->trials = r.trials;
+    rep->accepted = r.accepted;
+    rep->passes = r.passes;
+    rep->n_obs_used = c.n_obs_used;
+    rep->initial_cost = finite_or_zero(0.5 * c.initial_cost);
+    rep->final_cost = finite_or_zero(0.5 * c.cost);
+    rep->initial_rms_px = c.initial_n_obs > 0 ? finite_or_zero(sqrt(c.initial_raw2 / (4.0 * c.initial_n_obs))) : 0.0;
+    rep->final_rms_px = c.n_obs_used > 0 ? finite_or_zero(sqrt(c.raw2 / (4.0 * c.n_obs_used))) : 0.0;
+    rep->time_s = time_s;
+}
 
 } // namespace vmm

@@ -17,7 +17,9 @@
 // frame: a step (dt, dtheta) of the rig moves camera c by (R_c dt, R_c dtheta), so both halves of a row are multiplied
 // by R_c from the right.
 // The solver (lm_refine, solve6, inverse6, better / wave_winner, chain_camera / chain_tag) is pose_lm.hpp's and the
-// reductions and the stores of a result are image_sums.hpp's, as in k_localize.  The K camera models and extrinsics
+// reductions and the stores of a result are image_sums.hpp's, as in k_localize.  The localisation's body and its four
+// per-observation loops stay a copy of kernels_localize.hip's with the camera looked up per observation: as one
+// template over both (tried: DESIGN.md section 9) the same arithmetic compiled to other bits.  The K camera models and extrinsics
 // (21 doubles each) are expanded into LDS once per workgroup; a thread reads the ones of its observation's camera from
 // there, so nothing is indexed at run time in registers.  Pixels and world corners are read from global memory (the
 // view k_localize<false> uses): a frame is read by its own workgroup only and stays in the CU's cache, and one code
@@ -31,8 +33,7 @@
 // segment; one 256-thread workgroup per CU, as k_localize.
 #include <limits.h>
 
-#include "engine.hpp"
-#include "image_sums.hpp"
+#include "arrowhead.hpp"
 
 namespace vmm {
 
@@ -372,8 +373,10 @@ __global__ __launch_bounds__(kImageThreads) void k_rig_localize(const RigArgs ra
 }
 
 // ---- vmm_ba_rig_calibrate: the extrinsics and one rig pose per frame, refined together ---------------------------------
-// The arrowhead of kernels_calibrate.hip with the 6 K extrinsic parameters in the place of the camera model: every frame
-// eliminates its own 6 x 6 block and what is left is P x P, P = 6 K.  One Levenberg-Marquardt trial:
+// The arrowhead of arrowhead.hpp with the 6 K extrinsic parameters as the shared unknowns: every frame eliminates its own
+// 6 x 6 block and what is left is P x P, P = 6 K.  What the kernels below share with kernels_calibrate.hip is that
+// header's (the list is at its top); their own: one corner's 2 x 12 rows, spreading a camera's sums over the frame's
+// blocks, and the P x P system in LDS.  One Levenberg-Marquardt trial:
 //   k_rigcal_frame    workgroup = frame.  An observation touches the rig pose and ONE extrinsic, so the frame's sums are
 //                     formed camera by camera as 12 x 12 packed blocks (78 + 12 + 2 sums: thread-private in list order,
 //                     one butterfly per wave -- wave_sum32, three times --, the waves in order through LDS) and spread
@@ -384,7 +387,7 @@ __global__ __launch_bounds__(kImageThreads) void k_rig_localize(const RigArgs ra
 //                     inlier observation, P x P Cholesky in LDS (every entry's updates in column order), the step and
 //                     the candidate extrinsics
 //   k_rigcal_try      workgroup = frame: d rig = -L^-T (y + Y d ext), candidate pose, cost-only pass at the candidates
-//   k_rigcal_control  one workgroup: lm_refine's accept / stop rules on the whole problem
+//   k_rigcal_control  one workgroup: lm_refine's accept / stop rules on the whole problem (arrow_control)
 // At the result k_rigcal_frame and k_rigcal_solve run once more with lam = 0 (cov_mode): S^-1 = ext_cov, and
 // k_rigcal_cov_pose forms rig_cov_f = L^-T (I + Y S^-1 Y') L^-1.  Every sum has a fixed order; the sum over the frames
 // makes the bits depend on the order of the batch.
@@ -394,27 +397,14 @@ __global__ __launch_bounds__(kImageThreads) void k_rig_localize(const RigArgs ra
 //   k_rigcal_try          152          0                  0
 //   k_rigcal_classify 100, k_rigcal_cov_pose 86, k_rigcal_control 18, k_rigcal_begin 6: no spill, no private segment
 
-constexpr int kRcSums = 92;     // 78 (12 x 12 packed lower: rig 0..5, extrinsic 6..11) + 12 gradient + cost + sum |r|^2
-constexpr int kRcChunks = 3;    // wave_sum32 calls that cover them
+using RcSums = Wide<12>;        // 92 sums: 78 (12 x 12 packed lower: rig 0..5, extrinsic 6..11) + 12 gradient + cost + sum |r|^2
 constexpr int kRcThreads = kImageThreads;
 
-// row of packed-lower entry e (tri6 indexing)
-__device__ __forceinline__ int packed_row(const int e)
-{
-    int r = 0;
-    while (tri6(r + 1, 0) <= e)
-        ++r;
-    return r;
-}
+static_assert(RcSums::kSums == 92 && RcSums::kChunks == 3, "the layout k_rigcal_frame spreads");
 
 __global__ __launch_bounds__(64) void k_rigcal_begin(const RigCalArgs a)
 {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.rig.loc.n_imgs)
-        return;
-    const vmm_ba_localize_result r = a.rig.loc.res[p];
-    a.n_in[p] = r.n_inlier_obs;
-    a.part[p] = r.status == VMM_BA_LOC_OK && r.n_inlier_obs >= a.min_inliers;
+    arrow_begin(a.w, a.rig.loc.res, a.rig.loc.n_imgs);
 }
 
 // workgroup = frame: the localisation's classification under the current extrinsics, for the localised frames
@@ -429,11 +419,11 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_classify(const RigCalArgs
         return;
     const RigView f = open_frame(a.rig, a.ctl->ext, p, s_model, s_end);
     __syncthreads();
-    const int n = classify_frame(f, la.cam_qt + 7 * (int64_t)p, a.inlier2,
+    const int n = classify_frame(f, la.cam_qt + 7 * (int64_t)p, a.w.inlier2,
                                  la.obs_inlier + la.img_start[(int64_t)p * a.rig.n_rig_cams], s_cnt);
     if (threadIdx.x == 0) {
-        a.n_in[p] = n;
-        a.part[p] = n >= a.min_inliers;
+        a.w.n_in[p] = n;
+        a.w.part[p] = n >= a.w.min_inliers;
     }
 }
 
@@ -444,14 +434,9 @@ __device__ __forceinline__ void camera_normal_sums(const RigView& f, const uint8
                                                    const bool free_c, const bool robust, const double huber_a, double* s_red,
                                                    double* s_tot)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double acc[kRcChunks][32];
-#pragma unroll
-    for (int h = 0; h < kRcChunks; ++h)
-#pragma unroll
-        for (int k = 0; k < 32; ++k)
-            acc[h][k] = 0.0;
-#define VMM_ACC(i) acc[(i) >> 5][(i) & 31]
+    const int tid = threadIdx.x;
+    RcSums sums;
+    sums.zero();
     const Intrinsics K = f.intrinsics(c);
     Rigid ext, cam;
     f.extrinsic(c, ext);
@@ -489,53 +474,31 @@ __device__ __forceinline__ void camera_normal_sums(const RigView& f, const uint8
             }
             ru *= wgt;
             rv *= wgt;
-            VMM_ACC(90) += rho0;
-            VMM_ACC(91) += s;
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                VMM_ACC(78 + i) += J[0][i] * ru + J[1][i] * rv;
-#pragma unroll
-                for (int e = 0; e <= i; ++e)
-                    VMM_ACC(tri6(i, e)) += J[0][i] * J[0][e] + J[1][i] * J[1][e];
-            }
+            sums.add(J, ru, rv, rho0, s);
         }
     }
-#undef VMM_ACC
-#pragma unroll
-    for (int h = 0; h < kRcChunks; ++h) {
-        const double tot = wave_sum32(acc[h], lane);
-        s_red[(wave * kRcChunks + h) * 32 + wave_sum32_index(lane)] = tot;   // lanes 2 m and 2 m + 1 store the same value
-    }
-    __syncthreads();
-    if (tid < kRcSums) {
-        double t = s_red[tid];
-#pragma unroll
-        for (int w = 1; w < kImageWaves; ++w)
-            t += s_red[w * 32 * kRcChunks + tid];
-        s_tot[tid] = t;
-    }
-    __syncthreads();
+    sums.reduce(s_red, s_tot);
 }
 
 __global__ __launch_bounds__(kRcThreads) void k_rigcal_frame(const RigCalArgs a, const int cov_mode)
 {
     __shared__ double s_model[kRigModel * VMM_BA_RIG_MAX_CAMS];
     __shared__ int s_end[VMM_BA_RIG_MAX_CAMS];
-    __shared__ double s_red[kImageWaves * 32 * kRcChunks];
-    __shared__ double s_tot[32 * kRcChunks];
+    __shared__ double s_red[kImageWaves * 32 * RcSums::kChunks];
+    __shared__ double s_tot[32 * RcSums::kChunks];
     __shared__ double s_A[21], s_g[6], s_stat[2], s_L[21];
     __shared__ double s_B[6][kRigDof], s_C[VMM_BA_RIG_MAX_CAMS][21], s_gk[kRigDof];
     __shared__ double s_Y[6][kRigDof + 1];   // column P: y
     __shared__ int s_bad;
     const RigCalCtl* const ctl = a.ctl;
-    if (!cov_mode && ctl->done)
+    if (!cov_mode && ctl->lm.done)
         return;
     const LocalizeArgs& la = a.rig.loc;
     const int tid = threadIdx.x, p = blockIdx.x, n_cams = a.rig.n_rig_cams;
-    const int P = 6 * n_cams, T = P * (P + 1) / 2, n_rec = rig_rec_doubles(P), n_el = rig_elim_doubles(P);
-    double* const rec = a.rec + n_rec * (int64_t)p;
-    double* const el = a.elim + n_el * (int64_t)p;
-    if (!a.part[p]) {
+    const int P = 6 * n_cams, n_rec = arrow_rec_doubles(P), n_el = arrow_elim_doubles(P);
+    double* const rec = a.w.rec + n_rec * (int64_t)p;
+    double* const el = a.w.elim + n_el * (int64_t)p;
+    if (!a.w.part[p]) {
         for (int e = tid; e < n_rec; e += kRcThreads)
             rec[e] = 0.0;
         return;
@@ -549,11 +512,11 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_frame(const RigCalArgs a,
         s_stat[tid] = 0.0;
     __syncthreads();
     const uint8_t* const flags = la.obs_inlier + la.img_start[(int64_t)p * n_cams];
-    const int mask = ctl->refine_mask;
+    const int mask = ctl->lm.refine_mask;
     Rigid rig;
     load_rigid<true>(la.cam_qt + 7 * (int64_t)p, rig);
     for (int c = 0; c < n_cams; ++c) {
-        camera_normal_sums(f, flags, c, rig, (mask >> c) & 1, a.robustify != 0, a.huber_a, s_red, s_tot);
+        camera_normal_sums(f, flags, c, rig, (mask >> c) & 1, a.w.robustify != 0, a.w.huber_a, s_red, s_tot);
         // every LDS entry below has one writer per camera
         if (tid < 78) {
             const int i = packed_row(tid), j = tid - tri6(i, 0);
@@ -573,89 +536,22 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_frame(const RigCalArgs a,
         }
         __syncthreads();
     }
-    // L = chol(A + lam diag(max(A_ii, 1e-12))), as solve6 damps
-    if (tid == 0) {
-        const double lam = cov_mode ? 0.0 : ctl->lam;
-        double L[21];
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const double ajj = s_A[tri6(j, j)];
-            double d = ajj + lam * (ajj > 1e-12 ? ajj : 1e-12);
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                d -= L[tri6(j, k)] * L[tri6(j, k)];
-            ok = ok && d > 0.0 && finite_bits(d);
-            const double sq = sqrt(d);
-            L[tri6(j, j)] = sq;
-            const double is = 1.0 / sq;
-#pragma unroll
-            for (int i = j + 1; i < 6; ++i) {
-                double v = s_A[tri6(i, j)];
-#pragma unroll
-                for (int k = 0; k < j; ++k)
-                    v -= L[tri6(i, k)] * L[tri6(j, k)];
-                L[tri6(i, j)] = v * is;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 21; ++k)
-            s_L[k] = L[k];
-        s_bad = ok ? 0 : 1;
-    }
+    if (tid == 0)
+        s_bad = damped_chol6(s_A, cov_mode ? 0.0 : ctl->lm.lam, s_L) ? 0 : 1;
     __syncthreads();
     // column c of Y = L^-1 B (c < P) and y = L^-1 g (c == P)
-    if (tid <= P) {
-        double col[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double v = tid < P ? s_B[i][tid] : s_g[i];
-#pragma unroll
-            for (int k = 0; k < i; ++k)
-                v -= s_L[tri6(i, k)] * col[k];
-            col[i] = v / s_L[tri6(i, i)];
-            s_Y[i][tid] = col[i];
-        }
-    }
+    if (tid <= P)
+        forward_column6(s_L, [&](const int i) { return tid < P ? s_B[i][tid] : s_g[i]; }, &s_Y[0][tid], kRigDof + 1);
     __syncthreads();
-    for (int e = tid; e < n_rec; e += kRcThreads) {
-        double v;
-        if (e < T) {   // C - Y'Y, packed lower; C is block-diagonal
-            const int i = packed_row(e), j = e - tri6(i, 0);
-            v = i / 6 == j / 6 ? s_C[i / 6][tri6(i % 6, j % 6)] : 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                v -= s_Y[k][i] * s_Y[k][j];
-        } else if (e < T + P) {   // g_e - Y'y
-            const int c = e - T;
-            v = s_gk[c];
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                v -= s_Y[k][c] * s_Y[k][P];
-        } else if (e < T + 2 * P) {
-            const int c = e - T - P;
-            v = s_C[c / 6][tri6(c % 6, c % 6)];
-        } else {
-            const int k = e - T - 2 * P;
-            v = k == 0 ? s_stat[0] : k == 1 ? s_stat[1] : k == 2 ? (s_bad ? 1.0 : 0.0) : k == 3 ? (double)a.n_in[p] : 1.0;
-        }
-        rec[e] = v;
-    }
-    for (int e = tid; e < n_el; e += kRcThreads) {
-        double v;
-        if (e < 21)
-            v = s_L[e];
-        else if (e < 21 + 6 * P)
-            v = s_Y[(e - 21) / P][(e - 21) % P];
-        else
-            v = s_Y[e - 21 - 6 * P][P];
-        el[e] = v;
-    }
+    const double cost = s_stat[0], raw2 = s_stat[1];
+    const bool bad = s_bad != 0;
+    const int n_in = a.w.n_in[p];
+    for (int e = tid; e < n_rec; e += kRcThreads)   // C is block-diagonal
+        rec[e] = arrow_record_entry(e, P, [&](const int i, const int j) { return i / 6 == j / 6 ? s_C[i / 6][tri6(i % 6, j % 6)] : 0.0; },
+                                    [&](const int c) { return s_gk[c]; }, &s_Y[0][0], kRigDof + 1, cost, raw2, bad, n_in);
+    for (int e = tid; e < n_el; e += kRcThreads)
+        el[e] = arrow_elim_entry(e, P, s_L, &s_Y[0][0], kRigDof + 1);
 }
-
-// As kernels_calibrate.hip's: a pivot of the undamped S, scaled by diag(sum C), within a factor 100 of its rounding
-// noise is taken for the zero of a singular matrix.
-constexpr double kRcMinPivot = 1e-13;
 
 __global__ __launch_bounds__(kRcThreads) void k_rigcal_solve(const RigCalArgs a, const int cov_mode)
 {
@@ -666,60 +562,34 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_solve(const RigCalArgs a,
     __shared__ int s_act[kRigDof];
     __shared__ int s_go, s_ok;
     RigCalCtl* const ctl = a.ctl;
-    if (!cov_mode && ctl->done)
+    if (!cov_mode && ctl->lm.done)
         return;
     const int tid = threadIdx.x, n_cams = a.rig.n_rig_cams, n_frames = a.rig.loc.n_imgs;
-    const int P = 6 * n_cams, T = P * (P + 1) / 2, n_rec = rig_rec_doubles(P);
+    const int P = 6 * n_cams, T = P * (P + 1) / 2, n_rec = arrow_rec_doubles(P);
     for (int e = tid; e < n_rec; e += kRcThreads) {
         double t[4] = { 0.0, 0.0, 0.0, 0.0 };
         for (int i = 0; i < n_frames; i += 4)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 if (i + g < n_frames)
-                    t[g] += a.rec[n_rec * (int64_t)(i + g) + e];
+                    t[g] += a.w.rec[n_rec * (int64_t)(i + g) + e];
         s_tot[e] = ((t[0] + t[1]) + t[2]) + t[3];
     }
     __syncthreads();
-    const double* const st = s_tot + T + 2 * P;   // cost | raw2 | bad frames | inlier observations | frames
-    const double lam = cov_mode ? 0.0 : ctl->lam;
+    const double* const st = s_tot + arrow_rec_stat(P);
+    const double lam = cov_mode ? 0.0 : ctl->lm.lam;
     if (tid == 0) {
-        const double cost = st[0], raw2 = st[1];
-        const int n_used = (int)st[4], n_obs_used = (int)st[3];
-        int go = 1;
-        ctl->cost = cost;
-        ctl->raw2 = raw2;
-        ctl->n_used = n_used;
-        ctl->n_obs_used = n_obs_used;
-        if (ctl->first) {
-            ctl->first = 0;
-            ctl->initial_cost = cost;
-            ctl->initial_raw2 = raw2;
-            ctl->initial_n_obs = n_obs_used;
-        }
-        if (!cov_mode) {
-            if (n_used == 0 || !finite_bits(cost) || lam > kLamMax) {
-                ctl->done = 1;
-                ctl->stop = 1;
-                go = 0;
-            } else if (ctl->trials >= ctl->max_trials) {
-                ctl->done = 1;
-                ctl->stop = 2;
-                go = 0;
-            } else {
-                ctl->trials += 1;
-            }
-        }
-        s_go = go;
+        s_go = arrow_solve_begin(ctl->lm, st, cov_mode, lam) ? 1 : 0;
         s_ok = st[2] == 0.0 ? 1 : 0;
     }
     __syncthreads();
     if (!s_go)
         return;
     // damp, give the extrinsics that are held or unobserved unit rows, scale to a unit diagonal
-    const int mask = ctl->refine_mask;
+    const int mask = ctl->lm.refine_mask;
     if (tid < P) {
-        const double cjj = s_tot[T + P + tid];
-        const bool act = ((mask >> (tid / 6)) & 1) && s_tot[T + P + 6 * (tid / 6)] > 0.0;
+        const bool act = ((mask >> (tid / 6)) & 1) && s_tot[arrow_rec_diag(P) + 6 * (tid / 6)] > 0.0;
+        const double cjj = s_tot[arrow_rec_diag(P) + tid];
         const double d = act ? s_tot[tri6(tid, tid)] + lam * cjj : 1.0;
         if (!(d > 0.0 && finite_bits(d)))
             s_ok = 0;   // every writer writes 0
@@ -734,7 +604,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_solve(const RigCalArgs a,
     }
     __syncthreads();
     // Cholesky in place, column by column: every entry receives its updates in column order
-    const double min_pivot = cov_mode ? kRcMinPivot : 0.0;
+    const double min_pivot = cov_mode ? kMinPivot : 0.0;
     for (int j = 0; j < P; ++j) {
         if (tid == 0) {
             const double d = s_M[tri6(j, j)];
@@ -782,7 +652,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_solve(const RigCalArgs a,
                 sum += fabs(s_M[e]);
             if (!finite_bits(sum))
                 s_ok = 0;
-            ctl->cov_ok = s_ok;
+            ctl->lm.cov_ok = s_ok;
         }
         __syncthreads();
         const bool ok = s_ok != 0;
@@ -796,7 +666,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_solve(const RigCalArgs a,
     if (tid == 0) {
         bool ok = s_ok != 0;
         for (int i = 0; i < P; ++i) {
-            double v = s_act[i] ? -s_tot[T + i] * s_sc[i] : 0.0;
+            double v = s_act[i] ? -s_tot[arrow_rec_grad(P) + i] * s_sc[i] : 0.0;
             for (int k = 0; k < i; ++k)
                 v -= s_M[tri6(i, k)] * s_z[k];
             s_z[i] = v / s_M[tri6(i, i)];
@@ -819,7 +689,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_solve(const RigCalArgs a,
             for (int k = 0; k < 7; ++k)   // an inactive extrinsic keeps its bits
                 ctl->ext_cand[7 * c + k] = s_act[6 * c] ? cand[k] : ctl->ext[7 * c + k];
         }
-        ctl->solve_ok = ok ? 1 : 0;
+        ctl->lm.solve_ok = ok ? 1 : 0;
     }
 }
 
@@ -829,121 +699,45 @@ __global__ __launch_bounds__(kRcThreads) void k_rigcal_try(const RigCalArgs a)
     __shared__ int s_end[VMM_BA_RIG_MAX_CAMS];
     __shared__ double s_red[kImageWaves];
     const RigCalCtl* const ctl = a.ctl;
-    if (ctl->done || !ctl->solve_ok)
+    if (ctl->lm.done || !ctl->lm.solve_ok)
         return;
     const LocalizeArgs& la = a.rig.loc;
     const int p = blockIdx.x, n_cams = a.rig.n_rig_cams, P = 6 * n_cams;
-    if (!a.part[p]) {
+    if (!a.w.part[p]) {
         if (threadIdx.x == 0)
-            a.trial[2 * p] = a.trial[2 * p + 1] = 0.0;
+            a.w.trial[2 * p] = a.w.trial[2 * p + 1] = 0.0;
         return;
     }
-    const double* const el = a.elim + rig_elim_doubles(P) * (int64_t)p;
-    // d rig = -L^-T (y + Y d ext); every thread computes it
-    double w[6], dp[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double v = el[21 + 6 * P + k];
-        for (int c = 0; c < P; ++c)
-            v += el[21 + P * k + c] * ctl->dext[c];
-        w[k] = v;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = -w[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k)
-            v -= el[tri6(k, i)] * dp[k];
-        dp[i] = v / el[tri6(i, i)];
-    }
-    double cand[7];
+    double dp[6], cand[7];
+    arrow_pose_step(a.w.elim + arrow_elim_doubles(P) * (int64_t)p, P, ctl->dext, dp);
     pose_plus(la.cam_qt + 7 * (int64_t)p, dp, cand);
     const RigView f = open_frame(a.rig, ctl->ext_cand, p, s_model, s_end);
     __syncthreads();
     double A[21], g[6], raw2;   // not filled by the cost-only sum
-    const double cost = frame_sums<false>(f, cand, la.obs_inlier + la.img_start[(int64_t)p * n_cams], a.robustify != 0, a.huber_a,
-                                          s_red, A, g, raw2);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-            a.rig_cand[7 * (int64_t)p + k] = cand[k];
-        a.trial[2 * p] = cost;
-        a.trial[2 * p + 1] = max_abs6(dp);
-    }
+    const double cost = frame_sums<false>(f, cand, la.obs_inlier + la.img_start[(int64_t)p * n_cams], a.w.robustify != 0,
+                                          a.w.huber_a, s_red, A, g, raw2);
+    if (threadIdx.x == 0)
+        arrow_store_trial(a.w, p, cand, cost, dp);
 }
 
-// lm_refine's decision (pose_lm.hpp) on the whole problem.  The step's size: the largest tangent component of any rig
-// pose or extrinsic.
+// arrow_control with the extrinsics' step measured like a pose's: its largest tangent component
 __global__ __launch_bounds__(kRcThreads) void k_rigcal_control(const RigCalArgs a)
 {
     __shared__ double s_sum[kImageWaves], s_max[kImageWaves];
     RigCalCtl* const ctl = a.ctl;
-    if (ctl->done)
-        return;
-    const int tid = threadIdx.x, n_frames = a.rig.loc.n_imgs, n_cams = a.rig.n_rig_cams;
-    if (!ctl->solve_ok) {   // a trial spent on a system that was not positive definite
-        if (tid == 0)
-            ctl->lam *= 10.0;
-        return;
-    }
-    double cc = 0.0, sm = 0.0;
-    for (int i = tid; i < n_frames; i += kRcThreads) {
-        cc += a.trial[2 * i];
-        const double s = a.trial[2 * i + 1];
-        sm = s > sm ? s : sm;
-    }
-    cc = wave_sum(cc);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const double o = __shfl_xor(sm, s, 64);
-        sm = o > sm ? o : sm;
-    }
-    if ((tid & 63) == 0) {
-        s_sum[tid >> 6] = cc;
-        s_max[tid >> 6] = sm;
-    }
-    __syncthreads();
-    cc = s_sum[0];
-    sm = s_max[0];
-#pragma unroll
-    for (int w = 1; w < kImageWaves; ++w) {
-        cc += s_sum[w];
-        sm = s_max[w] > sm ? s_max[w] : sm;
-    }
-    for (int j = 0; j < 6 * n_cams; ++j) {
-        const double s = fabs(ctl->dext[j]);
-        sm = s > sm ? s : sm;
-    }
-    const double cost = ctl->cost, lam = ctl->lam;
-    __syncthreads();   // every thread has read the control block before thread 0 writes it
-    if (sm < 1e-14) {
-        if (tid == 0) {
-            ctl->done = 1;
-            ctl->stop = 1;
-        }
-        return;
-    }
-    if (finite_bits(cc) && cc < cost) {
-        double* const rig_qt = a.rig.loc.cam_qt;
-        for (int i = tid; i < n_frames; i += kRcThreads)
-            if (a.part[i])
-#pragma unroll
-                for (int k = 0; k < 7; ++k)
-                    rig_qt[7 * (int64_t)i + k] = a.rig_cand[7 * (int64_t)i + k];
-        if (tid == 0) {
-            for (int j = 0; j < 7 * n_cams; ++j)
-                ctl->ext[j] = ctl->ext_cand[j];
-            ctl->lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
-            ctl->accepted += 1;
-        }
-    } else if (tid == 0) {
-        if (sm < 1e-10 || cost_at_floor(cost, cc)) {
-            ctl->done = 1;
-            ctl->stop = 1;
-        } else {
-            ctl->lam = lam * 10.0;
-        }
-    }
+    const int n_cams = a.rig.n_rig_cams;
+    arrow_control(a.w, ctl->lm, a.rig.loc.n_imgs, a.rig.loc.cam_qt, s_sum, s_max,
+                  [&](double sm) {
+                      for (int j = 0; j < 6 * n_cams; ++j) {
+                          const double s = fabs(ctl->dext[j]);
+                          sm = s > sm ? s : sm;
+                      }
+                      return sm;
+                  },
+                  [&] {
+                      for (int j = 0; j < 7 * n_cams; ++j)
+                          ctl->ext[j] = ctl->ext_cand[j];
+                  });
 }
 
 // workgroup (one wave) = frame, after k_rigcal_frame and k_rigcal_solve in cov_mode: the joint marginal of the rig pose
@@ -953,24 +747,17 @@ __global__ __launch_bounds__(64) void k_rigcal_cov_pose(const RigCalArgs a)
     __shared__ double s_T[6][kRigDof];   // Y S^-1
     __shared__ double s_Mx[21];
     const LocalizeArgs& la = a.rig.loc;
-    const int tid = threadIdx.x, p = blockIdx.x, P = 6 * a.rig.n_rig_cams, T = P * (P + 1) / 2;
+    const int tid = threadIdx.x, p = blockIdx.x, P = 6 * a.rig.n_rig_cams;
     double* const out = la.cam_cov + 36 * (int64_t)p;
-    if (!a.part[p]) {
+    if (!a.w.part[p]) {
         if (tid < 36)
             out[tid] = 0.0;
         return;
     }
-    const double* const rec = a.rec + rig_rec_doubles(P) * (int64_t)p;
-    const double* const el = a.elim + rig_elim_doubles(P) * (int64_t)p;
-    if (tid == 0) {
-        const int n_in = a.n_in[p];
-        vmm_ba_localize_result r = la.res[p];
-        r.n_inlier_obs = n_in;
-        r.cost = 0.5 * rec[T + 2 * P];
-        r.rms_px = sqrt(rec[T + 2 * P + 1] / (4.0 * n_in));
-        la.res[p] = r;
-    }
-    if (!a.ctl->cov_ok) {
+    const double* const el = a.w.elim + arrow_elim_doubles(P) * (int64_t)p;
+    if (tid == 0)
+        arrow_result_update(la.res, p, a.w.n_in[p], a.w.rec + arrow_rec_doubles(P) * (int64_t)p + arrow_rec_stat(P));
+    if (!a.ctl->lm.cov_ok) {
         if (tid < 36)
             out[tid] = 0.0;
         return;
@@ -979,7 +766,7 @@ __global__ __launch_bounds__(64) void k_rigcal_cov_pose(const RigCalArgs a)
         const int i = e / P, c = e - P * i;
         double v = 0.0;
         for (int d = 0; d < P; ++d)
-            v += el[21 + P * i + d] * a.ext_cov[P * d + c];
+            v += el[arrow_elim_Y(P, i) + d] * a.ext_cov[P * d + c];
         s_T[i][c] = v;
     }
     __syncthreads();
@@ -987,47 +774,17 @@ __global__ __launch_bounds__(64) void k_rigcal_cov_pose(const RigCalArgs a)
         const int i = packed_row(tid), j = tid - tri6(i, 0);
         double v = i == j ? 1.0 : 0.0;
         for (int c = 0; c < P; ++c)
-            v += s_T[i][c] * el[21 + P * j + c];
+            v += s_T[i][c] * el[arrow_elim_Y(P, j) + c];
         s_Mx[tid] = v;
     }
     __syncthreads();
     if (tid != 0)
         return;
-    double M[21], W[21];   // W = L^-1, lower
+    double M[21];
 #pragma unroll
     for (int k = 0; k < 21; ++k)
         M[k] = s_Mx[k];
-    lower_inverse<6>(el, W);
-    // cov = W' M W: Q = M W (full 6 x 6), cov[r][c] = sum_k W[k][r] Q[k][c]
-    double Q[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = c; k < 6; ++k)
-                v += (i >= k ? M[tri6(i, k)] : M[tri6(k, i)]) * W[tri6(k, c)];
-            Q[i][c] = v;
-        }
-    double sum = 0.0, C[21];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = r; k < 6; ++k)
-                v += W[tri6(k, r)] * Q[k][c];
-            C[tri6(r, c)] = v;
-            sum += fabs(v);
-        }
-    const bool ok = finite_bits(sum);
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-            out[6 * r + c] = ok ? (r >= c ? C[tri6(r, c)] : C[tri6(c, r)]) : 0.0;
+    arrow_marginal_store(el, M, out);
 }
 
 } // namespace

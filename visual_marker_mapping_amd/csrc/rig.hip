@@ -2,8 +2,9 @@
 // one image per (frame, camera) slot; its checks, device memory, uploads and k_map_corners are used as they are.
 // RigBatch adds what both entries share: the checks on the rig, the quad poses camera by camera (k_quad_pose takes one
 // camera model per launch, so the observations are sorted by camera for it and their results scattered back),
-// k_rig_localize (kernels_rig.hip) and the copies back per frame.  vmm_ba_rig_calibrate's own: its options and result
-// arguments, six more buffers, and the trial loop of calibrate.hip around the kernels of the joint refinement.
+// k_rig_localize (kernels_rig.hip) and the copies back per frame.  vmm_ba_rig_calibrate's own: its arguments, the mask
+// rules, eight more buffers, the start values and writing back the extrinsics; the trial loop around the kernels of the
+// joint refinement, the check of the common options and the report are host.hpp's, shared with calibrate.hip.
 #include <math.h>
 #include <string.h>
 
@@ -155,17 +156,6 @@ struct RigBatch {
     }
 };
 
-void empty_report(vmm_ba_rig_calibrate_report* rep, int status, double time_s)
-{
-    if (!rep)
-        return;
-    memset(rep, 0, sizeof(*rep));
-    rep->status = status;
-    rep->time_s = time_s;
-}
-
-double finite_or_zero(double v) { return isfinite(v) ? v : 0.0; }
-
 } // namespace
 
 } // namespace vmm
@@ -254,9 +244,8 @@ int vmm_ba_rig_calibrate(int32_t n_rig_cams, const double* intr, const double* d
         return bad_argument(who, "refine_mask has bits at or above n_rig_cams");
     if (o.refine_mask == all)
         return bad_argument(who, "refine_mask frees every camera: at least one extrinsic must be held");
-    if (o.max_trials < 0 || o.reclassify_passes < 0 || o.min_inlier_tags < 1 || !(o.huber_a > 0.0) || !(o.inlier_px > 0.0)
-        || !isfinite(o.huber_a) || !isfinite(o.inlier_px))
-        return bad_argument(who, "bad options");
+    if ((rc = check_arrow_options(who, o)) != VMM_BA_OK)
+        return rc;
     const size_t P = 6 * (size_t)n_rig_cams;
     const auto start_values = [&]() {   // what comes back unless the refinement moves it
         memcpy(ext_qt, ext_qt0, 7 * (size_t)n_rig_cams * sizeof(double));
@@ -293,8 +282,8 @@ int vmm_ba_rig_calibrate(int32_t n_rig_cams, const double* intr, const double* d
             d_cand = a.take<double>(7 * nf);
             d_part = a.take<int32_t>(nf);
             d_n_in = a.take<int32_t>(nf);
-            d_rec = a.take<double>((size_t)rig_rec_doubles((int)P) * nf);
-            d_elim = a.take<double>((size_t)rig_elim_doubles((int)P) * nf);
+            d_rec = a.take<double>((size_t)arrow_rec_doubles((int)P) * nf);
+            d_elim = a.take<double>((size_t)arrow_elim_doubles((int)P) * nf);
             d_trial = a.take<double>(2 * nf);
             d_ctl = a.take<RigCalCtl>(1);
             d_ext_cov = a.take<double>(P * P);
@@ -302,70 +291,42 @@ int vmm_ba_rig_calibrate(int32_t n_rig_cams, const double* intr, const double* d
         return hip_failure(who, "hipMalloc: ", ar.err);
 
     RigCalArgs ca;
-    ca.rig_cand = d_cand;
-    ca.part = d_part;
-    ca.n_in = d_n_in;
-    ca.rec = d_rec;
-    ca.elim = d_elim;
-    ca.trial = d_trial;
+    ca.w.cand = d_cand;
+    ca.w.part = d_part;
+    ca.w.n_in = d_n_in;
+    ca.w.rec = d_rec;
+    ca.w.elim = d_elim;
+    ca.w.trial = d_trial;
+    set_arrow_options(ca.w, o);
     ca.ctl = d_ctl;
-    ca.robustify = o.robustify != 0;
-    ca.min_inliers = o.min_inlier_tags;
-    ca.huber_a = o.huber_a;
-    ca.inlier2 = o.inlier_px * o.inlier_px;
     ca.ext_cov = d_ext_cov;
 
     RigCalCtl ctl;
     memset(&ctl, 0, sizeof(ctl));
     memcpy(ctl.ext, ext_qt0, 7 * (size_t)n_rig_cams * sizeof(double));
     memcpy(ctl.ext_cand, ext_qt0, 7 * (size_t)n_rig_cams * sizeof(double));
-    ctl.refine_mask = o.refine_mask;
-    ctl.max_trials = o.max_trials;
-    ctl.first = 1;
+    ctl.lm.refine_mask = o.refine_mask;
+    ctl.lm.max_trials = o.max_trials;
+    ctl.lm.first = 1;
 
-    // everything on the null stream, in order; the blocking copies wait for the kernels
     ca.rig = rb.run(ar, ext_qt0, o.loc, [&](const RigArgs& a) {
         ca.rig = a;
         launch_rigcal_begin(nullptr, ca);
     });
-    int passes = 0, trials = 0, accepted = 0;
-    for (int pass = 0; pass <= o.reclassify_passes && ar.err == hipSuccess; ++pass) {
-        ctl.lam = kLamInit;
-        ctl.trials = ctl.accepted = ctl.done = ctl.stop = ctl.solve_ok = 0;
-        ar.copy(d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
-        if (pass > 0 && ar.err == hipSuccess)
-            launch_rigcal_classify(nullptr, ca);
-        // every trial either counts (k_rigcal_solve stops at max_trials) or sets done
-        for (int64_t t = 0; t <= (int64_t)o.max_trials + 1 && ar.err == hipSuccess; ++t) {
-            launch_rigcal_trial(nullptr, ca);
-            ar.err = hipGetLastError();
-            ar.copy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost);
-            if (ctl.done)
-                break;
-        }
-        ++passes;
-        trials += ctl.trials;
-        accepted += ctl.accepted;
-        if (ctl.n_used == 0)
-            break;
-    }
-    const int stop = ctl.stop;
-    if (ar.err == hipSuccess && ctl.n_used > 0) {
-        launch_rigcal_covariance(nullptr, ca);
-        ar.err = hipGetLastError();
-        ar.copy(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost);
-    }
+    const ArrowRun run = run_arrow(ar, ctl, d_ctl, o.reclassify_passes, [&] { launch_rigcal_classify(nullptr, ca); },
+                                   [&] { launch_rigcal_trial(nullptr, ca); }, [&] { launch_rigcal_covariance(nullptr, ca); });
+    const int n_used = ctl.lm.n_used;
     rb.results(ar, rig_qt, rig_cov, obs_inlier, res);
-    if (ext_cov && ctl.n_used > 0)
+    if (ext_cov && n_used > 0)
         ar.copy(ext_cov, d_ext_cov, 8 * P * P, hipMemcpyDeviceToHost);
     if (ar.err != hipSuccess)
         return hip_failure(who, "", ar.err);
-    if (ctl.n_used == 0) {   // no frame was localised well enough to take part: rig_cov holds the localisation's
+    if (n_used == 0) {   // no frame was localised well enough to take part: rig_cov holds the localisation's
         if (rig_cov)
             memset(rig_cov, 0, sizeof(double) * 36 * nf);
         empty_report(rep, VMM_BA_CAL_NO_IMAGES, elapsed());
         if (rep)
-            rep->passes = passes;
+            rep->passes = run.passes;
         return VMM_BA_OK;
     }
     bool finite = true;
@@ -379,19 +340,9 @@ int vmm_ba_rig_calibrate(int32_t n_rig_cams, const double* intr, const double* d
         memcpy(ext_qt, ctl.ext, 7 * (size_t)n_rig_cams * sizeof(double));
     }
     if (rep) {
-        memset(rep, 0, sizeof(*rep));
-        rep->status = !ctl.cov_ok ? VMM_BA_CAL_SINGULAR : (stop == 2 || !finite ? VMM_BA_CAL_NO_CONVERGENCE : VMM_BA_CAL_OK);
-        rep->trials = trials;
-        rep->accepted = accepted;
-        rep->passes = passes;
-        rep->n_frames_used = ctl.n_used;
-        rep->n_obs_used = ctl.n_obs_used;
+        fill_arrow_report(rep, ctl.lm, run, finite, elapsed());
+        rep->n_frames_used = n_used;
         rep->cams_refined = cams_refined;
-        rep->initial_cost = finite_or_zero(0.5 * ctl.initial_cost);
-        rep->final_cost = finite_or_zero(0.5 * ctl.cost);
-        rep->initial_rms_px = ctl.initial_n_obs > 0 ? finite_or_zero(sqrt(ctl.initial_raw2 / (4.0 * ctl.initial_n_obs))) : 0.0;
-        rep->final_rms_px = ctl.n_obs_used > 0 ? finite_or_zero(sqrt(ctl.raw2 / (4.0 * ctl.n_obs_used))) : 0.0;
-        rep->time_s = elapsed();
     }
     return VMM_BA_OK;
 }

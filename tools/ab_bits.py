@@ -7,8 +7,9 @@ vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every C
 --cases cov: vmm_ba_tag_translation_covariance (csrc/kernels_cov.hip) after a solve.
 --cases handle: the other entries that work on a handle after a solve (csrc/covariance.hip, selfcal.hip, initialize.hip
 and the evaluation entries of vmm_ba.hip).
+--cases triangulate: vmm_ba_triangulate (csrc/kernels_triangulate.hip, point_lm.hpp).
 
-    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|rig|cov|handle] [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|rig|cov|handle|triangulate] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
@@ -376,6 +377,64 @@ def _handle_cases(eng, make_scene, out):
             out[key + "init_avg_px"] = np.array([report["avg_reprojection_px"]])
 
 
+def _triangulate_cases(eng, out):
+    """Nine points in one batch against 70 cameras on an arc: in k_triangulate a wave is a point, a workgroup has four
+    and the lanes stride a point's views by 64, so nine points make three workgroups, the last with one wave at work.
+    Views per point: 1 (TOO_FEW_VIEWS), 2, 3, 64, 65 and 70 (the second trip of the stride), 70 with a third of its
+    pixels displaced by up to 60 px, 2 along parallel rays (cameras 68 and 69 share their rotation and the point has the
+    same pixel in both: spd3_solve's floor), 3.  max_pair_views 2 and 16, with and without cam_cov, robust and plain, 0
+    and 2 reclassification passes."""
+    from visual_marker_mapping_amd import _lib
+    n_cams = 70
+    rng = np.random.default_rng(4270)
+    phi = np.radians(np.linspace(-60.0, 60.0, n_cams))
+    phi[69] = phi[68]
+    cam_qt = np.zeros((n_cams, 7))
+    R = np.zeros((n_cams, 3, 3))
+    for i, a in enumerate(phi):
+        R[i] = [[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]]
+        centre = -4.0 * R[i, 2] + np.array([0.0, 0.3 * np.sin(7.0 * i), 0.0]) + (i == 69) * 0.5 * R[i, 0]
+        cam_qt[i] = [np.cos(a / 2), 0.0, np.sin(a / 2), 0.0, *(-R[i] @ centre)]
+    views = (1, 2, 3, 64, 65, 70, 70, 2, 3)
+    X = rng.uniform(-0.5, 0.5, (len(views), 3))
+    cams, uvs = [], []
+    for p, m in enumerate(views):
+        c = np.sort(rng.choice(n_cams, m, replace=False)).astype(np.int32)
+        if p == 7:
+            c = np.array([68, 69], np.int32)
+        uv = np.stack([eng.project_points(INTR, DIST, (R[k] @ X[p] + cam_qt[k, 4:])[None])[0] for k in c])
+        uv += rng.normal(size=uv.shape) * 0.3
+        if p == 6:
+            hit = rng.random(uv.shape) < 1.0 / 3.0
+            uv[hit] += rng.uniform(-60.0, 60.0, int(hit.sum()))
+        if p == 7:
+            uv[1] = uv[0]
+        cams.append(c)
+        uvs.append(uv)
+    start = np.concatenate([[0], np.cumsum(views)]).astype(np.int64)
+    cams, uvs = np.concatenate(cams), np.concatenate(uvs)
+    cov_in = np.zeros((n_cams, 6, 6))
+    for i in range(n_cams):
+        m = rng.normal(size=(6, 6)) * 1e-4
+        cov_in[i] = m @ m.T + 1e-8 * np.eye(6)
+    for pair in (2, 16):
+        for with_cov in (0, 1):
+            for robust in (1, 0):
+                for passes in (0, 2):
+                    xyz, cov, cov_cams, inl, res = eng.triangulate(INTR, DIST, cam_qt, start, cams, uvs,
+                                                                   cam_cov=cov_in if with_cov else None, max_pair_views=pair,
+                                                                   robustify=robust, reclassify_passes=passes)
+                    status = [r["status"] for r in res]
+                    # else the scene does not do what the text above says: pick another one
+                    assert status[0] == _lib.TRI_TOO_FEW_VIEWS and status[7] not in (_lib.TRI_OK, _lib.TRI_TOO_FEW_VIEWS), status
+                    assert all(st == _lib.TRI_OK for k, st in enumerate(status) if k not in (0, 7)), status
+                    assert passes == 0 or not inl[start[6]:start[7]].all(), "the displaced pixels of point 6 are all inliers"
+                    key = "tri_pair%d_%s_%s_p%d_" % (pair, "cov" if with_cov else "nocov", "robust" if robust else "plain", passes)
+                    out[key + "xyz"], out[key + "xyz_cov"], out[key + "xyz_cov_cams"], out[key + "inlier"] = xyz, cov, cov_cams, inl
+                    out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
+                    out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
+
+
 def child(path, cases):
     sys.path.insert(0, ROOT)
     from visual_marker_mapping_amd import engine as eng
@@ -394,6 +453,8 @@ def child(path, cases):
         _cov_cases(eng, make_scene, out)
     elif cases == "handle":
         _handle_cases(eng, make_scene, out)
+    elif cases == "triangulate":
+        _triangulate_cases(eng, out)
     else:
         _chol_dense_cases(eng, out)
         _chol_tree_cases(eng, make_scene, out)
@@ -404,7 +465,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
-    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "rig", "cov", "handle"), default="pose", help="which set of cases (default: pose)")
+    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "rig", "cov", "handle", "triangulate"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()

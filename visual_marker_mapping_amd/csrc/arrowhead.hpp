@@ -9,8 +9,9 @@
 // those kernels have in common exists here once; ArrowCtl, ArrowArgs and the sizes of a record are engine.hpp's.
 //   Wide<N>               the thread-private sums of weighted 2 x N row pairs (packed lower J'J, J'r, cost, sum |r|^2)
 //                         and their reduction into LDS: one butterfly per 32 sums and wave (wave_sum32), the waves in order
-//   damped_chol6          L = chol(A + lam diag(max(A_ii, 1e-12))) with its `ok`
-//   forward_column6       one column of Y = L^-1 B or y = L^-1 g
+//   damped_chol6          L = chol(A + lam diag(max(A_ii, 1e-12))) with its `ok`: the damped diagonal in front of
+//                         small_solve.hpp's cholesky<6>, and the copy to LDS
+//   forward_column6       one column of Y = L^-1 B or y = L^-1 g (small_solve.hpp's forward_substitute<6>)
 //   arrow_record_entry / arrow_elim_entry   the layout of an item's record and elimination, entry by entry
 //   arrow_solve_begin     the solve kernel's bookkeeping on the control block; false: nothing to solve
 //   arrow_pose_step       dp = -L^-T (y + Y ds) from an item's elimination
@@ -20,10 +21,12 @@
 //   arrow_begin           who takes part in the first refinement
 // The two factorisations of the reduced system stay apart: chol9 (kernels_calibrate.hip) holds the 9 x 9 matrix in one
 // thread's registers, k_rigcal_solve factors up to 48 x 48 in LDS with a barrier per column.  They are different
-// algorithms for different sizes, and one body for both would change k_calib_solve's speed.  The small Cholesky loops of
-// pose_lm.hpp (solve6, inverse6) keep their own pivot tests as well.  So does the four-line rule in front of the two
-// factorisations (damping by lam C_jj, a unit row for an inactive unknown, the Jacobi scale, the weight S_jj / C_jj): as a
-// function of its own, in any of four shapes, it cost k_calib_solve 55 to 58 registers (167 -> 222 .. 225).
+// algorithms for different sizes, and one body for both would change k_calib_solve's speed.  chol9 is small_solve.hpp's
+// cholesky<9> under its own pivot policy (PivotWeighted), like every other register-resident factorisation here.  The
+// four-line rule in front of the two factorisations stays written out twice (damping by lam C_jj, a unit row for an
+// inactive unknown, the Jacobi scale, the weight S_jj / C_jj): as a function of its own, in any of four shapes, it cost
+// k_calib_solve 55 to 58 registers (167 -> 222 .. 225).  So does the back substitution behind chol9: through
+// backward_substitute<9> one fused multiply-add of k_calib_solve became an add.
 // Every sum has a fixed order and nothing here depends on blockIdx.
 #pragma once
 #include "engine.hpp"
@@ -115,32 +118,20 @@ struct Wide {
     }
 };
 
-// One thread: L = chol(A + lam diag(max(A_ii, 1e-12))), as solve6 damps, into s_L; A packed lower.  false: a pivot was
+// One thread: L = chol(A + lam diag(max(A_ii, 1e-12))), as damped_solve damps, into s_L; A packed lower.  false: a pivot was
 // not positive or not finite.
 __device__ __forceinline__ bool damped_chol6(const double* A, const double lam, double* s_L)
 {
     double L[21];
-    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 21; ++k)
+        L[k] = A[k];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
         const double ajj = A[tri6(j, j)];
-        double d = ajj + lam * (ajj > 1e-12 ? ajj : 1e-12);
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= L[tri6(j, k)] * L[tri6(j, k)];
-        ok = ok && d > 0.0 && finite_bits(d);
-        const double sq = sqrt(d);
-        L[tri6(j, j)] = sq;
-        const double is = 1.0 / sq;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[tri6(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= L[tri6(i, k)] * L[tri6(j, k)];
-            L[tri6(i, j)] = v * is;
-        }
+        L[tri6(j, j)] = ajj + lam * (ajj > 1e-12 ? ajj : 1e-12);
     }
+    const bool ok = cholesky<6>(L, L, Packed{}, PivotPositive<true>{});
 #pragma unroll
     for (int k = 0; k < 21; ++k)
         s_L[k] = L[k];
@@ -151,16 +142,7 @@ __device__ __forceinline__ bool damped_chol6(const double* A, const double lam, 
 template <typename Rhs>
 __device__ __forceinline__ void forward_column6(const double* s_L, Rhs&& rhs, double* out, const int ld)
 {
-    double col[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = rhs(i);
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v -= s_L[tri6(i, k)] * col[k];
-        col[i] = v / s_L[tri6(i, i)];
-        out[ld * i] = col[i];
-    }
+    forward_substitute<6>(s_L, Packed{}, rhs, [&](const int i, const double v) { out[ld * i] = v; });
 }
 
 // Entry e of an item's record.  c_entry(i, j), i >= j: the item's C; grad(c): its g_s; Y [6][ld]: L^-1 B with y = L^-1 g
@@ -246,14 +228,7 @@ __device__ __forceinline__ void arrow_pose_step(const double* el, const int P, c
             v += el[arrow_elim_Y(P, k) + c] * ds[c];
         w[k] = v;
     }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = -w[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k)
-            v -= el[tri6(k, i)] * dp[k];
-        dp[i] = v / el[tri6(i, i)];
-    }
+    backward_substitute<6>(el, Packed{}, [&](const int i) { return -w[i]; }, dp);
 }
 
 // thread 0 of a try kernel
@@ -264,7 +239,7 @@ __device__ __forceinline__ void arrow_store_trial(const ArrowArgs& w, const int 
     for (int k = 0; k < 7; ++k)
         w.cand[7 * (int64_t)p + k] = cand[k];
     w.trial[2 * p] = cost;
-    w.trial[2 * p + 1] = max_abs6(dp);
+    w.trial[2 * p + 1] = max_abs<6>(dp);
 }
 
 // lm_refine's decision (pose_lm.hpp) on the whole problem, by one workgroup of kImageThreads.  The step's size is the

@@ -220,15 +220,11 @@ __global__ __launch_bounds__(64) void k_border_ye(int n_e, const double* __restr
         return;
     }
     const double* L = Le + 36 * (int64_t)e;
+#pragma unroll   // as the compiler unrolled the written-out loop by itself: ten independent columns in flight
     for (int c = 0; c < kBorderY; ++c) {
-        double y[6];
-        for (int r = 0; r < 6; ++r) {
-            double t = c < 9 ? B_e[54 * (int64_t)e + 9 * r + c] : g_e[6 * (int64_t)e + r];
-            for (int k = 0; k < r; ++k)
-                t -= L[6 * r + k] * y[k];
-            y[r] = t / L[6 * r + r];
-            out[r * kBorderY + c] = y[r];
-        }
+        forward_substitute<6>(
+            L, RowMajor<6>{}, [&](const int r) { return c < 9 ? B_e[54 * (int64_t)e + 9 * r + c] : g_e[6 * (int64_t)e + r]; },
+            [&](const int r, const double t) { out[r * kBorderY + c] = t; });
     }
 }
 

@@ -28,7 +28,9 @@
 // bookkeeping on the control block, dp from an elimination, the accept / stop rules of the control kernel, the result
 // update and the joint marginal, the begin rule and kMinPivot.  Shared with kernels_localize.hip through image_sums.hpp:
 // the image view, the rotation of a world corner, the classification (k_calib_classify is classify_image under the
-// current model) and the cost-only sum (k_calib_try's candidate cost is image_sums<false, false>); from pose_lm.hpp: tri6, project_camera_point_intrinsics and lower_inverse / lower_gram.  The camera model is loaded by
+// current model) and the cost-only sum (k_calib_try's candidate cost is image_sums<false, false>); from pose_lm.hpp:
+// project_camera_point_intrinsics; from small_solve.hpp: tri6, cholesky<9>, forward_substitute<9>, lower_inverse /
+// lower_gram.  The camera model is loaded by
 // engine.hpp's make_intrinsics.  Calibration's own: one corner's 2 x 15 rows (image_normal_sums), the 9 x 9 system in one
 // thread's registers (chol9, the solve and the inverse behind it) and the step size of the model in k_calib_control.
 //
@@ -176,27 +178,7 @@ __global__ __launch_bounds__(kCalThreads) void k_calib_image(const CalibArgs a, 
 // its weight is not above min_pivot, or not finite
 __device__ __forceinline__ bool chol9(double (&M)[45], const double (&weight)[9], const double min_pivot)
 {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        double d = M[tri6(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= M[tri6(j, k)] * M[tri6(j, k)];
-        ok = ok && d * weight[j] > min_pivot && finite_bits(d);
-        const double sq = sqrt(d);
-        M[tri6(j, j)] = sq;
-        const double is = 1.0 / sq;
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) {
-            double v = M[tri6(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= M[tri6(i, k)] * M[tri6(j, k)];
-            M[tri6(i, j)] = v * is;
-        }
-    }
-    return ok;
+    return cholesky<9>(M, M, Packed{}, PivotWeighted{ weight, min_pivot });
 }
 
 __global__ __launch_bounds__(kSolveThreads) void k_calib_solve(const CalibArgs a, const int cov_mode)
@@ -270,14 +252,8 @@ __global__ __launch_bounds__(kSolveThreads) void k_calib_solve(const CalibArgs a
     }
     // (L L') z = -D g_k, dk = D z
     double z[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        double v = ((mask >> i) & 1) ? -s_tot[arrow_rec_grad(P) + i] * sc[i] : 0.0;
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v -= M[tri6(i, k)] * z[k];
-        z[i] = v / M[tri6(i, i)];
-    }
+    forward_substitute<9>(M, Packed{}, [&](const int i) { return ((mask >> i) & 1) ? -s_tot[arrow_rec_grad(P) + i] * sc[i] : 0.0; },
+                          [&](const int i, const double v) { z[i] = v; });
 #pragma unroll
     for (int i = 8; i >= 0; --i) {
         double v = z[i];

@@ -12,6 +12,7 @@
 // chain), then subtracted from the rows below.  This runs once per reconstruction (final summary), so the
 // tile kernels are plain LDS-tiled f64 FMA code, not MFMA.
 #include "engine.hpp"
+#include "small_solve.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -187,17 +188,7 @@ __global__ __launch_bounds__(256) void k_cov_gram(const double* __restrict__ X, 
         // T = L_j^{-1} (lower), C = T^T (I + G) T
         const double* L = Le + 36 * (int64_t)j;
         double T[6][6];
-        for (int c = 0; c < 6; ++c)
-            for (int r = 0; r < 6; ++r) {
-                if (r < c) {
-                    T[r][c] = 0.0;
-                    continue;
-                }
-                double s = (r == c) ? 1.0 : 0.0;
-                for (int m = c; m < r; ++m)
-                    s -= L[6 * r + m] * T[m][c];
-                T[r][c] = s / L[6 * r + r];
-            }
+        lower_inverse_full<6>(L, RowMajor<6>{}, T);
         for (int a = 0; a < 6; ++a)
             G[a][a] += 1.0;
         double GT[6][6];
@@ -330,22 +321,6 @@ __global__ __launch_bounds__(256) void k_trsm_update_mfma(const double* __restri
     }
 }
 
-// T = L^{-1} of a lower-triangular 6x6 factor (k_cov_gram's substitution)
-__device__ void inv_lower6(const double* __restrict__ L, double (&T)[6][6])
-{
-    for (int c = 0; c < 6; ++c)
-        for (int r = 0; r < 6; ++r) {
-            if (r < c) {
-                T[r][c] = 0.0;
-                continue;
-            }
-            double s = (r == c) ? 1.0 : 0.0;
-            for (int m = c; m < r; ++m)
-                s -= L[6 * r + m] * T[m][c];
-            T[r][c] = s / L[6 * r + r];
-        }
-}
-
 // One workgroup per requested pair: G = C(a)^T C(b) over the n_rows rows of X in k_cov_gram's form (thread-private sums
 // in row order, LDS tree, no floating-point atomics; 21 sums and a mirror when both slots are the same), then thread 0
 // applies the sign, delta_ij and the L^{-T} .. L^{-1} transforms of the eliminated endpoints.  pair[4 p ..] = pose a,
@@ -433,7 +408,7 @@ __global__ __launch_bounds__(256) void k_cov_pair(const double* __restrict__ X, 
             G[a][a] += 1.0;
     double T[6][6], M[6][6];
     if (eb) {   // G <- G L_b^{-1}
-        inv_lower6(Le + 36 * (int64_t)(elim_cams ? pb : pb - n_cams), T);
+        lower_inverse_full<6>(Le + 36 * (int64_t)(elim_cams ? pb : pb - n_cams), RowMajor<6>{}, T);
         for (int a = 0; a < 6; ++a)
             for (int b = 0; b < 6; ++b) {
                 double s = 0.0;
@@ -446,7 +421,7 @@ __global__ __launch_bounds__(256) void k_cov_pair(const double* __restrict__ X, 
                 G[a][b] = M[a][b];
     }
     if (ea) {   // G <- L_a^{-T} G
-        inv_lower6(Le + 36 * (int64_t)(elim_cams ? pa : pa - n_cams), T);
+        lower_inverse_full<6>(Le + 36 * (int64_t)(elim_cams ? pa : pa - n_cams), RowMajor<6>{}, T);
         for (int a = 0; a < 6; ++a)
             for (int b = 0; b < 6; ++b) {
                 double s = 0.0;

@@ -12,7 +12,7 @@
 // The single-pose solver all three are built from lives in pose_lm.hpp and is shared with kernels_localize.hip: the
 // Levenberg-Marquardt trial loop (lm_refine: quad_refine and k_init_refine supply their sums as a lambda), the camera-side
 // projection with its Jacobian (project_camera_point: quad_corner forms the rotated point and calls it), the candidate
-// winner rule (better, wave_winner: k_init_score), the 21 + 6 sums (zero_normal, wave_sum_normal, accumulate_rows, solve6)
+// winner rule (better, wave_winner: k_init_score), the 21 + 6 sums (zero_normal, wave_sum_normal, accumulate_rows; small_solve.hpp solves them)
 // and the chaining of candidates (chain_camera, chain_tag, quat_from_R).  What is here is what differs: how a quad's
 // rotated point is formed (z = 0), which observations a pose sums over, and the bookkeeping of the growth rounds.
 // All f64, the projections of geom.hpp: k_quad_pose fits CameraModel::projectPoint (what vmm_ba_project_points computes,

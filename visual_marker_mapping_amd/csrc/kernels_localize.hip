@@ -14,9 +14,9 @@
 //                             (wave_sum32) and combined in LDS in wave order; every thread runs the same 6 x 6 solve
 //                   result    flags at the returned pose, (J^T J)^-1 by a 6 x 6 Cholesky in registers
 // The single-pose solver is pose_lm.hpp's, shared with kernels_init.hip: lm_refine (refine_image supplies image_sums as a
-// lambda; the sums hold barriers, so the workgroup runs the driver as one), better / wave_winner, solve6, chain_camera,
-// quat_from_R, inverse6.  The image view (LDS or global), world_corner, classify_image and image_sums with their
-// workgroup reductions and the stores of an image's result are image_sums.hpp's, shared with kernels_calibrate.hip and
+// lambda; the sums hold barriers, so the workgroup runs the driver as one), better / wave_winner, chain_camera,
+// quat_from_R, over small_solve.hpp's damped_solve<6> and spd_inverse<6>.  The image view (LDS or global), world_corner,
+// classify_image and image_sums with their workgroup reductions and the stores of an image's result are image_sums.hpp's, shared with kernels_calibrate.hip and
 // kernels_rig.hip.  Here: the staging, the candidate scoring and the passes.
 // An image's pixels and world corners (20 doubles per observation) are staged in LDS when the image has at most
 // kStage observations (k_localize<true>); larger images read them from global memory (k_localize<false>).  Both run the
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kLocThreads) void k_localize(const LocalizeArgs a)
         res.cost = 0.5 * cost;
         res.rms_px = sqrt(raw2 / (4.0 * res.n_inlier_obs));
         if (res.n_inlier_obs >= a.min_inliers) {
-            have_cov = inverse6(A, C);
+            have_cov = spd_inverse<6>(A, C);
             if (!have_cov)
                 res.status = VMM_BA_LOC_SINGULAR;
         }

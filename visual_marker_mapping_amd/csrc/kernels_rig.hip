@@ -16,8 +16,8 @@
 // The Jacobian over the rig's tangent is the camera Jacobian of project_camera_point (pose_lm.hpp) turned into the rig
 // frame: a step (dt, dtheta) of the rig moves camera c by (R_c dt, R_c dtheta), so both halves of a row are multiplied
 // by R_c from the right.
-// The solver (lm_refine, solve6, inverse6, better / wave_winner, chain_camera / chain_tag) is pose_lm.hpp's and the
-// reductions and the stores of a result are image_sums.hpp's, as in k_localize.  The localisation's body and its four
+// The solver (lm_refine, better / wave_winner, chain_camera / chain_tag) is pose_lm.hpp's over small_solve.hpp (the
+// damped 6 x 6 solve, spd_inverse<6>) and the reductions and the stores of a result are image_sums.hpp's, as in k_localize.  The localisation's body and its four
 // per-observation loops stay a copy of kernels_localize.hip's with the camera looked up per observation: as one
 // template over both (tried: DESIGN.md section 9) the same arithmetic compiled to other bits.  The K camera models and extrinsics
 // (21 doubles each) are expanded into LDS once per workgroup; a thread reads the ones of its observation's camera from
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(kImageThreads) void k_rig_localize(const RigArgs ra
         res.cost = 0.5 * cost;
         res.rms_px = sqrt(raw2 / (4.0 * res.n_inlier_obs));
         if (res.n_inlier_obs >= a.min_inliers) {
-            have_cov = inverse6(A, C);
+            have_cov = spd_inverse<6>(A, C);
             if (!have_cov)
                 res.status = VMM_BA_LOC_SINGULAR;
         }

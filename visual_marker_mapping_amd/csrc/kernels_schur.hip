@@ -11,37 +11,17 @@
 // (v_mfma_f64_16x16x4_f64); the (tile, K tile) work units are split evenly over the workgroups ("stream-K")
 // and the per-tile partial sums are added in a fixed order.
 #include "engine.hpp"
+#include "small_solve.hpp"
 
 namespace vmm {
 
 // ---- E-block factorisation ---------------------------------------------------------------------
 
-__device__ __forceinline__ bool chol6(double* A)
+// L_e in place over row-major M_e.  A pivot that is not positive or not finite becomes 1 (PivotOrOne): the thread carries
+// on with finite numbers and the pose's first observation reports lin_fail.
+__device__ __forceinline__ bool chol6(double (&A)[36])
 {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = A[6 * j + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= A[6 * j + k] * A[6 * j + k];
-        if (!(d > 0.0) || !isfinite(d)) {
-            ok = false;
-            d = 1.0;
-        }
-        d = sqrt(d);
-        A[6 * j + j] = d;
-        const double inv = 1.0 / d;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double s = A[6 * i + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                s -= A[6 * i + k] * A[6 * j + k];
-            A[6 * i + j] = s * inv;
-        }
-    }
-    return ok;
+    return cholesky<6>(A, A, RowMajor<6>{}, PivotOrOne{});
 }
 
 // One thread per observation (E order): M_e = s_e H_e s_e + D_e^2 = L_e L_e^T, z_e = L_e^{-1} s_e g_e and the
@@ -100,14 +80,7 @@ __global__ __launch_bounds__(256) void k_form_z(LmCtl* ctl, int64_t n_obs, int64
         for (int a = 0; a < 6; ++a)
             v[a] = se[a] * g_E[6 * (int64_t)e + a];
         // z = L^{-1} v
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            double t = v[r];
-#pragma unroll
-            for (int k = 0; k < r; ++k)
-                t -= L[6 * r + k] * v[k];
-            v[r] = t / L[6 * r + r];
-        }
+        forward_substitute<6>(L, RowMajor<6>{}, [&](const int r) { return v[r]; }, [&](const int r, const double t) { v[r] = t; });
 #pragma unroll
         for (int k = 0; k < 36; ++k)
             Le[36 * (int64_t)e + k] = L[k];
@@ -124,18 +97,7 @@ __global__ __launch_bounds__(256) void k_form_z(LmCtl* ctl, int64_t n_obs, int64
 #pragma unroll
         for (int b = 0; b < 6; ++b)
             X[6 * a + b] = se[a] * (double)W[(int64_t)(6 * a + b) * n_pad + i] * sf[b];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const double inv = 1.0 / L[6 * r + r];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            double t = X[6 * r + c];
-#pragma unroll
-            for (int k = 0; k < r; ++k)
-                t -= L[6 * r + k] * X[6 * k + c];
-            X[6 * r + c] = t * inv;
-        }
-    }
+    forward_block<6, 6>(L, RowMajor<6>{}, X);
     int64_t rs = ldz;
     double* zrow = Z + (int64_t)(6 * e) * ldz + 6 * f;
     if (SPARSE) {

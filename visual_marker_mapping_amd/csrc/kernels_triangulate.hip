@@ -415,7 +415,7 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulate(const TriangulateAr
             res.rms_px = sqrt(raw2 / res.n_inlier_obs);
         }
         if (res.n_inlier_obs >= a.min_inliers) {
-            have_cov = inverse3(H, C);
+            have_cov = spd_inverse<3, PivotPositive<true>>(H, C);
             if (!have_cov)
                 res.status = VMM_BA_TRI_SINGULAR;
         }

@@ -3,11 +3,11 @@
 //   undistort_pixel        pixel -> undistorted normalised image point (fixed-point iteration of the functor's distortion)
 //   project_world_point    residual of a world point in one camera frame, the depth, and with JAC the 2 x 6 camera
 //                          Jacobian (project_camera_point<false, true>'s columns) and the 2 x 3 point Jacobian
-//   spd3_solve             A x = b for a packed lower 3 x 3 A by Cholesky (the ray intersections)
-//   solve3 / lm_refine3    the damped solve and the Levenberg-Marquardt trial loop: solve6 / lm_refine with three unknowns
-//   inverse3               A^-1 by Cholesky (the covariance)
+//   spd3_solve             A x = b for a packed lower 3 x 3 A by Cholesky with a floor on the pivots (the ray intersections)
+//   lm_refine3             the Levenberg-Marquardt trial loop over the three coordinates (small_solve.hpp's lm_trials)
+// The covariance is small_solve.hpp's spd_inverse<3, PivotPositive<true>>.
 //   wave_count             butterfly sum of an int over the wave
-// Every test of finiteness asks the bits (finite_bits, pose_lm.hpp): v - v == 0 misfires when the compiler contracts
+// Every test of finiteness asks the bits (finite_bits, small_solve.hpp): v - v == 0 misfires when the compiler contracts
 // the subtraction with the arithmetic that produced v.
 // Everything is __forceinline__ and lives in registers.  Packed lower 3 x 3 matrices use tri6's indexing.
 #pragma once
@@ -65,144 +65,40 @@ __device__ __forceinline__ int wave_count(int n)
     return n;
 }
 
-// L L^T = A for a packed lower 3 x 3 A; false: a pivot is not positive or not finite (L is not valid).
-__device__ __forceinline__ bool cholesky3(const double (&A)[6], double (&L)[6])
-{
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double d = A[tri6(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= L[tri6(j, k)] * L[tri6(j, k)];
-        ok = ok && d > 0.0 && finite_bits(d);
-        const double s = sqrt(d);
-        L[tri6(j, j)] = s;
-        const double is = 1.0 / s;
-#pragma unroll
-        for (int i = j + 1; i < 3; ++i) {
-            double v = A[tri6(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= L[tri6(i, k)] * L[tri6(j, k)];
-            L[tri6(i, j)] = v * is;
-        }
-    }
-    return ok;
-}
-
-// L L^T x = b
-__device__ __forceinline__ void cholesky3_apply(const double (&L)[6], const double (&b)[3], double (&x)[3])
-{
-    double y[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v -= L[tri6(i, k)] * y[k];
-        y[i] = v / L[tri6(i, i)];
-    }
-#pragma unroll
-    for (int i = 2; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 3; ++k)
-            v -= L[tri6(k, i)] * x[k];
-        x[i] = v / L[tri6(i, i)];
-    }
-}
-
 // A x = b for a packed lower symmetric 3 x 3 A.  false: A is not positive definite beyond rounding, or x is not finite.
 // A sum of projectors I - d d^T has entries of order one, and two parallel rays leave a last pivot of rounding size that
 // may come out positive: a pivot below kSpdFloor times the largest diagonal entry counts as zero.
 constexpr double kSpdFloor = 1e-13;
 __device__ __forceinline__ bool spd3_solve(const double (&A)[6], const double (&b)[3], double (&x)[3])
 {
-    double L[6];
-    bool ok = cholesky3(A, L);
+    double L[6], y[3];
+    bool ok = cholesky<3>(A, L, Packed{}, PivotPositive<true>{});
     const double dmax = fmax(A[0], fmax(A[2], A[5]));
 #pragma unroll
     for (int j = 0; j < 3; ++j)
         ok = ok && L[tri6(j, j)] * L[tri6(j, j)] > kSpdFloor * dmax;
-    cholesky3_apply(L, b, x);
+    forward_substitute<3>(L, Packed{}, [&](const int i) { return b[i]; }, [&](const int i, const double v) { y[i] = v; });
+    backward_substitute<3>(L, Packed{}, [&](const int i) { return y[i]; }, x);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
         ok = ok && finite_bits(x[i]);
     return ok;
 }
 
-// (A + lam diag(max(A_ii, 1e-12))) step = -g by Cholesky: solve6 with three unknowns.
-__device__ __forceinline__ bool solve3(const double (&A)[6], const double (&g)[3], const double lam, double (&step)[3])
-{
-    double D[6], L[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        D[k] = A[k];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double d = A[tri6(a, a)];
-        D[tri6(a, a)] = d + lam * (d > 1e-12 ? d : 1e-12);
-    }
-    bool ok = cholesky3(D, L);
-    const double mg[3] = { -g[0], -g[1], -g[2] };
-    cholesky3_apply(L, mg, step);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        ok = ok && finite_bits(step[i]);
-    return ok;
-}
-
-// C = A^-1 (packed lower) for a packed lower 3 x 3 A by Cholesky; false: not positive definite (C is not valid).
-__device__ __forceinline__ bool inverse3(const double (&A)[6], double (&C)[6])
-{
-    double L[6], M[6];
-    const bool ok = cholesky3(A, L);
-    lower_inverse<3>(L, M);
-    return finite_bits(lower_gram<3>(M, C)) && ok;
-}
-
-// Levenberg-Marquardt over the 3 coordinates of X (in place), at most max_trials trials (accepted + rejected); returns
-// the trials spent.  lm_refine's damping schedule, thresholds and exits (kLamInit, x 0.1 / x 10, cost_at_floor,
-// step < 1e-14).  sums(jac, X, A, g) returns the cost at X (+inf: not admissible, the trial is rejected) and, when jac is
-// std::true_type, fills J^T J (packed lower) and J^T r.  cost receives the cost at the returned X.
-// The invariant of lm_refine holds here too: all lanes that run the driver together hold the same sums (every lane ends
-// a wave_sum with the total), so they run the same 3 x 3 solve and every branch is wave-uniform.
+// Levenberg-Marquardt over the 3 coordinates of X (in place): lm_trials (small_solve.hpp) with addition as the update.
+// cost receives the cost at the returned X.  The invariant holds here too: all lanes that run the driver together hold
+// the same sums (every lane ends a wave_sum with the total), so they run the same 3 x 3 solve and every branch is
+// wave-uniform.
 template <typename Sums>
 __device__ __forceinline__ int lm_refine3(double (&X)[3], const int max_trials, Sums&& sums, double& cost)
 {
-    double cand[3], A[6], g[3], step[3];
-    double lam = kLamInit;
-    cost = sums(std::true_type{}, X, A, g);
-    int it = 0;
-    for (; it < max_trials; ++it) {
-        if (!finite_bits(cost) || lam > kLamMax)
-            break;
-        if (!solve3(A, g, lam, step)) {
-            lam *= 10.0;
-            continue;
-        }
-        const double sm = fmax(fabs(step[0]), fmax(fabs(step[1]), fabs(step[2])));
-        if (sm < 1e-14)
-            break;
+    return lm_trials<3, 3, true, false>(X, max_trials, sums,
+                                        [](const double (&at)[3], const double (&step)[3], double (&cand)[3]) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-            cand[k] = X[k] + step[k];
-        double A2[6], g2[3];
-        const double cc = sums(std::false_type{}, cand, A2, g2);
-        if (finite_bits(cc) && cc < cost) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                X[k] = cand[k];
-            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
-            cost = sums(std::true_type{}, X, A, g);
-        } else {
-            if (sm < 1e-10 || cost_at_floor(cost, cc))
-                break;
-            lam *= 10.0;
-        }
-    }
-    return it;
+                                            for (int k = 0; k < 3; ++k)
+                                                cand[k] = at[k] + step[k];
+                                        },
+                                        cost);
 }
 
 } // namespace vmm

@@ -1,37 +1,24 @@
 // The single-pose solver shared by kernels_init.hip (map initialisation), kernels_localize.hip (localisation against
 // a finished map) and, through image_sums.hpp and the pieces named below, kernels_calibrate.hip: fit one
 // 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
-//   lm_refine               the Levenberg-Marquardt trial loop; the caller supplies the sums (cost, J^T J, J^T r)
+//   lm_refine               the Levenberg-Marquardt trial loop over a pose's six tangent unknowns (small_solve.hpp's
+//                           lm_trials with pose_plus as the update); the caller supplies the sums (cost, J^T J, J^T r)
 //   project_camera_point    camera-side projection of a rotated point with its 2 x 6 Jacobian over the pose's tangent
 //   project_camera_point_intrinsics   the same with the 2 x 9 Jacobian over the camera model (kernels_calibrate.hip)
 //   better / wave_winner    the candidate winner rule and its wave butterfly
-//   zero_normal / wave_sum_normal, accumulate_rows, solve6   the 21 + 6 sums of the normal equations and their solve
-//   lower_inverse / lower_gram   L^-1 and M^T M of packed lower matrices: the covariances of kernels_localize.hip (6 x 6)
-//                                and kernels_calibrate.hip (6 x 6 and 9 x 9)
-//   inverse6                the 6 x 6 covariance of one pose (kernels_localize.hip, kernels_rig.hip)
+//   zero_normal / wave_sum_normal, accumulate_rows   the 21 + 6 sums of the normal equations
 //   chain_camera / chain_tag, quat_from_R                    candidates chained through a placed pose
+// The algebra under it is small_solve.hpp's: tri6 and the tests of finiteness, the damped solve of the normal equations
+// (damped_solve<6, BITS>), the covariance of one pose (spd_inverse<6>: kernels_localize.hip, kernels_rig.hip) and
+// lower_inverse / lower_gram (kernels_calibrate.hip, arrowhead.hpp).
 // Everything is __forceinline__ and lives in registers.
 #pragma once
-#include <type_traits>
-
 #include "geom.hpp"
+#include "small_solve.hpp"
 
 namespace vmm {
 
 constexpr double kInf = __builtin_huge_val();
-constexpr double kLamInit = 1e-3, kLamMin = 1e-12, kLamMax = 1e12;
-
-__device__ __forceinline__ int tri6(int a, int b) { return a * (a + 1) / 2 + b; }   // a >= b: packed lower, any order
-
-__device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
-
-// The same question asked of the bits.  finite_d's subtraction may be contracted with the arithmetic that produced v
-// (v = a * b + c: v - v becomes fma(a, b, c - v), the rounding error of v instead of zero), which reports a perfectly
-// finite v as non-finite; where that would be wrong rather than merely slow, ask this one.
-__device__ __forceinline__ bool finite_bits(double v) { return __builtin_isfinite(v); }
-
-template <bool BITS>
-__device__ __forceinline__ bool finite_v(double v) { return BITS ? finite_bits(v) : finite_d(v); }
 
 // Eigen::Quaterniond(R) (trace test), normalised; R row-major.
 __device__ __forceinline__ void quat_from_R(const double* R, double* q)
@@ -97,129 +84,6 @@ __device__ __forceinline__ void chain_tag(const Rigid& rel, const Rigid& cam, Ri
         tag.t[i] = cam.R[i] * d0 + cam.R[3 + i] * d1 + cam.R[6 + i] * d2;
 }
 
-// (A + lam diag(max(A_ii, 1e-12))) step = -g by Cholesky; A packed lower (tri6).  false: not positive definite.
-// BITS: test finiteness with finite_bits instead of finite_d.
-template <bool BITS>
-__device__ __forceinline__ bool solve6(const double (&A)[21], const double (&g)[6], const double lam, double (&step)[6])
-{
-    double L[21];
-#pragma unroll
-    for (int k = 0; k < 21; ++k)
-        L[k] = A[k];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-        const double d = A[tri6(a, a)];
-        L[tri6(a, a)] = d + lam * (d > 1e-12 ? d : 1e-12);
-    }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = L[tri6(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= L[tri6(j, k)] * L[tri6(j, k)];
-        ok = ok && d > 0.0 && finite_v<BITS>(d);
-        const double s = sqrt(d);
-        L[tri6(j, j)] = s;
-        const double is = 1.0 / s;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = L[tri6(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= L[tri6(i, k)] * L[tri6(j, k)];
-            L[tri6(i, j)] = v * is;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v -= L[tri6(i, k)] * y[k];
-        y[i] = v / L[tri6(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k)
-            v -= L[tri6(k, i)] * step[k];
-        step[i] = v / L[tri6(i, i)];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        ok = ok && finite_v<BITS>(step[i]);
-    return ok;
-}
-
-// M = L^-1 for a packed lower N x N factor L (tri6 indexing; L: anything indexable, registers or memory).
-template <int N, typename Lower>
-__device__ __forceinline__ void lower_inverse(const Lower& L, double (&M)[N * (N + 1) / 2])
-{
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        M[tri6(j, j)] = 1.0 / L[tri6(j, j)];
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = j; k < i; ++k)
-                v -= L[tri6(i, k)] * M[tri6(k, j)];
-            M[tri6(i, j)] = v / L[tri6(i, i)];
-        }
-    }
-}
-
-// C = M^T M (packed lower) for a packed lower N x N M; returns sum |C_ab| over the packed entries: finite exactly when
-// every entry is.
-template <int N>
-__device__ __forceinline__ double lower_gram(const double (&M)[N * (N + 1) / 2], double (&C)[N * (N + 1) / 2])
-{
-    double sum = 0.0;
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int b = 0; b <= a; ++b) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = a; k < N; ++k)
-                v += M[tri6(k, a)] * M[tri6(k, b)];
-            C[tri6(a, b)] = v;
-            sum += fabs(v);
-        }
-    return sum;
-}
-
-// C = A^-1 for a packed lower 6 x 6 A by Cholesky, in registers; false: not positive definite (C is not valid).
-// One test at the end covers every pivot: a negative pivot makes its square root a NaN and a zero pivot its reciprocal
-// an infinity, and either reaches the last entry of every later row of L^-1 and from there C.
-__device__ __forceinline__ bool inverse6(const double (&A)[21], double (&C)[21])
-{
-    double L[21], M[21];   // A = L L^T, M = L^-1 (lower)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = A[tri6(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            d -= L[tri6(j, k)] * L[tri6(j, k)];
-        const double s = sqrt(d);
-        L[tri6(j, j)] = s;
-        const double is = 1.0 / s;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[tri6(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= L[tri6(i, k)] * L[tri6(j, k)];
-            L[tri6(i, j)] = v * is;
-        }
-    }
-    lower_inverse<6>(L, M);
-    return finite_bits(lower_gram<6>(M, C));
-}
-
 __device__ __forceinline__ void accumulate_rows(const double (&j)[2][6], const double ru, const double rv, double (&A)[21],
                                                 double (&g)[6])
 {
@@ -253,65 +117,13 @@ __device__ __forceinline__ void wave_sum_normal(double (&A)[21], double (&g)[6])
         g[k] = wave_sum(g[k]);
 }
 
-__device__ __forceinline__ double max_abs6(const double (&s)[6])
-{
-    double m = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        m = fabs(s[k]) > m ? fabs(s[k]) : m;
-    return m;
-}
-
-// A rejected LM trial whose cost equals the current one to rounding (pixel coordinates of a few thousand carry 1e-12
-// relative noise into a squared residual): the minimum is reached; raising the damping further would only repeat it.
-__device__ __forceinline__ bool cost_at_floor(const double cost, const double cand)
-{
-    return cand - cost <= 1e-10 * cost + 1e-20;
-}
-
-// Levenberg-Marquardt over the 6 tangent degrees of freedom of q (in place), at most max_trials trials (accepted +
-// rejected); returns the trials spent.  sums(jac, q, A, g) returns the cost at q and, when jac is std::true_type, fills
-// J^T J (packed lower) and J^T r.  cost receives the cost of the last evaluation with Jacobians: that of q, except
-// after the STOP_SMALL exit, where it is the cost before the last accepted step.
-// STOP_SMALL: also stop after an accepted step below 1e-9 (an initial guess for the bundle adjustment needs no more).
-// BITS: test finiteness with finite_bits instead of finite_d.
-// The invariant every caller keeps: all threads that run the driver together (a lane alone, a wave, or a workgroup when
-// sums contains __syncthreads) hold the same sums, so they take the same branches and reach the same barriers.
+// Levenberg-Marquardt over the 6 tangent degrees of freedom of q (7 doubles, in place): lm_trials (small_solve.hpp)
+// with pose_plus as the update; sums(jac, q, A, g) as described there.
 template <bool BITS, bool STOP_SMALL, typename Sums>
 __device__ __forceinline__ int lm_refine(double* q, const int max_trials, Sums&& sums, double& cost)
 {
-    double cand[7], A[21], g[6], step[6];
-    double lam = kLamInit;
-    cost = sums(std::true_type{}, q, A, g);
-    int it = 0;
-    for (; it < max_trials; ++it) {
-        if (!finite_v<BITS>(cost) || lam > kLamMax)
-            break;
-        if (!solve6<BITS>(A, g, lam, step)) {
-            lam *= 10.0;
-            continue;
-        }
-        const double sm = max_abs6(step);
-        if (sm < 1e-14)
-            break;
-        pose_plus(q, step, cand);
-        double A2[21], g2[6];
-        const double cc = sums(std::false_type{}, cand, A2, g2);
-        if (finite_v<BITS>(cc) && cc < cost) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k)
-                q[k] = cand[k];
-            lam = lam * 0.1 > kLamMin ? lam * 0.1 : kLamMin;
-            if (STOP_SMALL && sm < 1e-9)
-                break;
-            cost = sums(std::true_type{}, q, A, g);
-        } else {
-            if (sm < 1e-10 || cost_at_floor(cost, cc))
-                break;
-            lam *= 10.0;
-        }
-    }
-    return it;
+    return lm_trials<6, 7, BITS, STOP_SMALL>(q, max_trials, sums,
+                                             [](const double* at, const double (&step)[6], double (&cand)[7]) { pose_plus(at, step, cand); }, cost);
 }
 
 // The camera half of eval_corner (geom.hpp) on a point already rotated into the camera frame, b = R P: residual of

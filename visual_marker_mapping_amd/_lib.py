@@ -27,23 +27,6 @@ TRI_STATUS_NAMES = ("ok", "too_few_views", "no_candidate", "too_few_inliers", "s
 CAL_OK, CAL_NO_IMAGES, CAL_SINGULAR, CAL_NO_CONVERGENCE = 0, 1, 2, 3
 CAL_STATUS_NAMES = ("ok", "no_images", "singular", "no_convergence")
 
-# every symbol include/vmm_ba.h declares
-EXPORTS = ["vmm_ba_last_error", "vmm_ba_abi_version", "vmm_ba_default_options",
-           "vmm_ba_default_create_options", "vmm_ba_create", "vmm_ba_destroy", "vmm_ba_set_state",
-           "vmm_ba_get_state", "vmm_ba_get_points", "vmm_ba_set_allreduce", "vmm_ba_rccl_available", "vmm_ba_rccl_unique_id",
-           "vmm_ba_enable_rccl",
-           "vmm_ba_set_observation_mask", "vmm_ba_solve", "vmm_ba_cost",
-           "vmm_ba_reprojection_stats", "vmm_ba_tag_translation_covariance", "vmm_ba_covariance_blocks", "vmm_ba_project_points", "vmm_ba_eval_blocks",
-           "vmm_ba_dense_spd_solve", "vmm_ba_dense_syrk", "vmm_ba_time_kernels", "vmm_ba_pose_plus", "vmm_ba_debug_overlap",
-           "vmm_ba_debug_chol_schedule", "vmm_ba_debug_chol_tile",
-           "vmm_ba_quad_poses", "vmm_ba_default_init_options", "vmm_ba_initialize",
-           "vmm_ba_default_localize_options", "vmm_ba_localize", "vmm_ba_set_constant_poses",
-           "vmm_ba_rig_localize", "vmm_ba_default_rig_calibrate_options", "vmm_ba_rig_calibrate",
-           "vmm_ba_default_calibrate_options", "vmm_ba_calibrate",
-           "vmm_ba_default_triangulate_options", "vmm_ba_triangulate",
-           "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
-           "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"]
-
 
 class Problem(C.Structure):
     _fields_ = [("intr", C.c_double * 4), ("dist", C.c_double * 5), ("n_cams", C.c_int32),
@@ -170,6 +153,70 @@ class SelfcalReport(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
+# One line per export of include/vmm_ba.h, in its order: name -> (restype, argtypes).  A handle and every array travel as
+# void pointers (numpy's .ctypes.data_as), structs as typed pointers.
+_h = _a = C.c_void_p
+_i, _i32, _i64, _d, _P = C.c_int, C.c_int32, C.c_int64, C.c_double, C.POINTER
+_MAP = [_i32, _a, _a]                   # n_tags, tag_qt, tag_wh
+_BATCH = [_i32, _a, _a, _a]             # n_imgs / n_frames, img_start, obs_tag, obs_px
+SIGNATURES = {
+    "vmm_ba_last_error": (C.c_char_p, []),
+    "vmm_ba_abi_version": (_i, []),
+    "vmm_ba_default_options": (None, [_P(Options)]),
+    "vmm_ba_default_create_options": (None, [_P(CreateOptions)]),
+    "vmm_ba_create": (_i, [_P(Problem), _P(CreateOptions), _P(C.c_void_p)]),
+    "vmm_ba_destroy": (None, [_h]),
+    "vmm_ba_set_state": (_i, [_h, _a, _a]),
+    "vmm_ba_get_state": (_i, [_h, _a, _a]),
+    "vmm_ba_get_points": (_i, [_h, _a]),
+    "vmm_ba_set_allreduce": (_i, [_h, ALLREDUCE_FN, C.c_void_p]),
+    "vmm_ba_rccl_available": (_i, []),
+    "vmm_ba_rccl_unique_id": (_i, [_a]),
+    "vmm_ba_enable_rccl": (_i, [_h, _a]),
+    "vmm_ba_set_observation_mask": (_i, [_h, _a]),
+    "vmm_ba_set_constant_poses": (_i, [_h, _a, _a]),
+    "vmm_ba_solve": (_i, [_h, _P(Options), _P(Summary)]),
+    "vmm_ba_cost": (_i, [_h, _i, _d, _P(_d)]),
+    "vmm_ba_reprojection_stats": (_i, [_h, _a, _a, _P(_d), _a]),
+    "vmm_ba_tag_translation_covariance": (_i, [_h, _i, _d, _a]),
+    "vmm_ba_covariance_blocks": (_i, [_h, _i, _d, _i64, _a, _a, _a]),
+    "vmm_ba_project_points": (_i, [_a, _a, _i64, _a, _a, _i]),
+    "vmm_ba_quad_poses": (_i, [_a, _a, _i64, _a, _a, _a, _a, _i]),
+    "vmm_ba_default_init_options": (None, [_P(InitOptions)]),
+    "vmm_ba_initialize": (_i, [_h, _P(InitOptions), _P(InitReport), _a, _a]),
+    "vmm_ba_default_localize_options": (None, [_P(LocalizeOptions)]),
+    "vmm_ba_localize": (_i, [_a, _a] + _MAP + _BATCH + [_P(LocalizeOptions), _a, _a, _a, _a, _i]),
+    "vmm_ba_rig_localize": (_i, [_i32, _a, _a, _a] + _MAP + _BATCH + [_P(LocalizeOptions), _a, _a, _a, _a, _i]),
+    "vmm_ba_default_rig_calibrate_options": (None, [_P(RigCalibrateOptions)]),
+    "vmm_ba_rig_calibrate": (_i, [_i32, _a, _a, _a] + _MAP + _BATCH + [_P(RigCalibrateOptions), _a, _a, _a, _a, _a, _a,
+                                  _P(RigCalibrateReport), _i]),
+    "vmm_ba_default_triangulate_options": (None, [_P(TriangulateOptions)]),
+    "vmm_ba_triangulate": (_i, [_a, _a, _i32, _a, _a] + _BATCH + [_P(TriangulateOptions), _a, _a, _a, _a, _a, _i]),
+    "vmm_ba_default_calibrate_options": (None, [_P(CalibrateOptions)]),
+    "vmm_ba_calibrate": (_i, [_a, _a] + _MAP + _BATCH + [_P(CalibrateOptions), _a, _a, _a, _a, _a, _a, _a,
+                              _P(CalibrateReport), _i]),
+    "vmm_ba_set_intrinsics": (_i, [_h, _a, _a]),
+    "vmm_ba_get_intrinsics": (_i, [_h, _a, _a]),
+    "vmm_ba_intrinsics_system": (_i, [_h, _i, _d, _P(_d), _a, _a, _a, _a]),
+    "vmm_ba_default_selfcal_options": (None, [_P(SelfcalOptions)]),
+    "vmm_ba_solve_selfcal": (_i, [_h, _P(Options), _P(SelfcalOptions), _P(Summary), _P(SelfcalReport), _a, _a, _a]),
+    "vmm_ba_eval_blocks": (_i, [_h, _i, _d, _P(_d), _a, _a, _a, _a, _a]),
+    "vmm_ba_dense_spd_solve": (_i, [_i, _i, _a, _a, _a, _P(_i)]),
+    "vmm_ba_dense_syrk": (_i, [_i, _i, _i, _a, _a]),
+    "vmm_ba_pose_plus": (_i, [_i64, _a, _a, _a, _i]),
+    "vmm_ba_debug_overlap": (_i, [_h, _i, _a]),
+    "vmm_ba_debug_chol_schedule": (_i, [_i, _i, _i, _a, _i, _a, _a]),
+    "vmm_ba_debug_chol_tile": (_i, [_i, _a, _i, _a, _a]),
+    "vmm_ba_time_kernels": (_i, [_h, _P(Options), _i, _P(KernelTimes)]),
+}
+EXPORTS = list(SIGNATURES)   # every symbol include/vmm_ba.h declares
+# Additive within ABI 6: a library built before these entries (VMM_BA_LIB; tools/bench_covariance.py times the parent
+# commit's build) still loads, and calling the missing entry raises AttributeError.
+OPTIONAL = {"vmm_ba_covariance_blocks", "vmm_ba_rig_localize", "vmm_ba_default_rig_calibrate_options", "vmm_ba_rig_calibrate",
+            "vmm_ba_default_calibrate_options", "vmm_ba_calibrate", "vmm_ba_default_triangulate_options",
+            "vmm_ba_triangulate", "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
+            "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"}
+
 _LIB = None
 
 
@@ -187,92 +234,15 @@ def lib():
             raise ImportError("%s is missing: build it with __graft_entry__.build() or "
                               "make -C visual_marker_mapping_amd/csrc" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.vmm_ba_last_error.restype = C.c_char_p
         L.vmm_ba_abi_version.restype = C.c_int
         if L.vmm_ba_abi_version() != ABI_VERSION:
             raise ImportError("%s has ABI version %d, this binding needs %d: rebuild it"
                               % (LIB_PATH, L.vmm_ba_abi_version(), ABI_VERSION))
-        L.vmm_ba_destroy.restype = None
-        L.vmm_ba_destroy.argtypes = [C.c_void_p]
-        L.vmm_ba_create.argtypes = [C.POINTER(Problem), C.POINTER(CreateOptions), C.POINTER(C.c_void_p)]
-        L.vmm_ba_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vmm_ba_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vmm_ba_get_points.argtypes = [C.c_void_p, C.c_void_p]
-        L.vmm_ba_set_allreduce.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p]
-        L.vmm_ba_rccl_available.restype = C.c_int
-        L.vmm_ba_rccl_available.argtypes = []
-        L.vmm_ba_rccl_unique_id.argtypes = [C.c_void_p]
-        L.vmm_ba_enable_rccl.argtypes = [C.c_void_p, C.c_void_p]
-        L.vmm_ba_set_observation_mask.argtypes = [C.c_void_p, C.c_void_p]
-        L.vmm_ba_set_constant_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vmm_ba_solve.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(Summary)]
-        L.vmm_ba_cost.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double)]
-        L.vmm_ba_reprojection_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.POINTER(C.c_double), C.c_void_p]
-        L.vmm_ba_tag_translation_covariance.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_void_p]
-        # additive within ABI 6: a library built before the entry (VMM_BA_LIB, tools/bench_covariance.py times the parent
-        # commit's build) still loads; calling the missing entry raises AttributeError
-        if hasattr(L, "vmm_ba_covariance_blocks"):
-            L.vmm_ba_covariance_blocks.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p]
-        L.vmm_ba_project_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                            C.c_int]
-        L.vmm_ba_eval_blocks.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double),
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vmm_ba_dense_spd_solve.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.POINTER(C.c_int)]
-        L.vmm_ba_dense_syrk.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.vmm_ba_pose_plus.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.vmm_ba_time_kernels.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int,
-                                          C.POINTER(KernelTimes)]
-        L.vmm_ba_debug_overlap.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.vmm_ba_debug_chol_schedule.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.vmm_ba_quad_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_int]
-        L.vmm_ba_default_init_options.restype = None
-        L.vmm_ba_default_init_options.argtypes = [C.POINTER(InitOptions)]
-        L.vmm_ba_initialize.argtypes = [C.c_void_p, C.POINTER(InitOptions), C.POINTER(InitReport), C.c_void_p,
-                                        C.c_void_p]
-        L.vmm_ba_default_localize_options.restype = None
-        L.vmm_ba_default_localize_options.argtypes = [C.POINTER(LocalizeOptions)]
-        L.vmm_ba_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.POINTER(LocalizeOptions), C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_int]
-        if hasattr(L, "vmm_ba_rig_localize"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
-            L.vmm_ba_rig_localize.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.POINTER(LocalizeOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.c_int]
-            L.vmm_ba_default_rig_calibrate_options.restype = None
-            L.vmm_ba_default_rig_calibrate_options.argtypes = [C.POINTER(RigCalibrateOptions)]
-            L.vmm_ba_rig_calibrate.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(RigCalibrateOptions), C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RigCalibrateReport), C.c_int]
-        if hasattr(L, "vmm_ba_calibrate"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
-            L.vmm_ba_default_calibrate_options.restype = None
-            L.vmm_ba_default_calibrate_options.argtypes = [C.POINTER(CalibrateOptions)]
-            L.vmm_ba_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.POINTER(CalibrateOptions), C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(CalibrateReport), C.c_int]
-        if hasattr(L, "vmm_ba_triangulate"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
-            L.vmm_ba_default_triangulate_options.restype = None
-            L.vmm_ba_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
-            L.vmm_ba_triangulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.vmm_ba_debug_chol_tile.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        if hasattr(L, "vmm_ba_solve_selfcal"):   # additive within ABI 6, as vmm_ba_covariance_blocks above
-            L.vmm_ba_set_intrinsics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-            L.vmm_ba_get_intrinsics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-            L.vmm_ba_intrinsics_system.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.c_void_p]
-            L.vmm_ba_default_selfcal_options.restype = None
-            L.vmm_ba_default_selfcal_options.argtypes = [C.POINTER(SelfcalOptions)]
-            L.vmm_ba_solve_selfcal.argtypes = [C.c_void_p, C.POINTER(Options), C.POINTER(SelfcalOptions),
-                                               C.POINTER(Summary), C.POINTER(SelfcalReport), C.c_void_p, C.c_void_p,
-                                               C.c_void_p]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            if name in OPTIONAL and not hasattr(L, name):
+                continue
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 

@@ -25,18 +25,19 @@ from .tag_reconstructor import TagReconstructor
 PARAMETER_NAMES = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
 
 
+def parameters_tree(report):
+    """The tail calibration.json and selfcalibration.json share: the nine parameters with their names, standard
+    deviations and 9x9 covariance."""
+    return {"parameter_names": list(PARAMETER_NAMES), "parameters": [float(v) for v in report["intrinsics"]],
+            "standard_deviations": [float(v) for v in report["std"]], "covariance": _io.matrix_tree(report["covariance"])}
+
+
 def calibration_tree(report):
     """The property tree of calibration.json for the report of TagReconstructor.refineCameraModel."""
     tree = {"status": _lib.CAL_STATUS_NAMES[report["status"]]}
-    for k in ("trials", "accepted", "passes", "n_images_used", "n_obs_used"):
-        tree[k] = int(report[k])
-    for k in ("initial_cost", "final_cost", "initial_rms_px", "final_rms_px", "time_s"):
-        tree[k] = float(report[k])
-    tree["parameter_names"] = list(PARAMETER_NAMES)
-    tree["parameters"] = [float(v) for v in report["intrinsics"]]
-    tree["standard_deviations"] = [float(v) for v in report["std"]]
-    tree["covariance"] = {"rows": 9, "cols": 9, "coefficents": [float(v) for v in report["covariance"].reshape(-1)]}
-    return tree
+    tree.update((k, int(report[k])) for k in ("trials", "accepted", "passes", "n_images_used", "n_obs_used"))
+    tree.update((k, float(report[k])) for k in ("initial_cost", "final_cost", "initial_rms_px", "final_rms_px", "time_s"))
+    return dict(tree, **parameters_tree(report))
 
 
 def main(argv=None):
@@ -56,17 +57,10 @@ def main(argv=None):
         if not sep:
             ap.error("--option takes NAME=VALUE, not %r" % item)
         options[name] = float(value) if name.endswith(("_px", "huber_a")) else int(value, 0)
-    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
-    detections = a.detections or os.path.join(a.project_path, "marker_detections.json")
-    intrinsics = a.intrinsics or os.path.join(a.project_path, "camera_intrinsics.json")
+    recon = _io.project_file(a.project_path, a.map, "reconstruction.json", "map", "no map to calibrate against")
+    detections = _io.project_file(a.project_path, a.detections, "marker_detections.json", "detection file")
+    intrinsics = _io.project_file(a.project_path, a.intrinsics, "camera_intrinsics.json", "camera model file")
     out = a.output or os.path.join(a.project_path, "camera_intrinsics_calibrated.json")
-    if not os.path.isfile(recon):
-        raise FileNotFoundError("no map to calibrate against: '%s' does not exist (run the mapping step first: "
-                                "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (recon, a.project_path))
-    if not os.path.isfile(detections):
-        raise FileNotFoundError("detection file '%s' does not exist" % detections)
-    if not os.path.isfile(intrinsics):
-        raise FileNotFoundError("camera model file '%s' does not exist" % intrinsics)
     tags, _, _ = _io.parseReconstructions(recon)
     det = _io.readDetectionResult(detections)
     rec = TagReconstructor(det, device=a.device)

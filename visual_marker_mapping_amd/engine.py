@@ -4,6 +4,7 @@ This is the flat-array layer under TagReconstructor.doBundleAdjustment; it mirro
 /root/reference/src/TagReconstructor.cpp:646-743 builds (a ceres::Problem) and solves.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -16,14 +17,62 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def default_options(**kw):
-    o = _lib.Options()
-    _lib.lib().vmm_ba_default_options(C.byref(o))
+@functools.lru_cache(maxsize=None)
+def _fields(cls, skip=()):
+    """The field names of a struct class in order, without `reserved` and `skip` (cached: solve() asks per call)."""
+    return tuple(k for k, _ in cls._fields_ if k != "reserved" and k not in skip)
+
+
+def _set_fields(struct, kw, what, nested=None):
+    """Sets the keyword fields of an options struct and returns it.  nested = (prefix, member): `<prefix><field>` sets a
+    field of that member struct.  An unknown name, `reserved` and the member itself are refused."""
+    names = _fields(type(struct), nested[1:] if nested else ())
     for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError("unknown solver option %r" % k)
-        setattr(o, k, v)
-    return o
+        if k in names:
+            setattr(struct, k, v)
+        elif nested and k.startswith(nested[0]) and k[len(nested[0]):] in _fields(type(getattr(struct, nested[1]))):
+            setattr(getattr(struct, nested[1]), k[len(nested[0]):], v)
+        else:
+            raise AttributeError("unknown %s option %r" % (what, k))
+    return struct
+
+
+def _options(cls, default_fn, kw, what, nested=None):
+    """An options struct with the library's defaults (vmm_ba_default_*_options), then the keyword fields."""
+    o = cls()
+    getattr(_lib.lib(), default_fn)(C.byref(o))
+    return _set_fields(o, kw, what, nested)
+
+
+def _struct_dict(s, skip=()):
+    """Field -> value in field order, without `reserved`: every report, summary and kernel-times struct."""
+    return {k: getattr(s, k) for k in _fields(type(s), skip)}
+
+
+def _summary(trace_capacity):
+    """A vmm_ba_summary for a solve and its optional trace buffer."""
+    s, buf = _lib.Summary(), None
+    if trace_capacity > 0:
+        buf = (_lib.Iteration * trace_capacity)()
+        s.trace, s.trace_capacity = buf, trace_capacity
+    return s, buf
+
+
+def _summary_dict(s, buf, capacity):
+    out = _struct_dict(s, ("trace", "trace_capacity"))
+    out["trace"] = [_struct_dict(buf[i]) for i in range(min(s.iterations, capacity))] if buf is not None else []
+    return out
+
+
+def _model_arrays(intr, dist, rows=None):
+    """The camera model as the C entries take it: intr (4,) and dist (5,), or with `rows` one row per camera."""
+    lead = () if rows is None else (rows,)
+    return (np.ascontiguousarray(intr, np.float64).reshape(lead + (4,)),
+            np.ascontiguousarray(dist, np.float64).reshape(lead + (5,)))
+
+
+def default_options(**kw):
+    return _options(_lib.Options, "vmm_ba_default_options", kw, "solver")
 
 
 class BundleAdjuster:
@@ -32,8 +81,7 @@ class BundleAdjuster:
                  landmarks=LANDMARK_TAG_POSES, structure_obs=None):
         L = _lib.lib()
         self._h = C.c_void_p()
-        self.intr = np.ascontiguousarray(intr, np.float64).reshape(4)
-        self.dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+        self.intr, self.dist = _model_arrays(intr, dist)
         cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
         tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
         tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
@@ -156,37 +204,20 @@ class BundleAdjuster:
     # ---- the hot path ----
     def solve(self, options=None, trace_capacity=0, **kw):
         o = options or default_options(**kw)
-        s = _lib.Summary()
-        buf = None
-        if trace_capacity > 0:
-            buf = (_lib.Iteration * trace_capacity)()
-            s.trace, s.trace_capacity = buf, trace_capacity
+        s, buf = _summary(trace_capacity)
         _lib.check(_lib.lib().vmm_ba_solve(self._h, C.byref(o), C.byref(s)))
-        out = {k: getattr(s, k) for k, _ in _lib.Summary._fields_
-               if k not in ("trace", "trace_capacity", "reserved")}
-        trace = []
-        if buf is not None:
-            for i in range(min(s.iterations, trace_capacity)):
-                trace.append({k: getattr(buf[i], k) for k, _ in _lib.Iteration._fields_ if k != "reserved"})
-        out["trace"] = trace
-        return out
+        return _summary_dict(s, buf, trace_capacity)
 
     def initialize(self, **options):
         """Initial poses from the detections alone (vmm_ba_initialize): overwrites the device state of every pose
         reachable from the constant poses (the fixed tag, set_constant_poses), whose current poses are kept.
         options: the fields of vmm_ba_init_options (sweeps, min_tag_observations, score_cap_px, refine_iterations).
         Returns (report dict, cam_reached, tag_reached) with boolean masks; unreached poses keep their state."""
-        o = _lib.InitOptions()
-        _lib.lib().vmm_ba_default_init_options(C.byref(o))
-        for k, v in options.items():
-            if k == "reserved" or not hasattr(o, k):
-                raise AttributeError("unknown initialisation option %r" % k)
-            setattr(o, k, v)
+        o = _options(_lib.InitOptions, "vmm_ba_default_init_options", options, "initialisation")
         r = _lib.InitReport()
         cam, tag = np.zeros(self.n_cams, np.uint8), np.zeros(self.n_tags, np.uint8)
         _lib.check(_lib.lib().vmm_ba_initialize(self._h, C.byref(o), C.byref(r), _ptr(cam), _ptr(tag)))
-        report = {k: getattr(r, k) for k, _ in _lib.InitReport._fields_ if k != "reserved"}
-        return report, cam.astype(bool), tag.astype(bool)
+        return _struct_dict(r), cam.astype(bool), tag.astype(bool)
 
     def cost(self, robustify=True, huber_a=1.0):
         c = C.c_double(0)
@@ -232,8 +263,7 @@ class BundleAdjuster:
     def set_intrinsics(self, intr, dist):
         """Replaces the handle's camera model (vmm_ba_set_intrinsics): every later call behaves as a handle created with
         it; the next solve captures its iteration graph again."""
-        intr = np.ascontiguousarray(intr, np.float64).reshape(4)
-        dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+        intr, dist = _model_arrays(intr, dist)
         _lib.check(_lib.lib().vmm_ba_set_intrinsics(self._h, _ptr(intr), _ptr(dist)))
         self.intr, self.dist = intr.copy(), dist.copy()
 
@@ -258,26 +288,16 @@ class BundleAdjuster:
         options as solve() takes them; the four named arguments are the fields of vmm_ba_selfcal_options.
         Returns (intr, dist, intr_cov (9, 9), report dict, summary of the last inner solve as solve() returns it)."""
         o = options or default_options(**kw)
-        so = _lib.SelfcalOptions()
-        _lib.lib().vmm_ba_default_selfcal_options(C.byref(so))
-        for name, v in (("max_outer_iterations", max_outer_iterations), ("refine_mask", refine_mask),
-                        ("parameter_tolerance", parameter_tolerance), ("function_tolerance", function_tolerance)):
-            if v is not None:
-                setattr(so, name, v)
-        s, r = _lib.Summary(), _lib.SelfcalReport()
-        buf = None
-        if trace_capacity > 0:
-            buf = (_lib.Iteration * trace_capacity)()
-            s.trace, s.trace_capacity = buf, trace_capacity
+        named = dict(max_outer_iterations=max_outer_iterations, refine_mask=refine_mask,
+                     parameter_tolerance=parameter_tolerance, function_tolerance=function_tolerance)
+        so = _options(_lib.SelfcalOptions, "vmm_ba_default_selfcal_options",
+                      {k: v for k, v in named.items() if v is not None}, "self-calibration")
+        (s, buf), r = _summary(trace_capacity), _lib.SelfcalReport()
         intr, dist, cov = np.zeros(4), np.zeros(5), np.zeros((9, 9))
         _lib.check(_lib.lib().vmm_ba_solve_selfcal(self._h, C.byref(o), C.byref(so), C.byref(s), C.byref(r), _ptr(intr),
                                                    _ptr(dist), _ptr(cov)))
         self.intr, self.dist = intr.copy(), dist.copy()
-        out = {k: getattr(s, k) for k, _ in _lib.Summary._fields_ if k not in ("trace", "trace_capacity", "reserved")}
-        out["trace"] = [{k: getattr(buf[i], k) for k, _ in _lib.Iteration._fields_ if k != "reserved"}
-                        for i in range(min(s.iterations, trace_capacity))] if buf is not None else []
-        report = {k: getattr(r, k) for k, _ in _lib.SelfcalReport._fields_}
-        return intr, dist, cov, report, out
+        return intr, dist, cov, _struct_dict(r), _summary_dict(s, buf, trace_capacity)
 
     # ---- diagnostics ----
     def eval_blocks(self, robustify=True, huber_a=1.0, want_W=True):
@@ -302,7 +322,7 @@ class BundleAdjuster:
         o = options or default_options()
         t = _lib.KernelTimes()
         _lib.check(_lib.lib().vmm_ba_time_kernels(self._h, C.byref(o), int(reps), C.byref(t)))
-        return {k: getattr(t, k) for k, _ in _lib.KernelTimes._fields_}
+        return _struct_dict(t)
 
 
 def joint_covariance(caa, cab, cbb):
@@ -325,8 +345,7 @@ def rccl_unique_id():
 
 def project_points(intr, dist, points_cam, device=0):
     """CameraModel::projectPoint (/root/reference/src/CameraModel.cpp:6-26) for an (n,3) batch."""
-    intr = np.ascontiguousarray(intr, np.float64).reshape(4)
-    dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+    intr, dist = _model_arrays(intr, dist)
     pts = np.ascontiguousarray(points_cam, np.float64).reshape(-1, 3)
     uv = np.zeros((len(pts), 2))
     _lib.check(_lib.lib().vmm_ba_project_points(_ptr(intr), _ptr(dist), len(pts), _ptr(pts), _ptr(uv), device))
@@ -337,8 +356,7 @@ def quad_poses(intr, dist, tag_wh, obs_px, device=0):
     """Both planar tag->camera poses of n tag observations from each tag's own four corners (vmm_ba_quad_poses; the
     role of solvePnPEigen at src/TagReconstructor.cpp:208 of the reference).  tag_wh (n, 2), obs_px (n, 8).
     Returns qt2 (n, 2, 7), lower RMS first, and rms2 (n, 2) in pixels (+inf: degenerate)."""
-    intr = np.ascontiguousarray(intr, np.float64).reshape(4)
-    dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+    intr, dist = _model_arrays(intr, dist)
     px = np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8)
     wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
     if len(wh) != len(px):
@@ -350,25 +368,26 @@ def quad_poses(intr, dist, tag_wh, obs_px, device=0):
 
 
 def default_localize_options(**kw):
-    o = _lib.LocalizeOptions()
-    _lib.lib().vmm_ba_default_localize_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError("unknown localisation option %r" % k)
-        setattr(o, k, v)
-    return o
+    return _options(_lib.LocalizeOptions, "vmm_ba_default_localize_options", kw, "localisation")
 
 
-# vmm_ba_localize_result
-_LOC_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_obs", "<i4"), ("n_inlier_obs", "<i4"), ("trials", "<i4"),
-                              ("rms_px", "<f8"), ("cost", "<f8")])
+# one result layout for images, frames and points
+assert _lib.LocalizeResult._fields_ == _lib.TriangulateResult._fields_
 
 
-def _map_batch_arrays(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px):
-    """The camera model, the map and the batch of images as vmm_ba_localize and vmm_ba_calibrate take them: contiguous
-    arrays of the C types, refused when their lengths do not fit together."""
-    intr = np.ascontiguousarray(intr, np.float64).reshape(4)
-    dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+def _results(n):
+    """n vmm_ba_localize_result (or vmm_ba_triangulate_result) as one structured array, handed to C by pointer."""
+    return np.zeros(n, np.dtype(_lib.LocalizeResult))
+
+
+def _result_dicts(arr):
+    """One dict per item of _results: status, n_obs, n_inlier_obs, trials, rms_px, cost."""
+    return [dict(zip(arr.dtype.names, row)) for row in arr.tolist()]
+
+
+def _map_batch_arrays(tag_qt, tag_wh, img_start, obs_tag, obs_px):
+    """The map and the batch of images as vmm_ba_localize and vmm_ba_calibrate take them: contiguous arrays of the C
+    types, refused when their lengths do not fit together."""
     tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
     tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
     img_start = np.ascontiguousarray(img_start, np.int64).reshape(-1)
@@ -380,7 +399,7 @@ def _map_batch_arrays(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px):
         raise ValueError("observation arrays differ in length")
     if len(img_start) < 1 or img_start[-1] != len(obs_tag):
         raise ValueError("img_start must have n_imgs + 1 entries and end at the number of observations")
-    return intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px
+    return tag_qt, tag_wh, img_start, obs_tag, obs_px
 
 
 def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
@@ -390,30 +409,30 @@ def localize(intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, *
     observations [img_start[i], img_start[i + 1]) of obs_tag (n_obs,) and obs_px (n_obs, 8).  options: the fields of
     vmm_ba_localize_options.  Returns (cam_qt (n_imgs, 7) world->camera, cam_cov (n_imgs, 6, 6), obs_inlier (n_obs,)
     bool, results: one dict per image with status, n_obs, n_inlier_obs, trials, rms_px, cost)."""
-    intr, dist, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr, dist, tag_qt, tag_wh, img_start, obs_tag,
-                                                                               obs_px)
+    intr, dist = _model_arrays(intr, dist)
+    tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(tag_qt, tag_wh, img_start, obs_tag, obs_px)
     o = default_localize_options(**options)
     n_imgs = len(img_start) - 1
     cam_qt, cam_cov = np.zeros((n_imgs, 7)), np.zeros((n_imgs, 6, 6))
-    inl = np.zeros(len(obs_tag), np.uint8)
-    res = (_lib.LocalizeResult * max(n_imgs, 1))()
+    inl, res = np.zeros(len(obs_tag), np.uint8), _results(n_imgs)
     _lib.check(_lib.lib().vmm_ba_localize(_ptr(intr), _ptr(dist), len(tag_qt), _ptr(tag_qt), _ptr(tag_wh), n_imgs,
                                           _ptr(img_start), _ptr(obs_tag), _ptr(obs_px), C.byref(o), _ptr(cam_qt),
-                                          _ptr(cam_cov), _ptr(inl), C.cast(res, C.c_void_p), device))
-    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_imgs)
-    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_imgs)]
-    return cam_qt, cam_cov, inl.astype(bool), results
+                                          _ptr(cam_cov), _ptr(inl), _ptr(res), device))
+    return cam_qt, cam_cov, inl.astype(bool), _result_dicts(res)
 
 
-def _rig_arrays(intr, dist, ext_qt):
-    """The models and extrinsics of a rig's cameras as vmm_ba_rig_localize takes them; returns them and the number of
-    cameras."""
-    intr = np.ascontiguousarray(intr, np.float64).reshape(-1, 4)
-    dist = np.ascontiguousarray(dist, np.float64).reshape(-1, 5)
+def _rig_arrays(intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px):
+    """The models and extrinsics of a rig's K cameras, the map and the batch of frames as vmm_ba_rig_localize takes them;
+    returns the eight arrays, K and the number of frames."""
+    intr, dist = _model_arrays(intr, dist, -1)
     ext_qt = np.ascontiguousarray(ext_qt, np.float64).reshape(-1, 7)
     if not len(intr) == len(dist) == len(ext_qt):
         raise ValueError("intr, dist and ext_qt must have one row per camera of the rig")
-    return intr, dist, ext_qt, len(ext_qt)
+    tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(tag_qt, tag_wh, img_start, obs_tag, obs_px)
+    n_rig_cams, n_slots = len(ext_qt), len(img_start) - 1
+    if n_rig_cams < 1 or n_slots % n_rig_cams:
+        raise ValueError("img_start must have n_frames * K + 1 entries for the K >= 1 cameras of the rig")
+    return intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px, n_rig_cams, n_slots // n_rig_cams
 
 
 def rig_localize(intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
@@ -422,38 +441,21 @@ def rig_localize(intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px,
     engine.localize takes them, image (f, c) being slot f * K + c of img_start (n_frames * K + 1,); a missing image is an
     empty range.  options: the fields of vmm_ba_localize_options.  Returns (rig_qt (n_frames, 7) world->rig, rig_cov
     (n_frames, 6, 6), obs_inlier (n_obs,) bool, results: one dict per frame as engine.localize gives per image)."""
-    intr, dist, ext_qt, n_rig_cams = _rig_arrays(intr, dist, ext_qt)
-    _, _, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr[:1], dist[:1], tag_qt, tag_wh, img_start,
-                                                                         obs_tag, obs_px)
-    if n_rig_cams < 1 or (len(img_start) - 1) % n_rig_cams:
-        raise ValueError("img_start must have n_frames * K + 1 entries for the K >= 1 cameras of the rig")
+    intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px, n_rig_cams, n_frames = _rig_arrays(
+        intr, dist, ext_qt, tag_qt, tag_wh, img_start, obs_tag, obs_px)
     o = default_localize_options(**options)
-    n_frames = (len(img_start) - 1) // n_rig_cams
     rig_qt, rig_cov = np.zeros((n_frames, 7)), np.zeros((n_frames, 6, 6))
-    inl = np.zeros(len(obs_tag), np.uint8)
-    res = (_lib.LocalizeResult * max(n_frames, 1))()
+    inl, res = np.zeros(len(obs_tag), np.uint8), _results(n_frames)
     _lib.check(_lib.lib().vmm_ba_rig_localize(n_rig_cams, _ptr(intr), _ptr(dist), _ptr(ext_qt), len(tag_qt), _ptr(tag_qt),
                                               _ptr(tag_wh), n_frames, _ptr(img_start), _ptr(obs_tag), _ptr(obs_px),
-                                              C.byref(o), _ptr(rig_qt), _ptr(rig_cov), _ptr(inl), C.cast(res, C.c_void_p),
-                                              device))
-    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_frames)
-    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_frames)]
-    return rig_qt, rig_cov, inl.astype(bool), results
+                                              C.byref(o), _ptr(rig_qt), _ptr(rig_cov), _ptr(inl), _ptr(res), device))
+    return rig_qt, rig_cov, inl.astype(bool), _result_dicts(res)
 
 
 def default_rig_calibrate_options(**kw):
     """vmm_ba_rig_calibrate_options with its defaults; keywords are its fields, `loc_<field>` sets a field of the initial
     localisation's options."""
-    o = _lib.RigCalibrateOptions()
-    _lib.lib().vmm_ba_default_rig_calibrate_options(C.byref(o))
-    for k, v in kw.items():
-        if k.startswith("loc_") and k[4:] in dict(_lib.LocalizeOptions._fields_):
-            setattr(o.loc, k[4:], v)
-        elif k not in ("loc", "reserved") and hasattr(o, k):
-            setattr(o, k, v)
-        else:
-            raise AttributeError("unknown rig calibration option %r" % k)
-    return o
+    return _options(_lib.RigCalibrateOptions, "vmm_ba_default_rig_calibrate_options", kw, "rig calibration", ("loc_", "loc"))
 
 
 def rig_calibrate(intr, dist, ext_qt0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
@@ -463,26 +465,17 @@ def rig_calibrate(intr, dist, ext_qt0, tag_qt, tag_wh, img_start, obs_tag, obs_p
     default every camera but 0), `loc_<field>` for those of the initial localisation.  Returns (ext_qt (K, 7), ext_cov
     (6 K, 6 K), rig_qt (n_frames, 7), rig_cov (n_frames, 6, 6) the joint marginals, obs_inlier (n_obs,) bool, results:
     one dict per frame, report: dict of vmm_ba_rig_calibrate_report)."""
-    intr, dist, ext_qt0, n_rig_cams = _rig_arrays(intr, dist, ext_qt0)
-    _, _, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr[:1], dist[:1], tag_qt, tag_wh, img_start,
-                                                                         obs_tag, obs_px)
-    if n_rig_cams < 1 or (len(img_start) - 1) % n_rig_cams:
-        raise ValueError("img_start must have n_frames * K + 1 entries for the K >= 1 cameras of the rig")
+    intr, dist, ext_qt0, tag_qt, tag_wh, img_start, obs_tag, obs_px, n_rig_cams, n_frames = _rig_arrays(
+        intr, dist, ext_qt0, tag_qt, tag_wh, img_start, obs_tag, obs_px)
     o = default_rig_calibrate_options(**options)
-    n_frames = (len(img_start) - 1) // n_rig_cams
     ext_qt, ext_cov = np.zeros((n_rig_cams, 7)), np.zeros((6 * n_rig_cams, 6 * n_rig_cams))
     rig_qt, rig_cov = np.zeros((n_frames, 7)), np.zeros((n_frames, 6, 6))
-    inl = np.zeros(len(obs_tag), np.uint8)
-    res = (_lib.LocalizeResult * max(n_frames, 1))()
-    rep = _lib.RigCalibrateReport()
+    inl, res, rep = np.zeros(len(obs_tag), np.uint8), _results(n_frames), _lib.RigCalibrateReport()
     _lib.check(_lib.lib().vmm_ba_rig_calibrate(n_rig_cams, _ptr(intr), _ptr(dist), _ptr(ext_qt0), len(tag_qt), _ptr(tag_qt),
                                                _ptr(tag_wh), n_frames, _ptr(img_start), _ptr(obs_tag), _ptr(obs_px),
                                                C.byref(o), _ptr(ext_qt), _ptr(ext_cov), _ptr(rig_qt), _ptr(rig_cov),
-                                               _ptr(inl), C.cast(res, C.c_void_p), C.byref(rep), device))
-    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_frames)
-    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_frames)]
-    report = {k: getattr(rep, k) for k, _ in _lib.RigCalibrateReport._fields_}
-    return ext_qt, ext_cov, rig_qt, rig_cov, inl.astype(bool), results, report
+                                               _ptr(inl), _ptr(res), C.byref(rep), device))
+    return ext_qt, ext_cov, rig_qt, rig_cov, inl.astype(bool), _result_dicts(res), _struct_dict(rep)
 
 
 def _pose_matrix(qt):
@@ -528,16 +521,7 @@ def rig_extrinsics_start(n_rig_cams, n_frames, cam_qt, results):
 def default_calibrate_options(**kw):
     """vmm_ba_calibrate_options with its defaults; keywords are its fields, `loc_<field>` sets a field of the initial
     localisation's options (vmm_ba_calibrate_options.loc)."""
-    o = _lib.CalibrateOptions()
-    _lib.lib().vmm_ba_default_calibrate_options(C.byref(o))
-    for k, v in kw.items():
-        if k.startswith("loc_") and k[4:] in dict(_lib.LocalizeOptions._fields_):
-            setattr(o.loc, k[4:], v)
-        elif k not in ("loc", "reserved") and hasattr(o, k):
-            setattr(o, k, v)
-        else:
-            raise AttributeError("unknown calibration option %r" % k)
-    return o
+    return _options(_lib.CalibrateOptions, "vmm_ba_default_calibrate_options", kw, "calibration", ("loc_", "loc"))
 
 
 def calibrate(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0, **options):
@@ -547,33 +531,22 @@ def calibrate(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px, device=0
     those of the initial localisation.  Returns (intr (4,), dist (5,), intr_cov (9, 9), cam_qt (n_imgs, 7) world->camera,
     cam_cov (n_imgs, 6, 6) the joint marginals, obs_inlier (n_obs,) bool, results: one dict per image as
     engine.localize, report: dict of vmm_ba_calibrate_report)."""
-    intr0, dist0, tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(intr0, dist0, tag_qt, tag_wh, img_start, obs_tag,
-                                                                                  obs_px)
+    intr0, dist0 = _model_arrays(intr0, dist0)
+    tag_qt, tag_wh, img_start, obs_tag, obs_px = _map_batch_arrays(tag_qt, tag_wh, img_start, obs_tag, obs_px)
     o = default_calibrate_options(**options)
     n_imgs = len(img_start) - 1
     intr, dist, intr_cov = np.zeros(4), np.zeros(5), np.zeros((9, 9))
     cam_qt, cam_cov = np.zeros((n_imgs, 7)), np.zeros((n_imgs, 6, 6))
-    inl = np.zeros(len(obs_tag), np.uint8)
-    res = (_lib.LocalizeResult * max(n_imgs, 1))()
-    rep = _lib.CalibrateReport()
+    inl, res, rep = np.zeros(len(obs_tag), np.uint8), _results(n_imgs), _lib.CalibrateReport()
     _lib.check(_lib.lib().vmm_ba_calibrate(_ptr(intr0), _ptr(dist0), len(tag_qt), _ptr(tag_qt), _ptr(tag_wh), n_imgs,
                                            _ptr(img_start), _ptr(obs_tag), _ptr(obs_px), C.byref(o), _ptr(intr), _ptr(dist),
-                                           _ptr(intr_cov), _ptr(cam_qt), _ptr(cam_cov), _ptr(inl), C.cast(res, C.c_void_p),
+                                           _ptr(intr_cov), _ptr(cam_qt), _ptr(cam_cov), _ptr(inl), _ptr(res),
                                            C.byref(rep), device))
-    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_imgs)
-    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_imgs)]
-    report = {k: getattr(rep, k) for k, _ in _lib.CalibrateReport._fields_}
-    return intr, dist, intr_cov, cam_qt, cam_cov, inl.astype(bool), results, report
+    return intr, dist, intr_cov, cam_qt, cam_cov, inl.astype(bool), _result_dicts(res), _struct_dict(rep)
 
 
 def default_triangulate_options(**kw):
-    o = _lib.TriangulateOptions()
-    _lib.lib().vmm_ba_default_triangulate_options(C.byref(o))
-    for k, v in kw.items():
-        if k == "reserved" or not hasattr(o, k):
-            raise AttributeError("unknown triangulation option %r" % k)
-        setattr(o, k, v)
-    return o
+    return _options(_lib.TriangulateOptions, "vmm_ba_default_triangulate_options", kw, "triangulation")
 
 
 def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, device=0, **options):
@@ -585,8 +558,7 @@ def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, dev
     xyz_cov_cams (n_pts, 3, 3) the part propagated from cam_cov, camera by camera without their correlations (zeros
     without cam_cov), obs_inlier (n_obs,) bool, results: one dict per point with status, n_obs, n_inlier_obs, trials,
     rms_px, cost)."""
-    intr = np.ascontiguousarray(intr, np.float64).reshape(4)
-    dist = np.ascontiguousarray(dist, np.float64).reshape(5)
+    intr, dist = _model_arrays(intr, dist)
     cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
     pt_start = np.ascontiguousarray(pt_start, np.int64).reshape(-1)
     obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
@@ -602,15 +574,11 @@ def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, dev
     o = default_triangulate_options(**options)
     n_pts = len(pt_start) - 1
     xyz, cov, cov_cams = np.zeros((n_pts, 3)), np.zeros((n_pts, 3, 3)), np.zeros((n_pts, 3, 3))
-    inl = np.zeros(len(obs_cam), np.uint8)
-    res = (_lib.TriangulateResult * max(n_pts, 1))()
-    _lib.check(_lib.lib().vmm_ba_triangulate(_ptr(intr), _ptr(dist), len(cam_qt), _ptr(cam_qt),
-                                             None if cam_cov is None else _ptr(cam_cov), n_pts, _ptr(pt_start),
-                                             _ptr(obs_cam), _ptr(obs_uv), C.byref(o), _ptr(xyz), _ptr(cov), _ptr(cov_cams),
-                                             _ptr(inl), C.cast(res, C.c_void_p), device))
-    r = np.frombuffer(res, dtype=_LOC_RESULT_DTYPE, count=n_pts)   # vmm_ba_triangulate_result has the same layout
-    results = [{k: r[k][i].item() for k in r.dtype.names} for i in range(n_pts)]
-    return xyz, cov, cov_cams, inl.astype(bool), results
+    inl, res = np.zeros(len(obs_cam), np.uint8), _results(n_pts)
+    _lib.check(_lib.lib().vmm_ba_triangulate(_ptr(intr), _ptr(dist), len(cam_qt), _ptr(cam_qt), _ptr(cam_cov), n_pts,
+                                             _ptr(pt_start), _ptr(obs_cam), _ptr(obs_uv), C.byref(o), _ptr(xyz), _ptr(cov),
+                                             _ptr(cov_cams), _ptr(inl), _ptr(res), device))
+    return xyz, cov, cov_cams, inl.astype(bool), _result_dicts(res)
 
 
 def pose_plus(qt, delta, device=0):

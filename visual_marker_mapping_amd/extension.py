@@ -30,16 +30,10 @@ def main(argv=None):
     ap.add_argument("--output", default=None, help="output file (default: <project>/reconstruction_extended.json)")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     a = ap.parse_args(argv)
-    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
-    detections = os.path.join(a.project_path, "marker_detections.json")
-    intrinsics = os.path.join(a.project_path, "camera_intrinsics.json")
+    recon = _io.project_file(a.project_path, a.map, "reconstruction.json", "map", "no map to extend")
+    detections = _io.project_file(a.project_path, None, "marker_detections.json", None)
+    intrinsics = _io.project_file(a.project_path, None, "camera_intrinsics.json", None)
     out = a.output or os.path.join(a.project_path, "reconstruction_extended.json")
-    if not os.path.isfile(recon):
-        raise FileNotFoundError("no map to extend: '%s' does not exist (run the mapping step first: "
-                                "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (recon, a.project_path))
-    for f in (detections, intrinsics):
-        if not os.path.isfile(f):
-            raise FileNotFoundError("'%s' does not exist" % f)
     tags, _, _ = _io.parseReconstructions(recon)
     camera_model = _io.readCameraModel(intrinsics)
     rec = TagReconstructor(_io.readDetectionResult(detections), device=a.device)

@@ -20,6 +20,7 @@ import os
 
 import numpy as np
 
+from . import _lib
 from .tag_reconstructor import (Camera, CameraModel, DetectionResult, ReconstructedTag, Tag, TagImg,
                                 TagObservation)
 
@@ -115,6 +116,47 @@ def _vector(node, n):
     return np.array(vals, np.float64)
 
 
+# ---- the shared vocabulary of the output trees ----------------------------------------------------------
+
+
+def matrix_tree(m):
+    """The dynamic-matrix form of SURVEY.md Appendix B, spelling included: row-major {rows, cols, coefficents}."""
+    m = np.asarray(m, np.float64)
+    return {"rows": int(m.shape[0]), "cols": int(m.shape[1]), "coefficents": [float(v) for v in m.reshape(-1)]}
+
+
+def matrixFromPropertyTree(t, rows, cols):
+    """The rows x cols matrix of a matrix_tree; any other number of coefficients is refused."""
+    return _vector(_children(t, "coefficents"), rows * cols).reshape(rows, cols)
+
+
+def pose_tree(id, qt):
+    """A pose (qw, qx, qy, qz, tx, ty, tz) as reconstruction.json holds a camera; id None: without the `id` key, as
+    rig.json holds an `extrinsic`."""
+    return dict({} if id is None else {"id": int(id)},
+                rotation=[float(v) for v in qt[:4]], translation=[float(v) for v in qt[4:]])
+
+
+def localized_pose_tree(id, r):
+    """pose_tree extended by the per-item report of a localisation: an image of localization.json, a frame of
+    rig_localization.json."""
+    return dict(pose_tree(id, r["pose"]), status=_lib.LOC_STATUS_NAMES[r["status"]], num_observations=int(r["n_obs"]),
+                num_inlier_observations=int(r["n_inlier_obs"]), rms_px=float(r["rms_px"]),
+                covariance=matrix_tree(r["covariance"]))
+
+
+def project_file(project, override, name, what, hint=None):
+    """`override`, or <project>/<name>; FileNotFoundError when it is not a file.  `hint` ("no map to extend") turns the
+    message into the one that sends the user to the mapping step."""
+    path = override or os.path.join(project, name)
+    if not os.path.isfile(path):
+        if hint:
+            raise FileNotFoundError("%s: '%s' does not exist (run the mapping step first: "
+                                    "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (hint, path, project))
+        raise FileNotFoundError("%s'%s' does not exist" % (what + " " if what else "", path))
+    return path
+
+
 # ---- camera_intrinsics.json ----------------------------------------------------------------------------
 
 
@@ -193,10 +235,22 @@ def exportReconstructions(path, reconstructedTags, reconstructedCameras, camMode
         for i, c in enumerate(tag.computeMarkerCorners3D()):
             corners.append({"marker_id": tag.id, "corner_index": i, "coords": [float(v) for v in c]})
     for _, cam in sorted(reconstructedCameras.items()):
-        cams.append({"id": cam.cameraId, "rotation": [float(v) for v in cam.q],
-                     "translation": [float(v) for v in cam.t]})
+        cams.append(pose_tree(cam.cameraId, np.concatenate([cam.q, cam.t])))
     write_json(path, {"reconstructed_tags": tags, "reconstructed_marker_corners": corners,
                       "reconstructed_cameras": cams, "camera_model": cameraModelToPropertyTree(camModel)})
+
+
+def camerasFromPropertyTree(t, ok_only=False):
+    """{imageId: Camera} from a tree with a `reconstructed_cameras` list; ok_only skips the entries whose `status` is
+    not "ok" (localization.json)."""
+    cams = {}
+    for pt in _children(t, "reconstructed_cameras"):
+        if ok_only and "status" in pt and pt["status"] != "ok":
+            continue
+        i = _get(pt, "id", int)
+        cams[i] = Camera(cameraId=i, q=_vector(_children(pt, "rotation"), 4),
+                         t=_vector(_children(pt, "translation"), 3))
+    return cams
 
 
 def parseReconstructions(path):
@@ -206,17 +260,13 @@ def parseReconstructions(path):
     cameras onto key -1), the camera ids written by exportReconstructions are read
     back."""
     t = read_json(path)
-    tags, cams = {}, {}
+    tags = {}
     for pt in _children(t, "reconstructed_tags"):
         i = _get(pt, "id", int)
         tags[i] = ReconstructedTag(id=i, tagType=_get(pt, "type", str), q=_vector(_children(pt, "rotation"), 4),
                                    t=_vector(_children(pt, "translation"), 3),
                                    tagWidth=_get(pt, "width", float), tagHeight=_get(pt, "height", float))
-    for pt in _children(t, "reconstructed_cameras"):
-        i = _get(pt, "id", int)
-        cams[i] = Camera(cameraId=i, q=_vector(_children(pt, "rotation"), 4),
-                         t=_vector(_children(pt, "translation"), 3))
-    return tags, cams, propertyTreeToCameraModel(_children(t, "camera_model"))
+    return tags, camerasFromPropertyTree(t), propertyTreeToCameraModel(_children(t, "camera_model"))
 
 
 # ---- point_detections.json -------------------------------------------------------------------------------

@@ -14,25 +14,13 @@ import argparse
 import os
 import sys
 
-from . import _lib
 from . import io as _io
 from .tag_reconstructor import TagReconstructor
 
 
 def localization_tree(ids, report):
     """The property tree of localization.json for the per-image report of computeRelativeCameraPosesFromImgs."""
-    cams = []
-    for i in ids:
-        r = report[i]
-        cams.append({"id": int(i), "rotation": [float(v) for v in r["pose"][:4]],
-                     "translation": [float(v) for v in r["pose"][4:]],
-                     "status": _lib.LOC_STATUS_NAMES[r["status"]],
-                     "num_observations": int(r["n_obs"]),
-                     "num_inlier_observations": int(r["n_inlier_obs"]),
-                     "rms_px": float(r["rms_px"]),
-                     "covariance": {"rows": 6, "cols": 6,
-                                    "coefficents": [float(v) for v in r["covariance"].reshape(-1)]}})
-    return {"reconstructed_cameras": cams}
+    return {"reconstructed_cameras": [_io.localized_pose_tree(i, report[i]) for i in ids]}
 
 
 def main(argv=None):
@@ -42,14 +30,9 @@ def main(argv=None):
     ap.add_argument("--output", default=None, help="output file (default: <project>/localization.json)")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     a = ap.parse_args(argv)
-    recon = os.path.join(a.project_path, "reconstruction.json")
-    detections = a.detections or os.path.join(a.project_path, "marker_detections.json")
+    recon = _io.project_file(a.project_path, None, "reconstruction.json", "map", "no map to localise against")
+    detections = _io.project_file(a.project_path, a.detections, "marker_detections.json", "detection file")
     out = a.output or os.path.join(a.project_path, "localization.json")
-    if not os.path.isfile(recon):
-        raise FileNotFoundError("no map to localise against: '%s' does not exist (run the mapping step first: "
-                                "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (recon, a.project_path))
-    if not os.path.isfile(detections):
-        raise FileNotFoundError("detection file '%s' does not exist" % detections)
     tags, _, model = _io.parseReconstructions(recon)
     det = _io.readDetectionResult(detections)
     rec = TagReconstructor(det, device=a.device)

@@ -51,8 +51,7 @@ def write_rig(path, intrinsics_files, images, extrinsics=None):
     for c, (intr, names) in enumerate(zip(intrinsics_files, images)):
         cam = {"intrinsics": intr}
         if extrinsics is not None:
-            cam["extrinsic"] = {"rotation": [float(v) for v in extrinsics[c][:4]],
-                                "translation": [float(v) for v in extrinsics[c][4:]]}
+            cam["extrinsic"] = _io.pose_tree(None, extrinsics[c])
         cam["images"] = ["null" if n is None else n for n in names]
         cams.append(cam)
     _io.write_json(path, {"cameras": cams})
@@ -60,18 +59,8 @@ def write_rig(path, intrinsics_files, images, extrinsics=None):
 
 def rig_tree(report):
     """The property tree of rig_localization.json for the report of computeRigPosesFromFrames."""
-    frames = []
-    for f, r in enumerate(report["frames"]):
-        frames.append({"id": f, "rotation": [float(v) for v in r["pose"][:4]],
-                       "translation": [float(v) for v in r["pose"][4:]],
-                       "status": _lib.LOC_STATUS_NAMES[r["status"]],
-                       "num_observations": int(r["n_obs"]),
-                       "num_inlier_observations": int(r["n_inlier_obs"]),
-                       "rms_px": float(r["rms_px"]),
-                       "covariance": {"rows": 6, "cols": 6, "coefficents": [float(v) for v in r["covariance"].reshape(-1)]}})
-    ext = [{"id": c, "rotation": [float(v) for v in e[:4]], "translation": [float(v) for v in e[4:]]}
-           for c, e in enumerate(report["extrinsics"])]
-    return {"extrinsics": ext, "frames": frames}
+    return {"extrinsics": [_io.pose_tree(c, e) for c, e in enumerate(report["extrinsics"])],
+            "frames": [_io.localized_pose_tree(f, r) for f, r in enumerate(report["frames"])]}
 
 
 def calibrated_tree(rig_tree_in, report):
@@ -80,12 +69,10 @@ def calibrated_tree(rig_tree_in, report):
     cams = []
     for c, cam in enumerate(_io._children(rig_tree_in, "cameras")):
         e, cov = report["extrinsics"][c], report["covariance"][6 * c:6 * c + 6, 6 * c:6 * c + 6]
-        cams.append({"intrinsics": cam["intrinsics"],
-                     "extrinsic": {"rotation": [float(v) for v in e[:4]], "translation": [float(v) for v in e[4:]],
-                                   "covariance": {"rows": 6, "cols": 6, "coefficents": [float(v) for v in cov.reshape(-1)]}},
+        cams.append({"intrinsics": cam["intrinsics"], "extrinsic": dict(_io.pose_tree(None, e), covariance=_io.matrix_tree(cov)),
                      "images": cam["images"]})
     rep = {k: (_lib.CAL_STATUS_NAMES[v] if k == "status" else v) for k, v in report.items()
-           if k not in ("extrinsics", "covariance", "rigs", "frames", "reserved")}
+           if k not in ("extrinsics", "covariance", "rigs", "frames")}
     return {"cameras": cams, "report": rep}
 
 
@@ -98,13 +85,10 @@ def main(argv=None):
     ap.add_argument("--output", default=None, help="output file (default: <project>/rig_localization.json)")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     a = ap.parse_args(argv)
-    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
-    rig = a.rig or os.path.join(a.project_path, "rig.json")
-    detections = os.path.join(a.project_path, "marker_detections.json")
+    recon = _io.project_file(a.project_path, a.map, "reconstruction.json", "map")
+    rig = _io.project_file(a.project_path, a.rig, "rig.json", "rig description")
+    detections = _io.project_file(a.project_path, None, "marker_detections.json", "detection file")
     out = a.output or os.path.join(a.project_path, "rig_localization.json")
-    for what, path in (("map", recon), ("rig description", rig), ("detection file", detections)):
-        if not os.path.isfile(path):
-            raise FileNotFoundError("%s '%s' does not exist" % (what, path))
     tags, _, _ = _io.parseReconstructions(recon)
     det = _io.readDetectionResult(detections)
     models, extrinsics, images = read_rig(rig)

@@ -23,22 +23,16 @@ import sys
 
 from . import _lib
 from . import io as _io
-from .calibration import PARAMETER_NAMES
+from .calibration import parameters_tree
 from .tag_reconstructor import TagReconstructor
 
 
 def selfcalibration_tree(report):
     """The property tree of selfcalibration.json for TagReconstructor.lastSelfCalibrationReport."""
     tree = {"status": _lib.CAL_STATUS_NAMES[report["status"]]}
-    for k in ("outer_iterations", "accepted", "inner_lm_iterations"):
-        tree[k] = int(report[k])
-    for k in ("initial_cost", "final_cost", "time_s"):
-        tree[k] = float(report[k])
-    tree["parameter_names"] = list(PARAMETER_NAMES)
-    tree["parameters"] = [float(v) for v in report["intrinsics"]]
-    tree["standard_deviations"] = [float(v) for v in report["std"]]
-    tree["covariance"] = {"rows": 9, "cols": 9, "coefficents": [float(v) for v in report["covariance"].reshape(-1)]}
-    return tree
+    tree.update((k, int(report[k])) for k in ("outer_iterations", "accepted", "inner_lm_iterations"))
+    tree.update((k, float(report[k])) for k in ("initial_cost", "final_cost", "time_s"))
+    return dict(tree, **parameters_tree(report))
 
 
 def main(argv=None):
@@ -57,17 +51,12 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not 0 <= a.refine_mask <= 0x1FF:
         ap.error("--refine_mask must lie in [0, 0x1FF]")
-    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
-    detections = a.detections or os.path.join(a.project_path, "marker_detections.json")
-    intrinsics = a.intrinsics or os.path.join(a.project_path, "camera_intrinsics.json")
+    recon = _io.project_file(a.project_path, a.map, "reconstruction.json", "reconstruction", "no reconstruction to refine")
+    detections = _io.project_file(a.project_path, a.detections, "marker_detections.json", "detection file")
+    # the default model file may be missing (then the map's model is the start); one that was named may not
+    intrinsics = (_io.project_file(a.project_path, a.intrinsics, None, "camera model file") if a.intrinsics
+                  else os.path.join(a.project_path, "camera_intrinsics.json"))
     out = a.output or os.path.join(a.project_path, "reconstruction_selfcalibrated.json")
-    if not os.path.isfile(recon):
-        raise FileNotFoundError("no reconstruction to refine: '%s' does not exist (run the mapping step first: "
-                                "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (recon, a.project_path))
-    if not os.path.isfile(detections):
-        raise FileNotFoundError("detection file '%s' does not exist" % detections)
-    if a.intrinsics and not os.path.isfile(intrinsics):
-        raise FileNotFoundError("camera model file '%s' does not exist" % intrinsics)
     tags, cams, map_model = _io.parseReconstructions(recon)
     if not tags or not cams:
         raise RuntimeError("'%s' holds no reconstructed tags or no reconstructed cameras" % recon)

@@ -197,6 +197,21 @@ class TagReconstructor:
     def setOriginTagId(self, originTagId):
         self.originTagId = int(originTagId)
 
+    # -- the camera model as the engine takes and returns it --
+    def _model_args(self):
+        m = self.camModel
+        return [m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients
+
+    def _with_model(self, intr, dist):
+        """camModel with the nine numbers replaced; the resolutions stay."""
+        return CameraModel(fx=float(intr[0]), fy=float(intr[1]), cx=float(intr[2]), cy=float(intr[3]),
+                           distortionCoefficients=dist, verticalResolution=self.camModel.verticalResolution,
+                           horizontalResolution=self.camModel.horizontalResolution)
+
+    @staticmethod
+    def _model_report(report, intr, dist, cov):
+        return dict(report, intrinsics=np.concatenate([intr, dist]), covariance=cov, std=np.sqrt(np.diag(cov)))
+
     def startReconstruction(self, numThreads=1, deviceResident=True):
         """deviceResident: ONE device handle holds every image, tag and observation of the detection result for
         the whole run and each of the N+2 bundle adjustments / prunings only sends an observation mask and the
@@ -350,14 +365,10 @@ class TagReconstructor:
         result's tag list); which of them join the map is the caller's rule."""
         p = self._pack_resident(for_ba=True)
         full = self._full
-        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
-        try:
+        with self._handle(p, elimination=_engine.ELIM_AUTO) as ba:
             ba.set_observation_mask(None)
             report, cam_ok, tag_ok = ba.initialize(**init_options)
             cam, tag = ba.get_state()
-        except Exception:
-            self._drop_cached()
-            raise
         self.lastInitReport = report
         print("Initialized %d of %d cameras and %d of %d tags in %d rounds, average reprojection error %g"
               % (report["cams_reached"], len(cam_ok), report["tags_reached"], len(tag_ok), report["rounds"],
@@ -444,6 +455,19 @@ class TagReconstructor:
         R, t = _pnp.solvePnPRansac(np.asarray(X), np.asarray(px), intr, dist, seed=int(imageId) & 0x7FFFFFFF)
         return _pnp.quat_from_R(R), t
 
+    def _map_arrays(self):
+        """The reconstructed tags in id order: (tag_ids, tag_qt (n, 7), tag_wh (n, 2))."""
+        tag_ids = sorted(self.reconstructedTags)
+        tags = [self.reconstructedTags[t] for t in tag_ids]
+        return (tag_ids, np.array([np.concatenate([t.q, t.t]) for t in tags], np.float64).reshape(-1, 7),
+                np.array([[t.tagWidth, t.tagHeight] for t in tags], np.float64).reshape(-1, 2))
+
+    @staticmethod
+    def _item_report(res, pose, cov, order, inl, b, e):
+        """One image's or frame's entry of a localisation report: the result's fields, the pose, its covariance and the
+        observations [b, e) with their inlier flags."""
+        return dict(res, pose=pose.copy(), covariance=cov.copy(), observations=list(order[b:e]), inliers=inl[b:e].copy())
+
     def _pack_against_map(self, det, imageIds):
         """The flat arrays engine.localize and engine.calibrate take: the reconstructed tags as the map and the
         observations of those tags grouped by image.  Returns (ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px);
@@ -452,12 +476,8 @@ class TagReconstructor:
             ids = sorted({int(im.imageId) for im in det.images} | {int(ob.imageId) for ob in det.tagObservations})
         else:
             ids = [int(i) for i in imageIds]
-        tag_ids = sorted(self.reconstructedTags)
+        tag_ids, tag_qt, tag_wh = self._map_arrays()
         dense = {t: k for k, t in enumerate(tag_ids)}
-        tag_qt = np.array([np.concatenate([self.reconstructedTags[t].q, self.reconstructedTags[t].t]) for t in tag_ids],
-                          np.float64).reshape(-1, 7)
-        tag_wh = np.array([[self.reconstructedTags[t].tagWidth, self.reconstructedTags[t].tagHeight] for t in tag_ids],
-                          np.float64).reshape(-1, 2)
         per_img = {i: [] for i in ids}
         for k, ob in enumerate(det.tagObservations):
             if ob.imageId in per_img and ob.tagId in dense:
@@ -479,14 +499,11 @@ class TagReconstructor:
         observation (index into detectionResult.tagObservations)."""
         det = self.detectionResults_ if detectionResult is None else detectionResult
         ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_against_map(det, imageIds)
-        m = self.camModel
-        cam_qt, cam_cov, inl, res = _engine.localize([m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, tag_qt, tag_wh,
-                                                     img_start, obs_tag, obs_px, device=self.device, **options)
+        cam_qt, cam_cov, inl, res = _engine.localize(*self._model_args(), tag_qt, tag_wh, img_start, obs_tag, obs_px,
+                                                     device=self.device, **options)
         cams, report = {}, {}
         for n, i in enumerate(ids):
-            b, e = int(img_start[n]), int(img_start[n + 1])
-            report[i] = dict(res[n], pose=cam_qt[n].copy(), covariance=cam_cov[n].copy(),
-                             observations=list(order[b:e]), inliers=inl[b:e].copy())
+            report[i] = self._item_report(res[n], cam_qt[n], cam_cov[n], order, inl, int(img_start[n]), int(img_start[n + 1]))
             if res[n]["status"] == _engine._lib.LOC_OK:
                 cams[i] = Camera(i, cam_qt[n, :4], cam_qt[n, 4:])
         self.lastLocalizationReport = report
@@ -530,9 +547,8 @@ class TagReconstructor:
     def _rig_frames_report(K, order, img_start, rig_qt, rig_cov, inl, res):
         rigs, report = {}, []
         for f in range(len(res)):
-            b, e = int(img_start[f * K]), int(img_start[f * K + K])
-            report.append(dict(res[f], pose=rig_qt[f].copy(), covariance=rig_cov[f].copy(), observations=list(order[b:e]),
-                               inliers=inl[b:e].copy()))
+            report.append(TagReconstructor._item_report(res[f], rig_qt[f], rig_cov[f], order, inl, int(img_start[f * K]),
+                                                        int(img_start[f * K + K])))
             if res[f]["status"] == _engine._lib.LOC_OK:
                 rigs[f] = Camera(f, rig_qt[f, :4], rig_qt[f, 4:])
         return rigs, report
@@ -582,18 +598,13 @@ class TagReconstructor:
         pose).  The reference has no such member."""
         det = self.detectionResults_ if detectionResult is None else detectionResult
         ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_against_map(det, imageIds)
-        m = self.camModel
         intr, dist, intr_cov, cam_qt, cam_cov, inl, res, report = _engine.calibrate(
-            [m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, tag_qt, tag_wh, img_start, obs_tag, obs_px,
-            device=self.device, **options)
-        report = dict(report, intrinsics=np.concatenate([intr, dist]), covariance=intr_cov,
-                      std=np.sqrt(np.diag(intr_cov)),
+            *self._model_args(), tag_qt, tag_wh, img_start, obs_tag, obs_px, device=self.device, **options)
+        report = dict(self._model_report(report, intr, dist, intr_cov),
                       cameras={i: Camera(i, cam_qt[n, :4], cam_qt[n, 4:]) for n, i in enumerate(ids)
                                if res[n]["status"] == _engine._lib.LOC_OK})
         if report["status"] != _engine._lib.CAL_NO_IMAGES:
-            self.camModel = CameraModel(fx=float(intr[0]), fy=float(intr[1]), cx=float(intr[2]), cy=float(intr[3]),
-                                        distortionCoefficients=dist, verticalResolution=m.verticalResolution,
-                                        horizontalResolution=m.horizontalResolution)
+            self.camModel = self._with_model(intr, dist)
         return report
 
     @staticmethod
@@ -641,10 +652,8 @@ class TagReconstructor:
             for k, i in enumerate(cam_ids):
                 if i in cameraCovariances:
                     cam_cov[k] = np.asarray(cameraCovariances[i], np.float64).reshape(6, 6)
-        m = self.camModel
-        xyz, cov, cov_cams, inl, res = _engine.triangulate([m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients, cam_qt,
-                                                           pt_start, obs_cam, obs_uv, cam_cov=cam_cov, device=self.device,
-                                                           **options)
+        xyz, cov, cov_cams, inl, res = _engine.triangulate(*self._model_args(), cam_qt, pt_start, obs_cam, obs_uv,
+                                                           cam_cov=cam_cov, device=self.device, **options)
         out = {}
         for n, pid in enumerate(point_ids):
             b, e = int(pt_start[n]), int(pt_start[n + 1])
@@ -723,7 +732,9 @@ class TagReconstructor:
         reconstructed, in file order."""
         if self._resident:
             return self._pack_resident(for_ba)
-        tag_ids = sorted(self.reconstructedTags)
+        # the cost functor receives the DETECTION tag's width/height but builds the quad from the reconstructed tag's
+        # (:713 vs :718); only the quad enters the arithmetic, so tag_wh is the reconstructed tags'
+        tag_ids, tag_qt, tag_wh = self._map_arrays()
         ob_img, ob_tag, ob_px = self._obs_arrays()
         tag_arr = np.asarray(tag_ids, np.int64)
         tag_ok = np.isin(ob_tag, tag_arr)
@@ -738,16 +749,10 @@ class TagReconstructor:
         obs_px = ob_px[keep]
         cam_qt = np.array([np.r_[self.reconstructedCameras[c].q, self.reconstructedCameras[c].t] for c in cam_ids],
                           np.float64).reshape(-1, 7)
-        tag_qt = np.array([np.r_[self.reconstructedTags[t].q, self.reconstructedTags[t].t] for t in tag_ids],
-                          np.float64).reshape(-1, 7)
-        # the cost functor receives the DETECTION tag's width/height but builds the quad from the
-        # reconstructed tag's (:713 vs :718); only the quad enters the arithmetic
-        tag_wh = np.array([[self.reconstructedTags[t].tagWidth, self.reconstructedTags[t].tagHeight] for t in tag_ids],
-                          np.float64).reshape(-1, 2)
         fixed = tag_ids.index(self.originTagId) if self.originTagId in self.reconstructedTags else -1   # :669-673
-        intr = [self.camModel.fx, self.camModel.fy, self.camModel.cx, self.camModel.cy]
+        intr, dist = self._model_args()
         tag_const = np.isin(tag_arr, np.asarray(sorted(self.constantTagIds), np.int64)).astype(np.uint8)
-        return dict(tag_ids=tag_ids, cam_ids=cam_ids, intr=intr, dist=self.camModel.distortionCoefficients,
+        return dict(tag_ids=tag_ids, cam_ids=cam_ids, intr=intr, dist=dist,
                     cam_qt=cam_qt, tag_qt=tag_qt, tag_wh=tag_wh, fixed=fixed, tag_const=tag_const,
                     obs_cam=obs_cam, obs_tag=obs_tag, obs_px=np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8),
                     cam_rows=list(range(len(cam_ids))), tag_rows=list(range(len(tag_ids))), mask=None, key=None,
@@ -792,17 +797,15 @@ class TagReconstructor:
             tag_wh[r] = (self.reconstructedTags[t].tagWidth, self.reconstructedTags[t].tagHeight)
         fixed = (int(np.searchsorted(full["tags"], self.originTagId))
                  if self.originTagId in self.reconstructedTags else -1)
-        intr = [self.camModel.fx, self.camModel.fy, self.camModel.cx, self.camModel.cy]
-        key = ("resident", id(full), fixed, tuple(float(v) for v in intr),
-               tuple(float(v) for v in self.camModel.distortionCoefficients), tag_wh.tobytes())
+        intr, dist = self._model_args()
+        key = ("resident", id(full), fixed, tuple(float(v) for v in intr), tuple(float(v) for v in dist), tag_wh.tobytes())
         # constant tags: rows of the full arrays; only reconstructed ones (the others have no active observation)
         tag_const = np.zeros(len(full["tags"]), np.uint8)
         for t, r in zip(tag_ids, tag_rows):
             if t in self.constantTagIds:
                 tag_const[r] = 1
-        return dict(tag_ids=tag_ids, cam_ids=cam_ids, cam_rows=cam_rows, tag_rows=tag_rows, intr=intr,
-                    dist=self.camModel.distortionCoefficients, cam_qt=cam_qt, tag_qt=tag_qt, tag_wh=tag_wh,
-                    fixed=fixed, tag_const=tag_const, obs_cam=full["obs_cam"], obs_tag=full["obs_tag"], obs_px=full["obs_px"],
+        return dict(tag_ids=tag_ids, cam_ids=cam_ids, cam_rows=cam_rows, tag_rows=tag_rows, intr=intr, dist=dist,
+                    cam_qt=cam_qt, tag_qt=tag_qt, tag_wh=tag_wh, fixed=fixed, tag_const=tag_const, obs_cam=full["obs_cam"], obs_tag=full["obs_tag"], obs_px=full["obs_px"],
                     mask=mask, key=key, n_active=int(mask.sum()))
 
     def _engine_for(self, p, **kw):
@@ -835,6 +838,21 @@ class TagReconstructor:
         self._cached = (key, ba)
         return ba
 
+    @contextlib.contextmanager
+    def _handle(self, p, **kw):
+        """_engine_for(p, **kw) for the length of a block; a call that fails inside it drops the cached handle."""
+        ba = self._engine_for(p, **kw)
+        try:
+            yield ba
+        except Exception:
+            self._drop_cached()
+            raise
+
+    @staticmethod
+    def _is_empty(p, observations=True):
+        """No camera, no tag or (observations) no active observation in the packed problem."""
+        return len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or (observations and p["n_active"] == 0)
+
     @staticmethod
     def _set_constants(ba, p):
         """The packed constant-tag flags go to the handle when they differ from what it holds (constantTagIds)."""
@@ -863,7 +881,7 @@ class TagReconstructor:
         """The packed problem of a bundle adjustment, or None for an empty one -- Ceres solves that trivially:
         CONVERGENCE, nothing changes."""
         p = self._pack(for_ba=True)
-        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
+        if self._is_empty(p):
             print("Solution %d" % _engine.CONVERGENCE)
             self.lastSummary = {"termination_type": _engine.CONVERGENCE, "iterations": 1}
             return None
@@ -887,8 +905,7 @@ class TagReconstructor:
         p = self._pack_for_ba()
         if p is None:
             return
-        ba = self._engine_for(p, elimination=elimination)
-        try:
+        with self._handle(p, elimination=elimination) as ba:
             opts = _engine.default_options(max_num_iterations=int(maxNumIterations), robustify=int(bool(robustify)),
                                            num_threads=int(ceresThreads))
             trace_capacity = int(maxNumIterations) + 2 if printSummary else 0
@@ -902,21 +919,14 @@ class TagReconstructor:
                 summary = ba.solve(opts, trace_capacity=trace_capacity)
             cam, tag = ba.get_state()
             cov = ba.tag_translation_covariance(robustify, opts.huber_a) if printSummary else None   # :744-760
-        except Exception:
-            self._drop_cached()
-            raise
         self._write_back_cameras(p, cam)
         for k, tid in zip(p["tag_rows"], p["tag_ids"]):
             self.reconstructedTags[tid].q = tag[k, :4].copy()
             self.reconstructedTags[tid].t = tag[k, 4:].copy()
         self.lastSummary = summary
         if refineCameraModel:
-            m = self.camModel
-            self.camModel = CameraModel(fx=float(intr[0]), fy=float(intr[1]), cx=float(intr[2]), cy=float(intr[3]),
-                                        distortionCoefficients=dist, verticalResolution=m.verticalResolution,
-                                        horizontalResolution=m.horizontalResolution)
-            self.lastSelfCalibrationReport = dict(report, intrinsics=np.concatenate([intr, dist]), covariance=intr_cov,
-                                                  std=np.sqrt(np.diag(intr_cov)))
+            self.camModel = self._with_model(intr, dist)
+            self.lastSelfCalibrationReport = self._model_report(report, intr, dist, intr_cov)
             self._drop_cached()   # the cached handle is keyed by the model it was created with
             print("Camera model refined: status %d, %d outer iterations (%d accepted), cost %.6e -> %.6e" % (
                 report["status"], report["outer_iterations"], report["accepted"], report["initial_cost"],
@@ -955,14 +965,10 @@ class TagReconstructor:
         reference, which asks Ceres for the tags' (t, t) blocks only (src/TagReconstructor.cpp:744-783)."""
         self.lastPoseCovariances = {"tags": {}, "cameras": {}}
         p = self._pack(for_ba=True)
-        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0 or p["n_active"] == 0:
+        if self._is_empty(p):
             return self.lastPoseCovariances
-        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
-        try:
+        with self._handle(p, elimination=_engine.ELIM_AUTO) as ba:
             cam_cov, tag_cov = ba.pose_covariances(robustify, _engine.default_options().huber_a)
-        except Exception:
-            self._drop_cached()
-            raise
         self.lastPoseCovariances["tags"] = {t: tag_cov[k].copy() for k, t in zip(p["tag_rows"], p["tag_ids"])}
         self.lastPoseCovariances["cameras"] = {c: cam_cov[k].copy() for k, c in zip(p["cam_rows"], p["cam_ids"])}
         return self.lastPoseCovariances
@@ -979,16 +985,12 @@ class TagReconstructor:
         p = self._pack_for_ba()
         if p is None:
             return
-        ba = self._engine_for(p, elimination=elimination, landmarks=_engine.LANDMARK_POINTS)
-        try:
+        with self._handle(p, elimination=elimination, landmarks=_engine.LANDMARK_POINTS) as ba:
             opts = _engine.default_options(max_num_iterations=int(maxNumIterations), robustify=0,
                                            num_threads=int(ceresThreads))
             summary = ba.solve(opts, trace_capacity=int(maxNumIterations) + 2 if printSummary else 0)
             cam, tag = ba.get_state()
             pts = ba.get_points()
-        except Exception:
-            self._drop_cached()
-            raise
         self._write_back_cameras(p, cam)
         self.lastPoints = {}
         for k, tid in zip(p["tag_rows"], p["tag_ids"]):
@@ -1005,14 +1007,10 @@ class TagReconstructor:
     # -- reprojection statistics + pruning (src/TagReconstructor.cpp:340-455, 786-816) --
     def _stats(self, per_corner):
         p = self._pack(for_ba=False)
-        if len(p["cam_ids"]) == 0 or len(p["tag_ids"]) == 0:
+        if self._is_empty(p, observations=False):
             return p, np.zeros(0), np.zeros(0), 0.0, np.zeros((0, 8))
-        ba = self._engine_for(p, elimination=_engine.ELIM_AUTO)
-        try:
+        with self._handle(p, elimination=_engine.ELIM_AUTO) as ba:
             pc, pt, avg, corner = ba.reprojection_stats(per_corner=per_corner)
-        except Exception:
-            self._drop_cached()
-            raise
         return p, pc, pt, avg, corner
 
     def computeReprojectionErrorPerImg(self):

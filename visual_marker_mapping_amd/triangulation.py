@@ -26,12 +26,7 @@ import numpy as np
 
 from . import _lib
 from . import io as _io
-from .tag_reconstructor import Camera, DetectionResult, TagReconstructor
-
-
-def _matrix(m):
-    m = np.asarray(m, np.float64)
-    return {"rows": int(m.shape[0]), "cols": int(m.shape[1]), "coefficents": [float(v) for v in m.reshape(-1)]}
+from .tag_reconstructor import DetectionResult, TagReconstructor
 
 
 def triangulation_tree(points):
@@ -44,7 +39,8 @@ def triangulation_tree(points):
                     "status": _lib.TRI_STATUS_NAMES[r["status"]],
                     "num_observations": int(r["n_obs"]), "num_inlier_observations": int(r["n_inlier_obs"]),
                     "rms_px": float(r["rms_px"]), "sigma": [float(v) for v in np.sqrt(np.diag(total))],
-                    "covariance": _matrix(r["covariance"]), "covariance_cameras": _matrix(r["covariance_cameras"])})
+                    "covariance": _io.matrix_tree(r["covariance"]),
+                    "covariance_cameras": _io.matrix_tree(r["covariance_cameras"])})
     return {"points": out}
 
 
@@ -64,14 +60,7 @@ def tag_geometry_tree(geometry):
 def read_cameras(path):
     """{imageId: Camera} from any file with a `reconstructed_cameras` list; an entry with a `status` other than "ok"
     (localization.json) is skipped."""
-    cams = {}
-    for pt in _io._children(_io.read_json(path), "reconstructed_cameras"):
-        if "status" in pt and pt["status"] != "ok":
-            continue
-        i = _io._get(pt, "id", int)
-        cams[i] = Camera(cameraId=i, q=_io._vector(_io._children(pt, "rotation"), 4),
-                         t=_io._vector(_io._children(pt, "translation"), 3))
-    return cams
+    return _io.camerasFromPropertyTree(_io.read_json(path), ok_only=True)
 
 
 def read_camera_covariances(path):
@@ -80,7 +69,7 @@ def read_camera_covariances(path):
     for pt in _io._children(_io.read_json(path), "reconstructed_cameras"):
         if "covariance" not in pt or ("status" in pt and pt["status"] != "ok"):
             continue
-        cov[_io._get(pt, "id", int)] = _io._vector(_io._children(pt["covariance"], "coefficents"), 36).reshape(6, 6)
+        cov[_io._get(pt, "id", int)] = _io.matrixFromPropertyTree(pt["covariance"], 6, 6)
     return cov
 
 
@@ -97,23 +86,18 @@ def main(argv=None):
     ap.add_argument("--output", default=None, help="output file (default: <project>/triangulation.json or tag_geometry.json)")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     a = ap.parse_args(argv)
-    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
-    detections = os.path.join(a.project_path, "marker_detections.json")
-    points = a.points or os.path.join(a.project_path, "point_detections.json")
     out = a.output or os.path.join(a.project_path, "tag_geometry.json" if a.tag_corners else "triangulation.json")
-    if not os.path.isfile(recon):
-        raise FileNotFoundError("no map to triangulate against: '%s' does not exist (run the mapping step first: "
-                                "python -m visual_marker_mapping_amd.mapping --project_path %s)" % (recon, a.project_path))
-    needed = [(a.cameras, "camera file"), (a.camera_covariances, "camera covariance file"),
-              (detections, "detection file") if a.tag_corners else (points, "point detection file")]
-    for f, what in needed:
-        if f is not None and not os.path.isfile(f):
-            raise FileNotFoundError("%s '%s' does not exist" % (what, f))
+    recon = _io.project_file(a.project_path, a.map, "reconstruction.json", "map", "no map to triangulate against")
+    for f, what in ((a.cameras, "camera file"), (a.camera_covariances, "camera covariance file")):
+        if f is not None:
+            _io.project_file(a.project_path, f, None, what)
+    pixels = (_io.project_file(a.project_path, None, "marker_detections.json", "detection file") if a.tag_corners
+              else _io.project_file(a.project_path, a.points, "point_detections.json", "point detection file"))
     tags, cams, model = _io.parseReconstructions(recon)
     if a.cameras:
         cams = read_cameras(a.cameras)
     cov = read_camera_covariances(a.camera_covariances) if a.camera_covariances else None
-    rec = TagReconstructor(_io.readDetectionResult(detections) if a.tag_corners else DetectionResult(), device=a.device)
+    rec = TagReconstructor(_io.readDetectionResult(pixels) if a.tag_corners else DetectionResult(), device=a.device)
     rec.setCameraModel(model)
     rec.setReconstructedTags(tags)
     rec.setReconstructedCameras(cams)
@@ -122,7 +106,7 @@ def main(argv=None):
         _io.write_json(out, tag_geometry_tree(geometry))
         print("Triangulated the corners of %d tags; wrote %s!" % (len(geometry), out))
         return 0
-    result = rec.triangulatePoints(_io.readPointDetections(points), cameraCovariances=cov)
+    result = rec.triangulatePoints(_io.readPointDetections(pixels), cameraCovariances=cov)
     ok = sum(1 for r in result.values() if r["status"] == _lib.TRI_OK)
     _io.write_json(out, triangulation_tree(result))
     print("Triangulated %d of %d points (%d observations of images without a pose dropped); wrote %s!"

@@ -21,6 +21,9 @@ import sys
 
 import numpy as np
 
+from . import io as _io
+from .tag_reconstructor import TagReconstructor
+
 
 def uncertainty_tree(origin_tag_id, robustify, tag_cov, cam_cov):
     """The property tree of reconstruction_uncertainty.json from plain values: tag_cov and cam_cov map an id to its
@@ -29,8 +32,7 @@ def uncertainty_tree(origin_tag_id, robustify, tag_cov, cam_cov):
         out = []
         for i in sorted(cov):
             m = np.asarray(cov[i], np.float64).reshape(6, 6)
-            out.append({"id": int(i), "sigma": [float(v) for v in np.sqrt(np.diag(m))],
-                        "covariance": {"rows": 6, "cols": 6, "coefficents": [float(v) for v in m.reshape(-1)]}})
+            out.append({"id": int(i), "sigma": [float(v) for v in np.sqrt(np.diag(m))], "covariance": _io.matrix_tree(m)})
         return out
     return {"origin_tag_id": int(origin_tag_id), "robustify": bool(robustify),
             "reconstructed_tags": entries(tag_cov), "reconstructed_cameras": entries(cam_cov)}
@@ -38,13 +40,10 @@ def uncertainty_tree(origin_tag_id, robustify, tag_cov, cam_cov):
 
 def write_uncertainty(path, origin_tag_id, robustify, tag_cov, cam_cov):
     """Writes reconstruction_uncertainty.json (every scalar a quoted string, like the reference's output files)."""
-    from . import io as _io
     _io.write_json(path, uncertainty_tree(origin_tag_id, robustify, tag_cov, cam_cov))
 
 
 def main(argv=None):
-    from . import io as _io
-    from .tag_reconstructor import TagReconstructor
     ap = argparse.ArgumentParser(description="6x6 covariance of every tag and camera of a finished map")
     ap.add_argument("--project_path", required=True, help="Path to the project (holds camera_intrinsics.json, "
                     "marker_detections.json and the map)")
@@ -55,16 +54,13 @@ def main(argv=None):
     ap.add_argument("--robustify", action="store_true", help="apply the Huber loss of the mapping step to J")
     ap.add_argument("--device", type=int, default=0, help="HIP device ordinal")
     a = ap.parse_args(argv)
-    recon = a.map or os.path.join(a.project_path, "reconstruction.json")
+    recon = _io.project_file(a.project_path, a.map, "reconstruction.json", None)
+    intrinsics = _io.project_file(a.project_path, None, "camera_intrinsics.json", None)
+    detections = _io.project_file(a.project_path, None, "marker_detections.json", None)
     out = a.output or os.path.join(a.project_path, "reconstruction_uncertainty.json")
-    for f in (recon, os.path.join(a.project_path, "camera_intrinsics.json"),
-              os.path.join(a.project_path, "marker_detections.json")):
-        if not os.path.isfile(f):
-            raise FileNotFoundError("'%s' does not exist" % f)
     tags, cams, _ = _io.parseReconstructions(recon)
-    rec = TagReconstructor(_io.readDetectionResult(os.path.join(a.project_path, "marker_detections.json")),
-                           device=a.device)
-    rec.setCameraModel(_io.readCameraModel(os.path.join(a.project_path, "camera_intrinsics.json")))
+    rec = TagReconstructor(_io.readDetectionResult(detections), device=a.device)
+    rec.setCameraModel(_io.readCameraModel(intrinsics))
     rec.setReconstructedTags(tags)
     rec.setReconstructedCameras(cams)
     origin = a.start_tag_id if a.start_tag_id != -1 else min(tags)

@@ -13,7 +13,7 @@ starts from.  The one difference is around the call, not in it: cov_factor_and f
 (CovDensePath); neither is read by launch_eval_passes' kernels at use_ctl = false.
 
 H is the dense normal matrix over the free, active poses (cameras first, then tags), as
-test_gpu_constant_poses._free_system builds it.
+yardstick.free_system builds it.
 
 Truth.  inv(H) in np.longdouble, in eliminated form: rows and columns scaled by powers of two near 1 / sqrt(H_ii) (exact,
 and the metric below does not see it), the larger family eliminated by its 6x6 blocks, the small reduced matrix inverted by
@@ -215,7 +215,7 @@ def free_poses(sc):
 
 
 def free_system(sc, blk):
-    """Dense H over the free poses (cameras, then tags) from V, U, W, as test_gpu_constant_poses._free_system; the blocks
+    """Dense H over the free poses (cameras, then tags) from V, U, W, as yardstick.free_system; the blocks
     of every other pose must be zero.  Returns (H, free cameras, free tags)."""
     fc, ft = free_poses(sc)
     on = np.ones(sc.n_obs, bool) if sc.mask is None else np.asarray(sc.mask) != 0
@@ -411,12 +411,12 @@ def _model_measures(Sk, rk):
 
 class ModelCase:
     """vmm_ba_intrinsics_system on one scene at camera model k: the longdouble S_k, r_k, the deviations of references A
-    (test_selfcal_cpu.reduced_system on the oracle's Jacobian) and B (float64 Y = L^-1 [B | g], S_k = C - Y^T Y) in the two
+    (yardstick.reduced_system on the oracle's Jacobian) and B (float64 Y = L^-1 [B | g], S_k = C - Y^T Y) in the two
     metrics -- inv(S_k) entry by entry over sqrt(c_ii c_jj), the step inv(S_k) r_k in units of sqrt(c_ii) -- and the bounds
     MARGIN x the larger deviation."""
 
     def __init__(self, O, sc, k, robust, mask):
-        from test_selfcal_cpu import joint_system, reduced_system
+        from yardstick import joint_system, reduced_system
         self.scene, self.k, self.robust, self.mask = sc, np.asarray(k, np.float64), robust, mask
         A, B, g, C, gk, cost = _border_sums(sc, self.k, robust, mask, LD)
         X = refined_solution(A.astype(np.float64), np.column_stack([B, g]))
@@ -459,7 +459,7 @@ MODEL_VARIANTS = (("plain", False, False), ("robust", True, False), ("masked", T
 def model_case(O, name, variant):
     """ragged_tags / ragged_cams with ragged_constants at k = truth + 0.01 PERTURB (test_system_matches_the_host_jacobian):
     plain, robust, and robust with ragged_mask."""
-    from test_selfcal_cpu import PERTURB
+    from yardstick import PERTURB
     label, robust, masked = next(v for v in MODEL_VARIANTS if v[0] == variant)
 
     def make():

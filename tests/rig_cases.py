@@ -1,8 +1,8 @@
 """The yardstick of the rig tests (tests/test_rig_cpu.py proves it, tests/test_gpu_rig.py leans on it) and the scenes
 they share.
 
-rig_system is numpy around oracle/oracle.py: obs_eval gives the 8 residuals and the 8 x 6 camera Jacobian of one
-observation at the composed pose ext_c o rig_f, huber gives rho; the chain rule carries the camera Jacobian to the two
+rig_system is tests/yardstick.py's assemble over rig_rows: obs_eval gives the 8 residuals and the 8 x 6 camera Jacobian
+of one observation at the composed pose ext_c o rig_f; the chain rule carries the camera Jacobian to the two
 tangents.  With camera = (R_c R_f, R_c t_f + t_c) and every pose moving as vmm_ba_pose_plus moves it (translation
 added, rotation multiplied from the left by the half-angle step):
     a rig step (dt, dth) moves the camera by (R_c dt, R_c dth)                  J_rig = [Jc_t R_c | Jc_r R_c]
@@ -10,6 +10,8 @@ added, rotation multiplied from the left by the half-angle step):
 It never calls the code under test.
 """
 import numpy as np
+
+from yardstick import assemble, dense_lm, free_inverse, plain_step, rotation
 
 # rig->camera: identity; yaw 4 deg, t = (-0.3, 0, 0); yaw -15 deg, t = (0.2, 0.05, 0)
 def yaw(deg, t=(0.0, 0.0, 0.0)):
@@ -41,13 +43,6 @@ def rig_scene(name, ext=EXT3, **kw):
     return s
 
 
-def rot(q):
-    w, x, y, z = np.asarray(q, np.float64)[:4] / np.linalg.norm(q[:4])
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
 def compose(ext, rig):
     """ext o rig as (qw, qx, qy, qz, tx, ty, tz): the Hamilton product of the unit quaternions, t = R_c t_f + t_c."""
     a, b = ext[:4] / np.linalg.norm(ext[:4]), rig[:4] / np.linalg.norm(rig[:4])
@@ -55,7 +50,7 @@ def compose(ext, rig):
                   a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
                   a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1],
                   a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
-    return np.concatenate([q, rot(ext) @ rig[4:] + ext[4:]])
+    return np.concatenate([q, rotation(ext) @ rig[4:] + ext[4:]])
 
 
 def _cross(v):
@@ -65,7 +60,7 @@ def _cross(v):
 def rig_rows(O, intr, dist, ext, rig, tag_qt, wh, px):
     """One observation: residual (8,), Jacobian over the rig's tangent (8, 6) and over the extrinsic's (8, 6)."""
     r, Jc, _ = O.obs_eval(intr, dist, compose(ext, rig), tag_qt, wh, px)
-    Rc = rot(ext)
+    Rc = rotation(ext)
     J_rig = np.hstack([Jc[:, :3] @ Rc, Jc[:, 3:] @ Rc])
     J_ext = np.hstack([Jc[:, :3], Jc[:, 3:] - 2.0 * Jc[:, :3] @ _cross(Rc @ rig[4:])])
     return r, J_rig, J_ext
@@ -73,25 +68,15 @@ def rig_rows(O, intr, dist, ext, rig, tag_qt, wh, px):
 
 def rig_system(O, s, rig_qt, ext_qt, keep=None, robust=False, a=1.0):
     """The whole problem of scene s at (rig_qt, ext_qt) over the observations of `keep` (bool mask; None: all):
-    cost = 1/2 sum rho(|r_corner|^2), residuals (8 n,) and Jacobian (8 n, 6 F + 6 K), the rig blocks first, the loss
-    applied as Ceres' corrector does for rho'' <= 0 (rows and residuals scaled by sqrt(rho'))."""
-    idx = np.arange(len(s.obs_tag)) if keep is None else np.flatnonzero(keep)
+    yardstick.assemble's cost, residuals (8 n,) and Jacobian (8 n, 6 F + 6 K), the rig blocks first."""
     F, K = len(rig_qt), len(ext_qt)
-    r_all, J = np.zeros(8 * len(idx)), np.zeros((8 * len(idx), 6 * F + 6 * K))
-    cost = 0.0
-    for n, o in enumerate(idx):
-        f, c, t = int(s.obs_frame[o]), int(s.obs_cam[o]), int(s.obs_tag[o])
-        r, Jr, Je = rig_rows(O, s.intr[c], s.dist[c], ext_qt[c], rig_qt[f], s.tag_gt[t], s.tag_wh[t], s.obs_px[o])
-        for k in range(4):
-            sq = float(r[2 * k:2 * k + 2] @ r[2 * k:2 * k + 2])
-            rho = O.huber(a, sq) if robust else (sq, 1.0, 0.0)
-            cost += 0.5 * rho[0]
-            w = np.sqrt(rho[1])
-            rows = slice(8 * n + 2 * k, 8 * n + 2 * k + 2)
-            r_all[rows] = w * r[2 * k:2 * k + 2]
-            J[rows, 6 * f:6 * f + 6] = w * Jr[2 * k:2 * k + 2]
-            J[rows, 6 * F + 6 * c:6 * F + 6 * c + 6] = w * Je[2 * k:2 * k + 2]
-    return cost, r_all, J
+
+    def rows():
+        for o in (np.arange(len(s.obs_tag)) if keep is None else np.flatnonzero(keep)):
+            f, c, t = int(s.obs_frame[o]), int(s.obs_cam[o]), int(s.obs_tag[o])
+            r, Jr, Je = rig_rows(O, s.intr[c], s.dist[c], ext_qt[c], rig_qt[f], s.tag_gt[t], s.tag_wh[t], s.obs_px[o])
+            yield r, [(6 * f, Jr), (6 * F + 6 * c, Je)]
+    return assemble(O, 6 * F + 6 * K, rows(), robust, a)[:3]
 
 
 def frame_normal(O, s, f, q, ext_qt, keep, robust, a=1.0):
@@ -107,38 +92,8 @@ def frame_normal(O, s, f, q, ext_qt, keep, robust, a=1.0):
 def host_frame_optimum(O, s, f, q0, ext_qt, keep, robust):
     """Levenberg-Marquardt on frame f's 6 degrees of freedom from q0 over the observations of `keep`, run until the
     step is at the rounding floor of the pose.  Returns (pose, cost)."""
-    q = np.array(q0, np.float64)
-    cost, A, g = frame_normal(O, s, f, q, ext_qt, keep, robust)
-    lam = 1e-4
-    for _ in range(200):
-        try:
-            step = np.linalg.solve(A + lam * np.diag(np.maximum(np.diag(A), 1e-12)), -g)
-        except np.linalg.LinAlgError:
-            lam *= 10.0
-            continue
-        if np.abs(step).max() < 1e-13:
-            break
-        cand = O.pose_plus(q, step)
-        c2, A2, g2 = frame_normal(O, s, f, cand, ext_qt, keep, robust)
-        if c2 < cost:
-            q, cost, A, g = cand, c2, A2, g2
-            lam = max(lam * 0.1, 1e-15)
-        else:
-            if lam > 1e8:
-                break
-            lam *= 10.0
-    return q, cost
-
-
-def pose_gap(a, b):
-    """As tests/test_gpu_localize.py: max over the poses of |dq| (unit quaternions, sign-aligned) and |dt| / max(|t|, 1)."""
-    a, b = np.atleast_2d(a), np.atleast_2d(b)
-    qa = a[:, :4] / np.linalg.norm(a[:, :4], axis=1, keepdims=True)
-    qb = b[:, :4] / np.linalg.norm(b[:, :4], axis=1, keepdims=True)
-    sign = np.sign(np.sum(qa * qb, axis=1))[:, None]
-    dq = np.linalg.norm(qa * sign - qb, axis=1)
-    dt = np.linalg.norm(a[:, 4:] - b[:, 4:], axis=1) / np.maximum(np.linalg.norm(b[:, 4:], axis=1), 1.0)
-    return float(dq.max()), float(dt.max())
+    return dense_lm(lambda q: frame_normal(O, s, f, q, ext_qt, keep, robust), O.pose_plus, np.array(q0, np.float64),
+                    lambda sys, lam: plain_step(sys[1], sys[2], lam), 1e-13)[:2]
 
 
 def select(s, keep):
@@ -188,55 +143,31 @@ def host_rig_calibration(O, s, rig0, ext0, keep, robust, mask, a=1.0):
     """Levenberg-Marquardt on all the free rig poses and extrinsics at once (dense normal equations of rig_system, every
     block moved by the oracle's Plus) from (rig0, ext0), run until the step is at the rounding floor.  Returns (rig, ext,
     cost, H): H the undamped normal matrix at the result, the loss applied."""
-    rig, ext = np.array(rig0, np.float64), np.array(ext0, np.float64)
     F = s.n_frames
     free = free_columns(s, keep, mask)
 
-    def system(rig, ext):
-        cost, r, J = rig_system(O, s, rig, ext, keep, robust, a)
+    def system(x):
+        cost, r, J = rig_system(O, s, x[0], x[1], keep, robust, a)
         return cost, J.T @ J, J.T @ r
 
-    def moved(step):
-        r2, e2 = rig.copy(), ext.copy()
-        for f in range(F):
-            if free[6 * f]:
-                r2[f] = O.pose_plus(rig[f], step[6 * f:6 * f + 6])
-        for c in range(len(ext)):
-            if free[6 * F + 6 * c]:
-                e2[c] = O.pose_plus(ext[c], step[6 * F + 6 * c:6 * F + 6 * c + 6])
-        return r2, e2
+    def step(sys, lam):
+        d = np.zeros(len(free))
+        d[free] = plain_step(sys[1][np.ix_(free, free)], sys[2][free], lam)
+        return d
 
-    cost, H, g = system(rig, ext)
-    lam = 1e-4
-    for _ in range(200):
-        Hf, gf = H[np.ix_(free, free)], g[free]
-        try:
-            sf = np.linalg.solve(Hf + lam * np.diag(np.maximum(np.diag(Hf), 1e-12)), -gf)
-        except np.linalg.LinAlgError:
-            lam *= 10.0
-            continue
-        if np.abs(sf).max() < 1e-13:
-            break
-        step = np.zeros(len(free))
-        step[free] = sf
-        r2, e2 = moved(step)
-        c2, H2, g2 = system(r2, e2)
-        if c2 < cost:
-            rig, ext, cost, H, g = r2, e2, c2, H2, g2
-            lam = max(lam * 0.1, 1e-15)
-        else:
-            if lam > 1e8:
-                break
-            lam *= 10.0
+    def plus(x, d):
+        poses = np.concatenate(x)
+        return np.split(np.array([O.pose_plus(p, d[6 * n:6 * n + 6]) if free[6 * n] else p for n, p in enumerate(poses)]), [F])
+
+    (rig, ext), cost, (_, H, _), _ = dense_lm(system, plus, (np.array(rig0, np.float64), np.array(ext0, np.float64)), step,
+                                             1e-13)
     return rig, ext, cost, H
 
 
 def joint_covariance(s, H, keep, mask):
     """(ext_cov (6 K, 6 K), rig_cov (F, 6, 6), max |entry| of the joint inverse) from the normal matrix H: the inverse
     over the free columns, zero rows and columns for the others."""
-    F, K = s.n_frames, s.n_rig_cams
-    free = free_columns(s, keep, mask)
-    full = np.zeros_like(H)
-    full[np.ix_(free, free)] = np.linalg.inv(H[np.ix_(free, free)])
+    F = s.n_frames
+    full = free_inverse(H, free_columns(s, keep, mask))
     rig_cov = np.array([full[6 * f:6 * f + 6, 6 * f:6 * f + 6] for f in range(F)])
     return full[6 * F:, 6 * F:], rig_cov, float(np.abs(full).max())

@@ -1,10 +1,6 @@
 """CPU-only checks of the calibration entry points (ABI 6, additive): declared, listed, exported, laid out as the header
-says, validating their arguments before any device call -- and the yardstick of tests/test_gpu_calibrate.py, proven here
-before the GPU tests lean on it.
-
-The yardstick (calib_system, host_calibration) is numpy around oracle/oracle.py: obs_eval gives the 8 residuals and the
-8 x 6 camera Jacobian of one observation, huber gives rho; the nine intrinsic columns are the closed forms of the cost
-functor's projection, compared below with central differences of obs_eval.  It never calls the code under test.
+says, validating their arguments before any device call.  The yardstick of tests/test_gpu_calibrate.py is
+tests/yardstick.py, proven in tests/test_yardstick_cpu.py.
 """
 import ctypes as C
 import os
@@ -15,117 +11,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vmm_ba_default_calibrate_options", "vmm_ba_calibrate")
-ALL_FREE = 0x1FF
-
-
-# ---- the yardstick --------------------------------------------------------------------------------------------------
-
-def _rot(q):
-    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def intrinsic_columns(k, cam_qt, tag_qt, wh):
-    """The 8 x 9 Jacobian of one observation's residuals over k = (fx, fy, cx, cy, k1, k2, p1, p2, k3) for the cost
-    functor's projection: xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2), yd = y rad + 2 p2 x y + p1 (r2 + 2 y^2),
-    u = fx xd + cx, v = fy yd + cy.  Corners LL, LR, UR, UL."""
-    fx, fy = k[0], k[1]
-    Rc, Rt = _rot(cam_qt[:4]), _rot(tag_qt[:4])
-    J = np.zeros((8, 9))
-    for c, (sx, sy) in enumerate(((-1, -1), (1, -1), (1, 1), (-1, 1))):
-        pw = Rt @ np.array([sx * wh[0] / 2, sy * wh[1] / 2, 0.0]) + tag_qt[4:]
-        pc = Rc @ pw + cam_qt[4:]
-        x, y = pc[0] / pc[2], pc[1] / pc[2]
-        r2 = x * x + y * y
-        rad = 1 + r2 * (k[4] + r2 * (k[5] + r2 * k[8]))
-        xd = x * rad + 2 * k[6] * x * y + k[7] * (r2 + 2 * x * x)
-        yd = y * rad + 2 * k[7] * x * y + k[6] * (r2 + 2 * y * y)
-        J[2 * c] = [xd, 0, 1, 0, fx * x * r2, fx * x * r2 ** 2, fx * 2 * x * y, fx * (r2 + 2 * x * x), fx * x * r2 ** 3]
-        J[2 * c + 1] = [0, yd, 0, 1, fy * y * r2, fy * y * r2 ** 2, fy * (r2 + 2 * y * y), fy * 2 * x * y, fy * y * r2 ** 3]
-    return J
-
-
-def calib_system(O, k, cams, tag_qt, tag_wh, obs_img, obs_tag, obs_px, robust, a=1.0, mask=ALL_FREE):
-    """The calibration problem at (k, cams): cost = 1/2 sum rho(|r_corner|^2), the residuals (8 per observation) and the
-    dense Jacobian over (6 per image in `cams` order, then the nine of k), both with the loss applied as Ceres' corrector
-    does for rho'' <= 0 (rows and residuals scaled by sqrt(rho')).  obs_img indexes cams.  A parameter outside `mask`
-    has zero columns."""
-    n, n_img = len(obs_tag), len(cams)
-    r_all, J = np.zeros(8 * n), np.zeros((8 * n, 6 * n_img + 9))
-    free = np.array([(mask >> j) & 1 for j in range(9)], np.float64)
-    cost = 0.0
-    for o in range(n):
-        i, t = int(obs_img[o]), int(obs_tag[o])
-        r, Jc, _ = O.obs_eval(k[:4], k[4:], cams[i], tag_qt[t], tag_wh[t], obs_px[o])
-        Jk = intrinsic_columns(k, cams[i], tag_qt[t], tag_wh[t]) * free
-        for c in range(4):
-            rows = slice(2 * c, 2 * c + 2)
-            sq = float(r[rows] @ r[rows])
-            rho = O.huber(a, sq) if robust else (sq, 1.0, 0.0)
-            w = np.sqrt(rho[1])
-            cost += 0.5 * rho[0]
-            r_all[8 * o + 2 * c:8 * o + 2 * c + 2] = w * r[rows]
-            J[8 * o + 2 * c:8 * o + 2 * c + 2, 6 * i:6 * i + 6] = w * Jc[rows]
-            J[8 * o + 2 * c:8 * o + 2 * c + 2, 6 * n_img:] = w * Jk[rows]
-    return cost, r_all, J
-
-
-def _damped_step(H, g, lam, mask):
-    """(H + lam diag(H)) step = -g with unit rows for the parameters outside the mask."""
-    H, g = H.copy(), g.copy()
-    d = np.maximum(np.diag(H), 1e-12)
-    H[np.diag_indices_from(H)] += lam * d
-    n = len(g) - 9
-    for j in range(9):
-        if not (mask >> j) & 1:
-            H[n + j, :] = H[:, n + j] = 0.0
-            H[n + j, n + j] = 1.0
-            g[n + j] = 0.0
-    s = 1.0 / np.sqrt(np.diag(H))
-    return s * np.linalg.solve(H * s[:, None] * s[None, :], -g * s)
-
-
-def host_calibration(O, k0, cams0, tag_qt, tag_wh, obs_img, obs_tag, obs_px, robust, a=1.0, mask=ALL_FREE, max_iter=200):
-    """Dense Levenberg-Marquardt on the calibration problem from (k0, cams0), run until the step is at the rounding
-    floor of the unknowns.  Returns (k, cams, cost, J^T J at the result)."""
-    k, cams = np.array(k0, np.float64), np.array(cams0, np.float64)
-    n_img = len(cams)
-    cost, r, J = calib_system(O, k, cams, tag_qt, tag_wh, obs_img, obs_tag, obs_px, robust, a, mask)
-    lam = 1e-4
-    for _ in range(max_iter):
-        H, g = J.T @ J, J.T @ r
-        try:
-            step = _damped_step(H, g, lam, mask)
-        except np.linalg.LinAlgError:
-            lam *= 10.0
-            continue
-        size = max(np.abs(step[:6 * n_img]).max(), (np.abs(step[6 * n_img:]) / np.maximum(np.abs(k), 1.0)).max())
-        if size < 1e-15:
-            break
-        cand_k = k + step[6 * n_img:]
-        cand = np.array([O.pose_plus(cams[i], step[6 * i:6 * i + 6]) for i in range(n_img)])
-        c2, r2, J2 = calib_system(O, cand_k, cand, tag_qt, tag_wh, obs_img, obs_tag, obs_px, robust, a, mask)
-        if c2 < cost:
-            k, cams, cost, r, J = cand_k, cand, c2, r2, J2
-            lam = max(lam * 0.1, 1e-15)
-        else:
-            if lam > 1e8:
-                break
-            lam *= 10.0
-    return k, cams, cost, J.T @ J
-
-
-def joint_covariance(H, n_img, mask=ALL_FREE):
-    """(intr_cov (9, 9), cam_cov (n_img, 6, 6)): the blocks of the inverse of the full J^T J; the rows and columns of
-    the parameters outside the mask are zero."""
-    free = [6 * n_img + j for j in range(9) if (mask >> j) & 1]
-    keep = list(range(6 * n_img)) + free
-    inv = np.zeros_like(H)
-    inv[np.ix_(keep, keep)] = np.linalg.inv(H[np.ix_(keep, keep)])
-    cam_cov = np.array([inv[6 * i:6 * i + 6, 6 * i:6 * i + 6] for i in range(n_img)])
-    return inv[6 * n_img:, 6 * n_img:], cam_cov
 
 
 # ---- the entry points -----------------------------------------------------------------------------------------------
@@ -333,51 +218,3 @@ def test_calibration_main_needs_a_reconstruction(tmp_path):
     with pytest.raises(FileNotFoundError) as ei:
         calibration.main(["--project_path", str(tmp_path)])
     assert "marker_detections.json" in str(ei.value) and "does not exist" in str(ei.value)
-
-
-# ---- the yardstick against central differences ----------------------------------------------------------------------
-
-def test_reference_jacobian_matches_central_differences_of_the_oracle(oracle):
-    """calib_system's nine intrinsic columns against central differences of oracle.obs_eval on the distortion scene.
-    The residual is linear in each of the nine parameters (u = fx xd + cx, and xd is linear in k1, k2, k3, p1, p2), so a
-    central difference has no truncation error and the step can be large: h_j = 1e-3 max(|k_j|, 1).  What is left is
-    the rounding of the two residuals, 2 eps |u| / (2 h) <= 1.2e-16 * 1e4 / 1e-3 = 1.2e-9 per entry (pixel coordinates
-    stay below 1e4): the bound is 1e-8 absolute on every entry."""
-    from visual_marker_mapping_amd.synthetic import make_scene
-    s = make_scene(5, n_cams=12, n_tags=8, visibility=0.6)
-    assert np.abs(s.dist).max() > 0
-    k = np.concatenate([s.intr, s.dist])
-    n = min(len(s.obs_tag), 40)
-    img, tag, px = s.obs_cam[:n], s.obs_tag[:n], s.obs_px[:n]
-    cost, r, J = calib_system(oracle, k, s.cam_gt, s.tag_gt, s.tag_wh, img, tag, px, robust=False)
-    n_img = len(s.cam_gt)
-    assert J.shape == (8 * n, 6 * n_img + 9) and abs(cost - 0.5 * r @ r) <= 1e-12 * cost
-    worst = 0.0
-    for j in range(9):
-        h = 1e-3 * max(abs(k[j]), 1.0)
-        kp, km = k.copy(), k.copy()
-        kp[j] += h
-        km[j] -= h
-        num = np.concatenate([(oracle.obs_eval(kp[:4], kp[4:], s.cam_gt[img[o]], s.tag_gt[tag[o]], s.tag_wh[tag[o]], px[o], jac=False)
-                               - oracle.obs_eval(km[:4], km[4:], s.cam_gt[img[o]], s.tag_gt[tag[o]], s.tag_wh[tag[o]], px[o], jac=False))
-                              / (kp[j] - km[j]) for o in range(n)])
-        col = J[:, 6 * n_img + j]
-        err = np.abs(col - num).max()
-        print("parameter %d: max |column| %.3g, largest error %.3g" % (j, np.abs(num).max(), err))
-        worst = max(worst, err)
-        assert np.abs(px).max() < 1e4 and err <= 1e-8, (j, err)
-    # the pose columns are the oracle's own, each in its image's block; a masked parameter has a zero column
-    r0, Jc, _ = oracle.obs_eval(k[:4], k[4:], s.cam_gt[img[3]], s.tag_gt[tag[3]], s.tag_wh[tag[3]], px[3])
-    assert (J[24:32, 6 * img[3]:6 * img[3] + 6] == Jc).all() and (r[24:32] == r0).all()
-    assert np.count_nonzero(J[24:32, :6 * n_img]) == np.count_nonzero(Jc)
-    _, _, Jm = calib_system(oracle, k, s.cam_gt, s.tag_gt, s.tag_wh, img, tag, px, robust=False, mask=0xF)
-    assert (Jm[:, 6 * n_img + 4:] == 0).all() and (Jm[:, :6 * n_img + 4] == J[:, :6 * n_img + 4]).all()
-    # the loss: rows and residuals scaled by sqrt(rho'), cost = 1/2 sum rho
-    big = px.copy()
-    big[0] += 5.0
-    cost_h, r_h, J_h = calib_system(oracle, k, s.cam_gt, s.tag_gt, s.tag_wh, img, tag, big, robust=True)
-    cost_p, r_p, J_p = calib_system(oracle, k, s.cam_gt, s.tag_gt, s.tag_wh, img, tag, big, robust=False)
-    sq = r_p[0] ** 2 + r_p[1] ** 2
-    assert sq > 1.0 and abs(r_h[0] / r_p[0] - sq ** -0.25) <= 1e-12
-    assert np.allclose(J_h[0], J_p[0] * sq ** -0.25, rtol=1e-12, atol=0)
-    assert cost_h < cost_p

@@ -81,12 +81,12 @@ def test_a_single_precision_intermediate_misses_the_bound():
 # ---- the camera-model system ---------------------------------------------------------------------------------------------
 
 def test_model_columns_match_the_oracle(oracle):
-    """The longdouble J_k against test_selfcal_cpu.joint_system's (test_calibrate_cpu.intrinsic_columns, float64) on the
+    """The longdouble J_k against yardstick.joint_system's (yardstick.intrinsic_columns, float64) on the
     ragged scene, entry by entry over the entry's magnitude (the same formulas over absolute values).  An entry is a product
     of at most nine factors, each the result of a chain of under ten roundings (quaternion norm, rotation entry, two
     three-term sums, the division, r2 and its powers): 64 units of float64 roundoff bound it with room; a wrong column or
     power misses by the entry itself."""
-    from test_selfcal_cpu import joint_system
+    from yardstick import joint_system
     sc = cc.scene("ragged_tags")
     k = np.concatenate([sc.intr, sc.dist])
     n = 130
@@ -113,7 +113,7 @@ def test_model_system_references_are_sound(oracle, name, variant):
     for dev_cov, dev_step in case.refs.values():
         assert 0 < dev_cov <= cc.REFERENCE_CAP and 0 < dev_step <= cc.REFERENCE_CAP
     # the oracle's C and g_k against the longdouble sums, in test_gpu_selfcal.py's metric and at its bounds
-    from test_gpu_selfcal import BOUND_C, BOUND_COST, BOUND_G
+    from yardstick import BOUND_C, BOUND_COST, BOUND_G
     A, B, g, C, gk, cost = cc._border_sums(case.scene, case.k, case.robust, case.mask, cc.LD)
     o = case.oracle
     live = o["mag_C"] > 0

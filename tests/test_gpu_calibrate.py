@@ -1,11 +1,11 @@
 """GPU tests of the calibration against a finished map (vmm_ba_calibrate, engine.calibrate,
 TagReconstructor.refineCameraModel and the command line).
 
-Yardstick: tests/test_calibrate_cpu.py -- calib_system / host_calibration / joint_covariance, numpy around
-oracle/oracle.py, proven against central differences there; they never call the code under test.  Tolerances: 1e-9 on
-exact data, 1e-6 per pose between two optima, covariances to 1e-6 x max|ref| as the existing
-covariance tests, costs to 1e-9 relative (second order in the gap), parameters in units of their standard deviation
-(SIGMA_GAP below).  Scenes come from synthetic.make_scene, the map is tag_gt.
+Yardstick: tests/yardstick.py -- calib_system / host_calibration / calibration_covariance, numpy around
+oracle/oracle.py, proven against central differences in tests/test_yardstick_cpu.py; they never call the code under
+test.  Tolerances: 1e-9 on exact data, 1e-6 per pose between two optima, covariances to
+1e-6 x max|ref| as the existing covariance tests, costs to 1e-9 relative (second order in the gap), parameters in units of their standard deviation
+(yardstick.SIGMA_GAP).  Scenes come from synthetic.make_scene, the map is tag_gt.
 """
 import os
 import shutil
@@ -13,20 +13,11 @@ import shutil
 import numpy as np
 import pytest
 
-from test_calibrate_cpu import calib_system, host_calibration, joint_covariance
+from yardstick import PERTURB, SIGMA_GAP, calib_system, calibration_covariance, host_calibration, pose_gap
 
 pytestmark = pytest.mark.gpu
 
-# the start the issue's scipy check used: the truth plus this
-PERTURB = np.array([200.0, -150.0, 30.0, -25.0, 0.02, -0.05, 1e-3, -1e-3, 0.02])
 WIDE = dict(inlier_px=1e4, loc_inlier_px=1e4)   # the data hold no outliers: every observation is an inlier
-# Parameter gap between the device and the host optimum, in standard deviations of the parameter (from the
-# reference's covariance).  host_calibration and scipy.optimize.least_squares (trf, x_scale='jac', all tolerances 1e-15,
-# analytic Jacobian, poses re-centred until the step vanished), both started at the truth on make_scene(1) at its 0.3 px
-# noise, non-robust, ended 1.01e-6 sigma apart at the worst parameter (cx; costs 65.3073967012152 against
-# 65.3073967012186: the cost is flat to rounding over that distance).  Ten times that, the device stopping on yet another
-# criterion; the cap of 1e-3 sigma does not bind.
-SIGMA_GAP = 1.01e-5
 EXACT = {
     "config1_20x10": (1, dict()),
     "distortion_12x8": (5, dict(n_cams=12, n_tags=8, visibility=0.6)),
@@ -39,9 +30,7 @@ OUTLIER_SCENE = (5, dict(n_cams=30, n_tags=40, visibility=0.5))
 
 def _csr(s):
     """The scene's observations grouped by image: (img_start, obs_img, obs_tag, obs_px)."""
-    order = np.argsort(s.obs_cam, kind="stable")
-    start = np.zeros(len(s.cam_gt) + 1, np.int64)
-    start[1:] = np.cumsum(np.bincount(s.obs_cam, minlength=len(s.cam_gt)))
+    start, order = s.by_image()
     return start, s.obs_cam[order].astype(np.int64), s.obs_tag[order].astype(np.int32), s.obs_px[order].copy()
 
 
@@ -54,17 +43,6 @@ def _calibrate(s, k0, start, tag, px, **kw):
     out = eng.calibrate(k0[:4], k0[4:], s.tag_gt, s.tag_wh, start, tag, px, **kw)
     return dict(zip(("intr", "dist", "intr_cov", "cam", "cam_cov", "inl", "res", "report"), out),
                 k=np.concatenate([out[0], out[1]]))
-
-
-def _pose_gap(a, b):
-    """As tests/test_gpu_localize.py: max over the poses of |dq| (unit quaternions, sign-aligned) and |dt| / max(|t|, 1)."""
-    a, b = np.atleast_2d(a), np.atleast_2d(b)
-    qa = a[:, :4] / np.linalg.norm(a[:, :4], axis=1, keepdims=True)
-    qb = b[:, :4] / np.linalg.norm(b[:, :4], axis=1, keepdims=True)
-    sign = np.sign(np.sum(qa * qb, axis=1))[:, None]
-    dq = np.linalg.norm(qa * sign - qb, axis=1)
-    dt = np.linalg.norm(a[:, 4:] - b[:, 4:], axis=1) / np.maximum(np.linalg.norm(b[:, 4:], axis=1), 1.0)
-    return float(dq.max()), float(dt.max())
 
 
 def _assert_clean(d):
@@ -80,9 +58,9 @@ def _check_against_host(O, s, d, ref, used, label, mask=0x1FF):
     """The device's result `d` against the host optimum ref = (k, cams, cost, H) over the images `used`: poses to 1e-6,
     cost to 1e-9 relative on either side, every free parameter to SIGMA_GAP standard deviations."""
     k_ref, cams_ref, cost_ref, H = ref
-    icov, _ = joint_covariance(H, len(cams_ref), mask)
+    icov, _ = calibration_covariance(H, len(cams_ref), mask)
     sigma = np.sqrt(np.diag(icov))
-    gq, gt = _pose_gap(d["cam"][used], cams_ref)
+    gq, gt = pose_gap(d["cam"][used], cams_ref)
     rel = (d["report"]["final_cost"] - cost_ref) / cost_ref
     free = [j for j in range(9) if (mask >> j) & 1]
     gap = np.abs(d["k"] - k_ref)[free] / sigma[free]
@@ -105,7 +83,7 @@ def test_exact_data_recovers_the_camera_model_and_the_poses(name):
     start, _, tag, px = _csr(s)
     d = _calibrate(s, _truth(s) + PERTURB, start, tag, px, **WIDE)
     rep = d["report"]
-    gq, gt = _pose_gap(d["cam"], s.cam_gt)
+    gq, gt = pose_gap(d["cam"], s.cam_gt)
     err = np.abs(d["k"] - _truth(s)) / np.maximum(np.abs(_truth(s)), 1.0)
     print("%s: %d images %d observations; status %d trials %d accepted %d passes %d; rms %.3g -> %.3g px; |dq| %.3g |dt| %.3g; "
           "parameter errors %s" % (name, len(d["cam"]), len(tag), rep["status"], rep["trials"], rep["accepted"], rep["passes"],
@@ -160,7 +138,7 @@ def test_robust_loss_reaches_the_host_optimum(oracle, noisy):
 def test_covariances_match_the_inverse_of_the_full_normal_matrix(oracle, noisy):
     s, (start, img, tag, px), d, _ = noisy
     _, _, J = calib_system(oracle, d["k"], d["cam"], s.tag_gt, s.tag_wh, img, tag, px, robust=False)
-    icov, ccov = joint_covariance(J.T @ J, len(s.cam_gt))
+    icov, ccov = calibration_covariance(J.T @ J, len(s.cam_gt))
     err = np.abs(d["intr_cov"] - icov).max() / np.abs(icov).max()
     print("intr_cov: error %.3g of max|ref|; sigma %s" % (err, np.array2string(np.sqrt(np.diag(icov)), precision=3)))
     assert err <= 1e-6
@@ -304,7 +282,7 @@ def test_edges_single_tag_empty_images_and_an_unusable_image():
     assert (d["cam"][1] == [1, 0, 0, 0, 0, 0, 0]).all() and (d["cam_cov"][1] == 0).all() and not d["inl"][e1 - b1]
     assert d["report"]["status"] == _lib.CAL_OK and d["report"]["n_images_used"] == n - 1
     good = [0] + list(range(2, n))
-    gq, gt = _pose_gap(d["cam"][good], s.cam_gt[[1] + list(range(2, len(s.cam_gt)))])
+    gq, gt = pose_gap(d["cam"][good], s.cam_gt[[1] + list(range(2, len(s.cam_gt)))])
     err = np.abs(d["k"] - _truth(s)) / np.maximum(np.abs(_truth(s)), 1.0)
     print("unusable image among %d: |dq| %.3g |dt| %.3g parameter errors %s" % (n, gq, gt, np.array2string(err, precision=3)))
     assert gq <= 1e-9 and gt <= 1e-9 and (err <= 1e-9).all()
@@ -353,7 +331,7 @@ def test_command_line_and_reconstructor_member_recover_the_truth(tmp_path):
     assert report["intrinsics"].tobytes() == k.tobytes() and report["covariance"].tobytes() == cov.tobytes()
     m = rec.getCameraModel()
     assert np.concatenate([[m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients]).tobytes() == k.tobytes()
-    gq, gt = _pose_gap(np.array([np.concatenate([report["cameras"][i].q, report["cameras"][i].t]) for i in range(len(s.cam_gt))]),
+    gq, gt = pose_gap(np.array([np.concatenate([report["cameras"][i].q, report["cameras"][i].t]) for i in range(len(s.cam_gt))]),
                        s.cam_gt)
     assert sorted(report["cameras"]) == list(range(len(s.cam_gt))) and gq <= 1e-9 and gt <= 1e-9
     # the same "does not exist" errors as the localisation step

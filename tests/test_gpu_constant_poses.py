@@ -1,11 +1,10 @@
 """GPU tests of constant poses (vmm_ba_set_constant_poses) and of the map extension built on them.
 
 Yardsticks: a handle whose only constant is the problem's fixed_tag (same bits); the CPU oracle's per-observation
-residuals and Jacobians, accumulated here with the constant poses' columns zeroed (blocks, the restricted optimum, the
-covariance); exact data; and the optimum reached from the generator's perturbed truth.  Tolerances are those of the
-existing tests of the same quantities: blocks 1e-11 / 1e-10 (test_gpu_kernels.py), 1e-6 per pose between two optima
-(the form of test_gpu_init._pose_gap), 1e-6 of a block's largest entry for the covariance
-(test_gpu_solve.py).
+residuals and Jacobians, accumulated by tests/yardstick.py with the constant poses' columns zeroed (blocks, the restricted
+optimum, the covariance); exact data; and the optimum reached from the generator's perturbed truth.  Tolerances are those
+of the existing tests of the same quantities: blocks 1e-11 / 1e-10 (test_gpu_kernels.py), 1e-6 per pose between two
+optima (yardstick.pose_gap), 1e-6 of a block's largest entry for the covariance (test_gpu_solve.py).
 """
 import contextlib
 import json
@@ -13,6 +12,8 @@ import os
 
 import numpy as np
 import pytest
+
+import yardstick as ys
 
 pytestmark = pytest.mark.gpu
 
@@ -42,89 +43,9 @@ def _two_solves(eng, ba, trace_capacity=0):
     return a, b
 
 
-def _pose_gap(a, b):
-    """test_gpu_init._pose_gap: max over the poses of |dq| (unit quaternions, sign-aligned) and |dt| / max(|t|, 1)."""
-    if len(a) == 0:
-        return 0.0, 0.0
-    qa = a[:, :4] / np.linalg.norm(a[:, :4], axis=1, keepdims=True)
-    qb = b[:, :4] / np.linalg.norm(b[:, :4], axis=1, keepdims=True)
-    sign = np.sign(np.sum(qa * qb, axis=1))[:, None]
-    dq = np.linalg.norm(qa * sign - qb, axis=1)
-    dt = np.linalg.norm(a[:, 4:] - b[:, 4:], axis=1) / np.maximum(np.linalg.norm(b[:, 4:], axis=1), 1.0)
-    return float(dq.max()), float(dt.max())
-
-
-def _flags(n, idx):
-    f = np.zeros(n, np.uint8)
-    f[list(idx)] = 1
-    return f
-
-
 def _trace_bits(out):
     return [(t["cost"], t["trust_region_radius"], t["step_norm"], t["gradient_max_norm"], t["step_is_successful"])
             for t in out["trace"]]
-
-
-def _oracle_blocks(O, s, cam, tag, robust, cam_const, tag_const):
-    """V, U, W, g, cost from the oracle's per-observation residuals and Jacobians, evaluated WITHOUT any fixed tag
-    (as test_gpu_kernels._blocks_from_oracle with fixed_tag = -1); the rows of the constant poses are zeroed here."""
-    n_c, n_t = len(cam), len(tag)
-    V, U = np.zeros((n_c, 6, 6)), np.zeros((n_t, 6, 6))
-    W = np.zeros((len(s.obs_cam), 6, 6))
-    gc, gt = np.zeros((n_c, 6)), np.zeros((n_t, 6))
-    cost = 0.0
-    for i, (c, t) in enumerate(zip(s.obs_cam, s.obs_tag)):
-        r, Jc, Jt = O.obs_eval(s.intr, s.dist, cam[c], tag[t], s.tag_wh[t], s.obs_px[i])
-        for k in range(4):
-            sq = r[2 * k] ** 2 + r[2 * k + 1] ** 2
-            rho = O.huber(1.0, sq) if robust else np.array([sq, 1.0, 0.0])
-            cost += 0.5 * rho[0]
-            w = np.sqrt(rho[1])
-            Jc[2 * k:2 * k + 2] *= w
-            Jt[2 * k:2 * k + 2] *= w
-            r[2 * k:2 * k + 2] *= w
-        V[c] += Jc.T @ Jc
-        U[t] += Jt.T @ Jt
-        W[i] = Jc.T @ Jt
-        gc[c] += Jc.T @ r
-        gt[t] += Jt.T @ r
-    cc, tc = np.asarray(cam_const, bool), np.asarray(tag_const, bool)
-    V[cc] = 0.0
-    gc[cc] = 0.0
-    U[tc] = 0.0
-    gt[tc] = 0.0
-    W[cc[s.obs_cam] | tc[s.obs_tag]] = 0.0
-    return dict(V=V, U=U, W=W, g_cam=gc, g_tag=gt, cost=cost)
-
-
-def _free_system(s, blk, cam_const, tag_const):
-    """Dense H and g over the free poses (cameras first, then tags) from the blocks; index of every free pose."""
-    fc = np.flatnonzero(~np.asarray(cam_const, bool))
-    ft = np.flatnonzero(~np.asarray(tag_const, bool))
-    pos_c = {int(c): k for k, c in enumerate(fc)}
-    pos_t = {int(t): len(fc) + k for k, t in enumerate(ft)}
-    n = 6 * (len(fc) + len(ft))
-    H, g = np.zeros((n, n)), np.zeros(n)
-    for c, k in pos_c.items():
-        H[6 * k:6 * k + 6, 6 * k:6 * k + 6] = blk["V"][c]
-        g[6 * k:6 * k + 6] = blk["g_cam"][c]
-    for t, k in pos_t.items():
-        H[6 * k:6 * k + 6, 6 * k:6 * k + 6] = blk["U"][t]
-        g[6 * k:6 * k + 6] = blk["g_tag"][t]
-    for i, (c, t) in enumerate(zip(s.obs_cam.tolist(), s.obs_tag.tolist())):
-        if c in pos_c and t in pos_t:
-            a, b = pos_c[c], pos_t[t]
-            H[6 * a:6 * a + 6, 6 * b:6 * b + 6] += blk["W"][i]
-            H[6 * b:6 * b + 6, 6 * a:6 * a + 6] += blk["W"][i].T
-    return H, g, fc, ft
-
-
-def _const_sets(s, n_tag_const, n_cam_const):
-    """Constant flags that contain observation 0's camera and tag: one observation between two constant poses."""
-    tags = [int(s.obs_tag[0])] + [t for t in range(len(s.tag_gt)) if t != s.obs_tag[0]][:n_tag_const - 1]
-    cams = ([int(s.obs_cam[0])] + [c for c in range(len(s.cam_gt)) if c != s.obs_cam[0]][:n_cam_const - 1]
-            if n_cam_const else [])
-    return _flags(len(s.cam_gt), cams), _flags(len(s.tag_gt), tags)
 
 
 # ---- 1. the same bits as fixed_tag ----------------------------------------------------------------------------------
@@ -140,7 +61,7 @@ def test_constant_tag_zero_gives_the_bits_of_fixed_tag_zero(monkeypatch, name, s
     for fixed in (0, -1):
         with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=fixed) as ba:
             if fixed < 0:
-                ba.set_constant_poses(None, _flags(len(s.tag_gt), [0]))
+                ba.set_constant_poses(None, ys.flags(len(s.tag_gt), [0]))
             out = ba.solve(eng.default_options(robustify=robust), trace_capacity=256)
             res.append((out, ba.get_state()))
     (a, (cam_a, tag_a)), (b, (cam_b, tag_b)) = res
@@ -155,7 +76,7 @@ def test_constant_tag_zero_gives_the_bits_of_fixed_tag_zero(monkeypatch, name, s
 def test_clearing_the_constants_gives_the_bits_of_a_fresh_handle():
     from visual_marker_mapping_amd import engine as eng
     s = _scene("config1_20x10")
-    cam_const, tag_const = _const_sets(s, 3, 2)
+    cam_const, tag_const = ys.const_sets(s, 3, 2)
     opts = lambda: eng.default_options(robustify=1)
     with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=0) as ba:
         ba.set_constant_poses(cam_const, tag_const)
@@ -182,7 +103,7 @@ def test_clearing_the_constants_gives_the_bits_of_a_fresh_handle():
 def test_blocks_with_constant_poses_match_oracle(oracle, name, n_tag_const, n_cam_const, elim, robust):
     from visual_marker_mapping_amd import engine as eng
     s = _scene(name)
-    cam_const, tag_const = _const_sets(s, n_tag_const, n_cam_const)
+    cam_const, tag_const = ys.const_sets(s, n_tag_const, n_cam_const)
     if n_cam_const:
         assert cam_const[s.obs_cam[0]] and tag_const[s.obs_tag[0]]   # an observation between two constant poses
     mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
@@ -190,7 +111,7 @@ def test_blocks_with_constant_poses_match_oracle(oracle, name, n_tag_const, n_ca
         ba.set_constant_poses(cam_const if n_cam_const else None, tag_const)
         got = ba.eval_blocks(robustify=robust)
         cost = ba.cost(robustify=robust)
-    ref = _oracle_blocks(oracle, s, s.cam_init, s.tag_init, robust, cam_const, tag_const)
+    ref = ys.pose_blocks(oracle, s, s.cam_init, s.tag_init, robust, cam_const=cam_const, tag_const=tag_const)
     print("%s elim %s robust %d: cost gpu %.15g oracle %.15g" % (name, elim, robust, got["cost"], ref["cost"]))
     assert abs(got["cost"] - ref["cost"]) <= 1e-11 * ref["cost"]
     assert abs(cost - ref["cost"]) <= 1e-11 * ref["cost"]
@@ -209,7 +130,7 @@ def test_point_blocks_with_constant_poses_match_oracle(oracle):
     camera's rows are zero; a constant tag leaves the cameras' blocks as they are (its observations still count)."""
     from visual_marker_mapping_amd import engine as eng
     s = _scene("config1_20x10")
-    cam_const, tag_const = _const_sets(s, 3, 2)
+    cam_const, tag_const = ys.const_sets(s, 3, 2)
     sc, pts = oracle.point_scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, -1, s.obs_cam, s.obs_tag, s.obs_px)
     with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=-1, landmarks=eng.LANDMARK_POINTS) as ba:
         ba.set_constant_poses(cam_const, tag_const)
@@ -236,7 +157,7 @@ def test_point_blocks_with_constant_poses_match_oracle(oracle):
 def test_solves_never_move_a_constant_pose(elim):
     from visual_marker_mapping_amd import engine as eng
     s = _scene("config1_20x10")
-    cam_const, tag_const = _const_sets(s, 3, 2)
+    cam_const, tag_const = ys.const_sets(s, 3, 2)
     cc, tc = cam_const.astype(bool), tag_const.astype(bool)
     mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
     cam0, tag0 = np.ascontiguousarray(s.cam_init), np.ascontiguousarray(s.tag_init)
@@ -265,37 +186,10 @@ def test_solves_never_move_a_constant_pose(elim):
 
 # ---- 4. the optimum of the restricted problem -----------------------------------------------------------------------
 
-def _gauss_newton(O, s, cam, tag, cam_const, tag_const, max_iter=25):
-    """Undamped dense Gauss-Newton on the plain cost over the free poses, from (cam, tag), until |step|_inf < 1e-12."""
-    cam, tag = cam.copy(), tag.copy()
-    step = np.inf
-    for it in range(max_iter):
-        blk = _oracle_blocks(O, s, cam, tag, False, cam_const, tag_const)
-        H, g, fc, ft = _free_system(s, blk, cam_const, tag_const)
-        d = np.linalg.solve(H, -g)
-        step = float(np.abs(d).max())
-        for k, c in enumerate(fc):
-            cam[c] = O.pose_plus(cam[c], d[6 * k:6 * k + 6])
-        for k, t in enumerate(ft):
-            tag[t] = O.pose_plus(tag[t], d[6 * (len(fc) + k):6 * (len(fc) + k) + 6])
-        if step < 1e-12:
-            break
-    return cam, tag, step, it + 1
-
-
-def _gradient_max_norm(O, blk, cam, tag, cam_const, tag_const):
-    """Ceres' gradient max-norm |Plus(x, -g) - x|_inf over the free poses."""
-    gm = 0.0
-    for x, g, const in ((cam, blk["g_cam"], cam_const), (tag, blk["g_tag"], tag_const)):
-        for p in np.flatnonzero(~np.asarray(const, bool)):
-            gm = max(gm, float(np.abs(O.pose_plus(x[p], -g[p]) - x[p]).max()))
-    return gm
-
-
 def _restricted_optimum_case(name, n_tag_const, n_cam_const):
     from visual_marker_mapping_amd import engine as eng
     s = _scene(name)
-    cam_const, tag_const = _const_sets(s, n_tag_const, n_cam_const)
+    cam_const, tag_const = ys.const_sets(s, n_tag_const, n_cam_const)
     with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=-1) as ba:
         ba.set_constant_poses(cam_const if n_cam_const else None, tag_const)
         rob, plain = _two_solves(eng, ba, trace_capacity=2048)
@@ -308,12 +202,12 @@ def _restricted_optimum_case(name, n_tag_const, n_cam_const):
 def test_solve_reaches_the_optimum_of_the_restricted_problem(oracle, name, n_tag_const, n_cam_const):
     eng, s, cam_const, tag_const, rob, plain, cam, tag, _ = _restricted_optimum_case(name, n_tag_const, n_cam_const)
     assert rob["termination_type"] == plain["termination_type"] == eng.CONVERGENCE
-    ref_cam, ref_tag, step, iters = _gauss_newton(oracle, s, cam, tag, cam_const, tag_const)
+    ref_cam, ref_tag, step, iters = ys.gauss_newton(oracle, s, cam, tag, cam_const, tag_const)
     assert step < 1e-12, (step, iters)
-    gq_c, gt_c = _pose_gap(cam, ref_cam)
-    gq_t, gt_t = _pose_gap(tag, ref_tag)
-    blk = _oracle_blocks(oracle, s, cam, tag, False, cam_const, tag_const)
-    gm = _gradient_max_norm(oracle, blk, cam, tag, cam_const, tag_const)
+    gq_c, gt_c = ys.pose_gap(cam, ref_cam)
+    gq_t, gt_t = ys.pose_gap(tag, ref_tag)
+    blk = ys.pose_blocks(oracle, s, cam, tag, False, cam_const=cam_const, tag_const=tag_const)
+    gm = ys.gradient_max_norm(oracle, blk, cam, tag, cam_const, tag_const)
     gtol = eng.default_options().gradient_tolerance
     last = plain["trace"][-1]
     ended_on = "gradient_tolerance" if last["gradient_max_norm"] <= gtol else "function_tolerance or parameter_tolerance"
@@ -334,8 +228,8 @@ def test_solve_reaches_the_optimum_of_the_restricted_problem(oracle, name, n_tag
 @pytest.mark.parametrize("name,n_tag_const,n_cam_const", [("config1_20x10", 3, 2), ("100x60_vis0.30", 20, 0)])
 def test_covariance_is_conditional_on_the_constants(oracle, name, n_tag_const, n_cam_const):
     eng, s, cam_const, tag_const, _, _, cam, tag, cov = _restricted_optimum_case(name, n_tag_const, n_cam_const)
-    blk = _oracle_blocks(oracle, s, cam, tag, False, cam_const, tag_const)
-    H, _, fc, ft = _free_system(s, blk, cam_const, tag_const)
+    blk = ys.pose_blocks(oracle, s, cam, tag, False, cam_const=cam_const, tag_const=tag_const)
+    H, _, fc, ft = ys.free_system(s, blk, cam_const, tag_const)
     Hinv = np.linalg.inv(H)
     for t in np.flatnonzero(tag_const):
         assert np.all(cov[t] == 0.0), t
@@ -426,8 +320,8 @@ def test_extension_on_exact_data(name):
     assert report["cams_reached"] == want_cam.sum() and report["tags_reached"] == want_tag.sum()
     assert tag_ok[sp.map_tags].all() and cam_ok.any() and tag_ok[~sp.map_tags].any()
     new_tags = tag_ok & ~sp.map_tags
-    gq_c, gt_c = _pose_gap(cam[cam_ok], s.cam_gt[cam_ok])
-    gq_t, gt_t = _pose_gap(tag[new_tags], s.tag_gt[new_tags])
+    gq_c, gt_c = ys.pose_gap(cam[cam_ok], s.cam_gt[cam_ok])
+    gq_t, gt_t = ys.pose_gap(tag[new_tags], s.tag_gt[new_tags])
     print("   max |dq| cams %.3g new tags %.3g, max |dt| cams %.3g new tags %.3g" % (gq_c, gq_t, gt_c, gt_t))
     assert max(gq_c, gq_t) <= 1e-6 and max(gt_c, gt_t) <= 1e-6
     assert tag[sp.map_tags].tobytes() == np.ascontiguousarray(s.tag_gt[sp.map_tags]).tobytes()
@@ -457,8 +351,8 @@ def test_extension_under_noise_reaches_the_optimum_of_a_good_start(name):
             assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE, (label, a, b)
             res[label] = ba.get_state() + (b["final_cost"],)
     report, cam_ok, tag_ok = res["reach"]
-    gq_c, gt_c = _pose_gap(res["A"][0][cam_ok], res["B"][0][cam_ok])
-    gq_t, gt_t = _pose_gap(res["A"][1][tag_ok], res["B"][1][tag_ok])
+    gq_c, gt_c = ys.pose_gap(res["A"][0][cam_ok], res["B"][0][cam_ok])
+    gq_t, gt_t = ys.pose_gap(res["A"][1][tag_ok], res["B"][1][tag_ok])
     print("%s: reached %d/%d cameras %d/%d tags in %d rounds; max |dq| cams %.3g tags %.3g, max |dt| cams %.3g tags "
           "%.3g; final cost A %.12g B %.12g" % (name, cam_ok.sum(), len(cam_ok), tag_ok.sum(), len(tag_ok),
                                                 report["rounds"], gq_c, gq_t, gt_c, gt_t, res["A"][2], res["B"][2]))
@@ -481,7 +375,7 @@ def test_initialize_needs_a_constant_pose_and_grows_from_a_constant_camera():
         with pytest.raises(_lib.VmmBaError) as ei:
             ba.initialize()
         assert ei.value.status == _lib.ERR_ARGUMENT
-        ba.set_constant_poses(_flags(len(cam0), [seed]), None)
+        ba.set_constant_poses(ys.flags(len(cam0), [seed]), None)
         # a tag needs two active observations by default: with one the constant camera's tags are placed at once
         report, cam_ok, tag_ok = ba.initialize(min_tag_observations=1)
         cam_i, tag_i = ba.get_state()
@@ -497,7 +391,7 @@ def test_initialize_needs_a_constant_pose_and_grows_from_a_constant_camera():
     assert a["termination_type"] == b["termination_type"] == eng.CONVERGENCE
     assert cam_i[seed].tobytes() == cam[seed].tobytes() == cam0[seed].tobytes()
     assert not np.array_equal(tag_i[sees], tag0[sees])
-    gq, gt = _pose_gap(tag[sees], s.tag_gt[sees])
+    gq, gt = ys.pose_gap(tag[sees], s.tag_gt[sees])
     print("constant camera %d sees %d tags: placed, max |dq| %.3g |dt| %.3g; reached %d cameras %d tags"
           % (seed, len(sees), gq, gt, cam_ok.sum(), tag_ok.sum()))
     assert gq <= 1e-6 and gt <= 1e-6
@@ -542,7 +436,7 @@ def test_extension_command_line(tmp_path, capsys):
     new = sorted(set(tags) - {int(k) for k in before})
     assert new == np.flatnonzero(want_tag & ~sp.map_tags).tolist() and len(new) > 0
     got = np.array([np.r_[tags[t].q, tags[t].t] for t in new])
-    gq, gt = _pose_gap(got, s.tag_gt[new])
+    gq, gt = ys.pose_gap(got, s.tag_gt[new])
     n_see = len(np.unique(s.obs_cam[sp.map_tags[s.obs_tag]]))
     print("command line: %d map tags kept, %d new tags (max |dq| %.3g |dt| %.3g), %d cameras of %d images"
           % (len(before), len(new), gq, gt, len(cams), len(s.cam_gt)))
@@ -593,7 +487,7 @@ def test_fused_blocks_with_constant_poses_match_oracle(oracle, monkeypatch, prec
     from visual_marker_mapping_amd import engine as eng
     monkeypatch.setenv("VMM_BA_EVAL", "fused")
     s = _scene("config1_20x10")
-    cam_const, tag_const = _const_sets(s, 3, 2)
+    cam_const, tag_const = ys.const_sets(s, 3, 2)
     cc, tc = cam_const.astype(bool), tag_const.astype(bool)
     assert cc[s.obs_cam[0]] and tc[s.obs_tag[0]] and s.n_obs == len(s.cam_gt) * len(s.tag_gt)
     mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
@@ -602,7 +496,7 @@ def test_fused_blocks_with_constant_poses_match_oracle(oracle, monkeypatch, prec
         ba.set_constant_poses(cam_const, tag_const)
         got = ba.eval_blocks(robustify=robust)
         cost = ba.cost(robustify=robust)
-    ref = _oracle_blocks(oracle, s, s.cam_init, s.tag_init, robust, cam_const, tag_const)
+    ref = ys.pose_blocks(oracle, s, s.cam_init, s.tag_init, robust, cam_const=cam_const, tag_const=tag_const)
     print("fused %s elim %s robust %d: cost gpu %.15g oracle %.15g" % (precision, elim, robust, got["cost"], ref["cost"]))
     assert abs(got["cost"] - ref["cost"]) <= 1e-11 * ref["cost"]
     assert abs(cost - ref["cost"]) <= 1e-11 * ref["cost"]
@@ -625,7 +519,7 @@ def test_fused_solves_never_move_a_constant_pose(monkeypatch, elim, landmarks):
     poses end (1e-9 of the largest entry, as test_gpu_fused_eval.py compares the two kernels' solves)."""
     from visual_marker_mapping_amd import engine as eng
     s = _scene("config1_20x10")
-    cam_const, tag_const = _const_sets(s, 3, 2)
+    cam_const, tag_const = ys.const_sets(s, 3, 2)
     cc, tc = cam_const.astype(bool), tag_const.astype(bool)
     mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
     cam0, tag0 = np.ascontiguousarray(s.cam_init), np.ascontiguousarray(s.tag_init)
@@ -674,7 +568,7 @@ def test_point_handle_constant_tag_gives_the_bits_of_fixed_tag(elim):
             with _handle(eng, s, s.cam_init, s.tag_init, fixed_tag=fixed, elimination=mode,
                          landmarks=eng.LANDMARK_POINTS) as ba:
                 if fixed < 0:
-                    ba.set_constant_poses(None, _flags(len(s.tag_gt), [t]))
+                    ba.set_constant_poses(None, ys.flags(len(s.tag_gt), [t]))
                 pts0 = ba.get_points()
                 blk = ba.eval_blocks(robustify=False, want_W=False)
                 out = ba.solve(eng.default_options(robustify=0), trace_capacity=256)

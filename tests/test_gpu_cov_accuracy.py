@@ -196,7 +196,7 @@ def run_model(eng, O, name, elim):
     """intrinsics_system on a ragged scene (poses with 1, 63, 64, 65, 128 and 129 observations through border_body) at
     k = truth + 0.01 PERTURB: C, g_k and the cost in test_gpu_selfcal.py's metric and bounds, inv(S_k) and the step
     inv(S_k) r_k in cov_cases.ModelCase's metrics and bounds."""
-    from test_gpu_selfcal import BOUND_C, BOUND_COST, BOUND_G, _same_bytes
+    from yardstick import BOUND_C, BOUND_COST, BOUND_G, same_bytes
     sc = cc.scene(name)
     bad, recs = [], []
     first = cc.model_case(O, name, cc.MODEL_VARIANTS[0][0])
@@ -230,7 +230,7 @@ def run_model(eng, O, name, elim):
                                  deviation=d, ratio_to_bound=d / bound))
             if not np.array_equal(got["S_k"], got["S_k"].T):
                 bad.append("%s: S_k is not symmetric in its bits" % label)
-            if not _same_bytes(got, again):
+            if not same_bytes(got, again):
                 bad.append("%s: the second call gives other bits" % label)
     return bad, recs
 

@@ -255,7 +255,7 @@ def test_sharded_full_size(tmp_path, oracle, world, spin_rank):
     Trace against the 1-rank solve (1e-10) and against the oracle's Schur path; ranks bit-identical to each other.
     spin_rank: that rank's factorisation gives up waiting once -- every rank pauses in that pass and redoes it."""
     mp = pytest.importorskip("torch.multiprocessing")
-    from test_gpu_solve import _assert_same_solution, _assert_same_trace
+    from yardstick import assert_same_solution, assert_same_trace
     from visual_marker_mapping_amd import engine as eng
     R = _full_reference(oracle)
     s, ref = R["s"], R["ref"]
@@ -286,8 +286,8 @@ def test_sharded_full_size(tmp_path, oracle, world, spin_rank):
                trace=[dict(iteration=i, step_is_successful=int(k), cost=float(c), trust_region_radius=float(rad))
                       for i, (k, c, rad) in enumerate(zip(r0["ok"], r0["costs"], r0["radius"]))])
     assert got["num_successful_steps"] == ref["num_successful_steps"]
-    _assert_same_trace(got, R["summ"], R["trace"])
-    _assert_same_solution(r0["cam"], r0["tag"], R["sc"], s.tag_wh)
+    assert_same_trace(got, R["summ"], R["trace"])
+    assert_same_solution(r0["cam"], r0["tag"], R["sc"], s.tag_wh)
 
 
 @pytest.mark.parametrize("graph", ["1", "0"])

@@ -7,12 +7,12 @@ references on the same case and array: A, the oracle's functor summed in numpy, 
 Entries of magnitude 0 must be exactly 0.  The references set the bound, never the code under test; every test prints
 deviation, bound and ratio (tools/eval_accuracy.py records them, DESIGN.md section 4.13 holds the measured ones).
 """
-import functools
 
 import numpy as np
 import pytest
 
 import eval_cases as ec
+import yardstick as ys
 
 pytestmark = pytest.mark.gpu
 
@@ -218,8 +218,8 @@ def test_solve_with_another_width_matches_the_oracle(eng, oracle, a):
     out, cam, tag, summ, trace, sc = ts._run_both(eng, oracle, s, "auto", robustify=1, huber_a=a)
     print("huber_a %g: %d iterations, final cost device %.12g oracle %.12g" % (a, out["iterations"], out["final_cost"],
                                                                             summ["final_cost"]))
-    ts._assert_same_trace(out, summ, trace)
-    ts._assert_same_solution(cam, tag, sc, s.tag_wh)
+    ys.assert_same_trace(out, summ, trace)
+    ys.assert_same_solution(cam, tag, sc, s.tag_wh)
 
 
 @pytest.mark.parametrize("first,second", [(1.0, 2.5), (2.5, 1.0)])
@@ -301,7 +301,7 @@ def test_covariance_with_another_width_matches_the_inverse_normal_matrix(eng, or
 
 
 def test_localize_with_another_width_reaches_the_host_optimum(eng, oracle, monkeypatch):
-    """engine.localize(huber_a=0.5) against the small host LM of test_gpu_localize.py run with the same width, at its
+    """engine.localize(huber_a=0.5) against yardstick.image_optimum run with the same width, at its
     tolerance (1e-6 per pose).  make_scene(1) has 0.3 px of noise: a quarter of the corners have |r| > 0.5 px."""
     import test_gpu_localize as tl
     from visual_marker_mapping_amd import _lib
@@ -314,17 +314,15 @@ def test_localize_with_another_width_reaches_the_host_optimum(eng, oracle, monke
     cam1, _, _, _ = tl._localize(eng, s, start, tag, px, robustify=1)
     assert [r["status"] for r in res] == [_lib.LOC_OK] * len(cam)
     tl._assert_clean(cam, cov, res)
-    # _host_optimum evaluates through the module's _normal_equations, which takes the width
-    monkeypatch.setattr(tl, "_normal_equations", functools.partial(tl._normal_equations, a=a))
-    worst = tl._check_against_host(oracle, s, start, tag, px, cam, inl, res, range(len(cam)), True, "huber_a=%g" % a)
-    gap = tl._pose_gap(cam, cam1)
+    worst = tl._check_against_host(oracle, s, start, tag, px, cam, inl, res, range(len(cam)), True, "huber_a=%g" % a, a=a)
+    gap = ys.pose_gap(cam, cam1)
     print("huber_a %g: worst |dq| %.3g |dt| %.3g against the host; the default width lands |dq| %.3g |dt| %.3g away"
           % (a, worst[0], worst[1], gap[0], gap[1]))
     assert max(gap) > 1e-5      # ten times the tolerance: the comparison above can tell the two widths apart
 
 
 def test_calibrate_with_another_width_reaches_the_host_optimum(eng, oracle):
-    """engine.calibrate(huber_a=0.5) against test_calibrate_cpu.host_calibration(a=0.5) at the tolerances of
+    """engine.calibrate(huber_a=0.5) against yardstick.host_calibration(a=0.5) at the tolerances of
     test_gpu_calibrate.py."""
     import test_gpu_calibrate as tc
     from visual_marker_mapping_amd import _lib
@@ -333,17 +331,17 @@ def test_calibrate_with_another_width_reaches_the_host_optimum(eng, oracle):
     s = make_scene(1)
     assert s.noise_px == 0.3
     start, img, tag, px = tc._csr(s)
-    d = tc._calibrate(s, tc._truth(s) + tc.PERTURB, start, tag, px, robustify=1, huber_a=a, loc_huber_a=a,
+    d = tc._calibrate(s, tc._truth(s) + ys.PERTURB, start, tag, px, robustify=1, huber_a=a, loc_huber_a=a,
                       reclassify_passes=0, **tc.WIDE)
     tc._assert_clean(d)
     assert d["report"]["status"] == _lib.CAL_OK and d["inl"].all()
-    ref = tc.host_calibration(oracle, tc._truth(s), s.cam_gt, s.tag_gt, s.tag_wh, img, tag, px, robust=True, a=a)
+    ref = ys.host_calibration(oracle, tc._truth(s), s.cam_gt, s.tag_gt, s.tag_wh, img, tag, px, robust=True, a=a)
     tc._check_against_host(oracle, s, d, ref, np.arange(len(s.cam_gt)), "huber_a=%g" % a)
-    ref1 = tc.host_calibration(oracle, tc._truth(s), s.cam_gt, s.tag_gt, s.tag_wh, img, tag, px, robust=True)
-    icov, _ = tc.joint_covariance(ref[3], len(ref[1]), 0x1FF)
+    ref1 = ys.host_calibration(oracle, tc._truth(s), s.cam_gt, s.tag_gt, s.tag_wh, img, tag, px, robust=True)
+    icov, _ = ys.calibration_covariance(ref[3], len(ref[1]), 0x1FF)
     apart = np.abs(ref[0] - ref1[0]) / np.sqrt(np.diag(icov))
     print("host optima at width %g and at width 1 are %s sigma apart" % (a, np.array2string(apart, precision=3)))
-    assert (apart > 10 * tc.SIGMA_GAP).all()      # the comparison above can tell the two widths apart
+    assert (apart > 10 * ys.SIGMA_GAP).all()      # the comparison above can tell the two widths apart
 
 
 def test_initialize_then_solves_with_another_width_lead_to_the_same_optimum(eng, monkeypatch):

@@ -8,7 +8,7 @@
 import numpy as np
 import pytest
 
-from test_gpu_solve import _assert_same_solution, _assert_same_trace
+from yardstick import assert_same_solution, assert_same_trace
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +33,8 @@ def test_config5_full_size_matches_oracle(oracle):
     sc = oracle.Scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag, s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=1, num_threads=8))
     assert out["termination_type"] == eng.CONVERGENCE
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
     # statistics at the oracle's converged state (CameraModel::projectPoint arithmetic, src/CameraModel.cpp:20-23)
     opc, opt_, oavg, ocorner = oracle.reprojection_stats(sc)
     np.testing.assert_allclose(pc, opc, rtol=1e-6)
@@ -61,8 +61,8 @@ def test_sparse_visibility_full_size_matches_oracle(oracle):
     sc = oracle.Scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag, s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=0, num_threads=8))
     assert out["termination_type"] == eng.CONVERGENCE
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
     assert abs(out["final_cost"] - _expected_optimum(s, 500, 200)) < 0.03 * _expected_optimum(s, 500, 200)
 
 

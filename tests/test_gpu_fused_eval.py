@@ -95,8 +95,8 @@ def test_fused_blocks_match_the_oracle(oracle, monkeypatch):
         b = ba.eval_blocks(robustify=True)
     finally:
         ba.close()
-    from test_gpu_kernels import _blocks_from_oracle
-    ob = _blocks_from_oracle(oracle, s, s.cam_init, s.tag_init, True)
+    from yardstick import pose_blocks
+    ob = pose_blocks(oracle, s, s.cam_init, s.tag_init, True, fixed_tag=s.fixed_tag)
     np.testing.assert_allclose(b["cost"], ob["cost"], rtol=1e-12)
     for k in ("V", "U", "W", "g_cam", "g_tag"):
         scale = np.abs(ob[k]).max()

@@ -9,6 +9,8 @@ the solver ends in the same place from it.  Tolerances: 1e-9 on exact data, 1e-6
 import numpy as np
 import pytest
 
+import yardstick as ys
+
 pytestmark = pytest.mark.gpu
 
 INTR = (8075.29, 8083.17, 3016.39, 1996.29)
@@ -25,11 +27,6 @@ SCENES = {
 
 def _quad(w, h):
     return np.array([[-w / 2, -h / 2, 0], [w / 2, -h / 2, 0], [w / 2, h / 2, 0], [-w / 2, h / 2, 0]])
-
-
-def _R(q):
-    from visual_marker_mapping_amd.tag_reconstructor import _quat_to_R
-    return _quat_to_R(np.asarray(q) / np.linalg.norm(q))
 
 
 def _placeholders(s):
@@ -52,16 +49,6 @@ def _two_solves(eng, ba):
     return a, b
 
 
-def _pose_gap(a, b):
-    """max over the poses of |dq| (unit quaternions, sign-aligned) and of |dt| / max(|t|, 1)."""
-    qa = a[:, :4] / np.linalg.norm(a[:, :4], axis=1, keepdims=True)
-    qb = b[:, :4] / np.linalg.norm(b[:, :4], axis=1, keepdims=True)
-    sign = np.sign(np.sum(qa * qb, axis=1))[:, None]
-    dq = np.linalg.norm(qa * sign - qb, axis=1)
-    dt = np.linalg.norm(a[:, 4:] - b[:, 4:], axis=1) / np.maximum(np.linalg.norm(b[:, 4:], axis=1), 1.0)
-    return float(dq.max()), float(dt.max())
-
-
 def _same_optimum(eng, s, label, mask_init=None, mask_solve=None, keep_cam=None, keep_tag=None):
     """Check 3: handle A = placeholders + initialize, handle B = the perturbed ground truth; the same two solves."""
     cam0, tag0 = _placeholders(s)
@@ -79,8 +66,8 @@ def _same_optimum(eng, s, label, mask_init=None, mask_solve=None, keep_cam=None,
         camB, tagB = B.get_state()
     kc = np.ones(len(camA), bool) if keep_cam is None else keep_cam
     kt = np.ones(len(tagA), bool) if keep_tag is None else keep_tag
-    gq_c, gt_c = _pose_gap(camA[kc], camB[kc])
-    gq_t, gt_t = _pose_gap(tagA[kt], tagB[kt])
+    gq_c, gt_c = ys.pose_gap(camA[kc], camB[kc])
+    gq_t, gt_t = ys.pose_gap(tagA[kt], tagB[kt])
     print("%s: obs %d rounds %d reached %d/%d cams %d/%d tags, avg reprojection after initialize %.4g px; robust "
           "iterations A %d B %d, plain A %d B %d; max |dq| cams %.3g tags %.3g, max |dt| cams %.3g tags %.3g; "
           "final cost A %.12g B %.12g; initialize %.4f s"
@@ -113,7 +100,7 @@ def test_quad_poses_recover_exact_poses(dist):
     assert np.all(np.isfinite(qt2)) and np.all(rms2[:, 0] <= rms2[:, 1])
     worst = 0.0
     for i in range(10):
-        eR = np.abs(_R(qt2[i, 0, :4]) - Rs[i]).max()
+        eR = np.abs(ys.rotation(qt2[i, 0, :4]) - Rs[i]).max()
         et = np.abs(qt2[i, 0, 4:] - ts[i]).max()
         worst = max(worst, eR, et)
         print("pose %d: |dR| %.3g |dt| %.3g rms %.3g / %.3g px" % (i, eR, et, rms2[i, 0], rms2[i, 1]))
@@ -147,12 +134,12 @@ def test_quad_poses_against_pnp_on_config1():
         rms_cpu = np.sqrt(((pnp.project(Q, R, t, intr, dist) - px) ** 2).sum(axis=1).mean())
         # the kernel's own RMS is what it says it is
         for k in range(2):
-            e = pnp.project(Q, _R(qt2[i, k, :4]), qt2[i, k, 4:], intr, dist) - px
+            e = pnp.project(Q, ys.rotation(qt2[i, k, :4]), qt2[i, k, 4:], intr, dist) - px
             assert abs(np.sqrt((e ** 2).sum(axis=1).mean()) - rms2[i, k]) <= 1e-9 * max(1.0, rms2[i, k])
         worst_ratio = max(worst_ratio, rms2[i, 0] / rms_cpu)
         assert rms2[i, 0] <= rms_cpu * (1 + 1e-6), (i, rms2[i], rms_cpu)
-        Rg = _R(s.cam_gt[s.obs_cam[i], :4]) @ _R(s.tag_gt[s.obs_tag[i], :4])
-        ang = min(np.degrees(np.arccos(np.clip((np.trace(Rg.T @ _R(qt2[i, k, :4])) - 1) / 2, -1, 1))) for k in range(2))
+        Rg = ys.rotation(s.cam_gt[s.obs_cam[i], :4]) @ ys.rotation(s.tag_gt[s.obs_tag[i], :4])
+        ang = min(np.degrees(np.arccos(np.clip((np.trace(Rg.T @ ys.rotation(qt2[i, k, :4])) - 1) / 2, -1, 1))) for k in range(2))
         worst_angle = max(worst_angle, ang)
         assert ang < 10.0, (i, ang)
     print("200 observations: max rms_gpu / rms_cpu %.9f, worst angle of the better solution %.3f deg"
@@ -306,7 +293,7 @@ def test_start_reconstruction_global_matches_the_incremental_driver(cfg, tmp_pat
                                      len(glob.reconstructedTags), glob.lastInitReport))
     assert abs(fg - fi) <= 1e-6 * fi
     for t in glob.reconstructedTags:
-        er = np.abs(_R(glob.reconstructedTags[t].q) - _R(s.tag_gt[t, :4])).max()
+        er = np.abs(ys.rotation(glob.reconstructedTags[t].q) - ys.rotation(s.tag_gt[t, :4])).max()
         et = np.abs(glob.reconstructedTags[t].t - s.tag_gt[t, 4:]).max()
         assert er < 5e-3 and et < 5e-3, (t, er, et)
 

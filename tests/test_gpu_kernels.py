@@ -6,6 +6,8 @@ HIP path itself never touches either.
 import numpy as np
 import pytest
 
+import yardstick as ys
+
 pytestmark = pytest.mark.gpu
 
 
@@ -13,33 +15,6 @@ pytestmark = pytest.mark.gpu
 def eng():
     from visual_marker_mapping_amd import engine
     return engine
-
-
-def _blocks_from_oracle(O, s, cam, tag, robustify):
-    """V, U, W, g, cost from the oracle's per-observation residuals/Jacobians (numpy accumulation)."""
-    n_c, n_t = len(cam), len(tag)
-    V, U = np.zeros((n_c, 6, 6)), np.zeros((n_t, 6, 6))
-    W = np.zeros((len(s.obs_cam), 6, 6))
-    gc, gt = np.zeros((n_c, 6)), np.zeros((n_t, 6))
-    cost = 0.0
-    for i, (c, t) in enumerate(zip(s.obs_cam, s.obs_tag)):
-        r, Jc, Jt = O.obs_eval(s.intr, s.dist, cam[c], tag[t], s.tag_wh[t], s.obs_px[i])
-        if t == s.fixed_tag:
-            Jt = np.zeros_like(Jt)
-        for k in range(4):
-            sq = r[2 * k] ** 2 + r[2 * k + 1] ** 2
-            rho = O.huber(1.0, sq) if robustify else np.array([sq, 1.0, 0.0])
-            cost += 0.5 * rho[0]
-            w = np.sqrt(rho[1])
-            Jc[2 * k:2 * k + 2] *= w
-            Jt[2 * k:2 * k + 2] *= w
-            r[2 * k:2 * k + 2] *= w
-        V[c] += Jc.T @ Jc
-        U[t] += Jt.T @ Jt
-        W[i] = Jc.T @ Jt
-        gc[c] += Jc.T @ r
-        gt[t] += Jt.T @ r
-    return dict(V=V, U=U, W=W, g_cam=gc, g_tag=gt, cost=cost)
 
 
 def test_mfma_f64_syrk_matches_numpy(eng):
@@ -228,7 +203,7 @@ def test_accumulated_blocks_match_oracle(eng, oracle, elim, robust):
     mode = eng.ELIM_CAMERAS if elim == "cams" else eng.ELIM_TAGS
     ba = eng.BundleAdjuster(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam,
                             s.obs_tag, s.obs_px, elimination=mode)
-    ref = _blocks_from_oracle(oracle, s, s.cam_init, s.tag_init, robust)
+    ref = ys.pose_blocks(oracle, s, s.cam_init, s.tag_init, robust, fixed_tag=s.fixed_tag)
     got = ba.eval_blocks(robustify=robust)
     assert abs(got["cost"] - ref["cost"]) <= 1e-11 * ref["cost"]
     for k in ("V", "U", "W", "g_cam", "g_tag"):

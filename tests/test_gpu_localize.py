@@ -1,10 +1,10 @@
 """GPU tests of the localisation against a finished map (vmm_ba_localize, engine.localize, the batch member of
 TagReconstructor and the command line).
 
-Yardstick throughout: oracle/oracle.py -- obs_eval gives the 8 residuals and the 8 x 6 camera Jacobian of one
-observation, huber gives rho; the small Levenberg-Marquardt below is written around them and never calls the code
-under test.  Tolerances: 1e-9 on exact data, 1e-6 per pose between two optima, covariances
-to 1e-6 x max|ref| as the existing covariance tests.  Scenes come from synthetic.make_scene, the map is tag_gt.
+Yardstick throughout: tests/yardstick.py -- block_normal over image_rows and image_optimum, numpy around
+oracle/oracle.py; they never call the code under test.  Tolerances: 1e-9 on exact data, 1e-6 per pose between two
+optima, covariances to 1e-6 x max|ref| as the existing covariance tests.  Scenes come from
+synthetic.make_scene, the map is tag_gt.
 """
 import json
 import os
@@ -12,6 +12,8 @@ import shutil
 
 import numpy as np
 import pytest
+
+import yardstick as ys
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +24,7 @@ INLIER_PX = 8.0   # the default of vmm_ba_localize_options
 
 def _csr(s):
     """The scene's observations grouped by image: (img_start, obs_tag, obs_px, order)."""
-    order = np.argsort(s.obs_cam, kind="stable")
-    counts = np.bincount(s.obs_cam, minlength=len(s.cam_gt))
-    start = np.zeros(len(s.cam_gt) + 1, np.int64)
-    start[1:] = np.cumsum(counts)
+    start, order = s.by_image()
     return start, s.obs_tag[order].astype(np.int32), s.obs_px[order].copy(), order
 
 
@@ -33,67 +32,14 @@ def _localize(eng, s, start, tag, px, **kw):
     return eng.localize(s.intr, s.dist, s.tag_gt, s.tag_wh, start, tag, px, **kw)
 
 
-def _pose_gap(a, b):
-    """As tests/test_gpu_init.py: max over the poses of |dq| (unit quaternions, sign-aligned) and |dt| / max(|t|, 1)."""
-    a, b = np.atleast_2d(a), np.atleast_2d(b)
-    qa = a[:, :4] / np.linalg.norm(a[:, :4], axis=1, keepdims=True)
-    qb = b[:, :4] / np.linalg.norm(b[:, :4], axis=1, keepdims=True)
-    sign = np.sign(np.sum(qa * qb, axis=1))[:, None]
-    dq = np.linalg.norm(qa * sign - qb, axis=1)
-    dt = np.linalg.norm(a[:, 4:] - b[:, 4:], axis=1) / np.maximum(np.linalg.norm(b[:, 4:], axis=1), 1.0)
-    return float(dq.max()), float(dt.max())
-
-
-def _normal_equations(O, s, q, tags, pxs, robust, a=1.0):
-    """cost = 1/2 sum rho(|r_corner|^2), J^T J and J^T r of one image at pose q, the loss applied as Ceres' corrector
-    does for a loss with rho'' <= 0 (rows and residuals scaled by sqrt(rho'))."""
-    A, g, cost = np.zeros((6, 6)), np.zeros(6), 0.0
-    for t, px in zip(tags, pxs):
-        r, Jc, _ = O.obs_eval(s.intr, s.dist, q, s.tag_gt[t], s.tag_wh[t], px)
-        for k in range(4):
-            rk, Jk = r[2 * k:2 * k + 2], Jc[2 * k:2 * k + 2]
-            sq = float(rk @ rk)
-            rho = O.huber(a, sq) if robust else (sq, 1.0, 0.0)
-            cost += 0.5 * rho[0]
-            A += rho[1] * (Jk.T @ Jk)
-            g += rho[1] * (Jk.T @ rk)
-    return cost, A, g
-
-
-def _host_optimum(O, s, q0, tags, pxs, robust):
-    """Levenberg-Marquardt on the same objective from q0, run until the step is at the rounding floor of the pose."""
-    q = np.array(q0, np.float64)
-    cost, A, g = _normal_equations(O, s, q, tags, pxs, robust)
-    lam = 1e-4
-    for _ in range(200):
-        try:
-            step = np.linalg.solve(A + lam * np.diag(np.maximum(np.diag(A), 1e-12)), -g)
-        except np.linalg.LinAlgError:
-            lam *= 10.0
-            continue
-        if np.abs(step).max() < 1e-13:
-            break
-        cand = O.pose_plus(q, step)
-        c2, A2, g2 = _normal_equations(O, s, cand, tags, pxs, robust)
-        if c2 < cost:
-            q, cost, A, g = cand, c2, A2, g2
-            lam = max(lam * 0.1, 1e-15)
-        else:
-            if lam > 1e8:
-                break
-            lam *= 10.0
-    scale = np.sqrt(np.maximum(np.diag(A), 1e-300))
-    return q, cost, float(np.abs(g / scale).max())
-
-
-def _check_against_host(O, s, start, tag, px, cam, inl, res, images, robust, label):
-    """Device pose vs the host optimum over the same inlier set, started at cam_gt: 1e-6 per pose."""
+def _check_against_host(O, s, start, tag, px, cam, inl, res, images, robust, label, a=1.0):
+    """Device pose vs the host optimum (Huber width a) over the same inlier set, started at cam_gt: 1e-6 per pose."""
     worst = (0.0, 0.0)
     for i in images:
         b, e = int(start[i]), int(start[i + 1])
         keep = inl[b:e]
-        ref, cost, grad = _host_optimum(O, s, s.cam_gt[i], tag[b:e][keep], px[b:e][keep], robust)
-        gq, gt = _pose_gap(cam[i], ref)
+        ref, cost, grad = ys.image_optimum(O, s, s.cam_gt[i], tag[b:e][keep], px[b:e][keep], robust, a)
+        gq, gt = ys.pose_gap(cam[i], ref)
         print("%s image %d: obs %d inliers %d trials %d |dq| %.3g |dt| %.3g cost device %.12g host %.12g "
               "scaled gradient %.3g" % (label, i, e - b, int(keep.sum()), res[i]["trials"], gq, gt, res[i]["cost"], cost,
                                         grad))
@@ -126,7 +72,7 @@ def test_exact_data_recovers_the_ground_truth(name):
     s = make_scene(cfg, noise_px=0.0, outlier_frac=0.0, **kw)
     start, tag, px, _ = _csr(s)
     cam, cov, inl, res = _localize(eng, s, start, tag, px)
-    gq, gt = _pose_gap(cam, s.cam_gt)
+    gq, gt = ys.pose_gap(cam, s.cam_gt)
     print("%s: %d images %d observations, max |dq| %.3g |dt| %.3g, max rms %.3g px, trials %d..%d"
           % (name, len(cam), len(tag), gq, gt, max(r["rms_px"] for r in res), min(r["trials"] for r in res),
              max(r["trials"] for r in res)))
@@ -215,7 +161,8 @@ def test_covariance_matches_the_inverse_normal_matrix(oracle, name, robustify):
     for i in range(len(cam)):
         b, e = int(start[i]), int(start[i + 1])
         keep = inl[b:e]
-        _, A, _ = _normal_equations(oracle, s, cam[i], tag[b:e][keep], px[b:e][keep], bool(robustify))
+        _, A, _ = ys.block_normal(oracle, ys.image_rows(oracle, s.intr, s.dist, cam[i], s.tag_gt, s.tag_wh, tag[b:e][keep],
+                                                        px[b:e][keep]), bool(robustify))
         ref = np.linalg.inv(A)
         err = np.abs(cov[i] - ref).max() / np.abs(ref).max()
         worst = max(worst, err)
@@ -284,12 +231,12 @@ def test_edges_empty_image_single_tag_and_collapsed_observation():
     assert (cam[0] == [1, 0, 0, 0, 0, 0, 0]).all() and (cov[0] == 0).all()
     assert res[1]["status"] == _lib.LOC_OK and res[1]["n_inlier_obs"] == 1 and inl[0]
     assert np.linalg.eigvalsh(cov[1]).min() > 0
-    gq, gt = _pose_gap(cam[1], s.cam_gt[1])
+    gq, gt = ys.pose_gap(cam[1], s.cam_gt[1])
     print("single tag: |dq| %.3g |dt| %.3g" % (gq, gt))
     assert gq <= 1e-9 and gt <= 1e-9
     assert res[2]["status"] == _lib.LOC_OK
     assert not inl[1] and inl[2:].all() and res[2]["n_inlier_obs"] == e2 - b2 - 1
-    gq, gt = _pose_gap(cam[2], s.cam_gt[2])
+    gq, gt = ys.pose_gap(cam[2], s.cam_gt[2])
     print("collapsed observation: |dq| %.3g |dt| %.3g" % (gq, gt))
     assert gq <= 1e-9 and gt <= 1e-9
     assert np.linalg.eigvalsh(cov[2]).min() > 0

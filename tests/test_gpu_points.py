@@ -5,7 +5,7 @@ OpenCVReprojectionError (TagReconstructionCostFunction.h:9-84); the oracle's fun
 import numpy as np
 import pytest
 
-from test_gpu_solve import _assert_same_trace
+from yardstick import assert_same_trace
 
 pytestmark = pytest.mark.gpu
 REL = 1e-6
@@ -56,7 +56,7 @@ def test_point_solve_matches_oracle(oracle, elim):
                                   s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=0, linear_solver=oracle.DENSE_NORMAL))
     assert out["termination_type"] == eng.CONVERGENCE
-    _assert_same_trace(out, summ, trace)
+    assert_same_trace(out, summ, trace)
     scale = max(np.abs(sc.cam_qt).max(), np.abs(oracle.scene_points(sc)).max())
     np.testing.assert_allclose(cam, sc.cam_qt, rtol=0, atol=REL * scale)
     np.testing.assert_allclose(pts, oracle.scene_points(sc), rtol=0, atol=REL * scale)
@@ -98,7 +98,7 @@ def test_point_full_size_matches_oracle(oracle):
                                s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=0, num_threads=8))
     assert out["termination_type"] == eng.CONVERGENCE
-    _assert_same_trace(out, summ, trace)
+    assert_same_trace(out, summ, trace)
     scale = max(np.abs(sc.cam_qt).max(), np.abs(oracle.scene_points(sc)).max())
     np.testing.assert_allclose(cam, sc.cam_qt, rtol=0, atol=REL * scale)
     np.testing.assert_allclose(pts, oracle.scene_points(sc), rtol=0, atol=REL * scale)

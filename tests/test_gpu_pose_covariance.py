@@ -1,7 +1,7 @@
 """GPU tests of vmm_ba_covariance_blocks: any 6x6 marginal or cross block of the pose covariance.
 
 Yardstick: the numpy inverse of the dense H over the free poses, H assembled from the CPU oracle's per-observation
-residuals and Jacobians (test_gpu_constant_poses._oracle_blocks / _free_system).  Tolerances: a diagonal block 1e-6 of
+residuals and Jacobians (yardstick.pose_blocks / free_system).  Tolerances: a diagonal block 1e-6 of
 its largest entry (the project's figure for the same quantity in test_gpu_solve.py and test_gpu_constant_poses.py), a
 cross block 1e-6 * sqrt(max|Cov_aa| * max|Cov_bb|); two factorisation paths of one matrix 1e-9 (test_gpu_solve.py).
 """
@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_constant_poses import _const_sets, _free_system, _oracle_blocks
+from yardstick import const_sets, free_system, pose_blocks
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +30,8 @@ class _Reference:
             import copy
             s = copy.copy(s)
             s.obs_cam, s.obs_tag, s.obs_px = s.obs_cam[obs_mask], s.obs_tag[obs_mask], s.obs_px[obs_mask]
-        blk = _oracle_blocks(O, s, cam, tag, robust, cam_const, tag_const)
-        H, _, fc, ft = _free_system(s, blk, cam_const, tag_const)
+        blk = pose_blocks(O, s, cam, tag, robust, cam_const=cam_const, tag_const=tag_const)
+        H, _, fc, ft = free_system(s, blk, cam_const, tag_const)
         assert np.all(np.linalg.eigvalsh(H) > 0)
         self.order = len(H)
         self.inv = np.linalg.inv(H)
@@ -181,7 +181,7 @@ def test_constant_and_residual_free_poses_give_zero_blocks(oracle, elim):
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(1)
     n_c, n_t = len(s.cam_init), len(s.tag_init)
-    cam_const, tag_const = _const_sets(s, 3, 2)
+    cam_const, tag_const = const_sets(s, 3, 2)
     pairs = _all_pairs(n_c + n_t)
     lost = int(np.flatnonzero(cam_const == 0)[1])      # a free camera that loses all its observations
     mask = s.obs_cam != lost

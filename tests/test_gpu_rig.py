@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import rig_cases as rc
+import yardstick as ys
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +43,7 @@ def _check_against_host(O, s, rig, keep, res, which, robust, label):
     worst = (0.0, 0.0)
     for f in which:
         ref, cost = rc.host_frame_optimum(O, s, f, s.rig_gt[f], s.ext_qt, keep, robust)
-        gq, gt = rc.pose_gap(rig[f], ref)
+        gq, gt = ys.pose_gap(rig[f], ref)
         print("%s frame %d: obs %d inliers %d trials %d |dq| %.3g |dt| %.3g cost device %.12g host %.12g"
               % (label, f, res[f]["n_obs"], res[f]["n_inlier_obs"], res[f]["trials"], gq, gt, res[f]["cost"], cost))
         worst = (max(worst[0], gq), max(worst[1], gt))
@@ -57,7 +58,7 @@ def test_exact_data_recovers_the_rig_poses(name):
     from visual_marker_mapping_amd import _lib
     s = rc.rig_scene(name, noise_px=0.0)
     rig, cov, inl, res = _run(s)
-    gq, gt = rc.pose_gap(rig, s.rig_gt)
+    gq, gt = ys.pose_gap(rig, s.rig_gt)
     print("%s: %d frames %d observations, max |dq| %.3g |dt| %.3g, max rms %.3g px, trials %d..%d"
           % (name, s.n_frames, len(s.obs_tag), gq, gt, max(r["rms_px"] for r in res), min(r["trials"] for r in res),
              max(r["trials"] for r in res)))
@@ -77,7 +78,7 @@ def test_one_camera_with_the_identity_extrinsic_is_the_localisation(noise):
     s = rc.rig_scene("distortion_12x8", ext=rc.EXT3[:1], seed=5, **kw)
     rig, cov, inl, res = _run(s)
     cam, ccov, cinl, cres = eng.localize(s.intr[0], s.dist[0], s.tag_gt, s.tag_wh, s.img_start, s.obs_tag, s.obs_px)
-    gq, gt = rc.pose_gap(rig, cam)
+    gq, gt = ys.pose_gap(rig, cam)
     print("K = 1, noise %s: |dq| %.3g |dt| %.3g against engine.localize" % (s.noise_px, gq, gt))
     assert [r["status"] for r in res] == [r["status"] for r in cres] and (inl == cinl).all()
     assert [r["n_inlier_obs"] for r in res] == [r["n_inlier_obs"] for r in cres]
@@ -139,10 +140,10 @@ def test_a_weak_camera_0_and_a_strong_camera_2_give_the_joint_optimum(oracle):
     rig, cov, inl, res = _run(s)
     assert res[0]["status"] == _lib.LOC_OK and inl.all()
     joint, _ = rc.host_frame_optimum(oracle, s, 0, s.rig_gt[0], s.ext_qt, inl, True)
-    gq, gt = rc.pose_gap(rig[0], joint)
+    gq, gt = ys.pose_gap(rig[0], joint)
     # camera 0 on its own: engine.localize on its single tag (the extrinsic of camera 0 is the identity)
     alone, _, _, ares = eng.localize(s.intr[0], s.dist[0], s.tag_gt, s.tag_wh, s.img_start[:2], s.obs_tag[:1], s.obs_px[:1])
-    aq, at_ = rc.pose_gap(alone[0], joint)
+    aq, at_ = ys.pose_gap(alone[0], joint)
     print("joint optimum: |dq| %.3g |dt| %.3g; camera 0 alone is |dq| %.3g |dt| %.3g away from it" % (gq, gt, aq, at_))
     assert gq <= 1e-6 and gt <= 1e-6, (gq, gt)
     assert ares[0]["status"] == _lib.LOC_OK and max(aq, at_) > 1e-4
@@ -209,7 +210,7 @@ def test_edges_empty_frame_single_observation_and_too_few_inliers():
     assert (rig[0] == [1, 0, 0, 0, 0, 0, 0]).all() and (cov[0] == 0).all()
     assert res[1]["status"] == _lib.LOC_OK and res[1]["n_inlier_obs"] == 1 and inl[0]
     assert np.linalg.eigvalsh(cov[1]).min() > 0
-    gq, gt = rc.pose_gap(rig[1:], s.rig_gt[1:])
+    gq, gt = ys.pose_gap(rig[1:], s.rig_gt[1:])
     print("single observation in camera 2 and a full frame behind an empty one: |dq| %.3g |dt| %.3g" % (gq, gt))
     assert gq <= 1e-9 and gt <= 1e-9 and res[2]["status"] == _lib.LOC_OK and inl.all()
     # min_inlier_tags counts over the frame: two cameras with one tag each pass a floor of two, one tag alone does not
@@ -218,7 +219,7 @@ def test_edges_empty_frame_single_observation_and_too_few_inliers():
         two[np.flatnonzero((full.obs_frame == 4) & (full.obs_cam == c))[:1]] = True
     rig, cov, inl, res = _run(rc.frames(rc.select(full, two), [4]), min_inlier_tags=2)
     assert res[0]["status"] == _lib.LOC_OK and res[0]["n_inlier_obs"] == 2
-    assert max(rc.pose_gap(rig[0], full.rig_gt[4])) <= 1e-9
+    assert max(ys.pose_gap(rig[0], full.rig_gt[4])) <= 1e-9
     rig, cov, inl, res = _run(rc.frames(s, [1]), min_inlier_tags=2)
     _assert_clean(rig, cov, res)
     assert res[0]["status"] == _lib.LOC_TOO_FEW_INLIERS and (cov[0] == 0).all()
@@ -232,7 +233,7 @@ def test_eight_cameras_with_yaws_spread_over_thirty_degrees(oracle):
     counts = np.diff(exact.img_start).reshape(exact.n_frames, 8)
     assert exact.n_rig_cams == 8 and (counts.sum(axis=1) >= 20).all() and (counts > 0).sum(axis=1).min() >= 6
     rig, cov, inl, res = _run(exact)
-    gq, gt = rc.pose_gap(rig, exact.rig_gt)
+    gq, gt = ys.pose_gap(rig, exact.rig_gt)
     print("K = 8 exact: %d observations, |dq| %.3g |dt| %.3g" % (len(exact.obs_tag), gq, gt))
     assert [r["status"] for r in res] == [_lib.LOC_OK] * exact.n_frames and inl.all()
     assert gq <= 1e-9 and gt <= 1e-9
@@ -260,13 +261,13 @@ def test_per_camera_localisation_gives_the_starting_extrinsics():
             res[f * K + c] = r[f]
     assert res[1]["status"] == _lib.LOC_NO_OBSERVATIONS and res[K]["status"] == _lib.LOC_NO_OBSERVATIONS
     ext = eng.rig_extrinsics_start(K, F, cam, res)
-    gq, gt = rc.pose_gap(ext, s.ext_qt)
+    gq, gt = ys.pose_gap(ext, s.ext_qt)
     print("starting extrinsics from exact per-camera poses: |dq| %.3g |dt| %.3g" % (gq, gt))
     assert gq <= 1e-9 and gt <= 1e-9
     s.ext_qt = ext
     rig, cov, inl, rres = _run(s)
     assert [r["status"] for r in rres] == [_lib.LOC_OK] * F and inl.all()
-    assert max(rc.pose_gap(rig, s.rig_gt)) <= 1e-9
+    assert max(ys.pose_gap(rig, s.rig_gt)) <= 1e-9
 
 
 # ---- 9. front ends -------------------------------------------------------------------------------------------------
@@ -320,7 +321,7 @@ def test_command_line_and_reconstructor_member_match_the_engine(tmp_path):
     assert rig_cli.main(["--project_path", proj, "--rig", os.path.join(proj, "rig_free.json"), "--output", other]) == 0
     got = rec.computeRigPosesFromFrames(frames, models)
     ext = rec.lastRigLocalizationReport["extrinsics"]
-    gq, gt = rc.pose_gap(ext, s.ext_qt)
+    gq, gt = ys.pose_gap(ext, s.ext_qt)
     print("extrinsics from the per-camera localisation of noisy images: |dq| %.3g |dt| %.3g" % (gq, gt))
     assert (ext[0] == [1, 0, 0, 0, 0, 0, 0]).all() and gq <= 1e-2 and gt <= 1e-2 and sorted(got) == list(range(F))
     free = vio.read_json(other)
@@ -403,9 +404,9 @@ def test_calibration_recovers_perturbed_extrinsics_on_exact_data(oracle, name):
     from visual_marker_mapping_amd import _lib
     s = rc.rig_scene(name, noise_px=0.0)
     ext0 = _perturbed(oracle, s.ext_qt, (1, 2))
-    assert max(rc.pose_gap(ext0[1:], s.ext_qt[1:])) > 0.01
+    assert max(ys.pose_gap(ext0[1:], s.ext_qt[1:])) > 0.01
     ext, ext_cov, rig, rig_cov, inl, res, rep = _calibrate(s, ext0, **ROUGH_START)
-    ge, gr = rc.pose_gap(ext, s.ext_qt), rc.pose_gap(rig, s.rig_gt)
+    ge, gr = ys.pose_gap(ext, s.ext_qt), ys.pose_gap(rig, s.rig_gt)
     print("%s exact: extrinsics |dq| %.3g |dt| %.3g, rig poses |dq| %.3g |dt| %.3g, report %s" % (name, *ge, *gr, rep))
     assert rep["status"] == _lib.CAL_OK and rep["n_frames_used"] == s.n_frames and rep["cams_refined"] == 0b110
     assert inl.all() and [r["status"] for r in res] == [_lib.LOC_OK] * s.n_frames
@@ -424,7 +425,7 @@ def test_calibration_of_noisy_data_reaches_the_host_optimum_and_its_covariances(
     ext, ext_cov, rig, rig_cov, inl, res, rep = _calibrate(s, ext0, robustify=robustify, **ROUGH_START)
     assert rep["status"] == _lib.CAL_OK and rep["n_frames_used"] == s.n_frames and rep["n_obs_used"] == int(inl.sum())
     h_rig, h_ext, h_cost, H = rc.host_rig_calibration(oracle, s, s.rig_gt, s.ext_qt, inl, bool(robustify), 0b110)
-    ge, gr = rc.pose_gap(ext, h_ext), rc.pose_gap(rig, h_rig)
+    ge, gr = ys.pose_gap(ext, h_ext), ys.pose_gap(rig, h_rig)
     ref_ext, ref_rig, scale = rc.joint_covariance(s, H, inl, 0b110)
     e_ext, e_rig = np.abs(ext_cov - ref_ext).max() / scale, np.abs(rig_cov - ref_rig).max() / scale
     print("%s robustify=%d: extrinsics |dq| %.3g |dt| %.3g, rig |dq| %.3g |dt| %.3g, cost device %.12g host %.12g, "
@@ -450,16 +451,16 @@ def test_calibration_mask_holds_cameras_and_moves_the_gauge(oracle):
     assert ext[:2].tobytes() == ext0[:2].tobytes() and ext[2].tobytes() != ext0[2].tobytes()
     assert (ext_cov[:12] == 0).all() and (ext_cov[:, :12] == 0).all() and np.linalg.eigvalsh(ext_cov[12:, 12:]).min() > 0
     h_rig, h_ext, h_cost, _ = rc.host_rig_calibration(oracle, s, s.rig_gt, ext0, inl, True, 0b100)
-    assert max(rc.pose_gap(ext, h_ext)) <= 1e-6 and max(rc.pose_gap(rig, h_rig)) <= 1e-6
+    assert max(ys.pose_gap(ext, h_ext)) <= 1e-6 and max(ys.pose_gap(rig, h_rig)) <= 1e-6
     # holding camera 1 instead of camera 0 moves the gauge, not the rig: the same relative extrinsics
     a_ext = _calibrate(s, ext0, refine_mask=0b110, **ROUGH_START)[0]
     b_ext, _, _, _, _, _, b_rep = _calibrate(s, ext0, refine_mask=0b101, **ROUGH_START)
     assert b_rep["status"] == _lib.CAL_OK and b_rep["cams_refined"] == 0b101 and b_ext[1].tobytes() == ext0[1].tobytes()
-    inv = lambda e: np.concatenate([e[:4] * [1, -1, -1, -1], -rc.rot(e).T @ e[4:]])
+    inv = lambda e: np.concatenate([e[:4] * [1, -1, -1, -1], -ys.rotation(e).T @ e[4:]])
     worst = 0.0
     for c in (1, 2):
         rel_a, rel_b = rc.compose(a_ext[c], inv(a_ext[0])), rc.compose(b_ext[c], inv(b_ext[0]))
-        worst = max(worst, *rc.pose_gap(rel_a, rel_b))
+        worst = max(worst, *ys.pose_gap(rel_a, rel_b))
     print("relative extrinsics with camera 0 held and with camera 1 held differ by %.3g" % worst)
     assert worst <= 1e-6
     # a camera in the mask without any image is not refined: its bits come back
@@ -480,7 +481,7 @@ def test_calibration_with_camera_2_absent_from_every_other_frame(oracle):
     ext, ext_cov, rig, rig_cov, inl, res, rep = _calibrate(s, ext0, **ROUGH_START)
     assert rep["status"] == _lib.CAL_OK and rep["cams_refined"] == 0b110 and inl.all()
     h_rig, h_ext, h_cost, H = rc.host_rig_calibration(oracle, s, s.rig_gt, s.ext_qt, inl, True, 0b110)
-    ge, gr = rc.pose_gap(ext, h_ext), rc.pose_gap(rig, h_rig)
+    ge, gr = ys.pose_gap(ext, h_ext), ys.pose_gap(rig, h_rig)
     ref_ext, ref_rig, scale = rc.joint_covariance(s, H, inl, 0b110)
     print("camera 2 in every other frame: extrinsics |dq| %.3g |dt| %.3g, rig |dq| %.3g |dt| %.3g" % (*ge, *gr))
     assert max(ge) <= 1e-6 and max(gr) <= 1e-6 and abs(rep["final_cost"] - h_cost) <= 1e-9 * h_cost
@@ -503,7 +504,7 @@ def test_from_per_camera_localisation_to_the_calibrated_rig():
             res[f * K + c] = r[f]
     ext0 = eng.rig_extrinsics_start(K, F, cam, res)
     ext, _, rig, _, inl, _, rep = _calibrate(s, ext0)
-    ge, gr = rc.pose_gap(ext, s.ext_qt), rc.pose_gap(rig, s.rig_gt)
+    ge, gr = ys.pose_gap(ext, s.ext_qt), ys.pose_gap(rig, s.rig_gt)
     print("localise per camera -> start -> calibrate: extrinsics |dq| %.3g |dt| %.3g, rig |dq| %.3g |dt| %.3g" % (*ge, *gr))
     assert rep["status"] == _lib.CAL_OK and inl.all() and max(ge) <= 1e-9 and max(gr) <= 1e-9
 
@@ -520,7 +521,7 @@ def test_calibration_of_eight_cameras_reaches_the_host_optimum(oracle):
     ext, ext_cov, rig, rig_cov, inl, res, rep = _calibrate(s, ext0, **ROUGH_START)
     assert rep["status"] == _lib.CAL_OK and rep["cams_refined"] == 0xFE and inl.all()
     h_rig, h_ext, h_cost, H = rc.host_rig_calibration(oracle, s, s.rig_gt, ext_gt, inl, True, 0xFE)
-    ge, gr = rc.pose_gap(ext, h_ext), rc.pose_gap(rig, h_rig)
+    ge, gr = ys.pose_gap(ext, h_ext), ys.pose_gap(rig, h_rig)
     ref_ext, ref_rig, scale = rc.joint_covariance(s, H, inl, 0xFE)
     e_ext, e_rig = np.abs(ext_cov - ref_ext).max() / scale, np.abs(rig_cov - ref_rig).max() / scale
     print("K = 8: extrinsics |dq| %.3g |dt| %.3g, rig |dq| %.3g |dt| %.3g, cost device %.12g host %.12g, covariance error "

@@ -2,8 +2,8 @@
 vmm_ba_solve_selfcal, BundleAdjuster's members, TagReconstructor.doBundleAdjustment(refineCameraModel=True) and the
 selfcalibration command line).
 
-Yardstick: tests/test_selfcal_cpu.py -- joint_system / host_joint_lm / reduced_system / model_covariance, numpy around
-oracle/oracle.py, proven against central differences there; they never call the code under test.
+Yardstick: tests/yardstick.py -- joint_system / host_joint_lm / reduced_system / model_covariance, numpy around
+oracle/oracle.py, proven against central differences in tests/test_yardstick_cpu.py; they never call the code under test.
 
 Tolerances.
   C, g_k, cost   entry by entry in the metric of tests/eval_cases.py: |device - reference| over the entry's MAGNITUDE (the
@@ -25,9 +25,8 @@ import shutil
 import numpy as np
 import pytest
 
-from eval_cases import MARGIN
-from test_selfcal_cpu import (HOST_SIGMA_GAP, PERTURB, host_joint_lm, joint_system, model_covariance, pose_gap,
-                              reduced_system, scene_args)
+from yardstick import (BOUND_C, BOUND_COST, BOUND_G, HOST_SIGMA_GAP, PERTURB, host_joint_lm, joint_system, model_covariance,
+                       pose_gap, reduced_system, same_bytes, scene_args)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +36,6 @@ SCENES = {
     "distortion_12x8": (5, dict(n_cams=12, n_tags=8, visibility=0.6)),                     # non-zero distortion
 }
 ELIMS = ("tags", "cams")
-BOUND_C, BOUND_G, BOUND_COST = MARGIN * 1.26e-12, MARGIN * 2.06e-15, MARGIN * 1.458e-13
 TIGHT = dict(function_tolerance=1e-16, parameter_tolerance=1e-14, max_num_iterations=200)
 _cache = {}
 
@@ -76,10 +74,6 @@ def _reference(O, name, robust, mask=0x1FF, k_start=None):
         _cache[key] = host_joint_lm(O, _truth(s) if k_start is None else k_start, s.cam_gt, s.tag_gt, *scene_args(s),
                                     robust=robust, mask=mask)
     return _cache[key]
-
-
-def _same_bytes(a, b):
-    return all(np.asarray(a[key]).tobytes() == np.asarray(b[key]).tobytes() for key in ("cost", "g_k", "C", "r_k", "S_k"))
 
 
 # ---- 1. the system ---------------------------------------------------------------------------------------------------
@@ -145,9 +139,9 @@ def test_system_matches_the_host_jacobian(oracle, monkeypatch, name, elim):
             if not np.array_equal(got["S_k"], got["S_k"].T):
                 bad.append("%s: S_k is not symmetric in its bits" % label)
             # idempotent, and the same bits from a block-sparse, tree-ordered handle
-            if not _same_bytes(got, dense.intrinsics_system(robustify=robust)):
+            if not same_bytes(got, dense.intrinsics_system(robustify=robust)):
                 bad.append("%s: the second call gives other bits" % label)
-            if not _same_bytes(got, sparse.intrinsics_system(robustify=robust)):
+            if not same_bytes(got, sparse.intrinsics_system(robustify=robust)):
                 bad.append("%s: the block-sparse handle gives other bits" % label)
         cam, tag = dense.get_state()
         assert cam.tobytes() == s.cam_gt.tobytes() and tag.tobytes() == s.tag_gt.tobytes()   # the state is left alone
@@ -181,7 +175,7 @@ def test_set_intrinsics_makes_the_handle_one_created_with_the_new_model(elim):
             assert x.tobytes() == y.tobytes()
         pa, pb = used.reprojection_stats(), fresh.reprojection_stats()
         assert all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(pa, pb))
-        assert _same_bytes(used.intrinsics_system(), fresh.intrinsics_system())
+        assert same_bytes(used.intrinsics_system(), fresh.intrinsics_system())
     finally:
         used.close()
         fresh.close()
@@ -202,7 +196,7 @@ def test_exact_data_recovers_the_model_and_the_poses(name, elim):
         ba.close()
     k = np.concatenate([intr, dist])
     err = np.abs(k - _truth(s)) / np.maximum(np.abs(_truth(s)), 1.0)
-    gc, gt = pose_gap(cam, s.cam_gt), pose_gap(tag, s.tag_gt)
+    gc, gt = max(pose_gap(cam, s.cam_gt)), max(pose_gap(tag, s.tag_gt))
     print("%s %s: status %d outer %d accepted %d inner %d; cost %.3g -> %.3g; pose gaps %.3g %.3g; parameter errors %s"
           % (name, elim, rep["status"], rep["outer_iterations"], rep["accepted"], rep["inner_lm_iterations"],
              rep["initial_cost"], rep["final_cost"], gc, gt, np.array2string(err, precision=3)))
@@ -221,7 +215,7 @@ def _check_against_host(s, got, ref, label, mask=0x1FF):
     free = [j for j in range(9) if (mask >> j) & 1]
     sigma = np.sqrt(np.diag(cov_ref))[free]
     gap = np.abs(np.concatenate([intr, dist]) - k_ref)[free] / sigma
-    pg = max(pose_gap(cam, cams_ref), pose_gap(tag, tags_ref))
+    pg = max(*pose_gap(cam, cams_ref), *pose_gap(tag, tags_ref))
     rel = (rep["final_cost"] - cost_ref) / cost_ref
     d_cov = np.abs(cov - cov_ref).max() / np.abs(cov_ref).max()
     print("%s: status %d outer %d accepted %d inner %d; pose gap %.3g; cost device %.15g host %.15g (rel %.3g); covariance "
@@ -400,8 +394,8 @@ def test_reconstructor_member_and_command_line_recover_the_truth(tmp_path):
     def errors(m, tags, cams):
         k = np.concatenate([[m.fx, m.fy, m.cx, m.cy], m.distortionCoefficients])
         err = np.abs(k - _truth(s)) / np.maximum(np.abs(_truth(s)), 1.0)
-        gt = pose_gap(np.array([np.r_[tags[t].q, tags[t].t] for t in range(len(s.tag_gt))]), s.tag_gt)
-        gc = pose_gap(np.array([np.r_[cams[c].q, cams[c].t] for c in range(len(s.cam_gt))]), s.cam_gt)
+        gt = max(pose_gap(np.array([np.r_[tags[t].q, tags[t].t] for t in range(len(s.tag_gt))]), s.tag_gt))
+        gc = max(pose_gap(np.array([np.r_[cams[c].q, cams[c].t] for c in range(len(s.cam_gt))]), s.cam_gt))
         return k, err, max(gt, gc)
 
     assert selfcalibration.main(["--project_path", proj, "--intrinsics", start_file]) == 0

@@ -8,9 +8,10 @@ compared.
 import numpy as np
 import pytest
 
+from yardstick import REL, assert_same_solution, assert_same_trace
+
 pytestmark = pytest.mark.gpu
 
-REL = 1e-6  # north_star: "within 1e-6 relative"
 
 
 def _run_both(eng, O, s, elim, **opt):
@@ -27,41 +28,6 @@ def _run_both(eng, O, s, elim, **opt):
     return out, cam, tag, summ, trace, sc
 
 
-def _world_corners(qt, wh):
-    q = qt[:, :4] / np.linalg.norm(qt[:, :4], axis=1, keepdims=True)
-    w, x, y, z = q.T
-    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                  2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                  2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], axis=1).reshape(-1, 3, 3)
-    out = []
-    for sx, sy in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
-        p = np.stack([sx * wh[:, 0] / 2, sy * wh[:, 1] / 2, np.zeros(len(wh))], axis=1)
-        out.append(np.einsum("nij,nj->ni", R, p) + qt[:, 4:])
-    return np.stack(out, axis=1)
-
-
-def _assert_same_solution(cam, tag, sc, wh):
-    scale = max(np.abs(sc.cam_qt).max(), np.abs(sc.tag_qt).max())
-    np.testing.assert_allclose(cam, sc.cam_qt, rtol=0, atol=REL * scale)
-    np.testing.assert_allclose(tag, sc.tag_qt, rtol=0, atol=REL * scale)
-    a, b = _world_corners(tag, wh), _world_corners(sc.tag_qt, wh)
-    np.testing.assert_allclose(a, b, rtol=0, atol=REL * np.abs(b).max())
-
-
-def _assert_same_trace(out, summ, trace, rtol=1e-7):
-    assert out["termination_type"] == summ["termination_type"]
-    assert out["iterations"] == summ["iterations"]
-    assert out["num_successful_steps"] == summ["num_successful_steps"]
-    assert out["num_unsuccessful_steps"] == summ["num_unsuccessful_steps"]
-    for a, b in zip(out["trace"], trace):
-        assert a["iteration"] == b["iteration"]
-        assert a["step_is_successful"] == b["step_is_successful"]
-        np.testing.assert_allclose(a["cost"], b["cost"], rtol=rtol)
-        np.testing.assert_allclose(a["trust_region_radius"], b["trust_region_radius"], rtol=1e-5)
-    np.testing.assert_allclose(out["final_cost"], summ["final_cost"], rtol=rtol)
-    np.testing.assert_allclose(out["initial_cost"], summ["initial_cost"], rtol=1e-12)
-
-
 @pytest.mark.parametrize("elim", ["cams", "tags"])
 @pytest.mark.parametrize("robust", [0, 1])
 def test_config1_matches_oracle(oracle, elim, robust):
@@ -69,8 +35,8 @@ def test_config1_matches_oracle(oracle, elim, robust):
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(1)  # BASELINE.json configs[0]: 20 images x 10 tags
     out, cam, tag, summ, trace, sc = _run_both(eng, oracle, s, elim, robustify=robust)
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
 
 
 def test_distortion_outliers_robust_matches_oracle(oracle):
@@ -78,8 +44,8 @@ def test_distortion_outliers_robust_matches_oracle(oracle):
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(5, n_cams=30, n_tags=12)  # configs[4] shape at a size the dense oracle solves fast
     out, cam, tag, summ, trace, sc = _run_both(eng, oracle, s, "auto", robustify=1)
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
 
 
 def test_sparse_visibility_matches_oracle(oracle):
@@ -87,8 +53,8 @@ def test_sparse_visibility_matches_oracle(oracle):
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(1, n_cams=40, n_tags=30, visibility=0.25)
     out, cam, tag, summ, trace, sc = _run_both(eng, oracle, s, "auto", robustify=1)
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
 
 
 def test_zero_noise_scene_recovers_ground_truth():
@@ -152,8 +118,8 @@ def test_full_size_config2_properties(oracle, cfg):
     assert abs(out["final_cost"] - expect) < 0.02 * expect
     sc = oracle.Scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag, s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=0, num_threads=8))
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
 
 
 @pytest.mark.parametrize("elim", ["cams", "tags"])
@@ -302,9 +268,9 @@ def test_rejected_steps_match_oracle(oracle, elim):
         cam2, tag2 = ba.get_state()
     finally:
         ba.close()
-    _assert_same_trace(out, summ, trace, rtol=1e-6)
+    assert_same_trace(out, summ, trace, rtol=1e-6)
     assert [t["step_is_successful"] for t in out["trace"]].count(0) == summ["num_unsuccessful_steps"]
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
     assert out2["iterations"] == out["iterations"] and out2["final_cost"] == out["final_cost"]
     np.testing.assert_array_equal(cam2, cam)
     np.testing.assert_array_equal(tag2, tag)

@@ -89,7 +89,7 @@ def test_path_choice_follows_the_block_structure(monkeypatch):
 def test_close_up_full_size_matches_oracle(oracle, monkeypatch):
     """500 images x 200 tags, every image sees the 6..10 tags nearest to the wall point it stands in front of (4034
     tag observations, a block-sparse reduced system): trace and solution against the oracle."""
-    from test_gpu_solve import _assert_same_solution, _assert_same_trace
+    from yardstick import assert_same_solution, assert_same_trace
     from visual_marker_mapping_amd import engine as eng
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(2, neighbors_min=6, neighbors_max=10)
@@ -99,8 +99,8 @@ def test_close_up_full_size_matches_oracle(oracle, monkeypatch):
     assert out["block_sparse"] == 1 and out["termination_type"] == eng.CONVERGENCE
     sc = oracle.Scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag, s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=0, num_threads=8))
-    _assert_same_trace(out, summ, trace)
-    _assert_same_solution(cam, tag, sc, s.tag_wh)
+    assert_same_trace(out, summ, trace)
+    assert_same_solution(cam, tag, sc, s.tag_wh)
     np.testing.assert_array_equal(tag[0], s.tag_init[0])
 
 
@@ -110,7 +110,7 @@ def test_tree_ordering_of_the_kept_family(oracle, monkeypatch):
     one-launch factorisation and the back-substitution follow the block structure of the factor.  Same LM trajectory as
     the natural order (VMM_BA_ORDER=natural) and as the oracle; the covariance (dense, natural order inside) and a
     forced give-up of both one-launch kernels (redone on the launch-per-column path) go through the same handle."""
-    from test_gpu_solve import _assert_same_solution, _assert_same_trace
+    from yardstick import assert_same_solution, assert_same_trace
     from visual_marker_mapping_amd import engine as eng
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(2, neighbors_min=6, neighbors_max=10)
@@ -126,8 +126,8 @@ def test_tree_ordering_of_the_kept_family(oracle, monkeypatch):
         np.testing.assert_allclose(cov_t[t], cov_n[t], rtol=0, atol=1e-7 * np.abs(cov_n[t]).max())
     sc = oracle.Scene(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag, s.obs_px)
     summ, trace = oracle.solve(sc, oracle.default_options(robustify=0, num_threads=8))
-    _assert_same_trace(tree, summ, trace)
-    _assert_same_solution(cam_t, tag_t, sc, s.tag_wh)
+    assert_same_trace(tree, summ, trace)
+    assert_same_solution(cam_t, tag_t, sc, s.tag_wh)
     # every pass's factorisation gives up and is redone without inter-workgroup waits: same trajectory
     monkeypatch.delenv("VMM_BA_ORDER", raising=False)
     monkeypatch.setenv("VMM_BA_DEBUG_SPIN_LIMIT", "1")
@@ -195,7 +195,7 @@ def test_tree_ordering_at_2000_x_1000(oracle, monkeypatch):
     (3.0 ms).  Now only the non-zero blocks of the factor have a workgroup (109 block columns, ~1300 workgroups, masks of 256
     bits per block row) and the one-launch kernel takes it.  Checked: the first two LM iterations against the oracle, the whole
     trajectory against the natural order (the launch-per-column factorisation of the same handle type), no give-up."""
-    from test_gpu_solve import _assert_same_solution
+    from yardstick import assert_same_solution
     from visual_marker_mapping_amd import engine as eng
     from visual_marker_mapping_amd.synthetic import make_scene
     s = make_scene(4, neighbors_min=6, neighbors_max=10)
@@ -231,4 +231,4 @@ def test_tree_ordering_at_2000_x_1000(oracle, monkeypatch):
         assert two["trace"][k]["step_is_successful"] == trace[k]["step_is_successful"]
         np.testing.assert_allclose(two["trace"][k]["cost"], trace[k]["cost"], rtol=1e-8)
         np.testing.assert_allclose(two["trace"][k]["trust_region_radius"], trace[k]["trust_region_radius"], rtol=1e-6)
-    _assert_same_solution(cam2, tag2, sc, s.tag_wh)
+    assert_same_solution(cam2, tag2, sc, s.tag_wh)

@@ -1,10 +1,9 @@
 """GPU tests of the triangulation of free points against a finished map (vmm_ba_triangulate, engine.triangulate, the
 members of TagReconstructor and the command line).
 
-Yardstick throughout: oracle/oracle.py -- point_eval gives the residual, the 2 x 6 camera Jacobian and the 2 x 3 point
-Jacobian of one observation, huber gives rho; the small Levenberg-Marquardt below is written around them and never calls
-the code under test.  Scenes come from synthetic.make_scene, the cameras are cam_gt, the free points are the four world
-corners of every tag; the track of corner k of tag t is the images that observe t, sorted by camera, with the pixels
+Yardstick throughout: tests/yardstick.py -- point_optimum (block_normal over point_rows), numpy around oracle/oracle.py's
+point_eval; it never calls the code under test.  Scenes come from synthetic.make_scene, the cameras are cam_gt, the free
+points are the four world corners of every tag; the track of corner k of tag t is the images that observe t, sorted by camera, with the pixels
 obs_px[:, 2k:2k+2].  Tolerances: 1e-9 on exact data (the localisation's exact-data gate), 1e-6 x max(|X|, 1) between two
 optima, 1e-9 relative on the cost, covariances to 1e-6 x max|ref| as the existing covariance tests.
 """
@@ -14,6 +13,8 @@ import shutil
 
 import numpy as np
 import pytest
+
+import yardstick as ys
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +30,11 @@ EXACT = {
 
 # ---- helpers --------------------------------------------------------------------------------------------------------
 
-def _rotation(q):
-    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
 def _tag_corners(qt, wh, scale=(1.0, 1.0)):
     """World corners LL, LR, UR, UL of a tag of size wh * scale at pose qt."""
     hw, hh = 0.5 * wh[0] * scale[0], 0.5 * wh[1] * scale[1]
     local = np.array([[-hw, -hh, 0.0], [hw, -hh, 0.0], [hw, hh, 0.0], [-hw, hh, 0.0]])
-    return local @ _rotation(qt[:4]).T + qt[4:]
+    return local @ ys.rotation(qt[:4]).T + qt[4:]
 
 
 def _tracks(s):
@@ -70,43 +64,6 @@ def _assert_clean(xyz, cov, cov_cams, res):
     assert np.isfinite(xyz).all() and np.isfinite(cov).all() and np.isfinite(cov_cams).all()
     for r in res:
         assert np.isfinite(r["rms_px"]) and np.isfinite(r["cost"]), r
-
-
-def _normal_equations(O, s, X, cams, uvs, robust, a=1.0):
-    """cost = 1/2 sum rho(|r|^2), sum rho' Jp^T Jp and sum rho' Jp^T r of one point at X."""
-    A, g, cost = np.zeros((3, 3)), np.zeros(3), 0.0
-    for c, uv in zip(cams, uvs):
-        r, _, Jp = O.point_eval(s.intr, s.dist, s.cam_gt[c], X, uv)
-        sq = float(r @ r)
-        rho = O.huber(a, sq) if robust else (sq, 1.0, 0.0)
-        cost += 0.5 * rho[0]
-        A += rho[1] * (Jp.T @ Jp)
-        g += rho[1] * (Jp.T @ r)
-    return cost, A, g
-
-
-def _host_optimum(O, s, X0, cams, uvs, robust):
-    """Levenberg-Marquardt on the same objective from X0, run until the step is at the rounding floor of the point."""
-    X = np.array(X0, np.float64)
-    cost, A, g = _normal_equations(O, s, X, cams, uvs, robust)
-    lam = 1e-4
-    for _ in range(200):
-        try:
-            step = np.linalg.solve(A + lam * np.diag(np.maximum(np.diag(A), 1e-12)), -g)
-        except np.linalg.LinAlgError:
-            lam *= 10.0
-            continue
-        if np.abs(step).max() < 1e-14:
-            break
-        c2, A2, g2 = _normal_equations(O, s, X + step, cams, uvs, robust)
-        if c2 < cost:
-            X, cost, A, g = X + step, c2, A2, g2
-            lam = max(lam * 0.1, 1e-15)
-        else:
-            if lam > 1e8:
-                break
-            lam *= 10.0
-    return X, cost
 
 
 def _check_exact(_lib, start, truth, xyz, cov, cov_cams, inl, res, label):
@@ -206,7 +163,7 @@ def test_noisy_data_reaches_the_host_optimum(oracle):
     for p in range(len(xyz)):
         b, e = int(start[p]), int(start[p + 1])
         keep = inl[b:e]
-        ref, cost = _host_optimum(oracle, s, truth[p], cam[b:e][keep], uv[b:e][keep], True)
+        ref, cost = ys.point_optimum(oracle, s, truth[p], cam[b:e][keep], uv[b:e][keep], True)
         gap = np.abs(xyz[p] - ref).max() / max(np.abs(ref).max(), 1.0)
         cgap = abs(res[p]["cost"] - cost) / cost
         worst_x, worst_c = max(worst_x, gap), max(worst_c, cgap)
@@ -239,7 +196,7 @@ def test_covariances_match_the_formulas(oracle, robustify):
             if not inl[d]:
                 continue
             r, Jc, Jp = oracle.point_eval(s.intr, s.dist, s.cam_gt[cam[d]], xyz[p], uv[d])
-            w = oracle.huber(1.0, float(r @ r))[1] if robustify else 1.0
+            w = ys.corner_loss(oracle, r, bool(robustify))[0][1]
             H += w * (Jp.T @ Jp)
             G = w * (Jp.T @ Jc)
             S += G @ cam_cov[cam[d]] @ G.T
@@ -325,7 +282,7 @@ def test_edges_never_produce_a_nan(oracle):
         c, d = [], []
         for i in range(2):
             q = s.cam_gt[two_cam[i]]
-            R = _rotation(q[:4])
+            R = ys.rotation(q[:4])
             ray = R.T @ np.array([(pix[i, 0] - s.intr[2]) / s.intr[0], (pix[i, 1] - s.intr[3]) / s.intr[1], 1.0])
             c.append(-R.T @ q[4:])
             d.append(ray / np.linalg.norm(ray))

@@ -1,7 +1,7 @@
 """CPU-only checks of the rig entries (ABI 6, additive): vmm_ba_rig_localize and vmm_ba_rig_calibrate are declared, listed
 and exported, laid out as the header says and validate their arguments before any device call; engine.rig_extrinsics_start and synthetic.make_rig_scene do what they
-say; and the yardstick of tests/test_gpu_rig.py (tests/rig_cases.py: numpy around oracle/oracle.py) is proven here
-before the GPU tests lean on it.
+say.  The yardstick of tests/test_gpu_rig.py (tests/rig_cases.py over tests/yardstick.py) is proven in
+tests/test_yardstick_cpu.py.
 """
 import ctypes as C
 import os
@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import rig_cases as rc
+import yardstick as ys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -115,85 +116,6 @@ def test_rig_localize_validates_arguments_before_touching_the_device():
     assert ei.value.status == _lib.ERR_ARGUMENT
 
 
-# ---- the yardstick against central differences ----------------------------------------------------------------------
-
-def test_reference_jacobian_matches_central_differences_of_the_oracle(oracle):
-    """rig_system's columns over both tangents against central differences of oracle.obs_eval at the composed pose, the
-    poses moved by the oracle's Plus, on the distortion scene with three different camera models.
-    The bound.  A pixel coordinate is u = f xd(X / Z) with f <= 8200 and |X / Z| <= 0.42 inside the 6000 x 4000 image.
-    In a half-angle rotation step h the ray turns by 2 h, so d^3 u / dh^3 = 8 f tan''' <= 8 * 8200 * 2 (1 + x^2)(1 + 3 x^2)
-    <= 2.4e5; along the optical axis at depth Z it is 6 f |x| / Z^3 <= 2.1e4 / Z^3 <= 7.7e5 for Z >= 0.3 m (asserted
-    below; an extrinsic rotation moves the point by its lever arm, below 1 m here, which the same figure covers).  The
-    distortion of this scene changes the pixel by a few per cent; a factor 2 covers its derivatives: M3 <= 1.6e6.
-    Truncation h^2 M3 / 6 = 2.7e-5 at h = 1e-5.  Rounding: each residual carries a few eps |u| <= 5 * 2.2e-16 * 1e4, the
-    difference of two over 2 h gives 1.1e-6.  The bound is 5e-5 absolute on entries of magnitude 1e4."""
-    intr = np.array([[8075.0, 8083.0, 3016.0, 1996.0], [7900.0, 7950.0, 2950.0, 2050.0], [8150.0, 8100.0, 3060.0, 1960.0]])
-    dist = np.array([[-0.186, 0.370, -2.9e-4, 4.2e-4, 0.057], [-0.10, 0.15, 3e-4, -2e-4, 0.0], [0.0, 0.0, 0.0, 0.0, 0.0]])
-    s = rc.rig_scene("distortion_12x8", intr=intr, dist=dist, noise_px=0.5, seed=3)
-    keep = np.zeros(len(s.obs_tag), bool)
-    keep[::7] = True   # every camera and most frames, about 36 observations
-    idx = np.flatnonzero(keep)
-    assert set(s.obs_cam[idx]) == {0, 1, 2} and np.abs(s.obs_px).max() < 1e4
-    for o in idx:
-        cam = rc.compose(s.ext_qt[s.obs_cam[o]], s.rig_gt[s.obs_frame[o]])
-        assert (rc.rot(cam) @ s.tag_gt[s.obs_tag[o], 4:] + cam[4:])[2] >= 0.3 + 0.1
-    F, K = s.n_frames, s.n_rig_cams
-    cost, r, J = rc.rig_system(oracle, s, s.rig_gt, s.ext_qt, keep)
-    assert J.shape == (8 * len(idx), 6 * F + 6 * K) and abs(cost - 0.5 * r @ r) <= 1e-12 * cost
-    h = 1e-5
-    worst = 0.0
-    for col in range(6 * F + 6 * K):
-        step = np.zeros(6)
-        step[col % 6] = h
-        num = np.zeros(8 * len(idx))
-        for n, o in enumerate(idx):
-            f, c, t = int(s.obs_frame[o]), int(s.obs_cam[o]), int(s.obs_tag[o])
-            if (col < 6 * F and col // 6 != f) or (col >= 6 * F and (col - 6 * F) // 6 != c):
-                continue
-            side = []
-            for sgn in (1.0, -1.0):
-                rig, ext = s.rig_gt[f], s.ext_qt[c]
-                if col < 6 * F:
-                    rig = oracle.pose_plus(rig, sgn * step)
-                else:
-                    ext = oracle.pose_plus(ext, sgn * step)
-                side.append(oracle.obs_eval(s.intr[c], s.dist[c], rc.compose(ext, rig), s.tag_gt[t], s.tag_wh[t], s.obs_px[o],
-                                            jac=False))
-            num[8 * n:8 * n + 8] = (side[0] - side[1]) / (2 * h)
-        err = np.abs(J[:, col] - num).max()
-        worst = max(worst, err)
-        assert err <= 5e-5, (col, err)
-    print("largest |J| %.3g, largest error against central differences %.3g" % (np.abs(J).max(), worst))
-    assert np.abs(J).max() > 1e3
-    # an observation touches its frame and its camera only
-    o = 5
-    f, c = int(s.obs_frame[idx[o]]), int(s.obs_cam[idx[o]])
-    rows = J[8 * o:8 * o + 8]
-    mask = np.zeros(6 * F + 6 * K, bool)
-    mask[6 * f:6 * f + 6] = mask[6 * F + 6 * c:6 * F + 6 * c + 6] = True
-    assert (rows[:, ~mask] == 0).all() and np.count_nonzero(rows[:, mask]) == 96
-    # the loss: rows and residuals scaled by sqrt(rho'), cost = 1/2 sum rho
-    big = rc.select(s, keep)
-    big.obs_px = big.obs_px.copy()
-    big.obs_px[0] += 5.0
-    cost_h, r_h, J_h = rc.rig_system(oracle, big, s.rig_gt, s.ext_qt, None, robust=True)
-    cost_p, r_p, J_p = rc.rig_system(oracle, big, s.rig_gt, s.ext_qt, None, robust=False)
-    sq = r_p[0] ** 2 + r_p[1] ** 2
-    assert sq > 1.0 and abs(r_h[0] / r_p[0] - sq ** -0.25) <= 1e-12
-    assert np.allclose(J_h[0], J_p[0] * sq ** -0.25, rtol=1e-12, atol=0) and cost_h < cost_p
-
-
-def test_host_frame_optimum_recovers_the_truth_on_exact_data(oracle):
-    """The yardstick's own Levenberg-Marquardt from a perturbed start on exact data: back at the truth to 1e-9."""
-    s = rc.rig_scene("distortion_12x8", noise_px=0.0)
-    keep = np.ones(len(s.obs_tag), bool)
-    start = oracle.pose_plus(s.rig_gt[3], np.array([0.02, -0.01, 0.03, 0.004, -0.003, 0.002]))
-    q, cost = rc.host_frame_optimum(oracle, s, 3, start, s.ext_qt, keep, robust=True)
-    gq, gt = rc.pose_gap(q, s.rig_gt[3])
-    print("host optimum on exact data: |dq| %.3g |dt| %.3g cost %.3g" % (gq, gt, cost))
-    assert gq <= 1e-9 and gt <= 1e-9
-
-
 # ---- rig_extrinsics_start -------------------------------------------------------------------------------------------
 
 def test_rig_extrinsics_start_returns_the_exact_extrinsic_and_names_a_camera_without_a_shared_frame():
@@ -204,7 +126,7 @@ def test_rig_extrinsics_start_returns_the_exact_extrinsic_and_names_a_camera_wit
     ok = dict(status=_lib.LOC_OK, n_obs=5, n_inlier_obs=5, trials=3, rms_px=0.0, cost=0.0)
     res = [dict(ok) for _ in range(F * K)]
     ext = engine.rig_extrinsics_start(K, F, cam, res)
-    gq, gt = rc.pose_gap(ext, s.ext_qt)
+    gq, gt = ys.pose_gap(ext, s.ext_qt)
     assert ext.shape == (K, 7) and gq <= 1e-12 and gt <= 1e-12, (gq, gt)
     assert (ext[0] == [1, 0, 0, 0, 0, 0, 0]).all()
     # the frame with the most inliers over the two images is the one used; ties go to the lowest frame
@@ -214,7 +136,7 @@ def test_rig_extrinsics_start_returns_the_exact_extrinsic_and_names_a_camera_wit
     spoiled[7 * K + 2] = cam[7 * K + 2]
     res[7 * K + 2]["n_inlier_obs"] = 9
     ext = engine.rig_extrinsics_start(K, F, spoiled, res)
-    assert max(rc.pose_gap(ext[2], s.ext_qt[2])) <= 1e-12 and max(rc.pose_gap(ext[1], s.ext_qt[1])) > 1e-3
+    assert max(ys.pose_gap(ext[2], s.ext_qt[2])) <= 1e-12 and max(ys.pose_gap(ext[1], s.ext_qt[1])) > 1e-3
     res[11 * K + 2]["n_inlier_obs"] = 9   # a tie with a later frame changes nothing
     assert engine.rig_extrinsics_start(K, F, spoiled, res).tobytes() == ext.tobytes()
     # camera 1 never shares a localised frame with camera 0

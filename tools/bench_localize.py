@@ -38,9 +38,7 @@ def _spread(v):
 
 
 def _csr(s):
-    order = np.argsort(s.obs_cam, kind="stable")
-    start = np.zeros(len(s.cam_gt) + 1, np.int64)
-    start[1:] = np.cumsum(np.bincount(s.obs_cam, minlength=len(s.cam_gt)))
+    start, order = s.by_image()
     return start, s.obs_tag[order].astype(np.int32), s.obs_px[order].copy()
 
 

@@ -51,6 +51,12 @@ class SyntheticScene:
     def n_obs(self):
         return len(self.obs_cam)
 
+    def by_image(self):
+        """The observations grouped by image: (img_start (n_images + 1, int64), order), order a stable sort by obs_cam."""
+        start = np.zeros(len(self.cam_gt) + 1, np.int64)
+        start[1:] = np.cumsum(np.bincount(self.obs_cam, minlength=len(self.cam_gt)))
+        return start, np.argsort(self.obs_cam, kind="stable")
+
 
 def make_scene(config=2, **overrides):
     """config = index into BASELINE.json configs (1-based); overrides are SceneCfg fields."""

@@ -591,6 +591,56 @@ int vmm_ba_triangulate(const double intr[4], const double dist[5],
                        vmm_ba_triangulate_result* res, /* [n_pts] or NULL */
                        int device);
 
+/* ABI 6, additive.  Locates n_tags tags from cameras that are already known: the 6-DoF pose of every tag from its own
+ * observations, with a covariance.  The dual of vmm_ba_localize (the roles of camera and tag swapped) and stateless like
+ * it, every tag independent of the others in the batch.  Tag t owns the observations [tag_start[t], tag_start[t + 1]):
+ * obs_cam names the camera (strictly increasing within a tag, so one image appears at most once and the caller's
+ * ordering cannot change a result), obs_px the four corners.  It reuses vmm_ba_localize_options and
+ * vmm_ba_localize_result with the VMM_BA_LOC_* statuses, one result per tag; min_inlier_tags counts the tag's inlier
+ * observations.  Per tag:
+ *   candidates  the two planar solutions of each of its observations chained through the observing camera,
+ *               T_cam^-1 o T_rel; each scored by sum min(e^2, score_cap_px^2) over ALL the tag's corners in all its
+ *               observations with the residual the bundle adjustment minimises; lowest wins, ties to the lowest
+ *               observation then solution 0, non-finite loses
+ *   passes      reclassify_passes times: an observation is an inlier when its largest corner distance is at most
+ *               inlier_px; then Levenberg-Marquardt on the tag's 6 tangent degrees of freedom (translation, then
+ *               half-angle rotation) over the inliers, minimising 1/2 sum rho(|r_corner|^2), until the cost is at its
+ *               rounding floor or refine_iterations trials are spent.  A pass that finds fewer than min_inlier_tags
+ *               inliers ends the passes.  reclassify_passes == 0: one refinement over all observations.
+ *   result      tag_qt = tag->world, as the map stores it; obs_inlier = the classification at the returned pose; rms_px
+ *               and cost over those inliers;
+ *               tag_cov = H^-1 (row-major 6x6, the order vmm_ba_covariance_blocks uses for a tag), H = sum rho' Jt^T Jt
+ *               over the inliers' corners, the loss applied when robustify != 0: the part the pixel noise (unit
+ *               variance) causes, the cameras taken as exact.
+ *               tag_cov_cams = H^-1 (sum_i G_i C_i G_i^T) H^-1, G_i = sum over observation i's four corners of
+ *               rho' Jt^T Jc (6x6), Jc the 2x6 Jacobian over the observing camera's tangent and
+ *               C_i = cam_cov[36 obs_cam[i] ..], that camera's 6x6 marginal in the same order (vmm_ba_covariance_blocks'
+ *               or vmm_ba_localize's): first-order propagation of each camera's own uncertainty.  It IGNORES THE
+ *               CORRELATIONS BETWEEN CAMERAS (the cross blocks of the map's covariance), which a bundle adjustment leaves
+ *               positive between neighbours: treat it as the independent-cameras figure.  Zeros when cam_cov is NULL.
+ *               The total is the sum of the two parts.  Both matrices are symmetric to the last bit.
+ * NO_OBSERVATIONS / NO_CANDIDATE (every planar solution of the tag degenerate): pose (1,0,0,0, 0,0,0), zero covariances,
+ * zero flags.  TOO_FEW_INLIERS (fewer than min_inlier_tags at the returned pose): the best-effort pose and its flags,
+ * zero covariances.  SINGULAR: H is not positive definite; pose and flags are returned, both covariances are zeros.
+ * No output is ever NaN; a tag gives the same bits alone, in any batch, at any position and from run to run.
+ * VMM_BA_ERR_ARGUMENT (before any device call): null intr, dist, tag_start or tag_qt; negative sizes; tag_start not
+ * starting at 0 or decreasing; null observations while n_obs > 0; obs_cam outside [0, n_cams) or not strictly increasing
+ * within a tag; a non-finite camera model, pose, size, pixel or cam_cov; a zero quaternion; bad options.  n_tags == 0
+ * returns VMM_BA_OK without a device call. */
+int vmm_ba_locate_tags(const double intr[4], const double dist[5],
+                       int32_t n_cams, const double* cam_qt,      /* [7*n_cams] world->camera: the map's or the localisation's */
+                       const double* cam_cov,                     /* [36*n_cams] 6x6 per camera, tangent order, or NULL */
+                       int32_t n_tags, const double* tag_wh,      /* [2*n_tags] width, height */
+                       const int64_t* tag_start,                  /* [n_tags+1], CSR over tags */
+                       const int32_t* obs_cam, const double* obs_px,   /* [n_obs], [8*n_obs] */
+                       const vmm_ba_localize_options* o,
+                       double* tag_qt,              /* [7*n_tags] tag->world */
+                       double* tag_cov,             /* [36*n_tags] or NULL: measurement part */
+                       double* tag_cov_cams,        /* [36*n_tags] or NULL: part propagated from cam_cov (zeros when cam_cov is NULL) */
+                       uint8_t* obs_inlier,         /* [n_obs] or NULL */
+                       vmm_ba_localize_result* res, /* [n_tags] or NULL */
+                       int device);
+
 /* ABI 6, additive.  Calibrates a camera against a finished map: the nine numbers of the camera model
  * (fx, fy, cx, cy, k1, k2, p1, p2, k3) and one pose per image, the map held fixed.  Stateless like vmm_ba_localize.
  *   objective   1/2 sum rho(|r_corner|^2) over the inlier observations of the images that take part, with the residual

@@ -17,7 +17,7 @@ RIG_MAX_CAMS = 8         # VMM_BA_RIG_MAX_CAMS
 OK, ERR_ARGUMENT, ERR_HIP, ERR_COLLECTIVE, ERR_STATE, ERR_NUMERIC = 0, 1, 2, 3, 4, 5
 ELIM_AUTO, ELIM_TAGS, ELIM_CAMERAS = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
-# VMM_BA_LOC_*: status of one image of vmm_ba_localize
+# VMM_BA_LOC_*: status of one image of vmm_ba_localize (of one frame of vmm_ba_rig_localize, one tag of vmm_ba_locate_tags)
 LOC_OK, LOC_NO_OBSERVATIONS, LOC_NO_CANDIDATE, LOC_TOO_FEW_INLIERS, LOC_SINGULAR = 0, 1, 2, 3, 4
 LOC_STATUS_NAMES = ("ok", "no_observations", "no_candidate", "too_few_inliers", "singular")
 # VMM_BA_TRI_*: status of one point of vmm_ba_triangulate
@@ -192,6 +192,7 @@ SIGNATURES = {
                                   _P(RigCalibrateReport), _i]),
     "vmm_ba_default_triangulate_options": (None, [_P(TriangulateOptions)]),
     "vmm_ba_triangulate": (_i, [_a, _a, _i32, _a, _a] + _BATCH + [_P(TriangulateOptions), _a, _a, _a, _a, _a, _i]),
+    "vmm_ba_locate_tags": (_i, [_a, _a, _i32, _a, _a, _i32, _a, _a, _a, _a, _P(LocalizeOptions), _a, _a, _a, _a, _a, _i]),
     "vmm_ba_default_calibrate_options": (None, [_P(CalibrateOptions)]),
     "vmm_ba_calibrate": (_i, [_a, _a] + _MAP + _BATCH + [_P(CalibrateOptions), _a, _a, _a, _a, _a, _a, _a,
                               _P(CalibrateReport), _i]),
@@ -214,7 +215,7 @@ EXPORTS = list(SIGNATURES)   # every symbol include/vmm_ba.h declares
 # commit's build) still loads, and calling the missing entry raises AttributeError.
 OPTIONAL = {"vmm_ba_covariance_blocks", "vmm_ba_rig_localize", "vmm_ba_default_rig_calibrate_options", "vmm_ba_rig_calibrate",
             "vmm_ba_default_calibrate_options", "vmm_ba_calibrate", "vmm_ba_default_triangulate_options",
-            "vmm_ba_triangulate", "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
+            "vmm_ba_triangulate", "vmm_ba_locate_tags", "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
             "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"}
 
 _LIB = None

@@ -533,6 +533,30 @@ struct TriangulateArgs {
 void launch_cam_frames(hipStream_t st, int n_cams, const double* cam_qt, double* frames);
 void launch_triangulate(hipStream_t st, const TriangulateArgs& a);
 int preload_triangulate_kernels();
+// kernels_locate.hip: tag poses from known cameras (vmm_ba_locate_tags)
+struct LocateArgs {
+    Intrinsics K;
+    int n_tags;
+    const double* rigids;      // [12 * n_cams] R | t of every camera (k_camera_rigids)
+    const double* cam_cov;     // [36 * n_cams] or null
+    const double* tag_wh;      // [2 * n_tags]
+    const int64_t* tag_start;  // [n_tags + 1]
+    const int32_t* obs_cam;    // [n_obs]
+    const double* obs_px;      // [8 * n_obs]
+    const double* quad_qt;     // [14 * n_obs] planar tag->camera poses (k_quad_pose)
+    const double* quad_rms;    // [2 * n_obs]
+    int max_trials, robustify, passes, min_inliers;
+    double huber_a, cap2, inlier2;
+    double* tag_qt;            // [7 * n_tags]
+    double* tag_cov;           // [36 * n_tags]
+    double* tag_cov_cams;      // [36 * n_tags]
+    uint8_t* obs_inlier;       // [n_obs]: the active set of every pass, the final flags at the end
+    vmm_ba_localize_result* res;
+};
+void launch_camera_rigids(hipStream_t st, int n_cams, const double* cam_qt, double* rigids);
+void launch_locate_tags(hipStream_t st, const LocateArgs& a, bool any_staged, bool any_unstaged);
+int locate_stage_capacity();   // observations of one tag that k_locate_tags stages in LDS
+int preload_locate_kernels();
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
 constexpr int kCalRec = arrow_rec_doubles(9);     // 68
 constexpr int kCalElim = 84;                        // the stride of an image's elimination: arrow_elim_doubles(9) = 81 of it are used

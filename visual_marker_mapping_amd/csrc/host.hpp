@@ -1,5 +1,5 @@
 // What the host files of libvmm_ba.so share (vmm_ba.hip, covariance.hip, selfcal.hip, initialize.hip, standalone.hip,
-// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip).  No kernel; no kernels_*.hip includes this.
+// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip, locate.hip).  No kernel; no kernels_*.hip includes this.
 #pragma once
 
 #include <algorithm>
@@ -57,6 +57,8 @@ int tag_pose_handle(const Engine& e, const char* who);   // VMM_BA_ERR_STATE: "<
 int bad_argument(const char* who, const char* what);                 // VMM_BA_ERR_ARGUMENT, "<who>: <what>"
 int hip_failure(const char* who, const char* step, hipError_t err);  // VMM_BA_ERR_HIP, "<who>: <step><error string>"
 int check_camera_model(const char* who, const double intr[4], const double dist[5]);   // finite
+// known cameras (vmm_ba_triangulate, vmm_ba_locate_tags): finite poses, no zero quaternion, a finite cam_cov (may be null)
+int check_cameras(const char* who, int32_t n_cams, const double* cam_qt, const double* cam_cov);
 int check_batch(const char* who, MapBatch& mb, int32_t n_tags, const double* tag_qt, const double* tag_wh, int32_t n_imgs,
                 const int64_t* img_start, const int32_t* obs_tag, const double* obs_px, const double* cam_qt);
 int check_map(const char* who, const MapBatch& mb);

@@ -10,6 +10,7 @@
 // The two sums are workgroup functions: threads stride the observation list, one butterfly per wave, the waves combined
 // in order through LDS (s_cnt: kImageWaves ints; s_red: 32 kImageWaves doubles with JAC, kImageWaves without); they
 // hold barriers, so all kImageThreads threads call them together.
+// kernels_locate.hip (k_locate_tags: a tag against fixed cameras) takes the three reductions as they are for its own sums.
 #pragma once
 #include "engine.hpp"
 #include "pose_lm.hpp"

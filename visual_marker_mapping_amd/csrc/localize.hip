@@ -31,6 +31,25 @@ int check_camera_model(const char* who, const double intr[4], const double dist[
     return VMM_BA_OK;
 }
 
+int check_cameras(const char* who, int32_t n_cams, const double* cam_qt, const double* cam_cov)
+{
+    if (n_cams > 0 && !cam_qt)
+        return bad_argument(who, "null cam_qt");
+    for (int32_t i = 0; i < n_cams; ++i) {
+        const double* q = cam_qt + 7 * (int64_t)i;
+        for (int k = 0; k < 7; ++k)
+            if (!isfinite(q[k]))
+                return bad_argument(who, "non-finite camera pose");
+        if (!(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0))
+            return bad_argument(who, "zero camera quaternion");
+    }
+    if (cam_cov)
+        for (int64_t k = 0; k < 36 * (int64_t)n_cams; ++k)
+            if (!isfinite(cam_cov[k]))
+                return bad_argument(who, "non-finite cam_cov");
+    return VMM_BA_OK;
+}
+
 int check_batch(const char* who, MapBatch& mb, int32_t n_tags, const double* tag_qt, const double* tag_wh, int32_t n_imgs,
                 const int64_t* img_start, const int32_t* obs_tag, const double* obs_px, const double* cam_qt)
 {

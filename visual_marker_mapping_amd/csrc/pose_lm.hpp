@@ -1,6 +1,6 @@
 // The single-pose solver shared by kernels_init.hip (map initialisation), kernels_localize.hip (localisation against
-// a finished map) and, through image_sums.hpp and the pieces named below, kernels_calibrate.hip: fit one
-// 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
+// a finished map), kernels_locate.hip (a tag from known cameras) and, through image_sums.hpp and the pieces named below,
+// kernels_calibrate.hip: fit one 6-degree-of-freedom pose to pixel corners after picking the best of a list of candidates.
 //   lm_refine               the Levenberg-Marquardt trial loop over a pose's six tangent unknowns (small_solve.hpp's
 //                           lm_trials with pose_plus as the update); the caller supplies the sums (cost, J^T J, J^T r)
 //   project_camera_point    camera-side projection of a rotated point with its 2 x 6 Jacobian over the pose's tangent

@@ -21,25 +21,6 @@ int check_triangulate_options(const vmm_ba_triangulate_options& o)
     return VMM_BA_OK;
 }
 
-int check_cameras(int32_t n_cams, const double* cam_qt, const double* cam_cov)
-{
-    if (n_cams > 0 && !cam_qt)
-        return bad_argument(who, "null cam_qt");
-    for (int32_t i = 0; i < n_cams; ++i) {
-        const double* q = cam_qt + 7 * (int64_t)i;
-        for (int k = 0; k < 7; ++k)
-            if (!isfinite(q[k]))
-                return bad_argument(who, "non-finite camera pose");
-        if (!(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0))
-            return bad_argument(who, "zero camera quaternion");
-    }
-    if (cam_cov)
-        for (int64_t k = 0; k < 36 * (int64_t)n_cams; ++k)
-            if (!isfinite(cam_cov[k]))
-                return bad_argument(who, "non-finite cam_cov");
-    return VMM_BA_OK;
-}
-
 // any_pair: whether a point has two or more observations
 int check_tracks(int32_t n_cams, int32_t n_pts, const int64_t* pt_start, const int32_t* obs_cam, const double* obs_uv, bool& any_pair)
 {
@@ -126,7 +107,7 @@ int vmm_ba_triangulate(const double intr[4], const double dist[5], int32_t n_cam
     bool any_pair = false;
     int rc;
     if ((rc = check_tracks(n_cams, n_pts, pt_start, obs_cam, obs_uv, any_pair)) != VMM_BA_OK
-        || (rc = check_camera_model(who, intr, dist)) != VMM_BA_OK || (rc = check_cameras(n_cams, cam_qt, cam_cov)) != VMM_BA_OK
+        || (rc = check_camera_model(who, intr, dist)) != VMM_BA_OK || (rc = check_cameras(who, n_cams, cam_qt, cam_cov)) != VMM_BA_OK
         || (rc = check_triangulate_options(o)) != VMM_BA_OK)
         return rc;
     for (int32_t p = 0; p < n_pts; ++p)

@@ -581,6 +581,58 @@ def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, dev
     return xyz, cov, cov_cams, inl.astype(bool), _result_dicts(res)
 
 
+def locate_tags(intr, dist, cam_qt, tag_wh, tag_start, obs_cam, obs_px, cam_cov=None, device=0, **options):
+    """Poses of a batch of tags from cameras that are already known (vmm_ba_locate_tags, the dual of engine.localize).
+    cam_qt (n_cams, 7) world->camera; tag_wh (n_tags, 2).  tag_start (n_tags + 1,): tag t owns the observations
+    [tag_start[t], tag_start[t + 1]) of obs_cam (n_obs,), strictly increasing within a tag, and obs_px (n_obs, 8).
+    cam_cov (n_cams, 6, 6), optional: the cameras' marginal covariances in tangent order.  options: the fields of
+    vmm_ba_localize_options; min_inlier_tags counts the tag's inlier observations.  Returns (tag_qt (n_tags, 7)
+    tag->world, tag_cov (n_tags, 6, 6) the part the pixel noise causes, tag_cov_cams (n_tags, 6, 6) the part propagated
+    from cam_cov, camera by camera without their correlations (zeros without cam_cov), obs_inlier (n_obs,) bool, results:
+    one dict per tag as engine.localize gives per image)."""
+    intr, dist = _model_arrays(intr, dist)
+    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
+    tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
+    tag_start = np.ascontiguousarray(tag_start, np.int64).reshape(-1)
+    obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
+    obs_px = np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8)
+    if len(obs_cam) != len(obs_px):
+        raise ValueError("observation arrays differ in length")
+    if len(tag_start) != len(tag_wh) + 1 or tag_start[-1] != len(obs_cam):
+        raise ValueError("tag_start must have n_tags + 1 entries and end at the number of observations")
+    if cam_cov is not None:
+        cam_cov = np.ascontiguousarray(cam_cov, np.float64).reshape(-1, 6, 6)
+        if len(cam_cov) != len(cam_qt):
+            raise ValueError("cam_cov and cam_qt differ in length")
+    o = default_localize_options(**options)
+    n_tags = len(tag_wh)
+    tag_qt, cov, cov_cams = np.zeros((n_tags, 7)), np.zeros((n_tags, 6, 6)), np.zeros((n_tags, 6, 6))
+    inl, res = np.zeros(len(obs_cam), np.uint8), _results(n_tags)
+    _lib.check(_lib.lib().vmm_ba_locate_tags(_ptr(intr), _ptr(dist), len(cam_qt), _ptr(cam_qt), _ptr(cam_cov), n_tags,
+                                             _ptr(tag_wh), _ptr(tag_start), _ptr(obs_cam), _ptr(obs_px), C.byref(o),
+                                             _ptr(tag_qt), _ptr(cov), _ptr(cov_cams), _ptr(inl), _ptr(res), device))
+    return tag_qt, cov, cov_cams, inl.astype(bool), _result_dicts(res)
+
+
+def pose_minus(a, b):
+    """The tangent step d (6,) with pose_plus(b, d) == a, for two poses (7,) (host numpy, no device call): translation
+    is the difference, rotation the axis times the half angle of q_a q_b^-1, its sign chosen so that w >= 0."""
+    a, b = np.asarray(a, np.float64).reshape(7), np.asarray(b, np.float64).reshape(7)
+    qa, qb = a[:4] / np.linalg.norm(a[:4]), b[:4] / np.linalg.norm(b[:4])
+    w1, x1, y1, z1 = qa
+    w2, x2, y2, z2 = qb[0], -qb[1], -qb[2], -qb[3]
+    z = np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                  w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+    if z[0] < 0.0:
+        z = -z
+    s = np.linalg.norm(z[1:])
+    d = np.zeros(6)
+    d[:3] = a[4:] - b[4:]
+    if s > 0.0:
+        d[3:] = z[1:] * (np.arctan2(s, z[0]) / s)
+    return d
+
+
 def pose_plus(qt, delta, device=0):
     """Plus(qt, delta) for (n,7) poses and (n,6) tangent steps with the engine's device function
     (Ceres QuaternionParameterization::Plus on q, addition on t; tangent = translation then rotation)."""

@@ -160,6 +160,8 @@ class TagReconstructor:
         self.lastLocalizationReport = None                     # image id -> report (computeRelativeCameraPosesFromImgs)
         self.lastSelfCalibrationReport = None                  # report of doBundleAdjustment(refineCameraModel=True)
         self.lastTriangulationDropped = 0                      # observations triangulatePoints dropped (image without a pose)
+        self.lastTagLocationReport = None                      # tag id -> report (locateTags)
+        self.lastMapCheckReport = None                         # report of checkMap
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
         self._obs_cache = None                                 # observation list as arrays (see _obs_arrays)
         self._resident = False                                 # device-resident packing (startReconstruction)
@@ -468,10 +470,10 @@ class TagReconstructor:
         observations [b, e) with their inlier flags."""
         return dict(res, pose=pose.copy(), covariance=cov.copy(), observations=list(order[b:e]), inliers=inl[b:e].copy())
 
-    def _pack_against_map(self, det, imageIds):
+    def _pack_against_map(self, det, imageIds, skipTagIds=()):
         """The flat arrays engine.localize and engine.calibrate take: the reconstructed tags as the map and the
-        observations of those tags grouped by image.  Returns (ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px);
-        order[k] indexes det.tagObservations."""
+        observations of those tags grouped by image, but for the tags in skipTagIds.  Returns (ids, order, tag_qt, tag_wh,
+        img_start, obs_tag, obs_px); order[k] indexes det.tagObservations."""
         if imageIds is None:
             ids = sorted({int(im.imageId) for im in det.images} | {int(ob.imageId) for ob in det.tagObservations})
         else:
@@ -480,7 +482,7 @@ class TagReconstructor:
         dense = {t: k for k, t in enumerate(tag_ids)}
         per_img = {i: [] for i in ids}
         for k, ob in enumerate(det.tagObservations):
-            if ob.imageId in per_img and ob.tagId in dense:
+            if ob.imageId in per_img and ob.tagId in dense and ob.tagId not in skipTagIds:
                 per_img[ob.imageId].append(k)
         order = [k for i in ids for k in per_img[i]]
         img_start = np.zeros(len(ids) + 1, np.int64)
@@ -498,7 +500,11 @@ class TagReconstructor:
         per image id the status, counts, rms_px, cost, the pose, the 6x6 covariance and the inlier flag of each used
         observation (index into detectionResult.tagObservations)."""
         det = self.detectionResults_ if detectionResult is None else detectionResult
-        ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_against_map(det, imageIds)
+        return self._localize_images(det, imageIds, (), options)
+
+    def _localize_images(self, det, imageIds, skipTagIds, options):
+        """computeRelativeCameraPosesFromImgs with the observations of the tags in skipTagIds left out."""
+        ids, order, tag_qt, tag_wh, img_start, obs_tag, obs_px = self._pack_against_map(det, imageIds, skipTagIds)
         cam_qt, cam_cov, inl, res = _engine.localize(*self._model_args(), tag_qt, tag_wh, img_start, obs_tag, obs_px,
                                                      device=self.device, **options)
         cams, report = {}, {}
@@ -693,6 +699,116 @@ class TagReconstructor:
                       "out_of_plane": float(abs(np.dot(c[2] - c[0], normal)) / nn) if nn > 0 else 0.0,
                       "model_gap": float(gap), "status": max(pts[(t, k)]["status"] for k in range(4))}
         return out
+
+    def locateTags(self, cameras=None, cameraCovariances=None, tagIds=None, detectionResult=None, **options):
+        """Poses of tags from images with a known pose (vmm_ba_locate_tags): the dual of
+        computeRelativeCameraPosesFromImgs.  cameras: {imageId: Camera}, default reconstructedCameras (a localisation's
+        result works as well).  cameraCovariances: {imageId: 6x6} in tangent order; a camera without an entry counts as
+        exact.  tagIds: default every tag the reconstructor or `detectionResult` (default: the reconstructor's own
+        detections) knows the size of.  options: the fields of vmm_ba_localize_options; min_inlier_tags counts a tag's
+        inlier observations.  Observations in images without a pose are dropped.  Returns {tagId: ReconstructedTag} for
+        the tags with status OK; lastTagLocationReport holds per tag id the status, counts, rms_px, cost, the pose, the
+        6x6 covariance from the pixel noise (`covariance`), the part propagated from cameraCovariances camera by camera
+        (`covariance_cameras`) and the inlier flag of each used observation (index into detectionResult.tagObservations).
+        The reference has no such member."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        cams = self.reconstructedCameras if cameras is None else {int(k): v for k, v in dict(cameras).items()}
+        cam_ids = sorted(cams)
+        dense = {i: k for k, i in enumerate(cam_ids)}
+        known = {int(t.tagId): (t.tagType, t.width, t.height) for t in det.tags}
+        known.update({int(i): (t.tagType, t.tagWidth, t.tagHeight) for i, t in self.reconstructedTags.items()})
+        ids = sorted(known) if tagIds is None else [int(t) for t in tagIds]
+        per_tag = {t: [] for t in ids}
+        for k, ob in enumerate(det.tagObservations):
+            if ob.tagId in per_tag and ob.imageId in dense:
+                per_tag[ob.tagId].append((dense[ob.imageId], k))
+        order = []
+        for t in ids:
+            per_tag[t].sort()
+            seen = [c for c, _ in per_tag[t]]
+            if len(set(seen)) != len(seen):
+                raise ValueError("tag %r is observed twice in one image" % (t,))
+            order.extend(k for _, k in per_tag[t])
+        tag_start = np.zeros(len(ids) + 1, np.int64)
+        tag_start[1:] = np.cumsum([len(per_tag[t]) for t in ids])
+        obs_cam = np.array([dense[det.tagObservations[k].imageId] for k in order], np.int32)
+        obs_px = (np.stack([np.asarray(det.tagObservations[k].corners, np.float64).reshape(8) for k in order])
+                  if order else np.zeros((0, 8)))
+        cam_qt = np.array([np.concatenate([cams[i].q, cams[i].t]) for i in cam_ids], np.float64).reshape(-1, 7)
+        tag_wh = np.array([known[t][1:] for t in ids], np.float64).reshape(-1, 2)
+        cam_cov = None
+        if cameraCovariances is not None:
+            cam_cov = np.zeros((len(cam_ids), 6, 6))
+            for k, i in enumerate(cam_ids):
+                if i in cameraCovariances:
+                    cam_cov[k] = np.asarray(cameraCovariances[i], np.float64).reshape(6, 6)
+        tag_qt, cov, cov_cams, inl, res = _engine.locate_tags(*self._model_args(), cam_qt, tag_wh, tag_start, obs_cam, obs_px,
+                                                              cam_cov=cam_cov, device=self.device, **options)
+        tags, report = {}, {}
+        for n, t in enumerate(ids):
+            report[t] = self._item_report(res[n], tag_qt[n], cov[n], order, inl, int(tag_start[n]), int(tag_start[n + 1]))
+            report[t]["covariance_cameras"] = cov_cams[n].copy()
+            if res[n]["status"] == _engine._lib.LOC_OK:
+                tags[t] = ReconstructedTag(t, known[t][0], tag_qt[n, :4], tag_qt[n, 4:], known[t][1], known[t][2])
+        self.lastTagLocationReport = report
+        return tags
+
+    def checkMap(self, detectionResult=None, imageIds=None, sigma_px=1.0, chi2_threshold=22.458, min_views=2, rounds=2,
+                 **options):
+        """Which tags of the map are no longer where the map says?  Fresh images (`detectionResult`, default the
+        reconstructor's own detections; `imageIds` restricts them) are localised against the reconstructed tags
+        (vmm_ba_localize), then every map tag seen in at least min_views of the images whose localisation is OK is located
+        from those cameras (vmm_ba_locate_tags), the localisation's covariances passed on.  Per tag:
+        delta = engine.pose_minus(located, map), Sigma = sigma_px^2 (tag_cov + tag_cov_cams), d2 = delta^T Sigma^-1 delta,
+        moved = d2 > chi2_threshold (22.458: the 0.999 quantile of chi-square with 6 degrees of freedom), and the largest
+        displacement of the tag's four world corners in metres, which is reported and not thresholded.  When a round
+        flags something and rounds >= 2, the observations of the flagged tags are dropped from the localisation input,
+        the images are localised again, all tags are located again and that round is reported.  options: the fields of
+        vmm_ba_localize_options, given to both steps.
+        The statistic IGNORES the correlations between cameras (tag_cov_cams is the independent-cameras figure), the map's
+        own uncertainty (the map pose is taken as exact), and the fact that an unmoved tag helped localise the cameras it
+        is then tested against, which makes its d2 smaller than chi-square says.  Treat the threshold as a ranking
+        aid with a known bias towards "not moved", not as a calibrated test.
+        Returns and keeps as lastMapCheckReport: {"rounds", "sigma_px", "chi2_threshold", "images": {imageId: status},
+        "tags": {tagId: {"status", "n_obs", "n_inlier_obs", "rms_px", "pose", "covariance" (Sigma), "delta",
+        "mahalanobis2", "max_corner_displacement", "moved"}}, "skipped": tag ids with fewer than min_views views,
+        "moved": the flagged tag ids}."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        LOC_OK = _engine._lib.LOC_OK
+        flagged, report = [], None
+        for rnd in range(1, max(int(rounds), 1) + 1):
+            cams = self._localize_images(det, imageIds, set(flagged), options)
+            loc = self.lastLocalizationReport
+            views = {t: 0 for t in self.reconstructedTags}
+            for ob in det.tagObservations:
+                if ob.imageId in cams and ob.tagId in views:
+                    views[ob.tagId] += 1
+            checked = sorted(t for t, n in views.items() if n >= min_views)
+            self.locateTags(cams, {i: loc[i]["covariance"] for i in cams}, checked, det, **options)
+            tags = {}
+            for t in checked:
+                r, ref = self.lastTagLocationReport[t], self.reconstructedTags[t]
+                entry = {k: r[k] for k in ("status", "n_obs", "n_inlier_obs", "rms_px", "pose")}
+                sigma = sigma_px * sigma_px * (r["covariance"] + r["covariance_cameras"])
+                delta, d2, gap = np.zeros(6), 0.0, 0.0
+                if r["status"] == LOC_OK:
+                    delta = _engine.pose_minus(r["pose"], np.concatenate([ref.q, ref.t]))
+                    d2 = float(delta @ np.linalg.solve(sigma, delta))
+                    there = ReconstructedTag(t, ref.tagType, r["pose"][:4], r["pose"][4:], ref.tagWidth, ref.tagHeight)
+                    gap = max(float(np.linalg.norm(np.asarray(a) - np.asarray(b)))
+                              for a, b in zip(there.computeMarkerCorners3D(), ref.computeMarkerCorners3D()))
+                entry.update(covariance=sigma, delta=delta, mahalanobis2=d2, max_corner_displacement=gap,
+                             moved=bool(d2 > chi2_threshold))
+                tags[t] = entry
+            moved = [t for t in checked if tags[t]["moved"]]
+            report = {"rounds": rnd, "sigma_px": float(sigma_px), "chi2_threshold": float(chi2_threshold),
+                      "images": {i: loc[i]["status"] for i in sorted(loc)}, "tags": tags,
+                      "skipped": sorted(t for t in views if t not in tags), "moved": moved}
+            if not moved or set(moved) <= set(flagged):
+                break
+            flagged = sorted(set(flagged) | set(moved))
+        self.lastMapCheckReport = report
+        return report
 
     def moveTagIntoOrigin(self, tagId):
         """src/TagReconstructor.cpp:314-338 (applies the same map to tags AND cameras, as the reference does)."""

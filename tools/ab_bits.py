@@ -8,8 +8,9 @@ vmm_ba_quad_poses, vmm_ba_initialize and vmm_ba_localize.  --cases chol: every C
 --cases handle: the other entries that work on a handle after a solve (csrc/covariance.hip, selfcal.hip, initialize.hip
 and the evaluation entries of vmm_ba.hip).
 --cases triangulate: vmm_ba_triangulate (csrc/kernels_triangulate.hip, point_lm.hpp).
+--cases locate: vmm_ba_locate_tags (csrc/kernels_locate.hip behind k_quad_pose).
 
-    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|rig|cov|handle|triangulate] [--keep DIR]
+    python tools/ab_bits.py --a <libvmm_ba.so> --b <libvmm_ba.so> [--cases pose|chol|calibrate|rig|cov|handle|triangulate|locate] [--keep DIR]
 
 Each library runs in a fresh child process of its own (VMM_BA_LIB is read when the package is imported); the child
 writes every array the entries return to an .npz.  The parent compares them byte for byte and prints one JSON line:
@@ -221,7 +222,7 @@ def _rig_cases(eng, make_rig_scene, out):
                         out[key + n] = value
                     out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
                     out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
-                    ints = ("status", "trials", "accepted", "passes", "n_frames_used", "n_obs_used", "cams_refined", "reserved")
+                    ints = ("status", "trials", "accepted", "passes", "n_frames_used", "n_obs_used", "cams_refined")   # the binding leaves `reserved` out
                     floats = ("initial_cost", "final_cost", "initial_rms_px", "final_rms_px")
                     assert sorted(ints + floats + ("time_s",)) == sorted(rep), sorted(rep)   # a new field belongs in one of them
                     out[key + "report_int"] = np.array([rep[k] for k in ints], np.int64)
@@ -435,6 +436,57 @@ def _triangulate_cases(eng, out):
                     out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
 
 
+def _locate_cases(eng, make_scene, out):
+    """Nine tags in one batch against 260 cameras, each the first m of its observations in camera order: 0
+    (NO_OBSERVATIONS), 1 (TOO_FEW_INLIERS under min_inlier_tags 2), 2, 64, 65 (one wave plus a lane), 256 (the last
+    staged size), 257 (the first unstaged; second trip of the 256-thread stride), 64 with a tenth of its pixel
+    coordinates displaced by up to 60 px, 1 collapsed to a point (NO_CANDIDATE).  With and without cam_cov, robust and
+    plain, 0 and 2 reclassification passes."""
+    from visual_marker_mapping_amd import _lib
+    sizes = (0, 1, 2, 64, 65, 256, 257, 64, 1)
+    s = make_scene(1, seed=4280, n_cams=260, n_tags=len(sizes))
+    order = np.lexsort((s.obs_cam, s.obs_tag))
+    first = np.concatenate([[0], np.cumsum(np.bincount(s.obs_tag, minlength=len(sizes)))])
+    cams, pxs = [], []
+    for t, m in enumerate(sizes):
+        idx = order[first[t]:first[t + 1]][:m]
+        assert len(idx) == m, (t, len(idx))
+        cams.append(s.obs_cam[idx].astype(np.int32))
+        pxs.append(s.obs_px[idx].copy())
+    rng = np.random.default_rng(4281)
+    hit = rng.random(pxs[7].shape) < 0.1
+    pxs[7][hit] += rng.uniform(-60.0, 60.0, int(hit.sum()))
+    pxs[8][0] = np.tile(pxs[8][0, :2], 4)
+    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    cams, pxs = np.concatenate(cams), np.concatenate(pxs)
+    cov_in = np.zeros((len(s.cam_gt), 6, 6))
+    for i in range(len(cov_in)):
+        m = rng.normal(size=(6, 6)) * 1e-4
+        cov_in[i] = m @ m.T + 1e-8 * np.eye(6)
+    expected = [_lib.LOC_NO_OBSERVATIONS, _lib.LOC_TOO_FEW_INLIERS] + [_lib.LOC_OK] * 6 + [_lib.LOC_NO_CANDIDATE]
+    for with_cov in (0, 1):
+        for robust in (1, 0):
+            for passes in (0, 2):
+                tag, cov, cov_cams, inl, res = eng.locate_tags(s.intr, s.dist, s.cam_gt, s.tag_wh, start, cams, pxs,
+                                                               cam_cov=cov_in if with_cov else None, min_inlier_tags=2,
+                                                               robustify=robust, reclassify_passes=passes)
+                status = [r["status"] for r in res]
+                # else the scene does not do what the text above says: pick another one
+                assert status == expected, status
+                assert np.isfinite(tag).all() and np.isfinite(cov).all() and np.isfinite(cov_cams).all()
+                assert all(np.isfinite([r["rms_px"], r["cost"]]).all() for r in res)
+                for t in (0, 8):   # zero flags, the identity pose, zero covariances
+                    assert not inl[start[t]:start[t + 1]].any() and tag[t].tolist() == [1, 0, 0, 0, 0, 0, 0], t
+                    assert not cov[t].any() and not cov_cams[t].any(), t
+                assert not cov[1].any() and not cov_cams[1].any()
+                assert with_cov or not cov_cams.any()
+                assert passes == 0 or not inl[start[7]:start[8]].all(), "the displaced pixels of tag 7 are all inliers"
+                key = "locate_%s_%s_p%d_" % ("cov" if with_cov else "nocov", "robust" if robust else "plain", passes)
+                out[key + "tag_qt"], out[key + "tag_cov"], out[key + "tag_cov_cams"], out[key + "inlier"] = tag, cov, cov_cams, inl
+                out[key + "res_int"] = np.array([[r[k] for k in ("status", "n_obs", "n_inlier_obs", "trials")] for r in res], np.int32)
+                out[key + "res_f64"] = np.array([[r["rms_px"], r["cost"]] for r in res])
+
+
 def child(path, cases):
     sys.path.insert(0, ROOT)
     from visual_marker_mapping_amd import engine as eng
@@ -455,6 +507,8 @@ def child(path, cases):
         _handle_cases(eng, make_scene, out)
     elif cases == "triangulate":
         _triangulate_cases(eng, out)
+    elif cases == "locate":
+        _locate_cases(eng, make_scene, out)
     else:
         _chol_dense_cases(eng, out)
         _chol_tree_cases(eng, make_scene, out)
@@ -465,7 +519,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--a", help="first library")
     ap.add_argument("--b", help="second library")
-    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "rig", "cov", "handle", "triangulate"), default="pose", help="which set of cases (default: pose)")
+    ap.add_argument("--cases", choices=("pose", "chol", "calibrate", "rig", "cov", "handle", "triangulate", "locate"), default="pose", help="which set of cases (default: pose)")
     ap.add_argument("--keep", help="directory that receives a.npz and b.npz (default: a temporary one)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     args = ap.parse_args()

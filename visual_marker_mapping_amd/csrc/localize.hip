@@ -1,7 +1,8 @@
 // vmm_ba_localize (include/vmm_ba.h): host side, and the stage it shares with vmm_ba_calibrate (MapBatch, engine.hpp):
 // the checks on the batch, the map and the localisation options, the answers that need no device, the device memory of
 // the common buffers, the uploads, k_quad_pose -> k_map_corners -> k_localize (kernels_init.hip, kernels_localize.hip)
-// and the copies back.  vmm_ba_localize is that stage plus its return.
+// and the copies back.  vmm_ba_localize is that stage plus its return.  Also the checks every stateless entry shares
+// (host.hpp): the camera model, known cameras, and check_list, the one walk over an item list.
 #include <math.h>
 #include <string.h>
 
@@ -50,6 +51,36 @@ int check_cameras(const char* who, int32_t n_cams, const double* cam_qt, const d
     return VMM_BA_OK;
 }
 
+int check_list(const char* who, const ListWords& w, int32_t n_items, const int64_t* start, const int32_t* ids, const void* obs,
+               int32_t n_ids, int64_t& shortest, int64_t& longest)
+{
+    const std::string s(w.start), id(w.ids), item(w.item);
+    if (start[0] != 0)
+        return bad_argument(who, (s + "[0] is not 0").c_str());
+    shortest = INT64_MAX;
+    longest = 0;
+    for (int32_t i = 0; i < n_items; ++i) {
+        const int64_t m = start[i + 1] - start[i];
+        if (m < 0)
+            return bad_argument(who, (s + " decreases").c_str());
+        if (m > (int64_t)1 << 28)
+            return bad_argument(who, (item + " has too many observations").c_str());
+        shortest = std::min(shortest, m);
+        longest = std::max(longest, m);
+    }
+    const int64_t n_obs = start[n_items];
+    if (n_obs > 0 && (!ids || !obs))
+        return bad_argument(who, "null observations");
+    for (int64_t i = 0; i < n_obs; ++i)
+        if (ids[i] < 0 || ids[i] >= n_ids)
+            return bad_argument(who, (id + " outside [0, " + w.count + ")").c_str());
+    for (int32_t k = 0; k < n_items && w.ordered; ++k)
+        for (int64_t i = start[k] + 1; i < start[k + 1]; ++i)
+            if (ids[i] <= ids[i - 1])
+                return bad_argument(who, (id + " is not strictly increasing within " + item).c_str());
+    return VMM_BA_OK;
+}
+
 int check_batch(const char* who, MapBatch& mb, int32_t n_tags, const double* tag_qt, const double* tag_wh, int32_t n_imgs,
                 const int64_t* img_start, const int32_t* obs_tag, const double* obs_px, const double* cam_qt)
 {
@@ -57,27 +88,16 @@ int check_batch(const char* who, MapBatch& mb, int32_t n_tags, const double* tag
         return bad_argument(who, "null img_start or cam_qt");
     if (n_tags > 0 && (!tag_qt || !tag_wh))
         return bad_argument(who, "null map");
-    if (img_start[0] != 0)
-        return bad_argument(who, "img_start[0] is not 0");
-    mb.any_staged = mb.any_unstaged = false;
-    const int cap = localize_stage_capacity();
-    for (int32_t i = 0; i < n_imgs; ++i) {
-        const int64_t m = img_start[i + 1] - img_start[i];
-        if (m < 0)
-            return bad_argument(who, "img_start decreases");
-        if (m > (int64_t)1 << 28)
-            return bad_argument(who, "an image has too many observations");
-        (m <= cap ? mb.any_staged : mb.any_unstaged) = true;
-    }
-    const int64_t n_obs = img_start[n_imgs];
-    if (n_obs > 0 && (!obs_tag || !obs_px))
-        return bad_argument(who, "null observations");
-    for (int64_t i = 0; i < n_obs; ++i)
-        if (obs_tag[i] < 0 || obs_tag[i] >= n_tags)
-            return bad_argument(who, "obs_tag outside [0, n_tags)");
+    int64_t shortest, longest;
+    const int rc = check_list(who, { "img_start", "an image", "obs_tag", "n_tags", false }, n_imgs, img_start, obs_tag, obs_px, n_tags,
+                              shortest, longest);
+    if (rc != VMM_BA_OK)
+        return rc;
+    mb.any_staged = shortest <= localize_stage_capacity();
+    mb.any_unstaged = longest > localize_stage_capacity();
     mb.n_tags = n_tags;
     mb.n_imgs = n_imgs;
-    mb.n_obs = n_obs;
+    mb.n_obs = img_start[n_imgs];
     mb.h_tag_qt = tag_qt;
     mb.h_tag_wh = tag_wh;
     mb.h_start = img_start;
@@ -107,21 +127,6 @@ int check_localize_options(const char* who, const vmm_ba_localize_options& o)
         || o.min_inlier_tags < 1 || !isfinite(o.huber_a) || !isfinite(o.score_cap_px) || !isfinite(o.inlier_px))
         return bad_argument(who, "bad localisation options");
     return VMM_BA_OK;
-}
-
-void fill_no_observations(int32_t n_imgs, double* cam_qt, double* cam_cov, vmm_ba_localize_result* res)
-{
-    for (int32_t i = 0; i < n_imgs; ++i) {
-        double* q = cam_qt + 7 * (int64_t)i;
-        q[0] = 1.0;
-        q[1] = q[2] = q[3] = q[4] = q[5] = q[6] = 0.0;
-        if (res) {
-            memset(&res[i], 0, sizeof(res[i]));
-            res[i].status = VMM_BA_LOC_NO_OBSERVATIONS;
-        }
-    }
-    if (cam_cov)
-        memset(cam_cov, 0, sizeof(double) * 36 * (size_t)n_imgs);
 }
 
 int select_device(const char* who, int device, bool (&done)[64], std::initializer_list<int (*)()> preload)
@@ -171,13 +176,7 @@ LocalizeArgs MapBatch::args(const double intr[4], const double dist[5], const vm
     a.corners = corners;
     a.quad_qt = quad_qt;
     a.quad_rms = quad_rms;
-    a.max_trials = o.refine_iterations;
-    a.robustify = o.robustify != 0;
-    a.passes = o.reclassify_passes;
-    a.min_inliers = o.min_inlier_tags;
-    a.huber_a = o.huber_a;
-    a.cap2 = o.score_cap_px * o.score_cap_px;
-    a.inlier2 = o.inlier_px * o.inlier_px;
+    set_refine_options(a, o, o.min_inlier_tags);
     a.cam_qt = cam;
     a.cam_cov = cov;
     a.obs_inlier = inl;

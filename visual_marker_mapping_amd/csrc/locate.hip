@@ -1,6 +1,7 @@
 // vmm_ba_locate_tags (include/vmm_ba.h): host side.  The checks on the cameras, the tags' observations and the options,
-// the answers that need no device, one Arena, the uploads, k_quad_pose -> k_camera_rigids -> k_locate_tags
-// (kernels_init.hip, kernels_locate.hip) and the copies back.
+// the answer that needs no device, and the known-cameras stage (KnownCameras, host.hpp) with its own four pieces behind
+// and k_quad_pose -> k_camera_rigids -> k_locate_tags (kernels_init.hip, kernels_locate.hip) between its uploads and
+// its copies back.
 #include <math.h>
 #include <string.h>
 
@@ -20,43 +21,20 @@ int check_tags(int32_t n_cams, int32_t n_tags, const double* tag_wh, const int64
 {
     if (!tag_wh)
         return bad_argument(who, "null tag_wh");
-    if (tag_start[0] != 0)
-        return bad_argument(who, "tag_start[0] is not 0");
-    any_staged = any_unstaged = false;
-    const int cap = locate_stage_capacity();
-    for (int32_t t = 0; t < n_tags; ++t) {
-        const int64_t m = tag_start[t + 1] - tag_start[t];
-        if (m < 0)
-            return bad_argument(who, "tag_start decreases");
-        if (m > (int64_t)1 << 28)
-            return bad_argument(who, "a tag has too many observations");
-        (m <= cap ? any_staged : any_unstaged) = true;
-    }
-    const int64_t n_obs = tag_start[n_tags];
-    if (n_obs > 0 && (!obs_cam || !obs_px))
-        return bad_argument(who, "null observations");
-    for (int64_t i = 0; i < n_obs; ++i)
-        if (obs_cam[i] < 0 || obs_cam[i] >= n_cams)
-            return bad_argument(who, "obs_cam outside [0, n_cams)");
-    for (int32_t t = 0; t < n_tags; ++t)
-        for (int64_t i = tag_start[t] + 1; i < tag_start[t + 1]; ++i)
-            if (obs_cam[i] <= obs_cam[i - 1])
-                return bad_argument(who, "obs_cam is not strictly increasing within a tag");
+    int64_t shortest, longest;
+    const int rc = check_list(who, { "tag_start", "a tag", "obs_cam", "n_cams", true }, n_tags, tag_start, obs_cam, obs_px, n_cams,
+                              shortest, longest);
+    if (rc != VMM_BA_OK)
+        return rc;
+    any_staged = shortest <= locate_stage_capacity();
+    any_unstaged = longest > locate_stage_capacity();
     for (int64_t i = 0; i < 2 * (int64_t)n_tags; ++i)
         if (!isfinite(tag_wh[i]))
             return bad_argument(who, "non-finite tag size");
-    for (int64_t i = 0; i < 8 * n_obs; ++i)
+    for (int64_t i = 0; i < 8 * tag_start[n_tags]; ++i)
         if (!isfinite(obs_px[i]))
             return bad_argument(who, "non-finite obs_px");
     return VMM_BA_OK;
-}
-
-// n_obs == 0: every tag reports NO_OBSERVATIONS, the identity pose and zero covariances
-void fill_no_tags(int32_t n_tags, double* tag_qt, double* tag_cov, double* tag_cov_cams, vmm_ba_localize_result* res)
-{
-    fill_no_observations(n_tags, tag_qt, tag_cov, res);
-    if (tag_cov_cams)
-        memset(tag_cov_cams, 0, sizeof(double) * 36 * (size_t)n_tags);
 }
 
 } // namespace
@@ -87,9 +65,11 @@ int vmm_ba_locate_tags(const double intr[4], const double dist[5], int32_t n_cam
         || (rc = check_camera_model(who, intr, dist)) != VMM_BA_OK || (rc = check_cameras(who, n_cams, cam_qt, cam_cov)) != VMM_BA_OK
         || (rc = check_localize_options(who, o)) != VMM_BA_OK)
         return rc;
-    const size_t nc = (size_t)n_cams, nt = (size_t)n_tags, no = (size_t)tag_start[n_tags];
-    if (no == 0) {
-        fill_no_tags(n_tags, tag_qt, tag_cov, tag_cov_cams, res);
+    // per camera R | t, per observation four corners, per tag a pose and 6 x 6 covariances
+    KnownCameras<vmm_ba_localize_result> kc { n_cams, n_tags, cam_qt, cam_cov, tag_start, obs_cam, obs_px, 12, 8, 7, 36 };
+    const size_t nt = (size_t)n_tags, no = kc.n_obs();
+    if (no == 0) {   // every tag reports NO_OBSERVATIONS, the identity pose and zero covariances
+        fill_without_device(n_tags, tag_start, 7, 36, VMM_BA_LOC_NO_OBSERVATIONS, tag_qt, tag_cov, tag_cov_cams, obs_inlier, res);
         return VMM_BA_OK;
     }
     static bool preloaded[64] = {};
@@ -99,77 +79,44 @@ int vmm_ba_locate_tags(const double intr[4], const double dist[5], int32_t n_cam
     for (int32_t t = 0; t < n_tags; ++t)
         for (int64_t i = tag_start[t]; i < tag_start[t + 1]; ++i)
             obs_tag[(size_t)i] = t;
-    double *d_qt = nullptr, *d_rigids = nullptr, *d_cam_cov = nullptr, *d_wh = nullptr, *d_px = nullptr, *d_quad_qt = nullptr,
-           *d_quad_rms = nullptr, *d_tag = nullptr, *d_cov = nullptr, *d_cov_cams = nullptr;
-    int64_t* d_start = nullptr;
-    int32_t *d_cam = nullptr, *d_obs_tag = nullptr;
-    uint8_t* d_inl = nullptr;
-    vmm_ba_localize_result* d_res = nullptr;
+    double *d_wh = nullptr, *d_quad_qt = nullptr, *d_quad_rms = nullptr;
+    int32_t* d_obs_tag = nullptr;
     Arena ar;
     if (ar.layout([&](Arena& a) {
-            d_qt = a.take<double>(7 * nc);
-            d_rigids = a.take<double>(12 * nc);
-            d_cam_cov = a.take<double>(cam_cov ? 36 * nc : 0);
+            kc.carve(a);
             d_wh = a.take<double>(2 * nt);
-            d_start = a.take<int64_t>(nt + 1);
-            d_cam = a.take<int32_t>(no);
             d_obs_tag = a.take<int32_t>(no);
-            d_px = a.take<double>(8 * no);
             d_quad_qt = a.take<double>(14 * no);
             d_quad_rms = a.take<double>(2 * no);
-            d_tag = a.take<double>(7 * nt);
-            d_cov = a.take<double>(36 * nt);
-            d_cov_cams = a.take<double>(36 * nt);
-            d_inl = a.take<uint8_t>(no);
-            d_res = a.take<vmm_ba_localize_result>(nt);
         }) != hipSuccess)
         return hip_failure(who, "hipMalloc: ", ar.err);
-    ar.copy(d_qt, cam_qt, 8 * 7 * nc, hipMemcpyHostToDevice);
-    if (cam_cov)
-        ar.copy(d_cam_cov, cam_cov, 8 * 36 * nc, hipMemcpyHostToDevice);
+    kc.upload(ar);
     ar.copy(d_wh, tag_wh, 8 * 2 * nt, hipMemcpyHostToDevice);
-    ar.copy(d_start, tag_start, 8 * (nt + 1), hipMemcpyHostToDevice);
-    ar.copy(d_cam, obs_cam, 4 * no, hipMemcpyHostToDevice);
     ar.copy(d_obs_tag, obs_tag.data(), 4 * no, hipMemcpyHostToDevice);
-    ar.copy(d_px, obs_px, 8 * 8 * no, hipMemcpyHostToDevice);
     if (ar.err == hipSuccess) {
         LocateArgs a;
         a.K = make_intrinsics(intr, dist);
         a.n_tags = n_tags;
-        a.rigids = d_rigids;
-        a.cam_cov = cam_cov ? d_cam_cov : nullptr;
+        a.rigids = kc.derived;
+        a.cam_cov = kc.cam_cov;
         a.tag_wh = d_wh;
-        a.tag_start = d_start;
-        a.obs_cam = d_cam;
-        a.obs_px = d_px;
+        a.tag_start = kc.start;
+        a.obs_cam = kc.obs_cam;
+        a.obs_px = kc.px;
         a.quad_qt = d_quad_qt;
         a.quad_rms = d_quad_rms;
-        a.max_trials = o.refine_iterations;
-        a.robustify = o.robustify != 0;
-        a.passes = o.reclassify_passes;
-        a.min_inliers = o.min_inlier_tags;
-        a.huber_a = o.huber_a;
-        a.cap2 = o.score_cap_px * o.score_cap_px;
-        a.inlier2 = o.inlier_px * o.inlier_px;
-        a.tag_qt = d_tag;
-        a.tag_cov = d_cov;
-        a.tag_cov_cams = d_cov_cams;
-        a.obs_inlier = d_inl;
-        a.res = d_res;
-        launch_quad_poses(nullptr, a.K, (int64_t)no, d_wh, d_px, d_quad_qt, d_quad_rms, d_obs_tag);
-        launch_camera_rigids(nullptr, n_cams, d_qt, d_rigids);
+        set_refine_options(a, o, o.min_inlier_tags);
+        a.tag_qt = kc.value;
+        a.tag_cov = kc.cov;
+        a.tag_cov_cams = kc.cov_cams;
+        a.obs_inlier = kc.inl;
+        a.res = kc.res;
+        launch_quad_poses(nullptr, a.K, (int64_t)no, d_wh, kc.px, d_quad_qt, d_quad_rms, d_obs_tag);
+        launch_camera_rigids(nullptr, n_cams, kc.cam_qt, kc.derived);
         launch_locate_tags(nullptr, a, any_staged, any_unstaged);
         ar.err = hipGetLastError();
     }
-    ar.copy(tag_qt, d_tag, 8 * 7 * nt, hipMemcpyDeviceToHost);
-    if (tag_cov)
-        ar.copy(tag_cov, d_cov, 8 * 36 * nt, hipMemcpyDeviceToHost);
-    if (tag_cov_cams)
-        ar.copy(tag_cov_cams, d_cov_cams, 8 * 36 * nt, hipMemcpyDeviceToHost);
-    if (obs_inlier)
-        ar.copy(obs_inlier, d_inl, no, hipMemcpyDeviceToHost);
-    if (res)
-        ar.copy(res, d_res, sizeof(vmm_ba_localize_result) * nt, hipMemcpyDeviceToHost);
+    kc.results(ar, tag_qt, tag_cov, tag_cov_cams, obs_inlier, res);
     if (ar.err != hipSuccess)
         return hip_failure(who, "", ar.err);
     return VMM_BA_OK;

@@ -549,6 +549,31 @@ def default_triangulate_options(**kw):
     return _options(_lib.TriangulateOptions, "vmm_ba_default_triangulate_options", kw, "triangulation")
 
 
+def _known_camera_arrays(cam_qt, cam_cov, start, obs_cam, obs, width, what, n_items=None):
+    """Known cameras and a list of items over them as vmm_ba_triangulate and vmm_ba_locate_tags take them: contiguous
+    arrays of the C types (obs: `width` numbers per observation; cam_cov may be None), refused when their lengths do
+    not fit together.  what: the names of the start array and of its item count, for the error text."""
+    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
+    start = np.ascontiguousarray(start, np.int64).reshape(-1)
+    obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
+    obs = np.ascontiguousarray(obs, np.float64).reshape(-1, width)
+    if len(obs_cam) != len(obs):
+        raise ValueError("observation arrays differ in length")
+    n = len(start) - 1 if n_items is None else n_items
+    if n < 0 or len(start) != n + 1 or start[-1] != len(obs_cam):
+        raise ValueError("%s must have %s + 1 entries and end at the number of observations" % what)
+    if cam_cov is not None:
+        cam_cov = np.ascontiguousarray(cam_cov, np.float64).reshape(-1, 6, 6)
+        if len(cam_cov) != len(cam_qt):
+            raise ValueError("cam_cov and cam_qt differ in length")
+    return cam_qt, cam_cov, start, obs_cam, obs
+
+
+def _flags_and_results(n_obs, n_items):
+    """The inlier flags (uint8, one per observation) and the result records (one per item) that an entry fills."""
+    return np.zeros(n_obs, np.uint8), _results(n_items)
+
+
 def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, device=0, **options):
     """Free points (anything that is not a tag) from the cameras of a finished map or of a localisation
     (vmm_ba_triangulate).  cam_qt (n_cams, 7) world->camera.  pt_start (n_pts + 1,): point p owns the observations
@@ -559,22 +584,12 @@ def triangulate(intr, dist, cam_qt, pt_start, obs_cam, obs_uv, cam_cov=None, dev
     without cam_cov), obs_inlier (n_obs,) bool, results: one dict per point with status, n_obs, n_inlier_obs, trials,
     rms_px, cost)."""
     intr, dist = _model_arrays(intr, dist)
-    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
-    pt_start = np.ascontiguousarray(pt_start, np.int64).reshape(-1)
-    obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
-    obs_uv = np.ascontiguousarray(obs_uv, np.float64).reshape(-1, 2)
-    if len(obs_cam) != len(obs_uv):
-        raise ValueError("observation arrays differ in length")
-    if len(pt_start) < 1 or pt_start[-1] != len(obs_cam):
-        raise ValueError("pt_start must have n_pts + 1 entries and end at the number of observations")
-    if cam_cov is not None:
-        cam_cov = np.ascontiguousarray(cam_cov, np.float64).reshape(-1, 6, 6)
-        if len(cam_cov) != len(cam_qt):
-            raise ValueError("cam_cov and cam_qt differ in length")
+    cam_qt, cam_cov, pt_start, obs_cam, obs_uv = _known_camera_arrays(cam_qt, cam_cov, pt_start, obs_cam, obs_uv, 2,
+                                                                      ("pt_start", "n_pts"))
     o = default_triangulate_options(**options)
     n_pts = len(pt_start) - 1
     xyz, cov, cov_cams = np.zeros((n_pts, 3)), np.zeros((n_pts, 3, 3)), np.zeros((n_pts, 3, 3))
-    inl, res = np.zeros(len(obs_cam), np.uint8), _results(n_pts)
+    inl, res = _flags_and_results(len(obs_cam), n_pts)
     _lib.check(_lib.lib().vmm_ba_triangulate(_ptr(intr), _ptr(dist), len(cam_qt), _ptr(cam_qt), _ptr(cam_cov), n_pts,
                                              _ptr(pt_start), _ptr(obs_cam), _ptr(obs_uv), C.byref(o), _ptr(xyz), _ptr(cov),
                                              _ptr(cov_cams), _ptr(inl), _ptr(res), device))
@@ -591,23 +606,13 @@ def locate_tags(intr, dist, cam_qt, tag_wh, tag_start, obs_cam, obs_px, cam_cov=
     from cam_cov, camera by camera without their correlations (zeros without cam_cov), obs_inlier (n_obs,) bool, results:
     one dict per tag as engine.localize gives per image)."""
     intr, dist = _model_arrays(intr, dist)
-    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
     tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
-    tag_start = np.ascontiguousarray(tag_start, np.int64).reshape(-1)
-    obs_cam = np.ascontiguousarray(obs_cam, np.int32).reshape(-1)
-    obs_px = np.ascontiguousarray(obs_px, np.float64).reshape(-1, 8)
-    if len(obs_cam) != len(obs_px):
-        raise ValueError("observation arrays differ in length")
-    if len(tag_start) != len(tag_wh) + 1 or tag_start[-1] != len(obs_cam):
-        raise ValueError("tag_start must have n_tags + 1 entries and end at the number of observations")
-    if cam_cov is not None:
-        cam_cov = np.ascontiguousarray(cam_cov, np.float64).reshape(-1, 6, 6)
-        if len(cam_cov) != len(cam_qt):
-            raise ValueError("cam_cov and cam_qt differ in length")
-    o = default_localize_options(**options)
     n_tags = len(tag_wh)
+    cam_qt, cam_cov, tag_start, obs_cam, obs_px = _known_camera_arrays(cam_qt, cam_cov, tag_start, obs_cam, obs_px, 8,
+                                                                       ("tag_start", "n_tags"), n_tags)
+    o = default_localize_options(**options)
     tag_qt, cov, cov_cams = np.zeros((n_tags, 7)), np.zeros((n_tags, 6, 6)), np.zeros((n_tags, 6, 6))
-    inl, res = np.zeros(len(obs_cam), np.uint8), _results(n_tags)
+    inl, res = _flags_and_results(len(obs_cam), n_tags)
     _lib.check(_lib.lib().vmm_ba_locate_tags(_ptr(intr), _ptr(dist), len(cam_qt), _ptr(cam_qt), _ptr(cam_cov), n_tags,
                                              _ptr(tag_wh), _ptr(tag_start), _ptr(obs_cam), _ptr(obs_px), C.byref(o),
                                              _ptr(tag_qt), _ptr(cov), _ptr(cov_cams), _ptr(inl), _ptr(res), device))

@@ -613,29 +613,51 @@ class TagReconstructor:
             self.camModel = self._with_model(intr, dist)
         return report
 
+    def _known_cameras(self, cameras, cameraCovariances):
+        """The cameras that triangulatePoints and locateTags work from (default: reconstructedCameras) in image id order:
+        (cam_ids, dense {imageId: index}, cam_qt (n, 7), cam_cov (n, 6, 6) or None; a camera without an entry in
+        cameraCovariances keeps a zero block)."""
+        cams = self.reconstructedCameras if cameras is None else {int(k): v for k, v in dict(cameras).items()}
+        cam_ids = sorted(cams)
+        cam_qt = np.array([np.concatenate([cams[i].q, cams[i].t]) for i in cam_ids], np.float64).reshape(-1, 7)
+        cam_cov = None
+        if cameraCovariances is not None:
+            cam_cov = np.zeros((len(cam_ids), 6, 6))
+            for k, i in enumerate(cam_ids):
+                if i in cameraCovariances:
+                    cam_cov[k] = np.asarray(cameraCovariances[i], np.float64).reshape(6, 6)
+        return cam_ids, {i: k for k, i in enumerate(cam_ids)}, cam_qt, cam_cov
+
     @staticmethod
-    def _pack_tracks(tracks, camera_ids):
-        """The flat arrays engine.triangulate takes from {pointId: [(imageId, (u, v)), ...]}: every track sorted by image
-        id, observations of images outside `camera_ids` (ascending; position = the camera's index) dropped.  Returns
-        (point_ids, pt_start, obs_cam, obs_uv, obs_image, n_dropped); an image that appears twice in a track is refused."""
-        dense = {int(c): k for k, c in enumerate(camera_ids)}
-        point_ids = list(tracks)
-        pt_start, obs_cam, obs_uv, obs_image, dropped = [0], [], [], [], 0
-        for pid in point_ids:
-            kept = sorted(((int(i), uv) for i, uv in tracks[pid]), key=lambda e: e[0])
+    def _pack_items(items, dense, what):
+        """An item list over known cameras from [(item id, [(imageId, payload), ...]), ...]: every item's observations
+        sorted by image id, those of images outside `dense` dropped.  Returns (start, obs_cam, obs_image, payloads,
+        n_dropped); an image that appears twice in an item is refused ("<what> <id> is observed twice in one image")."""
+        start, obs_cam, obs_image, payloads, dropped = [0], [], [], [], 0
+        for item, observations in items:
+            kept = sorted(((int(i), p) for i, p in observations), key=lambda e: e[0])
             seen = [i for i, _ in kept]
             if len(set(seen)) != len(seen):
-                raise ValueError("point %r is observed twice in one image" % (pid,))
-            for i, uv in kept:
+                raise ValueError("%s %r is observed twice in one image" % (what, item))
+            for i, p in kept:
                 if i not in dense:
                     dropped += 1
                     continue
                 obs_cam.append(dense[i])
                 obs_image.append(i)
-                obs_uv.append(np.asarray(uv, np.float64).reshape(2))
-            pt_start.append(len(obs_cam))
-        obs_uv = np.stack(obs_uv) if obs_uv else np.zeros((0, 2))
-        return (point_ids, np.array(pt_start, np.int64), np.array(obs_cam, np.int32), obs_uv, obs_image, dropped)
+                payloads.append(p)
+            start.append(len(obs_cam))
+        return np.array(start, np.int64), np.array(obs_cam, np.int32), obs_image, payloads, dropped
+
+    @staticmethod
+    def _pack_tracks(tracks, camera_ids):
+        """The flat arrays engine.triangulate takes from {pointId: [(imageId, (u, v)), ...]} (_pack_items; camera_ids
+        ascending, position = the camera's index).  Returns (point_ids, pt_start, obs_cam, obs_uv, obs_image, n_dropped)."""
+        point_ids = list(tracks)
+        pt_start, obs_cam, obs_image, uvs, dropped = TagReconstructor._pack_items(
+            [(p, tracks[p]) for p in point_ids], {int(c): k for k, c in enumerate(camera_ids)}, "point")
+        obs_uv = np.stack([np.asarray(uv, np.float64).reshape(2) for uv in uvs]) if uvs else np.zeros((0, 2))
+        return point_ids, pt_start, obs_cam, obs_uv, obs_image, dropped
 
     def triangulatePoints(self, tracks, cameras=None, cameraCovariances=None, **options):
         """Free points (anything that is not a tag) in the map's frame from pixels in images with a known pose
@@ -647,17 +669,9 @@ class TagReconstructor:
         them).  Returns {pointId: {"point" (3,), "covariance" (3, 3) from the pixel noise, "covariance_cameras" (3, 3)
         propagated from cameraCovariances camera by camera, "status", "n_obs", "n_inlier_obs", "rms_px",
         "inliers": {imageId: bool}}}.  The reference has no such member."""
-        cams = self.reconstructedCameras if cameras is None else {int(k): v for k, v in dict(cameras).items()}
-        cam_ids = sorted(cams)
+        cam_ids, _, cam_qt, cam_cov = self._known_cameras(cameras, cameraCovariances)
         point_ids, pt_start, obs_cam, obs_uv, obs_image, dropped = self._pack_tracks(tracks, cam_ids)
         self.lastTriangulationDropped = dropped
-        cam_qt = np.array([np.concatenate([cams[i].q, cams[i].t]) for i in cam_ids], np.float64).reshape(-1, 7)
-        cam_cov = None
-        if cameraCovariances is not None:
-            cam_cov = np.zeros((len(cam_ids), 6, 6))
-            for k, i in enumerate(cam_ids):
-                if i in cameraCovariances:
-                    cam_cov[k] = np.asarray(cameraCovariances[i], np.float64).reshape(6, 6)
         xyz, cov, cov_cams, inl, res = _engine.triangulate(*self._model_args(), cam_qt, pt_start, obs_cam, obs_uv,
                                                            cam_cov=cam_cov, device=self.device, **options)
         out = {}
@@ -712,36 +726,18 @@ class TagReconstructor:
         (`covariance_cameras`) and the inlier flag of each used observation (index into detectionResult.tagObservations).
         The reference has no such member."""
         det = self.detectionResults_ if detectionResult is None else detectionResult
-        cams = self.reconstructedCameras if cameras is None else {int(k): v for k, v in dict(cameras).items()}
-        cam_ids = sorted(cams)
-        dense = {i: k for k, i in enumerate(cam_ids)}
+        _, dense, cam_qt, cam_cov = self._known_cameras(cameras, cameraCovariances)
         known = {int(t.tagId): (t.tagType, t.width, t.height) for t in det.tags}
         known.update({int(i): (t.tagType, t.tagWidth, t.tagHeight) for i, t in self.reconstructedTags.items()})
         ids = sorted(known) if tagIds is None else [int(t) for t in tagIds]
         per_tag = {t: [] for t in ids}
         for k, ob in enumerate(det.tagObservations):
             if ob.tagId in per_tag and ob.imageId in dense:
-                per_tag[ob.tagId].append((dense[ob.imageId], k))
-        order = []
-        for t in ids:
-            per_tag[t].sort()
-            seen = [c for c, _ in per_tag[t]]
-            if len(set(seen)) != len(seen):
-                raise ValueError("tag %r is observed twice in one image" % (t,))
-            order.extend(k for _, k in per_tag[t])
-        tag_start = np.zeros(len(ids) + 1, np.int64)
-        tag_start[1:] = np.cumsum([len(per_tag[t]) for t in ids])
-        obs_cam = np.array([dense[det.tagObservations[k].imageId] for k in order], np.int32)
+                per_tag[ob.tagId].append((ob.imageId, k))
+        tag_start, obs_cam, _, order, _ = self._pack_items([(t, per_tag[t]) for t in ids], dense, "tag")
         obs_px = (np.stack([np.asarray(det.tagObservations[k].corners, np.float64).reshape(8) for k in order])
                   if order else np.zeros((0, 8)))
-        cam_qt = np.array([np.concatenate([cams[i].q, cams[i].t]) for i in cam_ids], np.float64).reshape(-1, 7)
         tag_wh = np.array([known[t][1:] for t in ids], np.float64).reshape(-1, 2)
-        cam_cov = None
-        if cameraCovariances is not None:
-            cam_cov = np.zeros((len(cam_ids), 6, 6))
-            for k, i in enumerate(cam_ids):
-                if i in cameraCovariances:
-                    cam_cov[k] = np.asarray(cameraCovariances[i], np.float64).reshape(6, 6)
         tag_qt, cov, cov_cams, inl, res = _engine.locate_tags(*self._model_args(), cam_qt, tag_wh, tag_start, obs_cam, obs_px,
                                                               cam_cov=cam_cov, device=self.device, **options)
         tags, report = {}, {}

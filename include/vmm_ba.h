@@ -641,6 +641,79 @@ int vmm_ba_locate_tags(const double intr[4], const double dist[5],
                        vmm_ba_localize_result* res, /* [n_tags] or NULL */
                        int device);
 
+/* ABI 6, additive.  Predicts how well a camera would be localised against a finished map at poses that have no image
+ * behind them: which tags it would see, and the covariance vmm_ba_localize would report there.  Stateless like
+ * vmm_ba_localize, every pose independent of the others in the batch.
+ *   visibility  Tag t counts as visible from pose p when all of the following hold.
+ *               - All four corners have z_cam > min_depth.
+ *               - At all four corners the radial map is still rising at that radius: with r^2 the squared normalised
+ *                 radius, 1 + 3 k1 r^2 + 5 k2 r^4 + 7 k3 r^6 > 0.  Without this, a corner far outside the field of view
+ *                 of a lens with k1 < 0 folds back into the image.  (A model that folds and unfolds again inside that
+ *                 radius is not detected.)
+ *               - All four predicted pixels (u, v) satisfy margin_px <= u <= width - margin_px and
+ *                 margin_px <= v <= height - margin_px.  The pixel is that of the functor the bundle adjustment
+ *                 minimises, not CameraModel::projectPoint's aliased form.
+ *               - The tag faces the camera.  Let n = R_tag e_z.  Corners run LL, LR, UR, UL, counter-clockwise seen from
+ *                 +z, so +z is the printed side.  Let c be the tag's centre and C = -R^T t the camera centre.  Then
+ *                 n.(C - c) >= cos(max_view_angle) |C - c|.
+ *               - The shortest of the four projected sides is at least min_side_px.
+ *               OCCLUSION IS NOT MODELLED: a tag hidden by a wall counts as visible.
+ *   covariances The sums run over the visible tags, in the tangent every pose of the library moves in (translation,
+ *               then the half-angle rotation of vmm_ba_pose_plus).
+ *               cov_px = sigma_px^2 H^-1, H = sum Jc^T Jc over the 4 corners of every visible tag, Jc the 2x6 camera
+ *               Jacobian of the residual the bundle adjustment minimises.  No loss is applied: the expected residual
+ *               is zero and the Huber weight is 1 there.  Row-major 6x6, symmetric to the last bit.
+ *               cov_map = H^-1 M H^-1, M = sum_t G_t S_t G_t^T, G_t = sum over tag t's corners of Jc^T Jt (6x6, Jt the 2x6
+ *               Jacobian over the tag's tangent) and S_t = tag_cov[36 t ..], the tag's 6x6 marginal in the order
+ *               vmm_ba_covariance_blocks uses: the first-order response of the minimiser,
+ *               dx = -H^-1 sum_t G_t dy_t, with independent tags.  Like vmm_ba_triangulate's camera part, it ignores the
+ *               correlations between tags.  Neighbouring tags far from the origin move together, so for them this errs
+ *               towards too small.  Zeros when tag_cov is NULL.
+ *               sigma_pos_m and sigma_rot_rad come from cov_px + cov_map: the rotation in radians is twice the
+ *               tangent's rotation part, and the camera centre C = -R^T t answers a tangent step (dt, dr) with
+ *               dC = -R^T (dt + 2 [t]x dr).
+ *   statuses    NO_VISIBLE_TAG (n_visible == 0), TOO_FEW_TAGS (n_visible < min_tags) and SINGULAR (H is not positive
+ *               definite, or a result would not be finite): zero covariances and zero sigmas; n_visible and the visible
+ *               bytes are still those of the rules above.
+ * The predicted covariance is local: with one visible tag it says nothing of the two-fold planar ambiguity of a single
+ * tag's pose; min_tags is the caller's lever.
+ * No output is ever NaN; a pose gives the same bits alone, in any batch, at any position and from run to run.
+ * VMM_BA_ERR_ARGUMENT (before any device call): null intr, dist, cam_qt or o; negative sizes; a null map with
+ * n_tags > 0; a non-finite camera model, map pose, size, pose or tag_cov; a zero quaternion; image_width or
+ * image_height <= 0; sigma_px not finite or <= 0; a negative or non-finite margin_px, min_depth or min_side_px;
+ * max_view_angle_deg outside (0, 90]; min_tags < 1.  n_poses == 0 returns VMM_BA_OK without a device call; so does
+ * n_tags == 0, where every pose is NO_VISIBLE_TAG. */
+enum { VMM_BA_PRED_OK = 0, VMM_BA_PRED_NO_VISIBLE_TAG = 1, VMM_BA_PRED_TOO_FEW_TAGS = 2, VMM_BA_PRED_SINGULAR = 3 };
+typedef struct vmm_ba_predict_options {
+    int32_t image_width, image_height;  /* no default: must be > 0 (CameraModel's horizontal/verticalResolution) */
+    double  sigma_px;                   /* 1.0: standard deviation of one corner coordinate */
+    double  margin_px;                  /* 0.0: a corner must lie this far inside the image */
+    double  min_depth;                  /* 1e-3: a corner must have z_cam > min_depth */
+    double  max_view_angle_deg;         /* 70: angle between the tag's normal and the line tag centre -> camera centre */
+    double  min_side_px;                /* 10: shortest of the four projected sides */
+    int32_t min_tags;                   /* 1: fewer visible tags -> TOO_FEW_TAGS */
+    int32_t reserved;
+} vmm_ba_predict_options;
+
+typedef struct vmm_ba_predict_result {  /* one per pose */
+    int32_t status;                     /* VMM_BA_PRED_* */
+    int32_t n_visible;
+    double  sigma_pos_m;                /* sqrt(trace of the camera CENTRE's 3x3 covariance in the world), cov_px + cov_map */
+    double  sigma_rot_rad;              /* sqrt(trace of the rotation's 3x3 covariance in radians), cov_px + cov_map */
+} vmm_ba_predict_result;
+
+void vmm_ba_default_predict_options(vmm_ba_predict_options* o);
+int vmm_ba_predict_localization(const double intr[4], const double dist[5],
+                                int32_t n_tags, const double* tag_qt, const double* tag_wh,   /* the map, as vmm_ba_localize */
+                                const double* tag_cov,       /* [36*n_tags] tangent order as vmm_ba_covariance_blocks, or NULL */
+                                int32_t n_poses, const double* cam_qt,   /* [7*n_poses] world->camera */
+                                const vmm_ba_predict_options* o,
+                                double* cov_px,              /* [36*n_poses] or NULL */
+                                double* cov_map,             /* [36*n_poses] or NULL */
+                                uint8_t* visible,            /* [n_poses*n_tags] or NULL */
+                                vmm_ba_predict_result* res,  /* [n_poses] or NULL */
+                                int device);
+
 /* ABI 6, additive.  Calibrates a camera against a finished map: the nine numbers of the camera model
  * (fx, fy, cx, cy, k1, k2, p1, p2, k3) and one pose per image, the map held fixed.  Stateless like vmm_ba_localize.
  *   objective   1/2 sum rho(|r_corner|^2) over the inlier observations of the images that take part, with the residual

@@ -1,0 +1,243 @@
+"""Scenes and the host model of the localisation-accuracy prediction (vmm_ba_predict_localization).  No GPU, and nothing
+of the code under test: the visibility rules are written here from include/vmm_ba.h's words in numpy, H, G_t and the
+sandwich come from oracle.obs_eval's Jacobians, the inverses from cov_cases.refined_inverse.
+
+Scenes
+  edges   one camera (k1 = -0.3, 640 x 480) at the world's origin and nine hand-placed tags; EDGE_REASONS says which rule
+          rejects each: tags 1, 8 and 9 pass (8 just inside every limit, 9 is the second tag of the min_tags cases), tags 2
+          to 7 are rejected by exactly one rule each (depth, image, facing twice, side, monotone: five rules)
+  lanes   tags on a wall facing the poses, n_tags in LANE_TAGS x n_poses in LANE_POSES: lane striding beyond one round, a
+          partial last round, a partial last workgroup
+  scene   synthetic.make_scene at its smallest config; its own cameras plus the same cameras displaced by 0.3 m and 10 deg
+"""
+import numpy as np
+
+import cov_cases as cc
+import yardstick as ys
+
+OPTIONS = dict(sigma_px=1.0, margin_px=0.0, min_depth=1e-3, max_view_angle_deg=70.0, min_side_px=10.0, min_tags=1)
+RULES = ("facing", "depth", "monotone", "image", "side")
+# how far a deciding quantity must stay from its threshold: relative to the threshold for the depth, absolute on the cosine
+# (stricter than relative: the threshold is below 1) and on the monotone polynomial (its terms are of order 1), absolute
+# in pixels for the image and the sides
+MARGIN = dict(facing=1e-6, depth=1e-6, monotone=1e-6, image=1e-6, side=1e-6)
+LANE_TAGS, LANE_POSES = (1, 63, 64, 65, 130), (1, 3, 4, 5)
+
+
+# ---- poses ------------------------------------------------------------------------------------------------------------
+
+def quat_mul(a, b):
+    w1, x1, y1, z1 = a
+    w2, x2, y2, z2 = b
+    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+
+
+def axis_angle(axis, deg):
+    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    h = np.radians(deg) / 2
+    return np.concatenate([[np.cos(h)], np.sin(h) * axis])
+
+
+def quat_from_rotation(R):
+    """The unit quaternion (w >= 0) of a rotation matrix, through its largest component."""
+    K = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2],
+                  R[2, 2] - R[0, 0] - R[1, 1]])
+    i = int(np.argmax(K))
+    s = 2.0 * np.sqrt(1.0 + K[i])
+    if i == 0:
+        q = np.array([0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s])
+    elif i == 1:
+        q = np.array([(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s])
+    elif i == 2:
+        q = np.array([(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s])
+    else:
+        q = np.array([(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s])
+    q /= np.linalg.norm(q)
+    return q if q[0] >= 0 else -q
+
+
+def tag_towards(centre, eye, tilt_deg=0.0, spin_deg=0.0):
+    """A tag pose (7,) at `centre` whose normal makes tilt_deg with the line centre -> eye, spun by spin_deg in its own
+    plane.  The local x axis is the tilt axis, perpendicular to that line."""
+    centre, eye = np.asarray(centre, np.float64), np.asarray(eye, np.float64)
+    d = (eye - centre) / np.linalg.norm(eye - centre)
+    a = np.cross(d, [0.0, 1.0, 0.0])
+    a /= np.linalg.norm(a)
+    n = ys.rotation(axis_angle(a, tilt_deg)) @ d
+    R = np.stack([a, np.cross(n, a), n], axis=1)
+    q = quat_mul(quat_from_rotation(R), axis_angle([0, 0, 1], spin_deg))
+    return np.concatenate([q, centre])
+
+
+def camera_centre(cam_qt):
+    return -ys.rotation(cam_qt).T @ cam_qt[4:]
+
+
+def displaced(cam_qt, shift, axis, deg):
+    """The world->camera pose whose centre is moved by `shift` in the world and whose frame is turned by deg about `axis`
+    (camera frame)."""
+    q = quat_mul(axis_angle(axis, deg), cam_qt[:4] / np.linalg.norm(cam_qt[:4]))
+    return np.concatenate([q, -ys.rotation(q) @ (camera_centre(cam_qt) + shift)])
+
+
+# ---- the visibility rules, from the header's words ---------------------------------------------------------------------
+
+def world_corners(tag_qt, wh):
+    """(4, 3): LL, LR, UR, UL."""
+    R = ys.rotation(tag_qt)
+    return np.array([R @ [sx * wh[0] / 2, sy * wh[1] / 2, 0.0] + tag_qt[4:] for sx, sy in ((-1, -1), (1, -1), (1, 1), (-1, 1))])
+
+
+def functor_pixel(intr, dist, pc):
+    """The pixel of the functor the bundle adjustment minimises, and r^2, of a point in the camera frame."""
+    k1, k2, p1, p2, k3 = dist
+    x, y = pc[0] / pc[2], pc[1] / pc[2]
+    r2 = x * x + y * y
+    rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    xd = x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+    yd = y * rad + 2 * p2 * x * y + p1 * (r2 + 2 * y * y)
+    return np.array([intr[0] * xd + intr[2], intr[1] * yd + intr[3]]), r2
+
+
+def slacks(intr, dist, size, opt, tag_qt, wh, cam_qt):
+    """{rule: the signed distances of its quantities from their thresholds (>= 0: the rule holds)}.  The rules behind
+    the depth are evaluated only where every corner is in front of the camera: elsewhere their quantities mean nothing."""
+    R, t = ys.rotation(cam_qt), np.asarray(cam_qt[4:], np.float64)
+    d = camera_centre(cam_qt) - tag_qt[4:]
+    n = ys.rotation(tag_qt)[:, 2]
+    out = {"facing": np.array([n @ d / np.linalg.norm(d) - np.cos(np.radians(opt["max_view_angle_deg"]))])}
+    pc = world_corners(tag_qt, wh) @ R.T + t
+    out["depth"] = (pc[:, 2] - opt["min_depth"]) / (opt["min_depth"] if opt["min_depth"] > 0 else 1.0)
+    if (out["depth"] <= 0).any():
+        return out
+    uv, r2 = zip(*(functor_pixel(intr, dist, p) for p in pc))
+    uv, r2 = np.array(uv), np.array(r2)
+    out["monotone"] = 1 + 3 * dist[0] * r2 + 5 * dist[1] * r2 ** 2 + 7 * dist[4] * r2 ** 3
+    m = opt["margin_px"]
+    out["image"] = np.concatenate([uv[:, 0] - m, size[0] - m - uv[:, 0], uv[:, 1] - m, size[1] - m - uv[:, 1]])
+    out["side"] = np.linalg.norm(np.roll(uv, -1, axis=0) - uv, axis=1) - opt["min_side_px"]
+    return out
+
+
+def reasons(sl):
+    """The rules that reject the tag, in RULES order."""
+    return [r for r in RULES if r in sl and ((sl[r] <= 0).any() if r in ("depth", "monotone") else (sl[r] < 0).any())]
+
+
+def rests_on_rounding(sl):
+    """Whether the flag could turn with the rounding: a visible tag with a quantity nearer than MARGIN to its threshold, or
+    a rejected one none of whose failing rules fails by MARGIN."""
+    why = reasons(sl)
+    if not why:
+        return any((sl[r] < MARGIN[r]).any() for r in sl)
+    return not any(sl[r].min() <= -MARGIN[r] for r in why)
+
+
+def host_visible(case, opt=None):
+    """(n_poses, n_tags) bool, and the slacks per (pose, tag)."""
+    opt = dict(OPTIONS, **(opt or {}))
+    sl = [[slacks(case["intr"], case["dist"], case["size"], opt, tq, wh, cam) for tq, wh in zip(case["tag_qt"], case["tag_wh"])]
+          for cam in case["cam_qt"]]
+    return np.array([[not reasons(s) for s in row] for row in sl], bool).reshape(len(case["cam_qt"]), len(case["tag_qt"])), sl
+
+
+# ---- covariances ---------------------------------------------------------------------------------------------------------
+
+def centre_jacobian(cam_qt):
+    """dC / d(dt, dr) (3 x 6) of the camera centre C = -R^T t over the pose's tangent: -R^T [I | 2 [t]x]."""
+    R, t = ys.rotation(cam_qt), cam_qt[4:]
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    return -R.T @ np.hstack([np.eye(3), 2 * tx])
+
+
+RADIANS = 2.0   # the rotation in radians is twice the tangent's rotation part
+
+
+def host_sigmas(cam_qt, cov):
+    J = centre_jacobian(cam_qt)
+    return float(np.sqrt(np.trace(J @ cov @ J.T))), float(np.sqrt(RADIANS ** 2 * np.trace(cov[3:, 3:])))
+
+
+def host_pose(O, case, p, vis, tag_cov=None, opt=None):
+    """(cov_px, cov_map, sigma_pos_m, sigma_rot_rad, H) of pose p over the tags flagged in vis (n_tags,)."""
+    opt = dict(OPTIONS, **(opt or {}))
+    H, M = np.zeros((6, 6)), np.zeros((6, 6))
+    for t in np.flatnonzero(vis):
+        _, Jc, Jt = O.obs_eval(case["intr"], case["dist"], case["cam_qt"][p], case["tag_qt"][t], case["tag_wh"][t], np.zeros(8))
+        H += Jc.T @ Jc
+        if tag_cov is not None:
+            G = Jc.T @ Jt
+            M += G @ tag_cov[t] @ G.T
+    Hi = cc.refined_inverse(H)[0]
+    cov_px = (opt["sigma_px"] ** 2 * Hi).astype(np.float64)
+    cov_map = (Hi @ M.astype(cc.LD) @ Hi).astype(np.float64)
+    return (cov_px, cov_map) + host_sigmas(case["cam_qt"][p], cov_px + cov_map) + (H,)
+
+
+def projected(O, case, p, t):
+    """The noise-free corner pixels (8,) of tag t from pose p, with the host functor."""
+    return O.obs_eval(case["intr"], case["dist"], case["cam_qt"][p], case["tag_qt"][t], case["tag_wh"][t], np.zeros(8), jac=False)
+
+
+def random_tag_cov(n_tags, fixed=0, seed=20261020):
+    """Seeded SPD 6 x 6 blocks of the size a map's tag covariances have (millimetres, milliradians), zeros for `fixed`."""
+    rng = np.random.default_rng(seed)
+    A = rng.standard_normal((n_tags, 6, 6)) * np.array([2e-3, 2e-3, 2e-3, 1e-3, 1e-3, 1e-3])[None, :, None]
+    S = A @ np.swapaxes(A, 1, 2) + 1e-8 * np.eye(6)
+    S[fixed] = 0.0
+    return S
+
+
+# ---- scenes -------------------------------------------------------------------------------------------------------------
+
+EDGE_REASONS = ([], ["depth"], ["image"], ["facing"], ["facing"], ["side"], ["monotone"], [], [])
+
+
+def edges():
+    eye = np.zeros(3)
+    tags = [
+        (tag_towards([0.0, 0.0, 2.0], eye), (0.2, 0.2)),                    # 1 fully visible
+        (tag_towards([0.3, 0.0, -2.0], eye), (0.2, 0.2)),                   # 2 behind the camera, facing it
+        (tag_towards([1.46, 0.0, 2.0], [1.46, 0.0, 0.0], spin_deg=45.0), (0.2, 0.2)),   # 3 a diamond, its right corner outside
+        (tag_towards([-0.5, 0.3, 2.0], [-0.5, 0.3, 4.0]), (0.2, 0.2)),      # 4 facing away
+        (tag_towards([0.4, -0.3, 2.5], eye, tilt_deg=75.0), (0.4, 0.4)),    # 5 at 75 degrees, the limit at 70
+        (tag_towards([0.2, 0.35, 2.0], eye), (0.024, 0.2)),                 # 6 six pixels wide, the limit at 10
+        (tag_towards([3.2, 0.0, 2.0], eye, spin_deg=45.0), (0.3, 0.3)),     # 7 folds back into the image
+        (tag_towards([1.6, -0.6, 2.0], eye, tilt_deg=69.0), (0.09, 0.3)),   # 8 just inside the angle, the image and the side
+        (tag_towards([-0.4, -0.2, 1.5], eye, tilt_deg=20.0), (0.2, 0.2)),   # 9 fully visible
+    ]
+    return dict(intr=np.array([500.0, 500.0, 320.0, 240.0]), dist=np.array([-0.3, 0.0, 0.0, 0.0, 0.0]), size=(640, 480),
+                tag_qt=np.array([t for t, _ in tags]), tag_wh=np.array([wh for _, wh in tags]),
+                cam_qt=np.array([[1.0, 0, 0, 0, 0, 0, 0]]))
+
+
+def lanes(n_tags, n_poses):
+    """n_tags tags of 0.15 m on the wall z = 4, 13 to a row 0.3 m apart, facing the poses; pose p stands further to the
+    right, up and back and is turned a little more than pose p - 1, so that tags leave its image."""
+    tag_qt = np.array([tag_towards([0.3 * (k % 13) - 1.8, 0.3 * (k // 13) - 1.35, 4.0], [0.3 * (k % 13) - 1.8, 0.3 * (k // 13) - 1.35, 0.0],
+                                   spin_deg=7.0 * k) for k in range(n_tags)])
+    base = np.array([1.0, 0, 0, 0, 0, 0, 0])
+    cam_qt = np.array([displaced(base, np.array([0.4 * p, -0.2 * p, -0.1 * p]), [0.3, -1.0, 0.2], 4.0 * p) for p in range(n_poses)])
+    return dict(intr=np.array([500.0, 505.0, 322.0, 238.0]), dist=np.array([-0.05, 0.01, 1e-3, -5e-4, 0.0]), size=(640, 480),
+                tag_qt=tag_qt, tag_wh=np.full((n_tags, 2), 0.15), cam_qt=cam_qt)
+
+
+def scene():
+    """make_scene(1): 20 cameras, 10 tags, a 6000 x 4000 image; poses = its cameras, then the same cameras displaced."""
+    from visual_marker_mapping_amd.synthetic import make_scene
+    s = make_scene(1)
+    rng = np.random.default_rng(11)
+    moved = []
+    for cam in s.cam_gt:
+        shift = rng.standard_normal(3)
+        moved.append(displaced(cam, 0.3 * shift / np.linalg.norm(shift), rng.standard_normal(3), 10.0))
+    return dict(intr=s.intr, dist=s.dist, size=(6000, 4000), tag_qt=s.tag_gt, tag_wh=s.tag_wh,
+                cam_qt=np.concatenate([s.cam_gt, np.array(moved)]), fixed_tag=s.fixed_tag)
+
+
+def all_cases():
+    """(name, case) for every case the GPU test compares flags on."""
+    out = [("edges", edges())]
+    out += [("lanes_%dx%d" % (nt, np_), lanes(nt, np_)) for nt in LANE_TAGS for np_ in LANE_POSES]
+    return out + [("scene", scene())]

@@ -26,6 +26,9 @@ TRI_STATUS_NAMES = ("ok", "too_few_views", "no_candidate", "too_few_inliers", "s
 # VMM_BA_CAL_*: status of vmm_ba_calibrate
 CAL_OK, CAL_NO_IMAGES, CAL_SINGULAR, CAL_NO_CONVERGENCE = 0, 1, 2, 3
 CAL_STATUS_NAMES = ("ok", "no_images", "singular", "no_convergence")
+# VMM_BA_PRED_*: status of one pose of vmm_ba_predict_localization
+PRED_OK, PRED_NO_VISIBLE_TAG, PRED_TOO_FEW_TAGS, PRED_SINGULAR = 0, 1, 2, 3
+PRED_STATUS_NAMES = ("ok", "no_visible_tag", "too_few_tags", "singular")
 
 
 class Problem(C.Structure):
@@ -114,6 +117,16 @@ class TriangulateResult(C.Structure):
                 ("rms_px", C.c_double), ("cost", C.c_double)]
 
 
+class PredictOptions(C.Structure):
+    _fields_ = [("image_width", C.c_int32), ("image_height", C.c_int32), ("sigma_px", C.c_double), ("margin_px", C.c_double),
+                ("min_depth", C.c_double), ("max_view_angle_deg", C.c_double), ("min_side_px", C.c_double),
+                ("min_tags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PredictResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_visible", C.c_int32), ("sigma_pos_m", C.c_double), ("sigma_rot_rad", C.c_double)]
+
+
 class CalibrateOptions(C.Structure):
     _fields_ = [("loc", LocalizeOptions), ("max_trials", C.c_int32), ("refine_mask", C.c_int32),
                 ("robustify", C.c_int32), ("reclassify_passes", C.c_int32), ("min_inlier_tags", C.c_int32),
@@ -193,6 +206,8 @@ SIGNATURES = {
     "vmm_ba_default_triangulate_options": (None, [_P(TriangulateOptions)]),
     "vmm_ba_triangulate": (_i, [_a, _a, _i32, _a, _a] + _BATCH + [_P(TriangulateOptions), _a, _a, _a, _a, _a, _i]),
     "vmm_ba_locate_tags": (_i, [_a, _a, _i32, _a, _a, _i32, _a, _a, _a, _a, _P(LocalizeOptions), _a, _a, _a, _a, _a, _i]),
+    "vmm_ba_default_predict_options": (None, [_P(PredictOptions)]),
+    "vmm_ba_predict_localization": (_i, [_a, _a] + _MAP + [_a, _i32, _a, _P(PredictOptions), _a, _a, _a, _a, _i]),
     "vmm_ba_default_calibrate_options": (None, [_P(CalibrateOptions)]),
     "vmm_ba_calibrate": (_i, [_a, _a] + _MAP + _BATCH + [_P(CalibrateOptions), _a, _a, _a, _a, _a, _a, _a,
                               _P(CalibrateReport), _i]),
@@ -215,7 +230,8 @@ EXPORTS = list(SIGNATURES)   # every symbol include/vmm_ba.h declares
 # commit's build) still loads, and calling the missing entry raises AttributeError.
 OPTIONAL = {"vmm_ba_covariance_blocks", "vmm_ba_rig_localize", "vmm_ba_default_rig_calibrate_options", "vmm_ba_rig_calibrate",
             "vmm_ba_default_calibrate_options", "vmm_ba_calibrate", "vmm_ba_default_triangulate_options",
-            "vmm_ba_triangulate", "vmm_ba_locate_tags", "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
+            "vmm_ba_triangulate", "vmm_ba_locate_tags", "vmm_ba_default_predict_options", "vmm_ba_predict_localization",
+            "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
             "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"}
 
 _LIB = None

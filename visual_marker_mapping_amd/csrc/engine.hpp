@@ -557,6 +557,26 @@ void launch_camera_rigids(hipStream_t st, int n_cams, const double* cam_qt, doub
 void launch_locate_tags(hipStream_t st, const LocateArgs& a, bool any_staged, bool any_unstaged);
 int locate_stage_capacity();   // observations of one tag that k_locate_tags stages in LDS
 int preload_locate_kernels();
+// kernels_predict.hip: the localisation accuracy a pose would have against a finished map (vmm_ba_predict_localization)
+constexpr int kTagFace = 6;   // doubles of a tag's face: n = R e_z (3) | centre (3)
+struct PredictArgs {
+    Intrinsics K;
+    int n_tags, n_poses;
+    const double* corners;     // [12 * n_tags] world corners (k_map_corners)
+    const double* faces;       // [kTagFace * n_tags] (k_tag_faces)
+    const double* tag_cov;     // [36 * n_tags] or null (k_predict<false>)
+    const double* frames;      // [kCamFrame * n_poses] (k_cam_frames)
+    double u_lo, u_hi, v_lo, v_hi;   // margin_px, width - margin_px, margin_px, height - margin_px
+    double min_depth, cos_max_angle, min_side2, sigma2;   // min_side_px^2, sigma_px^2
+    int min_tags;
+    double* cov_px;            // [36 * n_poses] or null
+    double* cov_map;           // [36 * n_poses] or null
+    uint8_t* visible;          // [n_poses * n_tags] or null
+    vmm_ba_predict_result* res;   // [n_poses] or null
+};
+void launch_tag_faces(hipStream_t st, int n_tags, const double* tag_qt, double* faces);
+void launch_predict(hipStream_t st, const PredictArgs& a);
+int preload_predict_kernels();
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
 constexpr int kCalRec = arrow_rec_doubles(9);     // 68
 constexpr int kCalElim = 84;                        // the stride of an image's elimination: arrow_elim_doubles(9) = 81 of it are used

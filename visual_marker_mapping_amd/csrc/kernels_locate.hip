@@ -11,7 +11,7 @@
 //                               (wave_sum32) and combined in LDS in wave order; every thread runs the same 6 x 6 solve
 //                     result    flags at the returned pose, H^-1 by a 6 x 6 Cholesky in registers, and once, behind the
 //                               trial loop, sum G C G^T (camera_part: 21 sums through the same reduction)
-// The single-pose solver is pose_lm.hpp's (lm_refine, better / wave_winner, chain_tag, quat_from_R) over small_solve.hpp's
+// The single-pose solver is pose_lm.hpp's (lm_refine, better / wave_winner, chain_tag, quat_from_R, sandwich6) over small_solve.hpp's
 // damped_solve<6> and spd_inverse<6>; the workgroup reductions are image_sums.hpp's (workgroup_count, workgroup_normal,
 // workgroup_cost); the corner arithmetic is eval_corner<false, true> (geom.hpp), the residual and tag Jacobian of the
 // bundle adjustment.  The tag's own pose is workgroup-uniform and expanded once per evaluation.  Here: the view of a
@@ -242,40 +242,6 @@ __device__ __forceinline__ void camera_part(const Intrinsics& K, const TagView<S
     }
     double raw2;
     workgroup_normal(S, g, 0.0, 0.0, s_red, raw2);
-}
-
-__device__ __forceinline__ double sym6(const double (&P)[21], const int r, const int c) { return r >= c ? P[tri6(r, c)] : P[tri6(c, r)]; }
-
-// C S C (packed lower) of two symmetric 6 x 6 matrices; entry (r, c) is averaged with its mirror image, so that the
-// stored matrix is symmetric whatever the rounding.  Returns whether every entry is finite.
-__device__ __forceinline__ bool sandwich6(const double (&C)[21], const double (&S)[21], double (&CC)[21])
-{
-    double T[6][6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                t += sym6(C, r, k) * sym6(S, k, c);
-            T[r][c] = t;
-        }
-    double sum = 0.0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c) {
-            double x = 0.0, y = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                x += T[r][k] * sym6(C, k, c);
-                y += T[c][k] * sym6(C, k, r);
-            }
-            CC[tri6(r, c)] = 0.5 * (x + y);
-            sum += fabs(CC[tri6(r, c)]);
-        }
-    return finite_bits(sum);
 }
 
 // What thread 0 stores for tag p; have_cov / have_cams false: a zero matrix.

@@ -8,6 +8,7 @@
 //   better / wave_winner    the candidate winner rule and its wave butterfly
 //   zero_normal / wave_sum_normal, accumulate_rows   the 21 + 6 sums of the normal equations
 //   chain_camera / chain_tag, quat_from_R                    candidates chained through a placed pose
+//   sym6 / sandwich6        C S C of two packed symmetric 6 x 6 matrices (kernels_locate.hip, kernels_predict.hip)
 // The algebra under it is small_solve.hpp's: tri6 and the tests of finiteness, the damped solve of the normal equations
 // (damped_solve<6, BITS>), the covariance of one pose (spd_inverse<6>: kernels_localize.hip, kernels_rig.hip) and
 // lower_inverse / lower_gram (kernels_calibrate.hip, arrowhead.hpp).
@@ -202,6 +203,41 @@ __device__ __forceinline__ void project_camera_point_intrinsics(const Intrinsics
     jk[1][7] = K.fy * xy2;
     jk[0][8] = fxx * r6;
     jk[1][8] = fyy * r6;
+}
+
+// entry (r, c) of a symmetric 6 x 6 matrix held packed lower
+__device__ __forceinline__ double sym6(const double (&P)[21], const int r, const int c) { return r >= c ? P[tri6(r, c)] : P[tri6(c, r)]; }
+
+// C S C (packed lower) of two symmetric 6 x 6 matrices; entry (r, c) is averaged with its mirror image, so that the
+// stored matrix is symmetric whatever the rounding.  Returns whether every entry is finite.
+__device__ __forceinline__ bool sandwich6(const double (&C)[21], const double (&S)[21], double (&CC)[21])
+{
+    double T[6][6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                t += sym6(C, r, k) * sym6(S, k, c);
+            T[r][c] = t;
+        }
+    double sum = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c <= r; ++c) {
+            double x = 0.0, y = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                x += T[r][k] * sym6(C, k, c);
+                y += T[c][k] * sym6(C, k, r);
+            }
+            CC[tri6(r, c)] = 0.5 * (x + y);
+            sum += fabs(CC[tri6(r, c)]);
+        }
+    return finite_bits(sum);
 }
 
 // The candidate winner rule: the lowest score wins, ties go to the lowest index, NaN and +inf lose (a thread that found

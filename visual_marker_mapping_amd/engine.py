@@ -619,6 +619,74 @@ def locate_tags(intr, dist, cam_qt, tag_wh, tag_start, obs_cam, obs_px, cam_cov=
     return tag_qt, cov, cov_cams, inl.astype(bool), _result_dicts(res)
 
 
+def default_predict_options(**kw):
+    return _options(_lib.PredictOptions, "vmm_ba_default_predict_options", kw, "prediction")
+
+
+def predict_localization(intr, dist, tag_qt, tag_wh, cam_qt, image_size, tag_cov=None, device=0, want_visible=False,
+                         **options):
+    """How well a camera would be localised against a finished map at poses that have no image behind them
+    (vmm_ba_predict_localization).  tag_qt (n_tags, 7) tag->world and tag_wh (n_tags, 2): the map.  cam_qt (n_poses, 7)
+    world->camera.  image_size: (width, height) in pixels.  tag_cov (n_tags, 6, 6), optional: the tags' marginal
+    covariances in tangent order.  options: the other fields of vmm_ba_predict_options.  Returns (cov_px (n_poses, 6, 6)
+    the covariance the pixel noise causes, cov_map (n_poses, 6, 6) the part propagated from tag_cov, tag by tag without
+    their correlations (zeros without tag_cov), results: one dict per pose with status, n_visible, sigma_pos_m,
+    sigma_rot_rad) and, with want_visible, visible (n_poses, n_tags) bool as a fourth.  Occlusion is not modelled."""
+    intr, dist = _model_arrays(intr, dist)
+    tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
+    tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
+    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
+    if len(tag_wh) != len(tag_qt):
+        raise ValueError("tag_wh and tag_qt differ in length")
+    if tag_cov is not None:
+        tag_cov = np.ascontiguousarray(tag_cov, np.float64).reshape(-1, 6, 6)
+        if len(tag_cov) != len(tag_qt):
+            raise ValueError("tag_cov and tag_qt differ in length")
+    o = default_predict_options(image_width=int(image_size[0]), image_height=int(image_size[1]), **options)
+    n_tags, n_poses = len(tag_qt), len(cam_qt)
+    cov_px, cov_map = np.zeros((n_poses, 6, 6)), np.zeros((n_poses, 6, 6))
+    visible = np.zeros((n_poses, n_tags), np.uint8) if want_visible else None
+    res = np.zeros(n_poses, np.dtype(_lib.PredictResult))
+    _lib.check(_lib.lib().vmm_ba_predict_localization(_ptr(intr), _ptr(dist), n_tags, _ptr(tag_qt), _ptr(tag_wh),
+                                                      _ptr(tag_cov), n_poses, _ptr(cam_qt), C.byref(o), _ptr(cov_px),
+                                                      _ptr(cov_map), _ptr(visible), _ptr(res), device))
+    out = (cov_px, cov_map, _result_dicts(res))
+    return out + (visible.astype(bool),) if want_visible else out
+
+
+def grid_poses(lo, hi, shape, axes, up):
+    """World->camera poses (n, 7) at the nodes of the box lo..hi (3,) with shape = (nx, ny, nz) nodes per dimension (a
+    single node sits at lo): one pose per node and per optical-axis direction in `axes` (k, 3) (unit vectors in the
+    world, normalised here), the roll fixed by `up` (the image's y axis points away from it).  Node (ix, iy, iz) with
+    axis a is pose ((ix ny + iy) nz + iz) k + a.  An axis parallel to `up` is refused."""
+    from .pnp import quat_from_R
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    axes = np.asarray(axes, np.float64).reshape(-1, 3)
+    up = np.asarray(up, np.float64).reshape(3)
+    if any(int(n) < 1 for n in shape) or len(shape) != 3:
+        raise ValueError("shape must be three counts of at least 1")
+    if not np.linalg.norm(up) > 0.0:
+        raise ValueError("up must not be zero")
+    frames = []
+    for z in axes:
+        if not np.linalg.norm(z) > 0.0:
+            raise ValueError("an axis must not be zero")
+        z = z / np.linalg.norm(z)
+        x = np.cross(z, up)   # y = z x x points away from `up`
+        if np.linalg.norm(x) <= 1e-9 * np.linalg.norm(up):
+            raise ValueError("axis %s is parallel to up" % (tuple(float(v) for v in z),))
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])   # rows: the camera's axes in the world
+        frames.append((R, quat_from_R(R)))
+    nodes = np.stack(np.meshgrid(*[np.linspace(lo[d], hi[d], int(shape[d])) for d in range(3)], indexing="ij"), axis=-1)
+    nodes = nodes.reshape(-1, 3)
+    out = np.zeros((len(nodes), len(frames), 7))
+    for a, (R, q) in enumerate(frames):
+        out[:, a, :4] = q
+        out[:, a, 4:] = -(nodes @ R.T)   # t = -R C
+    return out.reshape(-1, 7)
+
+
 def pose_minus(a, b):
     """The tangent step d (6,) with pose_plus(b, d) == a, for two poses (7,) (host numpy, no device call): translation
     is the difference, rotation the axis times the half angle of q_a q_b^-1, its sign chosen so that w >= 0."""

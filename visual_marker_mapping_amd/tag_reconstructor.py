@@ -749,6 +749,37 @@ class TagReconstructor:
         self.lastTagLocationReport = report
         return tags
 
+    def predictLocalizationAccuracy(self, cameras, tagCovariances=None, **options):
+        """How well a camera would be localised against the reconstructed tags at poses that have no image behind them
+        (vmm_ba_predict_localization).  cameras: {id: Camera} or an (n, 7) array of world->camera poses (ids 0..n-1).
+        tagCovariances: {tagId: 6x6} in tangent order (computePoseCovariances()["tags"]); a tag without an entry (the
+        origin tag) counts as exact.  options: the fields of vmm_ba_predict_options; image_width / image_height default
+        to the camera model's horizontalResolution / verticalResolution.  Occlusion is not modelled.  Returns
+        {id: {"status", "n_visible", "sigma_pos_m", "sigma_rot_rad", "pose" (7,), "covariance" (6, 6) from the pixel noise,
+        "covariance_map" (6, 6) propagated from tagCovariances tag by tag, "visible_tags": [tag ids]}}.  The reference has
+        no such member."""
+        if isinstance(cameras, dict):
+            ids = sorted(int(k) for k in cameras)
+            cams = {int(k): v for k, v in cameras.items()}
+            cam_qt = np.array([np.concatenate([cams[i].q, cams[i].t]) for i in ids], np.float64).reshape(-1, 7)
+        else:
+            cam_qt = np.ascontiguousarray(cameras, np.float64).reshape(-1, 7)
+            ids = list(range(len(cam_qt)))
+        tag_ids, tag_qt, tag_wh = self._map_arrays()
+        tag_cov = None
+        if tagCovariances is not None:
+            tag_cov = np.zeros((len(tag_ids), 6, 6))
+            for k, t in enumerate(tag_ids):
+                if t in tagCovariances:
+                    tag_cov[k] = np.asarray(tagCovariances[t], np.float64).reshape(6, 6)
+        size = (options.pop("image_width", self.camModel.horizontalResolution),
+                options.pop("image_height", self.camModel.verticalResolution))
+        cov_px, cov_map, res, vis = _engine.predict_localization(*self._model_args(), tag_qt, tag_wh, cam_qt, size,
+                                                                 tag_cov=tag_cov, device=self.device, want_visible=True,
+                                                                 **options)
+        return {i: dict(res[n], pose=cam_qt[n].copy(), covariance=cov_px[n].copy(), covariance_map=cov_map[n].copy(),
+                        visible_tags=[tag_ids[k] for k in np.flatnonzero(vis[n])]) for n, i in enumerate(ids)}
+
     def checkMap(self, detectionResult=None, imageIds=None, sigma_px=1.0, chi2_threshold=22.458, min_views=2, rounds=2,
                  **options):
         """Which tags of the map are no longer where the map says?  Fresh images (`detectionResult`, default the

@@ -73,6 +73,12 @@ def read_camera_covariances(path):
     return cov
 
 
+def read_tag_covariances(path):
+    """{tagId: 6x6} from the `reconstructed_tags` of a reconstruction_uncertainty.json."""
+    return {_io._get(pt, "id", int): _io.matrixFromPropertyTree(pt["covariance"], 6, 6)
+            for pt in _io._children(_io.read_json(path), "reconstructed_tags") if "covariance" in pt}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Triangulates free points, or the tags' corners, against a finished map")
     ap.add_argument("--project_path", required=True, help="Path to the project (holds reconstruction.json)")

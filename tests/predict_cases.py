@@ -212,11 +212,12 @@ def edges():
                 cam_qt=np.array([[1.0, 0, 0, 0, 0, 0, 0]]))
 
 
-def lanes(n_tags, n_poses):
+def lanes(n_tags, n_poses, relief=0.0):
     """n_tags tags of 0.15 m on the wall z = 4, 13 to a row 0.3 m apart, facing the poses; pose p stands further to the
-    right, up and back and is turned a little more than pose p - 1, so that tags leave its image."""
-    tag_qt = np.array([tag_towards([0.3 * (k % 13) - 1.8, 0.3 * (k // 13) - 1.35, 4.0], [0.3 * (k % 13) - 1.8, 0.3 * (k // 13) - 1.35, 0.0],
-                                   spin_deg=7.0 * k) for k in range(n_tags)])
+    right, up and back and is turned a little more than pose p - 1, so that tags leave its image.  relief: tag k stands
+    relief * ((7 k) mod 5 - 2) / 2 behind the wall (in front of it where negative), so that the tags span 2 relief in depth."""
+    tag_qt = np.array([tag_towards([0.3 * (k % 13) - 1.8, 0.3 * (k // 13) - 1.35, 4.0 + relief * ((7 * k) % 5 - 2) / 2],
+                                   [0.3 * (k % 13) - 1.8, 0.3 * (k // 13) - 1.35, 0.0], spin_deg=7.0 * k) for k in range(n_tags)])
     base = np.array([1.0, 0, 0, 0, 0, 0, 0])
     cam_qt = np.array([displaced(base, np.array([0.4 * p, -0.2 * p, -0.1 * p]), [0.3, -1.0, 0.2], 4.0 * p) for p in range(n_poses)])
     return dict(intr=np.array([500.0, 505.0, 322.0, 238.0]), dist=np.array([-0.05, 0.01, 1e-3, -5e-4, 0.0]), size=(640, 480),

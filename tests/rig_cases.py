@@ -89,10 +89,10 @@ def frame_normal(O, s, f, q, ext_qt, keep, robust, a=1.0):
     return cost, Jf.T @ Jf, Jf.T @ r
 
 
-def host_frame_optimum(O, s, f, q0, ext_qt, keep, robust):
-    """Levenberg-Marquardt on frame f's 6 degrees of freedom from q0 over the observations of `keep`, run until the
-    step is at the rounding floor of the pose.  Returns (pose, cost)."""
-    return dense_lm(lambda q: frame_normal(O, s, f, q, ext_qt, keep, robust), O.pose_plus, np.array(q0, np.float64),
+def host_frame_optimum(O, s, f, q0, ext_qt, keep, robust, a=1.0):
+    """Levenberg-Marquardt on frame f's 6 degrees of freedom from q0 over the observations of `keep` (Huber width a), run
+    until the step is at the rounding floor of the pose.  Returns (pose, cost)."""
+    return dense_lm(lambda q: frame_normal(O, s, f, q, ext_qt, keep, robust, a), O.pose_plus, np.array(q0, np.float64),
                     lambda sys, lam: plain_step(sys[1], sys[2], lam), 1e-13)[:2]
 
 

@@ -7,6 +7,8 @@ tests/test_predict_cpu.py shows that no flag of its cases rests on rounding.  To
 1e-6 x max|ref| as the existing covariance tests (BASELINE.md section 3, test_gpu_localize.py); sigmas 1e-6 relative;
 against the localisation 2e-6 x max|ref| (each side within 1e-6 of the same inverse) and the localisation test's own
 1e-9 on the recovered pose.
+tests/test_finished_map_accuracy.py supersedes in strength the COV_REL comparisons of cov_px and cov_map and the 1e-6
+comparison of the sigmas: there every entry and both sigmas are held to float64 accuracy, at 1 to 129 tags in depth.
 """
 import os
 import shutil

@@ -581,23 +581,28 @@ def _split(rng, total, K):
     return 1 + rng.multinomial(total - K, np.full(K, 1.0 / K))
 
 
-def rig_scene(K, outliers, seed=20261205):
+def rig_scene(K, outliers, seed=20261205, extra=(), frames=None):
     """A rig of K cameras with different models (distorted and not, focal lengths 2 % apart) a few degrees and decimetres
     apart; one frame per total of RIG_TOTALS in a shuffled order, split over the cameras at random, and for K > 1 one frame
-    with all its observations in the last camera and one with an empty camera in the middle."""
+    with all its observations in the last camera and one with an empty camera in the middle.  extra: rows of K counts,
+    frames appended behind those; frames: rows of K counts that stand in the place of all of them (arrowhead_cases.py)."""
     def make():
         rng = np.random.default_rng(seed + K)
         models = [camera_model(MODELS[(c + 1) % 2]) for c in range(K)]
         intr = np.array([m[0] * (1 + 0.02 * c) for c, m in enumerate(models)])
         dist = np.array([m[1] for m in models])
         ext = np.array([rc.yaw(3.0 * (c - (K - 1) / 2), (0.1 * (c - (K - 1) / 2), 0.02 * (c % 3), 0.0)) for c in range(K)])
-        per_frame = [_split(rng, int(RIG_TOTALS[k]), K) for k in rng.permutation(len(RIG_TOTALS))]
-        if K > 1:
-            last = np.zeros(K, int)
-            last[-1] = RIG_ALL_IN_LAST
-            hole = _split(rng, RIG_EMPTY_MIDDLE, K - 1)
-            per_frame += [last, np.insert(hole, K // 2, 0)]
-        per_frame = np.array(per_frame)
+        if frames is None:
+            per_frame = [_split(rng, int(RIG_TOTALS[k]), K) for k in rng.permutation(len(RIG_TOTALS))]
+            if K > 1:
+                last = np.zeros(K, int)
+                last[-1] = RIG_ALL_IN_LAST
+                hole = _split(rng, RIG_EMPTY_MIDDLE, K - 1)
+                per_frame += [last, np.insert(hole, K // 2, 0)]
+            per_frame += [np.asarray(row, int) for row in extra]
+        else:
+            per_frame = [np.asarray(row, int) for row in frames]
+        per_frame = np.array(per_frame).reshape(-1, K)
         F = len(per_frame)
         tag_qt, wh = _tags(rng, int(per_frame.sum(axis=1).max()))
         rig = _cameras(rng, F)
@@ -624,7 +629,8 @@ def rig_scene(K, outliers, seed=20261205):
         d = np.linalg.norm((px[label] - clean[label]).reshape(-1, 4, 2), axis=2)
         assert (d <= INLIER_PX / 4).all()
         return s
-    return ec.cached(("finished map rig", K, bool(outliers), seed), make)
+    shape = (tuple(map(tuple, extra)), None if frames is None else tuple(map(tuple, frames)))
+    return ec.cached(("finished map rig", K, bool(outliers), seed) + (shape if shape != ((), None) else ()), make)
 
 
 class RigCase(Case):

@@ -6,6 +6,11 @@ oracle/oracle.py, proven against central differences in tests/test_yardstick_cpu
 test.  Tolerances: 1e-9 on exact data, 1e-6 per pose between two optima, covariances to
 1e-6 x max|ref| as the existing covariance tests, costs to 1e-9 relative (second order in the gap), parameters in units of their standard deviation
 (yardstick.SIGMA_GAP).  Scenes come from synthetic.make_scene, the map is tag_gt.
+tests/test_gpu_arrowhead_accuracy.py supersedes in strength the 1e-6 x max|ref| comparisons of intr_cov and cam_cov (under
+a max-norm the rows of k1 .. k3 of intr_cov could be wrong by their whole size), the 1e-9 comparison of final_cost with the
+host optimum and the finiteness checks of an image's cost, rms_px and of final_rms_px: there every entry over
+sqrt(truth_ii truth_jj), every scalar and one single trial are held to float64 accuracy at the device's own state, on
+images of 1 .. 513 tags and batches of 1 .. 257 images.  The tests here stay, their assertions unchanged.
 """
 import os
 import shutil

@@ -10,6 +10,11 @@ synthetic.make_rig_scene: 12 - 20 frames, 1 - 3 cameras (8 once), 8 - 30 tags, t
 tests/test_finished_map_accuracy.py supersedes in strength the 1e-6 comparisons of rig_cov for vmm_ba_rig_localize (among
 them the frames of 255, 256, 257 and 600 observations): there every entry, the cost and rms_px of a frame are held to
 float64 accuracy at the device's own state; the comparisons of vmm_ba_rig_calibrate are not touched by it.
+tests/test_gpu_arrowhead_accuracy.py supersedes in strength, for vmm_ba_rig_calibrate, the 1e-6 x max|ref| comparisons of
+ext_cov and the joint rig_cov, the 1e-9 comparison of final_cost with the host optimum and the finiteness checks of a
+frame's cost, rms_px and of final_rms_px: there every entry over sqrt(truth_ii truth_jj), every scalar and one single
+trial are held to float64 accuracy at the device's own state, at K = 2, 3, 4, 8 and at 1, 4, 5 and 65 frames.  The
+tests here stay, their assertions unchanged.
 """
 import json
 

@@ -336,6 +336,8 @@ int vmm_ba_project_points(const double intr[4], const double dist[5], int64_t n,
  * closed-form homography of the quad, decomposition, Levenberg-Marquardt on the 8 pixel residuals of
  * CameraModel::projectPoint -- and then the second planar solution (the tag normal mirrored about the line of sight to
  * the tag centre, refined the same way), which a small or distant tag makes nearly as good as the first.
+ * A solution whose refinement spends all its trials (a weak-perspective quad, whose decomposition lies at the saddle
+ * between the two solutions) is replaced by the refined first-order planar pose of its side, where that ends lower.
  * tag_wh[2*n]: width, height of observation i's tag; obs_px[8*n].
  * qt2[14*n]: two tag->camera poses per observation, lower RMS first; rms2[2*n]: their RMS corner distance in pixels.
  * A degenerate observation yields RMS = +inf and the pose (1,0,0,0, 0,0,1), never NaN. */
@@ -362,7 +364,8 @@ void vmm_ba_default_init_options(vmm_ba_init_options* o);
  * vmm_ba_set_constant_poses names, cameras included.  The constant poses keep their current values.  They count as
  * placed from round 0, are never overwritten, are skipped by the sweeps and are reported reached.
  * The steps: planar poses of all active observations; then rounds -- every camera with an active observation of a placed tag,
- * then every tag with >= min_tag_observations active observations that a placed camera sees: among the candidates
+ * then every tag with >= min_tag_observations active observations that a placed camera sees (the count is over all the
+ * tag's active observations, whoever made them; one of them from a placed camera is enough): among the candidates
  * (two per such observation, chained through the placed pose) the one with the lowest truncated squared reprojection
  * error over all the pose's corners on placed counterparts, refined on its own -- until a round places nothing;
  * then `sweeps` passes that redo selection and refinement for every placed pose except the constant ones.

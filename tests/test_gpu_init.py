@@ -5,6 +5,7 @@ the incremental driver uses) for the planar solver under noise; and for everythi
 bundle adjustment reaches from the scene generator's perturbed ground truth -- an initialisation is right when
 the solver ends in the same place from it.  Tolerances: 1e-9 on exact data, 1e-6 per pose between two optima
 (parity gate).
+The stronger check, stage by stage against a longdouble truth: tests/test_gpu_init_accuracy.py.
 """
 import numpy as np
 import pytest

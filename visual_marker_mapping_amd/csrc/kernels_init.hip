@@ -65,15 +65,63 @@ __device__ __forceinline__ double quad_cost(const Intrinsics& K, const double* q
     return cost;
 }
 
-// Levenberg-Marquardt on the tag->camera pose q (in place) of one quad; returns the final cost.
+// Levenberg-Marquardt on the tag->camera pose q (in place) of one quad; returns the final cost, trials: the trials spent.
+// lm_trials returns its loop counter, not the counter + 1: a stopping rule that fires in the last trial gives
+// kQuadTrials - 1, and kQuadTrials means that no rule ended the run.
 __device__ __forceinline__ double quad_refine(const Intrinsics& K, double* q, const double hw, const double hh,
-                                              const double (&px)[8])
+                                              const double (&px)[8], int& trials)
 {
     double cost;
-    lm_refine<false, false>(q, kQuadTrials, [&](auto jac, const double* at, double (&A)[21], double (&g)[6]) {
+    trials = lm_refine<false, false>(q, kQuadTrials, [&](auto jac, const double* at, double (&A)[21], double (&g)[6]) {
         return quad_cost<decltype(jac)::value>(K, at, hw, hh, px, A, g);
     }, cost);
     return cost;
+}
+
+// The two planar poses that the homography's first order at the tag centre allows (h1, h2, h3: its columns in the tag's
+// metric frame).  With the camera turned so that the line of sight to the centre is its axis (Q, the minimal rotation),
+// the 2 x 2 Jacobian of the image point over the tag's coordinates is the upper left block of the rotation over the
+// distance: its larger singular value gives the distance, the unit length of the two columns |r1z| and |r2z|, their
+// orthogonality the sign of r1z r2z, and the sign of r1z is the planar ambiguity itself.  Unlike the decomposition in
+// k_quad_pose, which averages the two solutions of a weak-perspective quad into the saddle between them, neither of
+// these starts lies there.
+__device__ __forceinline__ void quad_weak_starts(const double (&h1)[3], const double (&h2)[3], const double (&h3)[3],
+                                                 double (&w)[2][7])
+{
+    const double p0x = h3[0] / h3[2], p0y = h3[1] / h3[2];
+    const double j1x = (h1[0] - p0x * h1[2]) / h3[2], j1y = (h1[1] - p0y * h1[2]) / h3[2];
+    const double j2x = (h2[0] - p0x * h2[2]) / h3[2], j2y = (h2[1] - p0y * h2[2]) / h3[2];
+    const double m = sqrt(p0x * p0x + p0y * p0y + 1.0);
+    const double v[3] = { p0x / m, p0y / m, 1.0 / m };
+    const double kx = v[1], ky = -v[0], f = 1.0 / (1.0 + v[2]);   // Q = I + [k]x + [k]x^2 / (1 + v_z), k = v x e_z
+    const double Q[9] = { 1.0 - f * ky * ky, f * kx * ky, ky, f * kx * ky, 1.0 - f * kx * kx, -kx,
+                          -ky, kx, 1.0 - f * (kx * kx + ky * ky) };
+    const double a1x = (Q[0] * j1x + Q[1] * j1y) / m, a1y = (Q[3] * j1x + Q[4] * j1y) / m;
+    const double a2x = (Q[0] * j2x + Q[1] * j2y) / m, a2y = (Q[3] * j2x + Q[4] * j2y) / m;
+    const double sxx = a1x * a1x + a2x * a2x, syy = a1y * a1y + a2y * a2y, sxy = a1x * a1y + a2x * a2y;
+    const double lam = 0.5 * (sxx + syy) + sqrt(0.25 * (sxx - syy) * (sxx - syy) + sxy * sxy);
+    const double dist = 1.0 / sqrt(lam);
+    const double b1x = a1x * dist, b1y = a1y * dist, b2x = a2x * dist, b2y = a2y * dist;
+    const double u1 = 1.0 - (b1x * b1x + b1y * b1y), u2 = 1.0 - (b2x * b2x + b2y * b2y);
+    const double z1 = sqrt(u1 > 0.0 ? u1 : 0.0);
+    const double z2 = sqrt(u2 > 0.0 ? u2 : 0.0) * (b1x * b2x + b1y * b2y > 0.0 ? -1.0 : 1.0);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double sg = k ? -1.0 : 1.0;
+        const double r1[3] = { b1x, b1y, sg * z1 }, r2[3] = { b2x, b2y, sg * z2 };
+        const double r3[3] = { r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0] };
+        double R[9];   // Q^T [r1 r2 r3]
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            R[3 * i] = Q[i] * r1[0] + Q[3 + i] * r1[1] + Q[6 + i] * r1[2];
+            R[3 * i + 1] = Q[i] * r2[0] + Q[3 + i] * r2[1] + Q[6 + i] * r2[2];
+            R[3 * i + 2] = Q[i] * r3[0] + Q[3 + i] * r3[1] + Q[6 + i] * r3[2];
+        }
+        quat_from_R(R, w[k]);
+        w[k][4] = v[0] * dist;
+        w[k][5] = v[1] * dist;
+        w[k][6] = v[2] * dist;
+    }
 }
 
 struct QuadArgs {
@@ -166,7 +214,8 @@ __global__ __launch_bounds__(64) void k_quad_pose(const QuadArgs a)
         q[0][5] = h3[1] * s;
         q[0][6] = h3[2] * s;
         double cost[2];
-        cost[0] = quad_refine(K, q[0], hw, hh, px);
+        int trials[2];
+        cost[0] = quad_refine(K, q[0], hw, hh, px, trials[0]);
         // the second planar solution: the tag normal mirrored about the line of sight to the tag centre
         {
             Rigid T;
@@ -198,17 +247,56 @@ __global__ __launch_bounds__(64) void k_quad_pose(const QuadArgs a)
             q[1][5] = q[0][5];
             q[1][6] = q[0][6];
         }
-        cost[1] = quad_refine(K, q[1], hw, hh, px);
+        cost[1] = quad_refine(K, q[1], hw, hh, px, trials[1]);
+        // The fallback.  The start above lies at the saddle between the two planar minima when the perspective is weak;
+        // the gradient along the tilt is nearly zero there and the loop crawls.  A solution that spent all its trials is
+        // replaced by a weak-perspective start refined the same way, where that ends lower: both starts when both
+        // stalled, otherwise the one whose normal lies further from the solution that is kept.
+        const bool stall0 = trials[0] == kQuadTrials, stall1 = trials[1] == kQuadTrials;
+        if (stall0 || stall1) {
+            double w[2][7], wc[2];
+            quad_weak_starts(h1, h2, h3, w);
+#pragma unroll 1
+            for (int k = 0; k < 2; ++k) {
+                int spent;
+                wc[k] = quad_refine(K, w[k], hw, hh, px, spent);
+            }
+            int pick0 = 0, pick1 = 1;
+            if (!(stall0 && stall1)) {
+                Rigid keep, w0, w1;
+                load_rigid<true>(stall0 ? q[1] : q[0], keep);
+                load_rigid<true>(w[0], w0);
+                load_rigid<true>(w[1], w1);
+                const double d0 = w0.R[2] * keep.R[2] + w0.R[5] * keep.R[5] + w0.R[8] * keep.R[8];
+                const double d1 = w1.R[2] * keep.R[2] + w1.R[5] * keep.R[5] + w1.R[8] * keep.R[8];
+                pick0 = pick1 = d1 < d0 ? 1 : 0;
+            }
+            if (stall0 && finite_bits(wc[pick0]) && wc[pick0] < cost[0]) {
+                cost[0] = wc[pick0];
+#pragma unroll
+                for (int k = 0; k < 7; ++k)
+                    q[0][k] = pick0 ? w[1][k] : w[0][k];
+            }
+            if (stall1 && finite_bits(wc[pick1]) && wc[pick1] < cost[1]) {
+                cost[1] = wc[pick1];
+#pragma unroll
+                for (int k = 0; k < 7; ++k)
+                    q[1][k] = pick1 ? w[1][k] : w[0][k];
+            }
+        }
 #pragma unroll
         for (int sidx = 0; sidx < 2; ++sidx) {
             const double qn = 1.0 / sqrt(q[sidx][0] * q[sidx][0] + q[sidx][1] * q[sidx][1] + q[sidx][2] * q[sidx][2]
                                          + q[sidx][3] * q[sidx][3]);
-            bool ok = finite_d(cost[sidx]) && finite_d(qn);
+            // finite_bits, not finite_d: the compiler contracted finite_d's v - v with the product q * qn just above it
+            // into fma(q, qn, -v), the product's rounding error, for two components of the second solution, which then
+            // came back as +inf unless both products happened to be exact
+            bool ok = finite_bits(cost[sidx]) && finite_bits(qn);
 #pragma unroll
             for (int k = 0; k < 7; ++k) {
                 if (k < 4)
                     q[sidx][k] *= qn;
-                ok = ok && finite_d(q[sidx][k]);
+                ok = ok && finite_bits(q[sidx][k]);
             }
             if (ok) {
                 rms[sidx] = sqrt(0.25 * cost[sidx]);   // RMS corner distance in pixels
@@ -280,7 +368,7 @@ __device__ __forceinline__ double score_pose(const InitArgs& a, const Rigid& own
             eval_corner<false, false>(a.K, CAM ? own : oth, CAM ? oth : own, corner_sx(k) * hw, corner_sy(k) * hh,
                                       a.px[(2 * k) * a.n_pad + d], a.px[(2 * k + 1) * a.n_pad + d], ev);
             const double e2 = ev.ru * ev.ru + ev.rv * ev.rv;
-            sum += e2 < a.cap2 ? e2 : (finite_d(e2) ? a.cap2 : kInf);
+            sum += e2 < a.cap2 ? e2 : (finite_bits(e2) ? a.cap2 : kInf);   // not finite_d: e2 is a sum of two products (k_quad_pose's final tests)
         }
     }
     return sum;

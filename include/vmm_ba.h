@@ -717,6 +717,43 @@ int vmm_ba_predict_localization(const double intr[4], const double dist[5],
                                 vmm_ba_predict_result* res,  /* [n_poses] or NULL */
                                 int device);
 
+/* ABI 6, additive.  vmm_ba_predict_localization with the map's tags correlated: what it says holds here word for word,
+ * but for two arguments and for cov_map.
+ *   tag_cov_joint  The tags' joint covariance, [36 * n_tags * n_tags] doubles block-major: block (s, t) is the row-major
+ *               6x6 at 36 (s n_tags + t), which is what vmm_ba_covariance_blocks writes for the pair list
+ *               (n_cams + s, n_cams + t) with s the outer loop.  Required when n_tags > 0.  Only the blocks with s >= t are
+ *               read; S_ts is taken as S_st^T.  The diagonal blocks are read in full as given, as tag_cov is.  The upper
+ *               block triangle may hold anything, NaN included: it is neither validated nor touched.
+ *   visible_in  [n_poses * n_tags] or NULL.  When given, the visibility rules are not evaluated: tag t takes part in pose
+ *               p exactly when visible_in[p n_tags + t] != 0, and `visible` repeats it as 0 / 1.  This is how the inlier
+ *               set of a real localisation is fed in.  A pose with a selected tag that has a corner at or behind the
+ *               camera's plane (z_cam <= 0, where the projection means nothing), or whose sums come out non-finite or
+ *               with an indefinite H, is SINGULAR.
+ *   cov_map     H^-1 M H^-1 with M = sum_{s in V} G_s S_ss G_s^T + sum_{s in V} sum_{t in V, t < s} (X_st + X_st^T),
+ *               X_st = G_s S_st G_t^T, V the visible (selected) tags of the pose: the covariance of the first-order
+ *               response dx = -H^-1 sum_t G_t dy_t under the joint covariance of the dy_t.  On a block-diagonal
+ *               tag_cov_joint it is vmm_ba_predict_localization's cov_map up to rounding; cov_px is its cov_px bit for
+ *               bit.  sigma_pos_m and sigma_rot_rad come from cov_px + cov_map by the same formulas.
+ * OCCLUSION IS STILL NOT MODELLED.  With visible_in taken from a robust localisation, the response is that of the plain
+ * least-squares minimiser over the selected tags (unit weights, no loss), not of the robust one.
+ * No output is ever NaN; the matrices are symmetric to the last bit; a pose gives the same bits alone, in any batch, at
+ * any position and from run to run.  Statuses, and the zero outputs that go with them, as above.
+ * VMM_BA_ERR_ARGUMENT (before any device call): what vmm_ba_predict_localization rejects; a null tag_cov_joint with
+ * n_tags > 0; a non-finite entry in a block with s >= t.  VMM_BA_ERR_HIP with the byte count in the message when the
+ * device memory, 288 n_tags^2 bytes of it for tag_cov_joint, cannot be allocated.  n_poses == 0 and n_tags == 0 return
+ * VMM_BA_OK without a device call, as above. */
+int vmm_ba_predict_localization_joint(const double intr[4], const double dist[5],
+                                      int32_t n_tags, const double* tag_qt, const double* tag_wh,
+                                      const double* tag_cov_joint,   /* [36*n_tags*n_tags] block-major; blocks s >= t are read */
+                                      int32_t n_poses, const double* cam_qt,   /* [7*n_poses] world->camera */
+                                      const uint8_t* visible_in,     /* [n_poses*n_tags] or NULL: the selection */
+                                      const vmm_ba_predict_options* o,
+                                      double* cov_px,              /* [36*n_poses] or NULL */
+                                      double* cov_map,             /* [36*n_poses] or NULL */
+                                      uint8_t* visible,            /* [n_poses*n_tags] or NULL */
+                                      vmm_ba_predict_result* res,  /* [n_poses] or NULL */
+                                      int device);
+
 /* ABI 6, additive.  Calibrates a camera against a finished map: the nine numbers of the camera model
  * (fx, fy, cx, cy, k1, k2, p1, p2, k3) and one pose per image, the map held fixed.  Stateless like vmm_ba_localize.
  *   objective   1/2 sum rho(|r_corner|^2) over the inlier observations of the images that take part, with the residual

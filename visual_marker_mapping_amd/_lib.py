@@ -208,6 +208,7 @@ SIGNATURES = {
     "vmm_ba_locate_tags": (_i, [_a, _a, _i32, _a, _a, _i32, _a, _a, _a, _a, _P(LocalizeOptions), _a, _a, _a, _a, _a, _i]),
     "vmm_ba_default_predict_options": (None, [_P(PredictOptions)]),
     "vmm_ba_predict_localization": (_i, [_a, _a] + _MAP + [_a, _i32, _a, _P(PredictOptions), _a, _a, _a, _a, _i]),
+    "vmm_ba_predict_localization_joint": (_i, [_a, _a] + _MAP + [_a, _i32, _a, _a, _P(PredictOptions), _a, _a, _a, _a, _i]),
     "vmm_ba_default_calibrate_options": (None, [_P(CalibrateOptions)]),
     "vmm_ba_calibrate": (_i, [_a, _a] + _MAP + _BATCH + [_P(CalibrateOptions), _a, _a, _a, _a, _a, _a, _a,
                               _P(CalibrateReport), _i]),
@@ -231,6 +232,7 @@ EXPORTS = list(SIGNATURES)   # every symbol include/vmm_ba.h declares
 OPTIONAL = {"vmm_ba_covariance_blocks", "vmm_ba_rig_localize", "vmm_ba_default_rig_calibrate_options", "vmm_ba_rig_calibrate",
             "vmm_ba_default_calibrate_options", "vmm_ba_calibrate", "vmm_ba_default_triangulate_options",
             "vmm_ba_triangulate", "vmm_ba_locate_tags", "vmm_ba_default_predict_options", "vmm_ba_predict_localization",
+            "vmm_ba_predict_localization_joint",
             "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
             "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"}
 

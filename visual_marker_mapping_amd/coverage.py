@@ -1,6 +1,6 @@
 """Command-line coverage step: how well would a camera be localised against a finished map, and where is the map too thin?
 
-    python -m visual_marker_mapping_amd.coverage --project_path DIR [--map FILE] [--uncertainty FILE] \\
+    python -m visual_marker_mapping_amd.coverage --project_path DIR [--map FILE] [--uncertainty FILE [--correlated]] \\
         (--poses FILE | --grid X0 X1 NX Y0 Y1 NY Z0 Z1 NZ --axis X Y Z [--axis ...] --up X Y Z) \\
         [--sigma_px S] [--margin_px M] [--max_view_angle_deg A] [--min_side_px P] [--min_tags N] [--covariances] \\
         [--output FILE] [--device N]
@@ -12,7 +12,9 @@ one pose on every node of a box and for every optical axis given (unit vectors i
 (engine.grid_poses).  `--uncertainty` names a reconstruction_uncertainty.json: the part of a pose's covariance that the
 tags' own uncertainty causes is propagated tag by tag (vmm_ba_predict_localization, include/vmm_ba.h, which also says
 what the prediction ignores: occlusion, the correlations between tags, the planar ambiguity of a single tag).  All poses
-go through one device call.
+go through one device call.  `--correlated` propagates the tags' joint covariance instead, cross blocks included
+(vmm_ba_predict_localization_joint): the uncertainty file must have been written with `uncertainty.py --joint`, and
+coverage.json then says "map_covariance": "joint" at its top level.
 
 coverage.json:
     {"options": {image_width, image_height, sigma_px, margin_px, min_depth, max_view_angle_deg, min_side_px, min_tags},
@@ -31,6 +33,7 @@ from . import _lib, engine as _engine
 from . import io as _io
 from .tag_reconstructor import DetectionResult, TagReconstructor
 from .triangulation import read_cameras, read_tag_covariances
+from .uncertainty import read_tag_joint_covariance
 
 
 def coverage_tree(options, report, tag_ids, covariances=False):
@@ -69,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--project_path", required=True, help="Path to the project (holds camera_intrinsics.json and the map)")
     ap.add_argument("--map", default=None, help="map file (default: <project>/reconstruction.json)")
     ap.add_argument("--uncertainty", default=None, help="reconstruction_uncertainty.json with the tags' 6x6 covariances")
+    ap.add_argument("--correlated", action="store_true",
+                    help="propagate the tags' joint covariance (an --uncertainty file written with --joint)")
     ap.add_argument("--poses", default=None, help="file with a reconstructed_cameras list: the poses to predict")
     ap.add_argument("--grid", type=float, nargs=9, default=None, metavar=("X0", "X1", "NX", "Y0", "Y1", "NY", "Z0", "Z1", "NZ"),
                     help="a box of NX x NY x NZ nodes, one pose per node and --axis")
@@ -86,6 +91,8 @@ def main(argv=None):
         ap.error("give either --poses or --grid")
     if a.grid is not None and (not a.axis or a.up is None):
         ap.error("--grid needs at least one --axis and --up")
+    if a.correlated and a.uncertainty is None:
+        ap.error("--correlated needs --uncertainty")
     out = a.output or os.path.join(a.project_path, "coverage.json")
     recon = _io.project_file(a.project_path, a.map, "reconstruction.json", "map", "no map to predict against")
     intrinsics = _io.project_file(a.project_path, None, "camera_intrinsics.json", "camera model")
@@ -106,9 +113,17 @@ def main(argv=None):
     model = rec.getCameraModel()
     o = _engine.default_predict_options(image_width=int(model.horizontalResolution), image_height=int(model.verticalResolution),
                                         **given)
-    report = rec.predictLocalizationAccuracy(cameras, tagCovariances=read_tag_covariances(a.uncertainty) if a.uncertainty else None,
-                                             **given)
+    if a.correlated:
+        joint = read_tag_joint_covariance(a.uncertainty)
+        if joint is None:
+            raise RuntimeError("Could not find a joint covariance in %s: write it with uncertainty.py --joint." % a.uncertainty)
+        report = rec.predictLocalizationAccuracy(cameras, tagJointCovariance=joint, **given)
+    else:
+        report = rec.predictLocalizationAccuracy(cameras, tagCovariances=read_tag_covariances(a.uncertainty) if a.uncertainty else None,
+                                                 **given)
     tree = coverage_tree(_engine._struct_dict(o), report, sorted(tags), covariances=a.covariances)
+    if a.correlated:
+        tree["map_covariance"] = "joint"
     _io.write_json(out, tree)
     print(summary_line(report, len(tree["tags_never_seen"])) + "; wrote %s!" % out)
     return 0

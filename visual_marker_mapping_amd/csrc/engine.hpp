@@ -577,6 +577,14 @@ struct PredictArgs {
 void launch_tag_faces(hipStream_t st, int n_tags, const double* tag_qt, double* faces);
 void launch_predict(hipStream_t st, const PredictArgs& a);
 int preload_predict_kernels();
+// kernels_predict_joint.hip: the same with the map's joint covariance (vmm_ba_predict_localization_joint)
+struct PredictJointArgs {
+    PredictArgs p;                 // tag_cov unused; visible is never null: the kernel's second sweep reads what its first wrote
+    const double* tag_cov_joint;   // [36 * n_tags * n_tags] block-major, blocks s >= t read
+    const uint8_t* visible_in;     // [n_poses * n_tags] or null: the selection instead of the visibility rules
+};
+void launch_predict_joint(hipStream_t st, const PredictJointArgs& a);
+int preload_predict_joint_kernels();
 // kernels_calibrate.hip: the joint refinement of the camera model and one pose per image against a fixed map
 constexpr int kCalRec = arrow_rec_doubles(9);     // 68
 constexpr int kCalElim = 84;                        // the stride of an image's elimination: arrow_elim_doubles(9) = 81 of it are used

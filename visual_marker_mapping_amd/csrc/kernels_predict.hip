@@ -13,7 +13,10 @@
 //                   result   every lane runs the same spd_inverse<6>, the sandwich H^-1 M H^-1 and the two sigmas;
 //                            lane 0 stores 36 + 36 doubles and the record, all lanes store their visible bytes
 // The tag Jacobian is eval_corner<true, true>'s (geom.hpp) formed from the tables: the translation columns are
-// g^T R_cam, the rotation columns 2 (a x h) with a = world corner - centre.
+// g^T R_cam, the rotation columns 2 (a x h) with a = world corner - centre.  The rules, the fetch of the totals and the
+// store are in predict_common.hpp, which k_predict_joint (kernels_predict_joint.hip) shares; the tag Jacobian and the
+// tail below stand there a second time, because calling them from here changed this kernel's register allocation and
+// the last bits of cov_map.
 // No LDS, no barrier, no atomic.  A wave never waits on another, nothing but the selection of the pose depends on the
 // wave's place in the grid, and every sum has a fixed order (a lane's own sum in list order, then the butterfly): a pose
 // gives the same bits alone, anywhere in any batch and from run to run.  The tables (200 tags x 144 B) stay in L2; a
@@ -21,8 +24,7 @@
 //
 // Registers (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): see the kernel table of DESIGN.md
 // section 9.
-#include "engine.hpp"
-#include "image_sums.hpp"
+#include "predict_common.hpp"
 
 namespace vmm {
 
@@ -44,64 +46,6 @@ __global__ __launch_bounds__(256) void k_tag_faces(int n_tags, const double* __r
         f[k] = tag.R[3 * k + 2];
         f[3 + k] = tag.t[k];
     }
-}
-
-// the value wave_sum32 left for index k (lanes 2 m and 2 m + 1 hold index bit-reverse(m)), in every lane
-__device__ __forceinline__ double wave_sum32_fetch(const double tot, const int k)
-{
-    const int m = ((k & 1) << 4) | ((k & 2) << 2) | (k & 4) | ((k & 8) >> 2) | ((k & 16) >> 4);
-    return __shfl(tot, 2 * m, 64);
-}
-
-// Whether the tag with world corners w (4 x 3) and face f is visible from the pose `cam` with centre C; the rules and
-// their words are include/vmm_ba.h's.
-__device__ __forceinline__ bool tag_visible(const PredictArgs& a, const Intrinsics& K, const Rigid& cam, const double (&C)[3],
-                                            const double (&w)[12], const double (&f)[kTagFace])
-{
-    const double d0 = C[0] - f[3], d1 = C[1] - f[4], d2 = C[2] - f[5];
-    if (!(f[0] * d0 + f[1] * d1 + f[2] * d2 >= a.cos_max_angle * sqrt(d0 * d0 + d1 * d1 + d2 * d2)))
-        return false;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        ok = ok && (cam.R[6] * w[3 * k] + cam.R[7] * w[3 * k + 1] + cam.R[8] * w[3 * k + 2]) + cam.t[2] > a.min_depth;
-    if (!ok)
-        return false;
-    double u[4], v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        double b0, b1, b2, j[2][6];
-        rotate_world(cam, w[3 * k], w[3 * k + 1], w[3 * k + 2], b0, b1, b2);
-        const double iz = 1.0 / (b2 + cam.t[2]);
-        const double x = (b0 + cam.t[0]) * iz, y = (b1 + cam.t[1]) * iz;
-        const double r2 = x * x + y * y;
-        ok = ok && 1.0 + r2 * (3.0 * K.k1 + r2 * (5.0 * K.k2 + r2 * (7.0 * K.k3))) > 0.0;
-        project_camera_point<false, false>(K, b0, b1, b2, cam.t, 0.0, 0.0, u[k], v[k], j);
-        ok = ok && u[k] >= a.u_lo && u[k] <= a.u_hi && v[k] >= a.v_lo && v[k] <= a.v_hi;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double du = u[(k + 1) & 3] - u[k], dv = v[(k + 1) & 3] - v[k];
-        ok = ok && du * du + dv * dv >= a.min_side2;
-    }
-    return ok;
-}
-
-// What lane 0 stores for pose p; have false: zero matrices and sigmas.
-__device__ __forceinline__ void store_pose(const PredictArgs& a, const int p, const bool have, const double (&P)[21],
-                                           const double (&Q)[21], const vmm_ba_predict_result& res)
-{
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            if (a.cov_px)
-                a.cov_px[36 * (int64_t)p + 6 * r + c] = have ? sym6(P, r, c) : 0.0;
-            if (a.cov_map)
-                a.cov_map[36 * (int64_t)p + 6 * r + c] = have ? sym6(Q, r, c) : 0.0;
-        }
-    if (a.res)
-        a.res[p] = res;
 }
 
 template <bool MAP>

@@ -259,6 +259,19 @@ class BundleAdjuster:
         cov = self.covariance_blocks(np.stack([idx, idx], axis=1), robustify, huber_a)
         return cov[:self.n_cams], cov[self.n_cams:]
 
+    def tag_joint_covariance(self, robustify=False, huber_a=1.0):
+        """(n_tags, n_tags, 6, 6): the tags' joint covariance, block [s, t] the cross block of tags s and t in tangent
+        order.  One covariance_blocks call for the pairs s >= t; the upper block triangle is filled here by transposition,
+        so that the array, read as a 6 n_tags x 6 n_tags matrix, is symmetric.  What predict_localization's
+        tag_cov_joint takes."""
+        T = self.n_tags
+        s, t = np.tril_indices(T)
+        cov = self.covariance_blocks(np.stack([self.n_cams + s, self.n_cams + t], axis=1), robustify, huber_a)
+        out = np.zeros((T, T, 6, 6))
+        out[t, s] = np.swapaxes(cov, 1, 2)
+        out[s, t] = cov   # last: the diagonal blocks as the call gave them
+        return out
+
     # ---- the camera model ----
     def set_intrinsics(self, intr, dist):
         """Replaces the handle's camera model (vmm_ba_set_intrinsics): every later call behaves as a handle created with
@@ -624,34 +637,82 @@ def default_predict_options(**kw):
 
 
 def predict_localization(intr, dist, tag_qt, tag_wh, cam_qt, image_size, tag_cov=None, device=0, want_visible=False,
-                         **options):
+                         tag_cov_joint=None, visible_in=None, **options):
     """How well a camera would be localised against a finished map at poses that have no image behind them
     (vmm_ba_predict_localization).  tag_qt (n_tags, 7) tag->world and tag_wh (n_tags, 2): the map.  cam_qt (n_poses, 7)
     world->camera.  image_size: (width, height) in pixels.  tag_cov (n_tags, 6, 6), optional: the tags' marginal
     covariances in tangent order.  options: the other fields of vmm_ba_predict_options.  Returns (cov_px (n_poses, 6, 6)
     the covariance the pixel noise causes, cov_map (n_poses, 6, 6) the part propagated from tag_cov, tag by tag without
     their correlations (zeros without tag_cov), results: one dict per pose with status, n_visible, sigma_pos_m,
-    sigma_rot_rad) and, with want_visible, visible (n_poses, n_tags) bool as a fourth.  Occlusion is not modelled."""
+    sigma_rot_rad) and, with want_visible, visible (n_poses, n_tags) bool as a fourth.  Occlusion is not modelled.
+    tag_cov_joint (n_tags, n_tags, 6, 6) or anything that reshapes to it, instead of tag_cov: the tags' joint covariance
+    (BundleAdjuster.tag_joint_covariance); cov_map then holds the part propagated with the correlations between the tags
+    (vmm_ba_predict_localization_joint; only the blocks [s, t] with s >= t are read).  visible_in (n_poses, n_tags), only
+    with tag_cov_joint: the tags that take part in every pose, instead of the visibility rules."""
+    if tag_cov is not None and tag_cov_joint is not None:
+        raise ValueError("tag_cov and tag_cov_joint are given both: a map has one covariance")
+    if visible_in is not None and tag_cov_joint is None:
+        raise ValueError("visible_in needs tag_cov_joint")
     intr, dist = _model_arrays(intr, dist)
     tag_qt = np.ascontiguousarray(tag_qt, np.float64).reshape(-1, 7)
     tag_wh = np.ascontiguousarray(tag_wh, np.float64).reshape(-1, 2)
     cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
     if len(tag_wh) != len(tag_qt):
         raise ValueError("tag_wh and tag_qt differ in length")
+    n_tags, n_poses = len(tag_qt), len(cam_qt)
     if tag_cov is not None:
         tag_cov = np.ascontiguousarray(tag_cov, np.float64).reshape(-1, 6, 6)
         if len(tag_cov) != len(tag_qt):
             raise ValueError("tag_cov and tag_qt differ in length")
+    if tag_cov_joint is not None:
+        tag_cov_joint = np.ascontiguousarray(tag_cov_joint, np.float64)
+        if tag_cov_joint.size != 36 * n_tags * n_tags:
+            raise ValueError("tag_cov_joint does not have 36 n_tags^2 entries")
+        tag_cov_joint = tag_cov_joint.reshape(n_tags, n_tags, 6, 6)
+    if visible_in is not None:
+        visible_in = np.ascontiguousarray(np.asarray(visible_in) != 0, np.uint8)
+        if visible_in.size != n_poses * n_tags:
+            raise ValueError("visible_in does not have n_poses x n_tags entries")
+        visible_in = visible_in.reshape(n_poses, n_tags)
     o = default_predict_options(image_width=int(image_size[0]), image_height=int(image_size[1]), **options)
-    n_tags, n_poses = len(tag_qt), len(cam_qt)
     cov_px, cov_map = np.zeros((n_poses, 6, 6)), np.zeros((n_poses, 6, 6))
     visible = np.zeros((n_poses, n_tags), np.uint8) if want_visible else None
     res = np.zeros(n_poses, np.dtype(_lib.PredictResult))
-    _lib.check(_lib.lib().vmm_ba_predict_localization(_ptr(intr), _ptr(dist), n_tags, _ptr(tag_qt), _ptr(tag_wh),
-                                                      _ptr(tag_cov), n_poses, _ptr(cam_qt), C.byref(o), _ptr(cov_px),
-                                                      _ptr(cov_map), _ptr(visible), _ptr(res), device))
+    if tag_cov_joint is None:
+        _lib.check(_lib.lib().vmm_ba_predict_localization(_ptr(intr), _ptr(dist), n_tags, _ptr(tag_qt), _ptr(tag_wh),
+                                                          _ptr(tag_cov), n_poses, _ptr(cam_qt), C.byref(o), _ptr(cov_px),
+                                                          _ptr(cov_map), _ptr(visible), _ptr(res), device))
+    else:
+        _lib.check(_lib.lib().vmm_ba_predict_localization_joint(_ptr(intr), _ptr(dist), n_tags, _ptr(tag_qt), _ptr(tag_wh),
+                                                                _ptr(tag_cov_joint), n_poses, _ptr(cam_qt), _ptr(visible_in),
+                                                                C.byref(o), _ptr(cov_px), _ptr(cov_map), _ptr(visible),
+                                                                _ptr(res), device))
     out = (cov_px, cov_map, _result_dicts(res))
     return out + (visible.astype(bool),) if want_visible else out
+
+
+def localization_map_covariance(intr, dist, tag_qt, tag_wh, cam_qt, img_start, obs_tag, obs_inlier, tag_cov_joint, image_size,
+                                device=0, **options):
+    """The part of a localisation's covariance that the map's own uncertainty causes, with the correlations between the
+    tags: one predict_localization call with tag_cov_joint and visible_in built from the localisation's inlier flags.
+    cam_qt (n_imgs, 7): the poses engine.localize returned; img_start, obs_tag: its batch; obs_inlier (n_obs,): the flags
+    it returned.  An image's selected tags are those of its inlier observations.  Returns (cov_px, cov_map, results,
+    visible_in) as predict_localization does; the response is that of the plain least-squares minimiser over the selected
+    tags (unit weights, no loss)."""
+    cam_qt = np.ascontiguousarray(cam_qt, np.float64).reshape(-1, 7)
+    img_start = np.asarray(img_start, np.int64).reshape(-1)
+    obs_tag, obs_inlier = np.asarray(obs_tag, np.int64).reshape(-1), np.asarray(obs_inlier).reshape(-1) != 0
+    n_tags = len(np.asarray(tag_qt).reshape(-1, 7))
+    if len(img_start) != len(cam_qt) + 1 or len(obs_tag) != len(obs_inlier) or (len(img_start) and img_start[-1] != len(obs_tag)):
+        raise ValueError("img_start must have n_imgs + 1 entries and end at the number of observations")
+    if len(obs_tag) and (obs_tag.min() < 0 or obs_tag.max() >= n_tags):
+        raise ValueError("obs_tag outside the map")
+    visible_in = np.zeros((len(cam_qt), n_tags), np.uint8)
+    img = np.repeat(np.arange(len(cam_qt)), np.diff(img_start))
+    visible_in[img[obs_inlier], obs_tag[obs_inlier]] = 1
+    cov_px, cov_map, res = predict_localization(intr, dist, tag_qt, tag_wh, cam_qt, image_size, device=device,
+                                                tag_cov_joint=tag_cov_joint, visible_in=visible_in, **options)
+    return cov_px, cov_map, res, visible_in.astype(bool)
 
 
 def grid_poses(lo, hi, shape, axes, up):

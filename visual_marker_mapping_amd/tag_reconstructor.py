@@ -464,6 +464,21 @@ class TagReconstructor:
         return (tag_ids, np.array([np.concatenate([t.q, t.t]) for t in tags], np.float64).reshape(-1, 7),
                 np.array([[t.tagWidth, t.tagHeight] for t in tags], np.float64).reshape(-1, 2))
 
+    def _joint_for_map(self, ids, joint):
+        """The tags' joint covariance (ids, (T, T, 6, 6)) in the order of _map_arrays: (n, n, 6, 6)."""
+        ids = [int(t) for t in ids]
+        joint = np.asarray(joint, np.float64)
+        if joint.size != 36 * len(ids) ** 2 or len(set(ids)) != len(ids):
+            raise ValueError("the joint covariance does not have one 6x6 block per pair of its %d tag ids" % len(ids))
+        joint = joint.reshape(len(ids), len(ids), 6, 6)
+        row = {t: k for k, t in enumerate(ids)}
+        missing = [t for t in sorted(self.reconstructedTags) if t not in row]
+        if missing:
+            raise RuntimeError("The joint covariance does not cover the map: no entry for tag %s."
+                               % ", ".join(str(t) for t in missing))
+        rows = np.array([row[t] for t in sorted(self.reconstructedTags)], np.int64)
+        return np.ascontiguousarray(joint[np.ix_(rows, rows)])
+
     @staticmethod
     def _item_report(res, pose, cov, order, inl, b, e):
         """One image's or frame's entry of a localisation report: the result's fields, the pose, its covariance and the
@@ -514,6 +529,38 @@ class TagReconstructor:
                 cams[i] = Camera(i, cam_qt[n, :4], cam_qt[n, 4:])
         self.lastLocalizationReport = report
         return cams
+
+    def localizationMapCovariances(self, tagJointCovariance, detectionResult=None, **options):
+        """The part of every localised image's covariance that the map's own uncertainty causes, with the correlations
+        between the tags, for the images of lastLocalizationReport (engine.localization_map_covariance: one
+        vmm_ba_predict_localization_joint call whose visible_in holds, per image with status OK, the tags of its inlier
+        observations; any other image selects nothing and gets zeros).  tagJointCovariance: (tag ids, (T, T, 6, 6)) as
+        computePoseCovariances(jointTags=True)["tag_joint"].  detectionResult: the one that was localised (default: the
+        reconstructor's own).  options: the fields of vmm_ba_predict_options.  Adds "map_covariance" (6, 6), "sigma_pos_m"
+        and "sigma_rot_rad" (from covariance-of-the-pixels + map_covariance) to every image's report and returns the
+        report.  The response is that of the plain least-squares minimiser over the selected tags."""
+        det = self.detectionResults_ if detectionResult is None else detectionResult
+        report = self.lastLocalizationReport
+        ids = sorted(report)
+        tag_ids, tag_qt, tag_wh = self._map_arrays()
+        dense = {t: k for k, t in enumerate(tag_ids)}
+        joint = self._joint_for_map(*tagJointCovariance)
+        img_start, obs_tag, inl = [0], [], []
+        for i in ids:
+            r = report[i]
+            ok = r["status"] == _engine._lib.LOC_OK
+            obs_tag += [dense[det.tagObservations[k].tagId] for k in r["observations"]]
+            inl += [bool(f) and ok for f in r["inliers"]]
+            img_start.append(len(obs_tag))
+        cam_qt = np.array([report[i]["pose"] for i in ids], np.float64).reshape(-1, 7)
+        size = (options.pop("image_width", self.camModel.horizontalResolution),
+                options.pop("image_height", self.camModel.verticalResolution))
+        _, cov_map, res, _ = _engine.localization_map_covariance(*self._model_args(), tag_qt, tag_wh, cam_qt, img_start, obs_tag, inl,
+                                                                 joint, size, device=self.device, **options)
+        for n, i in enumerate(ids):
+            report[i].update(map_covariance=cov_map[n].copy(), sigma_pos_m=res[n]["sigma_pos_m"],
+                             sigma_rot_rad=res[n]["sigma_rot_rad"])
+        return report
 
     def _pack_rig(self, det, frames, cameraModels, extrinsics, loc_options):
         """The flat arrays engine.rig_localize and engine.rig_calibrate take for `frames` (one list of K image ids per
@@ -749,7 +796,7 @@ class TagReconstructor:
         self.lastTagLocationReport = report
         return tags
 
-    def predictLocalizationAccuracy(self, cameras, tagCovariances=None, **options):
+    def predictLocalizationAccuracy(self, cameras, tagCovariances=None, tagJointCovariance=None, **options):
         """How well a camera would be localised against the reconstructed tags at poses that have no image behind them
         (vmm_ba_predict_localization).  cameras: {id: Camera} or an (n, 7) array of world->camera poses (ids 0..n-1).
         tagCovariances: {tagId: 6x6} in tangent order (computePoseCovariances()["tags"]); a tag without an entry (the
@@ -757,7 +804,14 @@ class TagReconstructor:
         to the camera model's horizontalResolution / verticalResolution.  Occlusion is not modelled.  Returns
         {id: {"status", "n_visible", "sigma_pos_m", "sigma_rot_rad", "pose" (7,), "covariance" (6, 6) from the pixel noise,
         "covariance_map" (6, 6) propagated from tagCovariances tag by tag, "visible_tags": [tag ids]}}.  The reference has
-        no such member."""
+        no such member.
+        tagJointCovariance: (tag ids, (T, T, 6, 6)) as computePoseCovariances(jointTags=True)["tag_joint"], instead of
+        tagCovariances: covariance_map is then propagated with the correlations between the tags
+        (vmm_ba_predict_localization_joint).  Its ids must cover the reconstructed tags."""
+        if tagJointCovariance is not None:
+            if tagCovariances is not None:
+                raise ValueError("tagCovariances and tagJointCovariance are given both: a map has one covariance")
+            options["tag_cov_joint"] = self._joint_for_map(*tagJointCovariance)
         if isinstance(cameras, dict):
             ids = sorted(int(k) for k in cameras)
             cams = {int(k): v for k, v in cameras.items()}
@@ -1100,20 +1154,28 @@ class TagReconstructor:
             avg_diag /= len(p["tag_ids"])
             print("Marker Position RMS = %.6g" % np.linalg.norm(np.sqrt(avg_diag)))
 
-    def computePoseCovariances(self, robustify=False):
+    def computePoseCovariances(self, robustify=False, jointTags=False):
         """The 6x6 covariance (tangent order: translation, then rotation) of every reconstructed tag and camera at the
         current poses, no solve: the problem doBundleAdjustment builds (origin tag and constantTagIds constant), then
         one vmm_ba_covariance_blocks call for all marginals.  Fills and returns self.lastPoseCovariances =
         {"tags": {id: 6x6}, "cameras": {id: 6x6}}; the origin tag and the constant tags are zeros.  Not in the
-        reference, which asks Ceres for the tags' (t, t) blocks only (src/TagReconstructor.cpp:744-783)."""
+        reference, which asks Ceres for the tags' (t, t) blocks only (src/TagReconstructor.cpp:744-783).
+        jointTags: one more call for the tags' cross blocks; "tag_joint": (tag ids, (T, T, 6, 6)) holds the tags' joint
+        covariance, block [i, j] that of tag_ids[i] and tag_ids[j] (BundleAdjuster.tag_joint_covariance)."""
         self.lastPoseCovariances = {"tags": {}, "cameras": {}}
         p = self._pack(for_ba=True)
         if self._is_empty(p):
             return self.lastPoseCovariances
+        joint = None
         with self._handle(p, elimination=_engine.ELIM_AUTO) as ba:
             cam_cov, tag_cov = ba.pose_covariances(robustify, _engine.default_options().huber_a)
+            if jointTags:
+                joint = ba.tag_joint_covariance(robustify, _engine.default_options().huber_a)
         self.lastPoseCovariances["tags"] = {t: tag_cov[k].copy() for k, t in zip(p["tag_rows"], p["tag_ids"])}
         self.lastPoseCovariances["cameras"] = {c: cam_cov[k].copy() for k, c in zip(p["cam_rows"], p["cam_ids"])}
+        if jointTags:
+            rows = np.asarray(list(p["tag_rows"]), np.int64)
+            self.lastPoseCovariances["tag_joint"] = ([int(t) for t in p["tag_ids"]], joint[np.ix_(rows, rows)].copy())
         return self.lastPoseCovariances
 
     def doBundleAdjustment_points(self, maxNumIterations, ceresThreads=1, printSummary=False,

@@ -15,8 +15,8 @@ for bit, on the CPU the start or the host optimum.  At that state
                                the candidate is k + dk and pose_plus of every pose and extrinsic
 
 Truth.  np.longdouble: eval_cases.corner_chain for the residuals and the pose columns (for the rig the camera stands at
-ext_c o rig_f and the columns are turned as finished_map_cases.RigCase.chain turns them), cov_cases.model_columns for the
-nine model columns, and the extrinsic columns derived here from vmm_ba.h's definition: extrinsic c moves in its own
+ext_c o rig_f and the columns are turned by ref_geometry.turn_to_rig, as finished_map_cases.RigCase.chain's),
+cov_cases.model_columns for the nine model columns, and ref_geometry.extrinsic_columns, derived from vmm_ba.h's definition: extrinsic c moves in its own
 tangent as vmm_ba_pose_plus moves a pose, so a step (ds, dphi) gives t_c + ds and R(2 dphi) R_c, the camera
 R(2 dphi) R_c R_f, R(2 dphi) R_c t_f + t_c + ds: it moves by (ds + 2 dphi x (R_c t_f), dphi) in its own tangent, and
 J_ext = [Jc_t | Jc_r - 2 Jc_t [R_c t_f]x].  The whole matrix is inverted at once (whole_inverse: cov_cases.refined_inverse,
@@ -24,7 +24,7 @@ and for orders above DENSE_LIMIT the same Newton iteration with the residual in 
 correction multiplied in float64) -- deliberately not the device's scheme, which eliminates every item and uses
 A^-1 + A^-1 B S^-1 B^T A^-1.
 
-References.  A: the oracle's functor through yardstick.calib_system / rig_cases.rig_system with np.linalg.inv and
+References (B's small algebra and summation orders: ref_algebra.py).  A: the oracle's functor through yardstick.calib_system / rig_cases.rig_system with np.linalg.inv and
 np.linalg.solve on the full matrix; the per-item cost and rms through finished_map_cases' reference A.  B: the device's
 scheme in float64, read from arrowhead.hpp, kernels_calibrate.hip and kernels_rig.hip: row pairs scaled by sqrt(rho'), sums
 in list order, the damped 6 x 6 Cholesky per item, Y = L^-1 B, y = L^-1 g, the records C_i - Y'Y, g_s - Y'y summed in four
@@ -41,8 +41,11 @@ import numpy as np
 import cov_cases as cc
 import eval_cases as ec
 import finished_map_cases as fm
+import ref_algebra as ra
+import ref_geometry as rg
 import rig_cases as rc
 import yardstick as ys
+from ref_geometry import pose_minus, pose_plus
 
 LD = cc.LD
 MARGIN = ec.MARGIN
@@ -70,30 +73,6 @@ RIG_CAMS = (2, 3, 4, 8)
 SECOND_TRIP = 258
 QUANTITIES = ("cost", "rms", "shared_cov", "item_cov", "step_shared", "step_pose")
 REFS = ("A oracle, numpy inverse", "B device scheme")
-
-
-# ---- poses in any precision ------------------------------------------------------------------------------------------------
-
-def pose_plus(qt, d, dtype=LD):
-    """vmm_ba_pose_plus: the translation added, the quaternion multiplied from the left by (cos |d|, sin |d| d / |d|)."""
-    qt, d = np.asarray(qt, dtype), np.asarray(d, dtype)
-    out = qt.copy()
-    out[4:] = qt[4:] + d[:3]
-    nd = np.sqrt((d[3:] * d[3:]).sum())
-    if nd > 0:
-        out[:4] = ec._qmul(np.concatenate([[np.cos(nd)], np.sin(nd) / nd * d[3:]]), qt[:4])
-    return out
-
-
-def pose_minus(a, b, dtype=LD):
-    """The tangent d with pose_plus(b, d) = a (the quaternions taken as rotations: their lengths and signs do not count)."""
-    a, b = np.asarray(a, dtype), np.asarray(b, dtype)
-    z = ec._qmul(a[:4], np.concatenate([b[:1], -b[1:4]]))
-    z = z / np.sqrt((z * z).sum())
-    z = -z if z[0] < 0 else z
-    nv = np.sqrt((z[1:] * z[1:]).sum())
-    rot = z[1:] * (np.arctan2(nv, z[0]) / nv) if nv > 0 else np.zeros(3, dtype)
-    return np.concatenate([a[4:] - b[4:], rot])
 
 
 # ---- the inverse of the whole matrix -----------------------------------------------------------------------------------------
@@ -127,54 +106,6 @@ def whole_inverse(H, n_items, force_mixed=False):
     return s[:, None] * X * s[None, :], s[:, None] * corr * s[None, :]
 
 
-# ---- the device's small algebra in float64 -----------------------------------------------------------------------------------
-
-def _chol(A):
-    """Lower Cholesky factor, column by column, every entry's updates in ascending k (small_solve.hpp's cholesky)."""
-    n = len(A)
-    L = np.zeros((n, n))
-    for j in range(n):
-        d = A[j, j]
-        for k in range(j):
-            d = d - L[j, k] * L[j, k]
-        L[j, j] = np.sqrt(d)
-        inv = 1.0 / L[j, j]
-        for i in range(j + 1, n):
-            v = A[i, j]
-            for k in range(j):
-                v = v - L[i, k] * L[j, k]
-            L[i, j] = v * inv
-    return L
-
-
-def _forward(L, b):
-    """L^-1 b, b a vector or the columns of a matrix."""
-    out = np.zeros_like(b, dtype=np.float64)
-    for i in range(len(L)):
-        v = b[i]
-        for k in range(i):
-            v = v - L[i, k] * out[k]
-        out[i] = v / L[i, i]
-    return out
-
-
-def _backward(L, b):
-    """L^-T b."""
-    out = np.zeros_like(b, dtype=np.float64)
-    for i in range(len(L) - 1, -1, -1):
-        v = b[i]
-        for k in range(i + 1, len(L)):
-            v = v - L[k, i] * out[k]
-        out[i] = v / L[i, i]
-    return out
-
-
-def _chains(x):
-    """The records of all items summed in four interleaved chains (item i in chain i mod 4), combined ((0 + 1) + 2) + 3."""
-    t = [fm._ordered_sum(x[g::4]) if len(x[g::4]) else np.zeros(x.shape[1:]) for g in range(4)]
-    return ((t[0] + t[1]) + t[2]) + t[3]
-
-
 def _rel(got, truth):
     return float(abs(LD(got) - truth) / truth)
 
@@ -192,12 +123,7 @@ class ArrowCase:
     def span(self, i):
         return int(self.scene.start[i]), int(self.scene.start[i + 1])
 
-    def _loss(self, r, dtype):
-        sq = (r * r).sum(axis=-1)
-        if not self.robust:
-            return sq, sq, np.ones_like(sq)
-        rho = ec.huber(self.a, sq, dtype)
-        return sq, rho[..., 0], rho[..., 1]
+    loss_terms = fm.Case.loss_terms
 
     def flags_list(self, obs_flags):
         return [np.asarray(obs_flags[slice(*self.span(i))], bool) for i in range(self.n_items)]
@@ -212,7 +138,7 @@ class ArrowCase:
         r, Jp, Js = self.columns(i, shared, pose, dtype)
         J = np.concatenate([Jp, np.where(self.held(), dtype(0), Js)], axis=-1)[on]
         r = r[on]
-        sq, rho0, rho1 = self._loss(r, dtype)
+        sq, rho0, rho1 = self.loss_terms(r, dtype)
         if not ordered:
             return (np.einsum("mk,mkrp,mkrq->pq", rho1, J, J), np.einsum("mk,mkrp,mkr->p", rho1, J, r), rho0.sum(dtype=dtype),
                     sq.sum(dtype=dtype))
@@ -222,9 +148,9 @@ class ArrowCase:
         N = np.zeros((n, n))
         for m in range(0, len(J), 64):      # in pieces: a frame of 513 observations at P = 48 is 48 MB of products at once
             Pm = J[m:m + 64, :, 0, :, None] * J[m:m + 64, :, 0, None, :] + J[m:m + 64, :, 1, :, None] * J[m:m + 64, :, 1, None, :]
-            N = fm._ordered_sum(np.concatenate([N[None], Pm.reshape(-1, n, n)]))
-        g = fm._ordered_sum((J[:, :, 0, :] * r[:, :, 0, None] + J[:, :, 1, :] * r[:, :, 1, None]).reshape(-1, n))
-        return N, g, fm._ordered_sum(rho0.reshape(-1)), fm._ordered_sum(sq.reshape(-1))
+            N = ra.ordered_sum(np.concatenate([N[None], Pm.reshape(-1, n, n)]))
+        g = ra.ordered_sum((J[:, :, 0, :] * r[:, :, 0, None] + J[:, :, 1, :] * r[:, :, 1, None]).reshape(-1, n))
+        return N, g, ra.ordered_sum(rho0.reshape(-1)), ra.ordered_sum(sq.reshape(-1))
 
     # -- the truth --
     def truth(self, shared, poses, flags, part, lam=None):
@@ -275,7 +201,7 @@ class ArrowCase:
         for i in range(self.n_items):
             if part[i]:
                 r, _, _ = self.columns(i, shared, poses[i], LD)
-                total += self._loss(r[flags[i]], LD)[1].sum(dtype=LD)
+                total += self.loss_terms(r[flags[i]], LD)[1].sum(dtype=LD)
         return total / LD(2)
 
     def classify(self, shared, poses):
@@ -324,10 +250,8 @@ class ArrowCase:
         elim = {}
         for i in items:
             N, gv, rho, sq = self.item_sums(i, shared, poses[i], flags[i], np.float64, ordered=True)
-            A = N[:6, :6].copy()
-            A[np.diag_indices(6)] += damp * np.maximum(np.diag(A), 1e-12)
-            L = _chol(A)
-            Yy = _forward(L, np.column_stack([N[:6, 6:], gv[:6]]))
+            L = ra.cholesky(ra.damped(N[:6, :6], damp))
+            Yy = ra.forward(L, np.column_stack([N[:6, 6:], gv[:6]]))
             Y, y = Yy[:, :P], Yy[:, P]
             S, gs = N[6:, 6:].copy(), gv[6:].copy()
             for k in range(6):
@@ -335,7 +259,7 @@ class ArrowCase:
                 gs = gs - Y[k] * y[k]
             rec_S[i], rec_g[i], rec_d[i], stat[i] = S, gs, np.diag(N[6:, 6:]), (rho, sq, float(np.sum(flags[i])))
             elim[i] = (L, Y, y)
-        S, gs, Cd, st = _chains(rec_S), _chains(rec_g), _chains(rec_d), _chains(stat)
+        S, gs, Cd, st = ra.chains4(rec_S), ra.chains4(rec_g), ra.chains4(rec_d), ra.chains4(stat)
         act = ~self.held() & (self.active_probe(Cd) > 0)
         free = np.flatnonzero(act)
         d = np.where(act, np.diag(S) + damp * Cd, 1.0)
@@ -345,21 +269,21 @@ class ArrowCase:
         out = dict(cost={i: 0.5 * stat[i, 0] for i in items}, rms={i: np.sqrt(stat[i, 1] / (4.0 * stat[i, 2])) for i in items},
                    final_cost=0.5 * st[0], final_rms=np.sqrt(st[1] / (4.0 * st[2])), free=free)
         if lam is None:
-            Si = np.where(act[:, None] & act[None, :], fm.spd_inverse_f64(M) * sc[:, None] * sc[None, :], 0.0)
+            Si = np.where(act[:, None] & act[None, :], ra.spd_inverse(M) * sc[:, None] * sc[None, :], 0.0)
             out["shared_cov"], out["item_cov"] = Si, {}
             for i in items:
                 L, Y, _ = elim[i]
-                W = _forward(L, np.eye(6))
+                W = ra.forward(L, np.eye(6))
                 cov = W.T @ ((np.eye(6) + (Y @ Si) @ Y.T) @ W)
                 out["item_cov"][i] = np.tril(cov) + np.tril(cov, -1).T
             return out
-        Lm = _chol(M)
-        ds = _backward(Lm, _forward(Lm, np.where(act, -gs * sc, 0.0))) * sc
+        Lm = ra.cholesky(M)
+        ds = ra.backward(Lm, ra.forward(Lm, np.where(act, -gs * sc, 0.0))) * sc
         ds = np.where(act, ds, 0.0)
         out.update(shared_cand=self.shared_plus(shared, ds, np.float64), pose_cand={})
         for i in items:
             L, Y, y = elim[i]
-            out["pose_cand"][i] = pose_plus(poses[i], _backward(L, -(y + Y @ ds)), np.float64)
+            out["pose_cand"][i] = pose_plus(poses[i], ra.backward(L, -(y + Y @ ds)), np.float64)
         return out
 
     def active_probe(self, Cd):
@@ -525,22 +449,16 @@ class RigCalCase(ArrowCase):
         """r (m, 4, 2), the rig columns (m, 4, 2, 6) and the extrinsic columns (m, 4, 2, 6 K: six per observation that are
         not zero, its camera's) of frame i; the module's docstring derives them."""
         s, (b, e) = self.scene, self.span(i)
-        rig = np.asarray(pose, dtype)
-        rq = rig[:4] / np.sqrt((rig[:4] * rig[:4]).sum())
         r, Jr, Je = np.zeros((e - b, 4, 2), dtype), np.zeros((e - b, 4, 2, 6), dtype), np.zeros((e - b, 4, 2, self.P), dtype)
         for c in np.unique(s.obs_cam[b:e]):
             of = np.flatnonzero(s.obs_cam[b:e] == c)
-            ext = np.asarray(shared[c], dtype)
-            eq = ext[:4] / np.sqrt((ext[:4] * ext[:4]).sum())
-            Rc = ec._rotation(ext[None, :4], dtype)[0]
-            v = Rc @ rig[4:]
-            cam = np.concatenate([ec._qmul(eq, rq), v + ext[4:]])
+            cam, Rc, v = rg.compose_rig(shared[c], pose, dtype)
             t = s.obs_tag[b:e][of]
             rr, _, Jc, _ = ec.corner_chain(s.intr[c], s.dist[c], np.tile(cam, (len(of), 1)), s.tag_gt[t], s.tag_wh[t],
                                            s.obs_px[b:e][of], dtype)
             r[of] = rr
-            Jr[of] = np.concatenate([Jc[..., :3] @ Rc, Jc[..., 3:] @ Rc], axis=-1)
-            Je[of, :, :, 6 * c:6 * c + 6] = np.concatenate([Jc[..., :3], Jc[..., 3:] - dtype(2) * (Jc[..., :3] @ ec._skew(v))], axis=-1)
+            Jr[of] = rg.turn_to_rig(Jc, Rc)
+            Je[of, :, :, 6 * c:6 * c + 6] = rg.extrinsic_columns(Jc, v, dtype)
         return r, Jr, Je
 
     def shared_plus(self, shared, d, dtype):
@@ -602,7 +520,6 @@ RIG_TRIAL_CASES = [(K, True, l, None) for K in (2, 4, 8) for l in ("plain", "hub
 
 def case_id(args):
     """K2-outliers-plain-default for an edge case (mask: default or hexadecimal), n5-huber0.5-inactive for a batch of n."""
-    edge = len(args) == 4
-    return "-".join("mask%x" % a if edge and i == 3 and a is not None else "default" if a is None else
-                    ("outliers" if a else "clean") if edge and isinstance(a, bool) else ("inactive" if a else "active") if isinstance(a, bool)
-                    else (("K%d" if edge else "n%d") % a if isinstance(a, int) else str(a)) for i, a in enumerate(args))
+    if len(args) == 4:
+        return fm.case_id(args[:3]) + ("-default" if args[3] is None else "-mask%x" % args[3])
+    return "-".join(("inactive" if a else "active") if isinstance(a, bool) else "n%d" % a if isinstance(a, int) else str(a) for a in args)

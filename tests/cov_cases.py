@@ -13,7 +13,7 @@ starts from.  The one difference is around the call, not in it: cov_factor_and f
 (CovDensePath); neither is read by launch_eval_passes' kernels at use_ctl = false.
 
 H is the dense normal matrix over the free, active poses (cameras first, then tags), as
-yardstick.free_system builds it.
+yardstick.free_system builds it.  The geometry of the model columns is ref_geometry.py's (conventions there).
 
 Truth.  inv(H) in np.longdouble, in eliminated form: rows and columns scaled by powers of two near 1 / sqrt(H_ii) (exact,
 and the metric below does not see it), the larger family eliminated by its 6x6 blocks, the small reduced matrix inverted by
@@ -31,6 +31,8 @@ Never a figure that the kernels produced.
 import numpy as np
 
 import eval_cases as ec
+import ref_geometry as rg
+import yardstick as ys
 from linalg_cases import MARGIN, refined_solution
 
 LD = np.longdouble
@@ -207,7 +209,7 @@ def cpu_blocks(sc):
 
 def free_poses(sc):
     """(free cameras, free tags): not constant, not the origin, at least one observation that is switched on."""
-    cc, tc = ec._flags(sc, sc.cam_const, sc.tag_const)
+    cc, tc = ec.flags(sc, sc.cam_const, sc.tag_const)
     on = np.ones(sc.n_obs, bool) if sc.mask is None else np.asarray(sc.mask) != 0
     seen_c = np.bincount(sc.obs_cam[on], minlength=len(sc.cam_qt)) > 0
     seen_t = np.bincount(sc.obs_tag[on], minlength=len(sc.tag_qt)) > 0
@@ -215,29 +217,15 @@ def free_poses(sc):
 
 
 def free_system(sc, blk):
-    """Dense H over the free poses (cameras, then tags) from V, U, W, as yardstick.free_system; the blocks
-    of every other pose must be zero.  Returns (H, free cameras, free tags)."""
+    """Dense H over the free poses (cameras, then tags) from V, U, W by yardstick.free_system; the blocks of every other
+    pose and of every switched-off observation must be zero.  Returns (H, free cameras, free tags)."""
     fc, ft = free_poses(sc)
     on = np.ones(sc.n_obs, bool) if sc.mask is None else np.asarray(sc.mask) != 0
-    pos_c = -np.ones(len(sc.cam_qt), int)
-    pos_c[fc] = np.arange(len(fc))
-    pos_t = -np.ones(len(sc.tag_qt), int)
-    pos_t[ft] = len(fc) + np.arange(len(ft))
-    assert not np.asarray(blk["V"])[pos_c < 0].any() and not np.asarray(blk["U"])[pos_t < 0].any()
-    n = 6 * (len(fc) + len(ft))
-    H = np.zeros((n, n))
-    for c in fc:
-        H[6 * pos_c[c]:6 * pos_c[c] + 6, 6 * pos_c[c]:6 * pos_c[c] + 6] = blk["V"][c]
-    for t in ft:
-        H[6 * pos_t[t]:6 * pos_t[t] + 6, 6 * pos_t[t]:6 * pos_t[t] + 6] = blk["U"][t]
-    for i, (c, t) in enumerate(zip(sc.obs_cam.tolist(), sc.obs_tag.tolist())):
-        if pos_c[c] >= 0 and pos_t[t] >= 0 and on[i]:
-            a, b = 6 * pos_c[c], 6 * pos_t[t]
-            H[a:a + 6, b:b + 6] += blk["W"][i]
-            H[b:b + 6, a:a + 6] += blk["W"][i].T
-        else:
-            assert not np.asarray(blk["W"][i]).any(), i
-    return H, fc, ft
+    held_c, held_t = np.ones(len(sc.cam_qt), bool), np.ones(len(sc.tag_qt), bool)
+    held_c[fc], held_t[ft] = False, False
+    assert not np.asarray(blk["V"])[held_c].any() and not np.asarray(blk["U"])[held_t].any()
+    assert not np.asarray(blk["W"])[held_c[sc.obs_cam] | held_t[sc.obs_tag] | ~on].any()
+    return ys.free_system(sc, blk, held_c, held_t)[0], fc, ft
 
 
 class Case:
@@ -335,17 +323,10 @@ def model_columns(intr, dist, cam_qt, tag_qt, wh, dtype=LD, want_magnitude=False
     cam_qt, tag_qt = np.asarray(cam_qt, dtype).reshape(-1, 7), np.asarray(tag_qt, dtype).reshape(-1, 7)
     wh = np.asarray(wh, dtype).reshape(-1, 2)
     two = dtype(2)
-    Rc, Rt = ec._rotation(cam_qt[:, :4], dtype), ec._rotation(tag_qt[:, :4], dtype)
-    local = np.zeros((len(wh), 4, 3), dtype)
-    local[:, :, :2] = ec._CORNER_SIGNS.astype(dtype)[None] * (wh / two)[:, None, :]
-    pw = np.einsum("nij,nkj->nki", Rt, local) + tag_qt[:, None, 4:]
-    pc = np.einsum("nij,nkj->nki", Rc, pw) + cam_qt[:, None, 4:]
+    pc, Rc, _, _ = rg.camera_points(cam_qt, tag_qt, wh, dtype, parts=True)
 
-    def columns(x, y, fx, fy, k1, k2, p1, p2, k3):
-        r2 = x * x + y * y
-        rad = dtype(1) + r2 * (k1 + r2 * (k2 + r2 * k3))
-        xd = x * rad + two * p1 * x * y + p2 * (r2 + two * x * x)
-        yd = y * rad + two * p2 * x * y + p1 * (r2 + two * y * y)
+    def columns(x, y, fx, fy, *k):
+        xd, yd, r2, _ = rg.distort(x, y, k, dtype)
         zero, one = np.zeros_like(x), np.ones_like(x)
         Ju = np.stack([xd, zero, one, zero, fx * x * r2, fx * x * r2 * r2, fx * two * x * y, fx * (r2 + two * x * x),
                        fx * x * r2 * r2 * r2], axis=-1)
@@ -356,13 +337,13 @@ def model_columns(intr, dist, cam_qt, tag_qt, wh, dtype=LD, want_magnitude=False
     Jk = columns(pc[..., 0] / pc[..., 2], pc[..., 1] / pc[..., 2], intr[0], intr[1], *dist)
     if not want_magnitude:
         return Jk
-    pw_m = np.einsum("nij,nkj->nki", np.abs(Rt), np.abs(local)) + np.abs(tag_qt[:, None, 4:])
+    pw_m = np.einsum("nij,nkj->nki", np.abs(rg.rotation(tag_qt, dtype)), np.abs(rg.local_corners(wh, dtype))) + np.abs(tag_qt[:, None, 4:])
     pc_m = np.einsum("nij,nkj->nki", np.abs(Rc), pw_m) + np.abs(cam_qt[:, None, 4:])
     iz = dtype(1) / np.abs(pc[..., 2])
     return Jk, columns(pc_m[..., 0] * iz, pc_m[..., 1] * iz, abs(intr[0]), abs(intr[1]), *np.abs(dist))
 
 
-def _border_sums(sc, k, robust, mask, dtype):
+def border_sums(sc, k, robust, mask, dtype):
     """A (dense, over the free poses), B (rows of A x 9), g, C, g_k, cost in `dtype` from the restated chain."""
     s = CovScene(**dict(sc.__dict__, intr=np.asarray(k[:4], np.float64), dist=np.asarray(k[4:], np.float64), mask=mask,
                         robust=robust))
@@ -416,9 +397,8 @@ class ModelCase:
     MARGIN x the larger deviation."""
 
     def __init__(self, O, sc, k, robust, mask):
-        from yardstick import joint_system, reduced_system
         self.scene, self.k, self.robust, self.mask = sc, np.asarray(k, np.float64), robust, mask
-        A, B, g, C, gk, cost = _border_sums(sc, self.k, robust, mask, LD)
+        A, B, g, C, gk, cost = border_sums(sc, self.k, robust, mask, LD)
         X = refined_solution(A.astype(np.float64), np.column_stack([B, g]))
         # refined_solution's residual is against the float64 rounding of A: two more rounds against A itself
         A64 = A.astype(np.float64)
@@ -434,13 +414,13 @@ class ModelCase:
         # reference A and the oracle's float64 quantities for C, g_k and the cost (test_gpu_selfcal.py's comparison)
         on = None if mask is None else np.asarray(mask) != 0
         n6 = 6 * (len(sc.cam_qt) + len(sc.tag_qt))
-        cc, tc = ec._flags(sc, sc.cam_const, sc.tag_const)
-        o_cost, r, J, rmag = joint_system(O, self.k, sc.cam_qt, sc.tag_qt, sc.tag_wh, sc.fixed_tag, sc.obs_cam, sc.obs_tag,
+        cc, tc = ec.flags(sc, sc.cam_const, sc.tag_const)
+        o_cost, r, J, rmag = ys.joint_system(O, self.k, sc.cam_qt, sc.tag_qt, sc.tag_wh, sc.fixed_tag, sc.obs_cam, sc.obs_tag,
                                           sc.obs_px, robust, obs_on=on, cam_const=cc, tag_const=tc, want_magnitude=True)
-        gk_o, C_o, rk_o, Sk_o = reduced_system(r, J, n6)
+        gk_o, C_o, rk_o, Sk_o = ys.reduced_system(r, J, n6)
         Jk_abs = np.abs(J[:, n6:])
         self.oracle = dict(cost=o_cost, g_k=gk_o, C=C_o, mag_C=Jk_abs.T @ Jk_abs, mag_g=Jk_abs.T @ rmag)
-        A6, B6, g6, C6, gk6, _ = _border_sums(sc, self.k, robust, mask, np.float64)
+        A6, B6, g6, C6, gk6, _ = border_sums(sc, self.k, robust, mask, np.float64)
         Y = np.linalg.solve(np.linalg.cholesky(A6), np.column_stack([B6, g6]))
         self.refs = {"A oracle reduced_system": self.deviation(Sk_o, rk_o),
                      "B device form": self.deviation(C6 - Y[:, :9].T @ Y[:, :9], gk6 - Y[:, :9].T @ Y[:, 9])}
@@ -459,12 +439,11 @@ MODEL_VARIANTS = (("plain", False, False), ("robust", True, False), ("masked", T
 def model_case(O, name, variant):
     """ragged_tags / ragged_cams with ragged_constants at k = truth + 0.01 PERTURB (test_system_matches_the_host_jacobian):
     plain, robust, and robust with ragged_mask."""
-    from yardstick import PERTURB
     label, robust, masked = next(v for v in MODEL_VARIANTS if v[0] == variant)
 
     def make():
         sc = scene(name)
-        k = np.concatenate([sc.intr, sc.dist]) + 0.01 * PERTURB
+        k = np.concatenate([sc.intr, sc.dist]) + 0.01 * ys.PERTURB
         return ModelCase(O, sc, k, robust, ec.ragged_mask(sc) if masked else None)
     return ec.cached(("cov model case", name, label), make)
 

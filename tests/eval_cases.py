@@ -2,8 +2,8 @@
 tools/eval_accuracy.py).  numpy only: nothing here calls the engine.
 
 The corner chain (tag corner -> world -> camera -> distorted pixel -> residual, its 2x6 tangent Jacobians, the Huber
-weight) is restated from the formulas of tests/golden/make_kats.py, vectorised over observations, in a dtype of the
-caller's choice:
+weight) is restated from the formulas of tests/golden/make_kats.py over ref_geometry.py's pieces (conventions there),
+vectorised over observations, in a dtype of the caller's choice:
 
     np.longdouble   the reference every deviation is measured against
     np.float64      reference B: what a plain f64 evaluation achieves
@@ -24,13 +24,14 @@ import os
 
 import numpy as np
 
+import ref_geometry as rg
+
 LD = np.longdouble
 MARGIN = 8.0          # the device may deviate 8 x as far as the worse of references A and B (tests/linalg_cases.py)
 ARRAYS = ("V", "U", "W", "g_cam", "g_tag", "cost")
 README_INTR = [8.0752937867635346e+03, 8.0831676114192869e+03, 3.0163896805084278e+03, 1.9962896554785455e+03]
 README_DIST = [-1.8618183262669760e-01, 3.7018092365577054e-01, -2.9390604003594177e-04, 4.1533180829908799e-04,
                5.7043887874185996e-02]
-_CORNER_SIGNS = np.array([[-1.0, -1.0], [1.0, -1.0], [1.0, 1.0], [-1.0, 1.0]])   # LL, LR, UR, UL
 
 
 class Scene:
@@ -46,26 +47,6 @@ class Scene:
 
 # ---- the corner chain -------------------------------------------------------------------------------------------------
 
-def _rotation(q, dtype):
-    """(n, 3, 3) rotation of q / |q| (make_kats.quat_rotate)."""
-    q = np.asarray(q, dtype)
-    q = q / np.sqrt((q * q).sum(axis=1, keepdims=True))
-    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    one, two = dtype(1), dtype(2)
-    R = np.stack([one - two * (y * y + z * z), two * (x * y - w * z), two * (x * z + w * y),
-                  two * (x * y + w * z), one - two * (x * x + z * z), two * (y * z - w * x),
-                  two * (x * z - w * y), two * (y * z + w * x), one - two * (x * x + y * y)], axis=1)
-    return R.reshape(-1, 3, 3)
-
-
-def _skew(v):
-    """(..., 3, 3) matrix [v]x with [v]x u = v x u."""
-    z = np.zeros_like(v[..., 0])
-    return np.stack([np.stack([z, -v[..., 2], v[..., 1]], axis=-1),
-                     np.stack([v[..., 2], z, -v[..., 0]], axis=-1),
-                     np.stack([-v[..., 1], v[..., 0], z], axis=-1)], axis=-2)
-
-
 def corner_chain(intr, dist, cam_qt, tag_qt, wh, px, dtype=LD, want_magnitude=False):
     """n observations: cam_qt (n, 7), tag_qt (n, 7), wh (n, 2), px (n, 8).  Returns the residuals r (n, 4, 2), the
     projections proj (n, 4, 2) and the tangent Jacobians Jc, Jt (n, 4, 2, 6) (translation, then half-angle rotation:
@@ -77,20 +58,11 @@ def corner_chain(intr, dist, cam_qt, tag_qt, wh, px, dtype=LD, want_magnitude=Fa
     cam_qt, tag_qt = np.asarray(cam_qt, dtype).reshape(-1, 7), np.asarray(tag_qt, dtype).reshape(-1, 7)
     wh, px = np.asarray(wh, dtype).reshape(-1, 2), np.asarray(px, dtype).reshape(-1, 4, 2)
     two = dtype(2)
-    Rc, Rt = _rotation(cam_qt[:, :4], dtype), _rotation(tag_qt[:, :4], dtype)
-    local = np.zeros((len(wh), 4, 3), dtype)
-    local[:, :, :2] = _CORNER_SIGNS.astype(dtype)[None] * (wh / two)[:, None, :]
-    a = np.einsum("nij,nkj->nki", Rt, local)                  # R_t p
-    pw = a + tag_qt[:, None, 4:]
-    b = np.einsum("nij,nkj->nki", Rc, pw)                     # R_c P_w
-    pc = b + cam_qt[:, None, 4:]
+    pc, Rc, a, b = rg.camera_points(cam_qt, tag_qt, wh, dtype, parts=True)      # a = R_t p, b = R_c P_w
     x, y = pc[..., 0] / pc[..., 2], pc[..., 1] / pc[..., 2]
     k1, k2, p1, p2, k3 = dist
-    r2 = x * x + y * y
-    rad = dtype(1) + r2 * (k1 + r2 * (k2 + r2 * k3))
-    xd = x * rad + two * p1 * x * y + p2 * (r2 + two * x * x)
-    yd = y * rad + two * p2 * x * y + p1 * (r2 + two * y * y)
-    proj = np.stack([intr[0] * xd + intr[2], intr[1] * yd + intr[3]], axis=-1)
+    xd, yd, r2, rad = rg.distort(x, y, dist, dtype)
+    proj = rg.pixel(intr, xd, yd)
     r = proj - px
     # d(xd, yd) / d(x, y)
     drad = k1 + r2 * (two * k2 + dtype(3) * k3 * r2)          # d rad / d r2
@@ -107,15 +79,15 @@ def corner_chain(intr, dist, cam_qt, tag_qt, wh, px, dtype=LD, want_magnitude=Fa
     Pi[..., 0, 2] = -x * iz
     Pi[..., 1, 2] = -y * iz
     G = np.einsum("r,nkrs,nksj->nkrj", intr[:2], D, Pi)       # d residual / d P_c  (n, 4, 2, 3)
-    Jc = np.concatenate([G, -two * np.einsum("nkri,nkij->nkrj", G, _skew(b))], axis=-1)
+    Jc = np.concatenate([G, -two * np.einsum("nkri,nkij->nkrj", G, rg.skew(b))], axis=-1)
     Gw = np.einsum("nkri,nij->nkrj", G, Rc)                   # d residual / d P_w
-    Jt = np.concatenate([Gw, -two * np.einsum("nkri,nkij->nkrj", Gw, _skew(a))], axis=-1)
+    Jt = np.concatenate([Gw, -two * np.einsum("nkri,nkij->nkrj", Gw, rg.skew(a))], axis=-1)
     if not want_magnitude:
         return r, proj, Jc, Jt
     Ga = np.einsum("r,nkrs,nksj->nkrj", np.abs(intr[:2]), np.abs(D), np.abs(Pi))
-    Jc_mag = np.concatenate([Ga, two * np.einsum("nkri,nkij->nkrj", Ga, np.abs(_skew(b)))], axis=-1)
+    Jc_mag = np.concatenate([Ga, two * np.einsum("nkri,nkij->nkrj", Ga, np.abs(rg.skew(b)))], axis=-1)
     Gwa = np.einsum("nkri,nij->nkrj", Ga, np.abs(Rc))
-    Jt_mag = np.concatenate([Gwa, two * np.einsum("nkri,nkij->nkrj", Gwa, np.abs(_skew(a)))], axis=-1)
+    Jt_mag = np.concatenate([Gwa, two * np.einsum("nkri,nkij->nkrj", Gwa, np.abs(rg.skew(a)))], axis=-1)
     return r, proj, Jc, Jt, Jc_mag, Jt_mag
 
 
@@ -136,7 +108,8 @@ def huber(a, s, dtype=LD):
 
 # ---- the blocks of a scene --------------------------------------------------------------------------------------------
 
-def _flags(s, cam_const, tag_const):
+def flags(s, cam_const, tag_const):
+    """(cameras, tags) held constant, bool: the given sets and the fixed tag."""
     cc = np.zeros(len(s.cam_qt), bool) if cam_const is None else np.asarray(cam_const) != 0
     tc = np.zeros(len(s.tag_qt), bool) if tag_const is None else np.asarray(tag_const) != 0
     tc = tc.copy()
@@ -174,7 +147,7 @@ def assemble(s, a=1.0, robust=True, dtype=LD, products=None, mask=None, cam_cons
     chain_dtype = np.float64 if products is not None else dtype
     r, proj, Jc, Jt = corner_chain(s.intr, s.dist, s.cam_qt[s.obs_cam], s.tag_qt[s.obs_tag], s.tag_wh[s.obs_tag],
                                    s.obs_px, chain_dtype)
-    cc, tc = _flags(s, cam_const, tag_const)
+    cc, tc = flags(s, cam_const, tag_const)
     on = np.ones(s.n_obs, bool) if mask is None else np.asarray(mask) != 0
     Jc = np.where(cc[s.obs_cam][:, None, None, None], chain_dtype(0), Jc)
     Jt = np.where(tc[s.obs_tag][:, None, None, None], chain_dtype(0), Jt)
@@ -195,7 +168,7 @@ def blocks_from_oracle(O, s, a=1.0, robust=True, mask=None, cam_const=None, tag_
     """Reference A: the oracle's residuals, Jacobians (O.obs_eval) and Huber values (O.huber(a, .)), summed in numpy f64 in
     the caller's order, as test_gpu_kernels._blocks_from_oracle does for a = 1."""
     n_c, n_t = len(s.cam_qt), len(s.tag_qt)
-    cc, tc = _flags(s, cam_const, tag_const)
+    cc, tc = flags(s, cam_const, tag_const)
     V, U, W = np.zeros((n_c, 6, 6)), np.zeros((n_t, 6, 6)), np.zeros((s.n_obs, 6, 6))
     gc, gt = np.zeros((n_c, 6)), np.zeros((n_t, 6))
     cost = 0.0
@@ -278,31 +251,14 @@ def cached(key, make):
 
 # ---- scenes -----------------------------------------------------------------------------------------------------------
 
-def _qmul(z, w):
-    return np.array([z[0] * w[0] - z[1] * w[1] - z[2] * w[2] - z[3] * w[3],
-                     z[0] * w[1] + z[1] * w[0] + z[2] * w[3] - z[3] * w[2],
-                     z[0] * w[2] - z[1] * w[3] + z[2] * w[0] + z[3] * w[1],
-                     z[0] * w[3] + z[1] * w[2] - z[2] * w[1] + z[3] * w[0]])
-
-
-def _small_quat(rng, sigma=0.08):
-    v = np.r_[1.0, rng.normal(0, sigma, 3)]
-    return v / np.linalg.norm(v)
-
-
 def _wall(rng, n_cams, n_tags):
     """Tags near the plane z = 0, cameras about 3 m in front of it looking at it (the layout of the `obs` KATs)."""
-    tag = np.array([np.r_[_small_quat(rng), rng.uniform(-1, 1), rng.uniform(-0.6, 0.6), rng.normal(0, 0.05)]
+    tag = np.array([np.r_[rg.small_quat(rng), rng.uniform(-1, 1), rng.uniform(-0.6, 0.6), rng.normal(0, 0.05)]
                     for _ in range(n_tags)])
-    cam = np.array([np.r_[_qmul(_small_quat(rng), [0.0, 1.0, 0.0, 0.0]), rng.uniform(-0.5, 0.5), rng.uniform(-0.4, 0.4),
+    cam = np.array([np.r_[rg.qmul(rg.small_quat(rng), [0.0, 1.0, 0.0, 0.0]), rng.uniform(-0.5, 0.5), rng.uniform(-0.4, 0.4),
                           rng.uniform(2.5, 4.0)] for _ in range(n_cams)])
     wh = np.where(rng.random(n_tags)[:, None] < 0.5, [[0.1285, 0.1285]], [[0.1165, 0.0923]])
     return cam, tag, wh
-
-
-def _observe(rng, intr, dist, cam, tag, wh, obs_cam, obs_tag, noise_px):
-    _, proj, _, _ = corner_chain(intr, dist, cam[obs_cam], tag[obs_tag], wh[obs_tag], np.zeros((len(obs_cam), 8)), LD)
-    return proj.reshape(-1, 8).astype(np.float64) + rng.normal(0, noise_px, (len(obs_cam), 8))
 
 
 def mixed_scene(a):
@@ -312,7 +268,7 @@ def mixed_scene(a):
         rng = np.random.default_rng(20261101)
         cam, tag, wh = _wall(rng, 12, 9)
         oc, ot = (v.reshape(-1).astype(np.int32) for v in np.meshgrid(np.arange(12), np.arange(9), indexing="ij"))
-        px = _observe(rng, README_INTR, README_DIST, cam, tag, wh, oc, ot, float(a) / np.sqrt(2 * np.log(2)))
+        px = rg.pixels(rng, README_INTR, README_DIST, cam[oc], tag[ot], wh[ot], float(a) / np.sqrt(2 * np.log(2)))[1]
         return Scene(intr=np.array(README_INTR), dist=np.array(README_DIST), cam_qt=cam, tag_qt=tag, tag_wh=wh, fixed_tag=0,
                      obs_cam=oc, obs_tag=ot, obs_px=px)
     return cached(("mixed", float(a)), make)
@@ -347,7 +303,7 @@ def ragged_scene(few="tags"):
         else:
             cam, tag, wh = _wall(rng, 6, 130)
             oc, ot, fixed = six, many, 3
-        px = _observe(rng, README_INTR, README_DIST, cam, tag, wh, oc, ot, 0.8)
+        px = rg.pixels(rng, README_INTR, README_DIST, cam[oc], tag[ot], wh[ot], 0.8)[1]
         last_of_65 = int(np.flatnonzero(six == RAGGED_COUNTS.index(65))[-1])
         return Scene(intr=np.array(README_INTR), dist=np.array(README_DIST), cam_qt=cam, tag_qt=tag, tag_wh=wh,
                      fixed_tag=fixed, obs_cam=oc, obs_tag=ot, obs_px=px, few=few, last_of_65=last_of_65,
@@ -387,14 +343,13 @@ def load_kats():
 def _inverse_pose(qt):
     """world->camera pose as camera->world (unit quaternion), longdouble."""
     qt = np.asarray(qt, LD)
-    R = _rotation(qt[None, :4], LD)[0]
-    q = qt[:4] / np.sqrt((qt[:4] * qt[:4]).sum())
-    return np.r_[q[0], -q[1:]], -R.T @ qt[4:]
+    q = rg.unit(qt)
+    return np.r_[q[0], -q[1:]], -rg.rotation(qt).T @ qt[4:]
 
 
 def _compose(q1, t1, q2, t2):
     """x -> R1 (R2 x + t2) + t1."""
-    return _qmul(q1, q2), _rotation(np.asarray(q1, LD)[None], LD)[0] @ t2 + t1
+    return rg.qmul(q1, q2), rg.rotation(q1) @ t2 + t1
 
 
 def single_record_scene(case):
@@ -429,7 +384,7 @@ def hard_batch(strong, kats=None):
                                               np.asarray(other["cam_qt"][4:], LD), qo / np.sqrt((qo * qo).sum()), to)
                         wh, resid = other["wh"], np.array(other["residual"])
                     else:
-                        q_ct = _qmul(_small_quat(rng), [0.0, 1.0, 0.0, 0.0]).astype(LD)
+                        q_ct = rg.qmul(rg.small_quat(rng), [0.0, 1.0, 0.0, 0.0]).astype(LD)
                         t_ct = np.array([rng.uniform(-1, 1), rng.uniform(-0.6, 0.6), rng.uniform(2.5, 4.0)], LD)
                         wh, resid = [0.1285, 0.1285], -rng.normal(0, 0.8, 8)
                     q, t = _compose(qi, ti, q_ct, t_ct)

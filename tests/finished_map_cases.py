@@ -15,15 +15,15 @@ read bit for bit, on the CPU the host yardstick's optimum over the clean observa
                                                       xyz_cov_cams (G_i = rho'_i Jp_i^T Jc_i), cov_map (G_t = sum Jc^T Jt)
     the largest corner distance of every observation  the classification (triangulate: and Z > 0)
 
-Truth.  np.longdouble throughout: eval_cases.corner_chain for residuals and Jacobians (a free point is a tag of zero
+Truth.  np.longdouble throughout (geometry and conventions: ref_geometry.py): eval_cases.corner_chain for residuals and Jacobians (a free point is a tag of zero
 size at the point: its tag-translation columns are Jp), eval_cases.huber, cov_cases.refined_inverse (power-of-two Jacobi
 scaling, Newton refinement of the float64 inverse).
 
 References.  A: the oracle's functor (yardstick.image_rows / point_rows, tag_cases.tag_rows, predict_cases.host_pose's
 sums) through yardstick.block_normal, inverted with np.linalg.inv.  B: a float64 restatement of the device's scheme from
 small_solve.hpp's and pose_lm.hpp's words: corner_chain in float64, rows scaled by sqrt(rho'), sums in list order
-(np.cumsum is sequential), cholesky -> lower_inverse -> lower_gram as spd_inverse lays them out, the symmetrised C S C
-of sandwich6 for the propagated parts.  Neither calls the library.
+(ref_algebra.ordered_sum), ref_algebra.spd_inverse (cholesky -> lower_inverse -> lower_gram), the symmetrised C S C
+of ref_algebra.sandwich for the propagated parts.  Neither calls the library.
 
 Metric.  Covariances entry by entry, |got - truth| / sqrt(truth_ii truth_jj) (cov_cases.entry_deviation); cost, rms and
 the sigmas relative.  The bound of a case and quantity is MARGIN (8) x the larger deviation of A and B over ALL items of
@@ -34,6 +34,8 @@ import numpy as np
 import cov_cases as cc
 import eval_cases as ec
 import predict_cases as pc
+import ref_algebra as ra
+import ref_geometry as rg
 import rig_cases as rc
 import tag_cases as tc
 import yardstick as ys
@@ -67,7 +69,7 @@ def camera_model(name):
 
 def _tags(rng, n):
     """n small tags in a slab 0.8 m deep (not a plane), tilted by some tens of degrees, facing +z."""
-    qt = np.array([np.r_[ec._small_quat(rng, 0.12), rng.uniform(-1.2, 1.2), rng.uniform(-0.8, 0.8), rng.uniform(-0.4, 0.4)]
+    qt = np.array([np.r_[rg.small_quat(rng, 0.12), rng.uniform(-1.2, 1.2), rng.uniform(-0.8, 0.8), rng.uniform(-0.4, 0.4)]
                    for _ in range(n)])
     wh = np.where(rng.random(n)[:, None] < 0.5, [[0.1285, 0.1285]], [[0.1165, 0.0923]])
     return qt, wh
@@ -75,19 +77,8 @@ def _tags(rng, n):
 
 def _cameras(rng, n, spread=(0.4, 0.3)):
     """n world->camera poses 3.2 .. 4.5 m in front of the slab, looking at it (eval_cases._wall's layout)."""
-    return np.array([np.r_[ec._qmul(ec._small_quat(rng, 0.04), [0.0, 1.0, 0.0, 0.0]), rng.uniform(-spread[0], spread[0]),
+    return np.array([np.r_[rg.qmul(rg.small_quat(rng, 0.04), [0.0, 1.0, 0.0, 0.0]), rng.uniform(-spread[0], spread[0]),
                            rng.uniform(-spread[1], spread[1]), rng.uniform(3.2, 4.5)] for _ in range(n)])
-
-
-def camera_points(cam_qt, tag_qt, wh):
-    """(n, 4, 3) corners in the camera frame, longdouble (corner_chain's first three lines)."""
-    cam_qt, tag_qt = np.asarray(cam_qt, LD).reshape(-1, 7), np.asarray(tag_qt, LD).reshape(-1, 7)
-    wh = np.asarray(wh, LD).reshape(-1, 2)
-    Rc, Rt = ec._rotation(cam_qt[:, :4], LD), ec._rotation(tag_qt[:, :4], LD)
-    local = np.zeros((len(wh), 4, 3), LD)
-    local[:, :, :2] = ec._CORNER_SIGNS.astype(LD)[None] * (wh / LD(2))[:, None, :]
-    pw = np.einsum("nij,nkj->nki", Rt, local) + tag_qt[:, None, 4:]
-    return np.einsum("nij,nkj->nki", Rc, pw) + cam_qt[:, None, 4:]
 
 
 def radial_slope(dist, p_cam):
@@ -104,13 +95,6 @@ NEAR_DEPTH = 1.2   # m: how far the only camera of a one-observation item stands
 def _in_front(cam_qt, at):
     """The world point at camera coordinates `at` of the world->camera pose cam_qt."""
     return ys.rotation(cam_qt).T @ (np.asarray(at, np.float64) - cam_qt[4:])
-
-
-def _pixels(rng, intr, dist, cam, tag, wh, noise_px):
-    """(clean pixels from the longdouble chain rounded to double, the same with seeded Gaussian noise)."""
-    _, proj, _, _ = ec.corner_chain(intr, dist, cam, tag, wh, np.zeros((len(cam), 8)), LD)
-    clean = proj.reshape(-1, 8).astype(np.float64)
-    return clean, clean + rng.normal(0, noise_px, clean.shape)
 
 
 def outlier_positions(m):
@@ -133,12 +117,6 @@ def _place_outliers(rng, px, start, width):
     return label
 
 
-def _start(counts):
-    start = np.zeros(len(counts) + 1, np.int64)
-    start[1:] = np.cumsum(counts)
-    return start
-
-
 def _assert_conditions(s, p_cam):
     """The builder's conditions (test_finished_map_cases_cpu.py asserts them again from the scene)."""
     assert (p_cam[..., 2] > 0).all(), "a corner behind its camera"
@@ -157,12 +135,12 @@ def localize_scene(model, outliers, counts=LOCALIZE_COUNTS, seed=20261201):
         cam = _cameras(rng, len(cnt))
         obs_tag = np.concatenate([rng.permutation(len(tag_qt))[:c] for c in cnt]).astype(np.int32)
         obs_img = np.repeat(np.arange(len(cnt)), cnt)
-        clean, px = _pixels(rng, intr, dist, cam[obs_img], tag_qt[obs_tag], wh[obs_tag], NOISE_PX)
-        start = _start(cnt)
+        clean, px = rg.pixels(rng, intr, dist, cam[obs_img], tag_qt[obs_tag], wh[obs_tag], NOISE_PX)
+        start = rg.start(cnt)
         label = _place_outliers(rng, px, start, 8) if outliers else np.ones(len(px), bool)
         s = ec.Scene(kind="localize", model=model, intr=intr, dist=dist, tag_gt=tag_qt, tag_wh=wh, cam_gt=cam, counts=cnt,
                      start=start, obs_tag=obs_tag, obs_item=obs_img, obs_px=px, clean_px=clean, label=label)
-        _assert_conditions(s, camera_points(cam[obs_img], tag_qt[obs_tag], wh[obs_tag]))
+        _assert_conditions(s, rg.camera_points(cam[obs_img], tag_qt[obs_tag], wh[obs_tag]))
         return s
     return ec.cached(("finished map localize", model, bool(outliers), tuple(counts), seed), make)
 
@@ -181,16 +159,16 @@ def locate_scene(model, outliers, counts=LOCATE_COUNTS, seed=20261202):
         # the tag with one observation stands NEAR_DEPTH in front of its only camera: 4 m away its propagated part came
         # out of the two references a factor 15 apart (condition 7e2), here they agree (condition 45)
         t1 = cnt.index(1)
-        tag_qt[t1, 4:] = _in_front(cam[obs_cam[_start(cnt)[t1]]], [0.05, -0.04, NEAR_DEPTH])
-        clean, px = _pixels(rng, intr, dist, cam[obs_cam], tag_qt[obs_tag], wh[obs_tag], NOISE_PX)
-        start = _start(cnt)
+        tag_qt[t1, 4:] = _in_front(cam[obs_cam[rg.start(cnt)[t1]]], [0.05, -0.04, NEAR_DEPTH])
+        clean, px = rg.pixels(rng, intr, dist, cam[obs_cam], tag_qt[obs_tag], wh[obs_tag], NOISE_PX)
+        start = rg.start(cnt)
         label = _place_outliers(rng, px, start, 8) if outliers else np.ones(len(px), bool)
         s = ec.Scene(kind="locate", model=model, intr=intr, dist=dist, tag_gt=tag_qt, tag_wh=wh, cam_gt=cam, counts=cnt,
                      start=start, obs_cam=obs_cam, obs_item=obs_tag, obs_px=px, clean_px=clean, label=label,
                      cam_cov=pc.random_tag_cov(len(cam), fixed=[], seed=seed))
         for t in range(len(cnt)):
             assert (np.diff(obs_cam[start[t]:start[t + 1]]) > 0).all()
-        _assert_conditions(s, camera_points(cam[obs_cam], tag_qt[obs_tag], wh[obs_tag]))
+        _assert_conditions(s, rg.camera_points(cam[obs_cam], tag_qt[obs_tag], wh[obs_tag]))
         return s
     return ec.cached(("finished map locate", model, bool(outliers), tuple(counts), seed), make)
 
@@ -214,14 +192,14 @@ def triangulate_scene(model, outliers, counts=TRACK_COUNTS, seed=20261203):
         obs_cam = np.concatenate(views).astype(np.int32)
         obs_pt = np.repeat(np.arange(len(cnt)), cnt)
         tag = point_as_tag(pts)
-        clean, px = _pixels(rng, intr, dist, cam[obs_cam], tag[obs_pt], np.zeros((len(obs_pt), 2)), NOISE_PX)
+        clean, px = rg.pixels(rng, intr, dist, cam[obs_cam], tag[obs_pt], np.zeros((len(obs_pt), 2)), NOISE_PX)
         clean, px = clean[:, :2].copy(), px[:, :2].copy()
-        start = _start(cnt)
+        start = rg.start(cnt)
         label = _place_outliers(rng, px, start, 2) if outliers else np.ones(len(px), bool)
         s = ec.Scene(kind="triangulate", model=model, intr=intr, dist=dist, pts_gt=pts, cam_gt=cam, counts=cnt, start=start,
                      obs_cam=obs_cam, obs_item=obs_pt, obs_px=px, clean_px=clean, label=label,
                      cam_cov=pc.random_tag_cov(len(cam), fixed=[], seed=seed))
-        _assert_conditions(s, camera_points(cam[obs_cam], tag[obs_pt], np.zeros((len(obs_pt), 2))))
+        _assert_conditions(s, rg.camera_points(cam[obs_cam], tag[obs_pt], np.zeros((len(obs_pt), 2))))
         return s
     return ec.cached(("finished map triangulate", model, bool(outliers), tuple(counts), seed), make)
 
@@ -234,68 +212,6 @@ def point_as_tag(X):
     out[:, 0] = 1
     out[:, 4:] = X
     return out
-
-
-# ---- the device's small algebra in float64 (small_solve.hpp, pose_lm.hpp) ------------------------------------------------
-
-def spd_inverse_f64(A):
-    """small_solve.hpp's spd_inverse: L L^T = A (d -= L_jk^2 and v -= L_ik L_jk in ascending k, one reciprocal per
-    column), M = L^-1 (lower_inverse), C = M^T M (lower_gram, k from a up), one IEEE double operation at a time."""
-    A = np.asarray(A, np.float64)
-    n = len(A)
-    L, M, C = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
-    for j in range(n):
-        d = A[j, j]
-        for k in range(j):
-            d = d - L[j, k] * L[j, k]
-        L[j, j] = np.sqrt(d)
-        inv = 1.0 / L[j, j]
-        for i in range(j + 1, n):
-            v = A[i, j]
-            for k in range(j):
-                v = v - L[i, k] * L[j, k]
-            L[i, j] = v * inv
-    for j in range(n):
-        M[j, j] = 1.0 / L[j, j]
-        for i in range(j + 1, n):
-            v = 0.0
-            for k in range(j, i):
-                v = v - L[i, k] * M[k, j]
-            M[i, j] = v / L[i, i]
-    for a in range(n):
-        for b in range(a + 1):
-            v = 0.0
-            for k in range(a, n):
-                v = v + M[k, a] * M[k, b]
-            C[a, b] = C[b, a] = v
-    return C
-
-
-def sandwich_f64(C, S):
-    """pose_lm.hpp's sandwich6 (and k_triangulate's 3 x 3 twin): T = C S, entry (r, c) of T C averaged with its mirror
-    image."""
-    n = len(C)
-    T = np.zeros((n, n))
-    for r in range(n):
-        for c in range(n):
-            t = 0.0
-            for k in range(n):
-                t = t + C[r, k] * S[k, c]
-            T[r, c] = t
-    out = np.zeros((n, n))
-    for r in range(n):
-        for c in range(r + 1):
-            x = y = 0.0
-            for k in range(n):
-                x = x + T[r, k] * C[k, c]
-                y = y + T[c, k] * C[k, r]
-            out[r, c] = out[c, r] = 0.5 * (x + y)
-    return out
-
-
-def _ordered_sum(terms):
-    """The sum of terms[0], terms[1], ... in that order (np.cumsum adds one after the other)."""
-    return np.cumsum(terms, axis=0)[-1]
 
 
 # ---- one entry point on one scene under one loss ------------------------------------------------------------------------
@@ -345,12 +261,13 @@ class Case:
         on = np.asarray(flags, bool)
         r = self.chain(i, state, LD)[0][on]
         px = self.pixels(i)[on].astype(LD)
-        sq, rho0, rho1 = self._loss(r, LD)
+        sq, rho0, rho1 = self.loss_terms(r, LD)
         moved = LD(U64) * np.abs(r) * (np.abs(r + px) + np.abs(px))
         return dict(cost=float((rho1[..., None] * moved).sum() / (rho0.sum() / LD(2))), rms=float(moved.sum() / sq.sum()))
 
     # -- the truth --
-    def _loss(self, r, dtype):
+    def loss_terms(self, r, dtype):
+        """(|r|^2, rho, rho') per corner of r (..., 2) under the case's loss."""
         sq = (r * r).sum(axis=-1)
         if not self.robust:
             return sq, sq, np.ones_like(sq)
@@ -368,13 +285,13 @@ class Case:
 
     def ld_cost(self, i, state, flags):
         r, _, _, _ = self.chain(i, state, LD)
-        _, rho0, _ = self._loss(r[flags], LD)
+        _, rho0, _ = self.loss_terms(r[flags], LD)
         return rho0.sum(dtype=LD) / LD(2)
 
     def truth(self, i, state, flags):
         r, J, Jo, _ = self.chain(i, state, LD)
         on = np.asarray(flags, bool)
-        sq, rho0, rho1 = self._loss(r[on], LD)
+        sq, rho0, rho1 = self.loss_terms(r[on], LD)
         n_in = int(on.sum())
         H = np.einsum("mk,mkrp,mkrq->pq", rho1, J[on], J[on])
         cov, corr = cc.refined_inverse(H)
@@ -408,14 +325,14 @@ class Case:
     def reference_b(self, i, state, flags):
         r, J, Jo, _ = self.chain(i, state, np.float64)
         on = np.asarray(flags, bool)
-        sq, rho0, rho1 = self._loss(r[on], np.float64)
+        sq, rho0, rho1 = self.loss_terms(r[on], np.float64)
         wgt = np.sqrt(rho1)
         j = J[on] * wgt[..., None, None]
         P = j[:, :, 0, :, None] * j[:, :, 0, None, :] + j[:, :, 1, :, None] * j[:, :, 1, None, :]
-        H = _ordered_sum(P.reshape(-1, self.n, self.n))
-        cov = spd_inverse_f64(H)
+        H = ra.ordered_sum(P.reshape(-1, self.n, self.n))
+        cov = ra.spd_inverse(H)
         n_in = int(on.sum())
-        out = dict(cost=0.5 * _ordered_sum(rho0.reshape(-1)), rms=np.sqrt(_ordered_sum(sq.reshape(-1)) / (float(self.corners) * n_in)),
+        out = dict(cost=0.5 * ra.ordered_sum(rho0.reshape(-1)), rms=np.sqrt(ra.ordered_sum(sq.reshape(-1)) / (float(self.corners) * n_in)),
                    cov=cov, prop=None)
         C = self.other_cov(i)
         if C is not None:
@@ -424,8 +341,8 @@ class Case:
             G = np.zeros((n_in, self.n, 6))
             for k in range(self.corners):
                 G += w2[:, k, None, None] * (J[on][:, k, 0, :, None] * jo[:, k, 0, None, :] + J[on][:, k, 1, :, None] * jo[:, k, 1, None, :])
-            S = _ordered_sum((G @ C[on]) @ np.swapaxes(G, 1, 2))
-            out["prop"] = sandwich_f64(cov, S)
+            S = ra.ordered_sum((G @ C[on]) @ np.swapaxes(G, 1, 2))
+            out["prop"] = ra.sandwich(cov, S)
         return out
 
     @staticmethod
@@ -547,7 +464,7 @@ class TriangulateCase(Case):
         tag = np.tile(point_as_tag(np.asarray(state, np.float64)), (e - b, 1))
         cam = s.cam_gt[s.obs_cam[b:e]]
         r, _, Jc, Jt = ec.corner_chain(s.intr, s.dist, cam, tag, np.zeros((e - b, 2)), np.tile(s.obs_px[b:e], (1, 4)), dtype)
-        depth = camera_points(cam, tag, np.zeros((e - b, 2)))[:, :1, 2]
+        depth = rg.camera_points(cam, tag, np.zeros((e - b, 2)))[:, :1, 2]
         return r[:, :1], Jt[:, :1, :, :3], Jc[:, :1], depth
 
     def oracle_rows(self, O, i, state, keep):
@@ -615,14 +532,14 @@ def rig_scene(K, outliers, seed=20261205, extra=(), frames=None):
         for c in range(K):
             of = obs_cam == c
             if of.any():
-                clean[of], px[of] = _pixels(rng, intr[c], dist[c], cam[of], tag_qt[obs_tag[of]], wh[obs_tag[of]], NOISE_PX)
-        start = _start(per_frame.sum(axis=1))
+                clean[of], px[of] = rg.pixels(rng, intr[c], dist[c], cam[of], tag_qt[obs_tag[of]], wh[obs_tag[of]], NOISE_PX)
+        start = rg.start(per_frame.sum(axis=1))
         label = _place_outliers(rng, px, start, 8) if outliers else np.ones(len(px), bool)
         s = ec.Scene(kind="rig", model="K%d" % K, intr=intr, dist=dist, ext_qt=ext, tag_gt=tag_qt, tag_wh=wh, rig_gt=rig,
-                     counts=[int(v) for v in per_frame.sum(axis=1)], per_frame=per_frame, start=start, img_start=_start(slots),
+                     counts=[int(v) for v in per_frame.sum(axis=1)], per_frame=per_frame, start=start, img_start=rg.start(slots),
                      obs_frame=obs_frame, obs_cam=obs_cam, obs_tag=obs_tag, obs_item=obs_frame, obs_px=px, clean_px=clean,
                      label=label, n_frames=F, n_rig_cams=K)
-        p_cam = camera_points(cam, tag_qt[obs_tag], wh[obs_tag])
+        p_cam = rg.camera_points(cam, tag_qt[obs_tag], wh[obs_tag])
         assert (p_cam[..., 2] > 0).all()
         for c in range(K):
             assert (radial_slope(dist[c], p_cam[obs_cam == c]) > 0).all()
@@ -639,20 +556,15 @@ class RigCase(Case):
 
     def chain(self, i, state, dtype):
         s, (b, e) = self.scene, self.span(i)
-        rig = np.asarray(state, dtype)
-        rq = rig[:4] / np.sqrt((rig[:4] * rig[:4]).sum())
         r, J = np.zeros((e - b, 4, 2), dtype), np.zeros((e - b, 4, 2, 6), dtype)
         for c in np.unique(s.obs_cam[b:e]):
             of = np.flatnonzero(s.obs_cam[b:e] == c)
-            ext = np.asarray(s.ext_qt[c], dtype)
-            eq = ext[:4] / np.sqrt((ext[:4] * ext[:4]).sum())
-            Rc = ec._rotation(ext[None, :4], dtype)[0]
-            cam = np.concatenate([ec._qmul(eq, rq), Rc @ rig[4:] + ext[4:]])
+            cam, Rc, _ = rg.compose_rig(s.ext_qt[c], state, dtype)
             t = s.obs_tag[b:e][of]
             rr, _, Jc, _ = ec.corner_chain(s.intr[c], s.dist[c], np.tile(cam, (len(of), 1)), s.tag_gt[t], s.tag_wh[t],
                                            s.obs_px[b:e][of], dtype)
             r[of] = rr
-            J[of] = np.concatenate([Jc[..., :3] @ Rc, Jc[..., 3:] @ Rc], axis=-1)
+            J[of] = rg.turn_to_rig(Jc, Rc)
         return r, J, None, None
 
     def oracle_rows(self, O, i, state, keep):
@@ -749,8 +661,8 @@ class PredictCase:
     @staticmethod
     def _sigmas(cam_qt, cov, dtype):
         q = np.asarray(cam_qt, dtype)
-        R, t = ec._rotation(q[None, :4], dtype)[0], q[4:]
-        J = -R.T @ np.concatenate([np.eye(3, dtype=dtype), dtype(2) * ec._skew(t)], axis=1)
+        R, t = rg.rotation(q, dtype), q[4:]
+        J = -R.T @ np.concatenate([np.eye(3, dtype=dtype), dtype(2) * rg.skew(t)], axis=1)
         return np.sqrt(np.trace(J @ cov @ J.T)), np.sqrt(dtype(pc.RADIANS) ** 2 * np.trace(cov[3:, 3:]))
 
     def truth(self, p, vis):
@@ -787,14 +699,14 @@ class PredictCase:
     def reference_b(self, p, vis):
         t, Jc, Jt = self._jacobians(p, vis, np.float64)
         P = Jc[:, :, 0, :, None] * Jc[:, :, 0, None, :] + Jc[:, :, 1, :, None] * Jc[:, :, 1, None, :]
-        Hi = spd_inverse_f64(_ordered_sum(P.reshape(-1, 6, 6)))
+        Hi = ra.spd_inverse(ra.ordered_sum(P.reshape(-1, 6, 6)))
         cov_px = (self.sigma_px * self.sigma_px) * Hi
         prop, total = None, cov_px
         if self.with_map:
             G = np.zeros((len(t), 6, 6))
             for k in range(4):
                 G += Jc[:, k, 0, :, None] * Jt[:, k, 0, None, :] + Jc[:, k, 1, :, None] * Jt[:, k, 1, None, :]
-            prop = sandwich_f64(Hi, _ordered_sum((G @ self.tag_cov[t]) @ np.swapaxes(G, 1, 2)))
+            prop = ra.sandwich(Hi, ra.ordered_sum((G @ self.tag_cov[t]) @ np.swapaxes(G, 1, 2)))
             total = cov_px + prop
         sp, sr = self._sigmas(self.case["cam_qt"][p], total, np.float64)
         return dict(cov=cov_px, prop=prop, sigma_pos=float(sp), sigma_rot=float(sr))

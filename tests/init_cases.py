@@ -7,9 +7,10 @@ Input.  Every stage of the recipe is observable through the call's own options: 
 returns the pure selection, refine_iterations = 1 one Levenberg-Marquardt trial, constant poses turn a pass into one round
 with known counterparts.  A test reads the device's state bit for bit and forms the truth there in np.longdouble.
 
-Truth.  project_cm is CameraModel::projectPoint (the aliased term 2 p2 (xd - x) y included), which k_quad_pose fits;
+Truth (geometry and conventions: ref_geometry.py; B's algebra and summation orders: ref_algebra.py).  project_cm is
+CameraModel::projectPoint (ref_geometry.distort's aliased term 2 p2 (xd - x) y included), which k_quad_pose fits;
 eval_cases.corner_chain is the functor's projection, which scoring, refinement and the report use.  Candidates are
-quat_from_R(chain(quad pose, counterpart)); a score is sum min(e^2, cap^2) over the usable observations' corners; one trial
+ref_geometry.quat_from_R(chain(quad pose, counterpart)); a score is sum min(e^2, cap^2) over the usable observations' corners; one trial
 is -(H + lam diag max(H_jj, 1e-12))^-1 g at lam = kLamInit through cov_cases.refined_inverse and the longdouble pose_plus.
 
 References.  A: the oracle's functor through yardstick (image_rows / tag_rows, block_normal, plain_step), for the planar
@@ -19,12 +20,14 @@ deviation of A and B over all items of the case -- never a figure the kernels pr
 """
 import numpy as np
 
-import arrowhead_cases as ah
 import cov_cases as cc
 import eval_cases as ec
 import finished_map_cases as fm
+import ref_algebra as ra
+import ref_geometry as rg
 import tag_cases as tc
 import yardstick as ys
+from ref_geometry import quat_from_R
 
 LD = ec.LD
 MARGIN = ec.MARGIN
@@ -51,41 +54,6 @@ FAMILIES = ("cam", "tag")
 
 # ---- small geometry in a dtype of the caller's choice ---------------------------------------------------------------------
 
-def rot(q, dtype=LD):
-    """(n, 3, 3) of (n, 4+) quaternions, normalised first (load_rigid<true>)."""
-    return ec._rotation(np.asarray(q, dtype).reshape(-1, np.shape(q)[-1])[:, :4], dtype)
-
-
-def quat_from_R(R, dtype=LD):
-    """pose_lm.hpp's quat_from_R (Eigen's trace test) for (n, 3, 3).  Returns (q (n, 4) normalised, branch (n,) in 0..3)."""
-    R = np.asarray(R, dtype).reshape(-1, 3, 3)
-    tr = R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2]
-    branch = np.where(tr > 0, 0, np.where((R[:, 0, 0] >= R[:, 1, 1]) & (R[:, 0, 0] >= R[:, 2, 2]), 1,
-                                          np.where(R[:, 1, 1] >= R[:, 2, 2], 2, 3)))
-    q = np.zeros((len(R), 4), dtype)
-    one, two, quarter = dtype(1), dtype(2), dtype(0.25)
-    for b in range(4):
-        m = branch == b
-        if not m.any():
-            continue
-        r = R[m]
-        if b == 0:
-            s = np.sqrt(tr[m] + one) * two
-            q[m] = np.stack([quarter * s, (r[:, 2, 1] - r[:, 1, 2]) / s, (r[:, 0, 2] - r[:, 2, 0]) / s,
-                             (r[:, 1, 0] - r[:, 0, 1]) / s], axis=1)
-        else:
-            i = b - 1
-            j, k = (i + 1) % 3, (i + 2) % 3
-            s = np.sqrt(r[:, i, i] - r[:, j, j] - r[:, k, k] + one) * two
-            v = np.zeros((len(r), 4), dtype)
-            v[:, 0] = (r[:, k, j] - r[:, j, k]) / s
-            v[:, 1 + i] = quarter * s
-            v[:, 1 + j] = (r[:, j, i] + r[:, i, j]) / s
-            v[:, 1 + k] = (r[:, k, i] + r[:, i, k]) / s
-            q[m] = v
-    return q / np.sqrt((q * q).sum(axis=1, keepdims=True)), branch
-
-
 def _mat3(a, b, transpose_b=False):
     """a @ b (or a @ b^T) for stacks of 3 x 3, the three products of an entry added from left to right."""
     if transpose_b:
@@ -101,7 +69,7 @@ def chain(fam, rel_qt, oth_qt, dtype=LD):
     """chain_camera (fam "cam": T_cam = T_rel o T_tag^-1) or chain_tag (T_tag = T_cam^-1 o T_rel) for (n, 7) each.
     Returns (R (n, 3, 3), t (n, 3))."""
     rel_qt, oth_qt = np.asarray(rel_qt, dtype).reshape(-1, 7), np.asarray(oth_qt, dtype).reshape(-1, 7)
-    Rr, Ro = rot(rel_qt, dtype), rot(oth_qt, dtype)
+    Rr, Ro = rg.rotation(rel_qt, dtype), rg.rotation(oth_qt, dtype)
     if fam == "cam":
         R = _mat3(Rr, Ro, transpose_b=True)
         return R, rel_qt[:, 4:] - _matvec(R, oth_qt[:, 4:])
@@ -149,15 +117,9 @@ def project_cm(intr, dist, pc, dtype=LD):
     """CameraModel::projectPoint of camera-frame points pc (..., 3): the functor's projection with the y tangential term
     formed from the already distorted x, yd = y rad + 2 p2 xd y + p1 (r2 + 2 y^2) = functor + 2 p2 (xd - x) y."""
     intr, dist, pc = np.asarray(intr, dtype), np.asarray(dist, dtype), np.asarray(pc, dtype)
-    k1, k2, p1, p2, k3 = dist
-    one, two = dtype(1), dtype(2)
-    iz = one / pc[..., 2]
-    x, y = pc[..., 0] * iz, pc[..., 1] * iz
-    r2 = x * x + y * y
-    rad = one + r2 * (k1 + r2 * (k2 + r2 * k3))
-    xd = x * rad + two * p1 * x * y + p2 * (r2 + two * x * x)
-    yd = y * rad + two * p2 * xd * y + p1 * (r2 + two * y * y)
-    return np.stack([intr[0] * xd + intr[2], intr[1] * yd + intr[3]], axis=-1)
+    iz = dtype(1) / pc[..., 2]
+    xd, yd, _, _ = rg.distort(pc[..., 0] * iz, pc[..., 1] * iz, dist, dtype, aliased=True)
+    return rg.pixel(intr, xd, yd)
 
 
 def chain_points(model):
@@ -182,20 +144,18 @@ def project_cm_a(intr, dist, pc):
     from visual_marker_mapping_amd import pnp
     pc = np.asarray(pc, np.float64).reshape(-1, 3)
     uv = pnp.project(pc, np.eye(3), np.zeros(3), tuple(intr), tuple(dist))
-    k1, k2, p1, p2, k3 = dist
+    p2 = dist[3]
     if p2 != 0.0:
         x, y = pc[:, 0] / pc[:, 2], pc[:, 1] / pc[:, 2]
-        r2 = x * x + y * y
-        xd = x * (1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))) + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
-        uv[:, 1] += intr[1] * (2.0 * p2 * (xd - x) * y)
+        uv[:, 1] += intr[1] * (2.0 * p2 * (rg.distort(x, y, dist, np.float64)[0] - x) * y)
     return uv
 
 
 def quad_points(qt, wh, dtype=LD):
     """(n, 4, 3): the quad's corners (LL, LR, UR, UL) under the tag->camera poses qt, and the rotated corners b = R X."""
     qt, wh = np.asarray(qt, dtype).reshape(-1, 7), np.asarray(wh, dtype).reshape(-1, 2)
-    R = rot(qt, dtype)
-    X = ec._CORNER_SIGNS.astype(dtype)[None] * (wh / dtype(2))[:, None, :]           # (n, 4, 2)
+    R = rg.rotation(qt, dtype)
+    X = rg.local_corners(wh, dtype)
     b = R[:, None, :, 0] * X[:, :, 0, None] + R[:, None, :, 1] * X[:, :, 1, None]    # z = 0: two columns of R
     return b + qt[:, None, 4:], b
 
@@ -221,9 +181,7 @@ def quad_rms_a(intr, dist, qt, wh, px):
     qt, wh, px = np.asarray(qt, np.float64).reshape(-1, 7), np.asarray(wh).reshape(-1, 2), np.asarray(px).reshape(-1, 4, 2)
     out = np.zeros(len(qt))
     for i in range(len(qt)):
-        Q = np.zeros((4, 3))
-        Q[:, :2] = ec._CORNER_SIGNS * wh[i] / 2
-        pc = Q @ ys.rotation(qt[i]).T + qt[i, 4:]
+        pc = rg.local_corners(wh[i], np.float64)[0] @ ys.rotation(qt[i]).T + qt[i, 4:]
         e = project_cm_a(intr, dist, pc) - px[i]
         out[i] = np.sqrt((e ** 2).sum(axis=1).mean())
     return out
@@ -240,10 +198,7 @@ def quad_sums(intr, dist, qt, wh, px):
     px = np.asarray(px, np.float64).reshape(-1, 4, 2)
     iz = 1.0 / pc[..., 2]
     x, y = pc[..., 0] * iz, pc[..., 1] * iz
-    r2 = x * x + y * y
-    rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
-    xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
-    yd = y * rad + 2.0 * p2 * xd * y + p1 * (r2 + 2.0 * y * y)
+    xd, yd, r2, rad = rg.distort(x, y, dist, np.float64, aliased=True)
     ru, rv = fx * xd + cx - px[..., 0], fy * yd + cy - px[..., 1]
     dr = k1 + r2 * (2.0 * k2 + 3.0 * k3 * r2)
     D00 = rad + 2.0 * x * x * dr + 2.0 * p1 * y + 6.0 * p2 * x
@@ -263,12 +218,6 @@ def quad_sums(intr, dist, qt, wh, px):
         A = A + (J[:, k, 0, :, None] * J[:, k, 0, None, :] + J[:, k, 1, :, None] * J[:, k, 1, None, :])
         gr = gr + (J[:, k, 0] * ru[:, k, None] + J[:, k, 1] * rv[:, k, None])
     return cost, A, gr
-
-
-def pose_plus_batch(qt, d):
-    """geom.hpp's pose_plus for (n, 7) and (n, 6), float64."""
-    import linalg_cases as lc
-    return lc.pose_plus(np.asarray(qt, np.float64).reshape(-1, 7), np.asarray(d, np.float64).reshape(-1, 6))
 
 
 # ---- small_solve.hpp's trial loop in numpy ------------------------------------------------------------------------------
@@ -317,7 +266,7 @@ def lm_model(sums, x0, max_trials, stop_small):
         idx, step, sm = idx[sm >= 1e-14], step[sm >= 1e-14], sm[sm >= 1e-14]
         if not len(idx):
             continue
-        cand = pose_plus_batch(x[idx], step)
+        cand = rg.pose_plus(x[idx], step)
         cc_, _, _ = sums(cand, idx)
         acc = np.isfinite(cc_) & (cc_ < cost[idx])
         rej = idx[~acc]
@@ -424,7 +373,7 @@ def quad_weak_starts(intr, dist, wh, px):
 def quad_mirror(qt):
     """The second planar start: the tag normal mirrored about the line of sight to the tag centre (k_quad_pose)."""
     qt = np.asarray(qt, np.float64).reshape(-1, 7)
-    R = rot(qt, np.float64)
+    R = rg.rotation(qt, np.float64)
     t = qt[:, 4:]
     v = t / np.sqrt((t * t).sum(axis=1, keepdims=True))
     nrm = R[:, :, 2]
@@ -436,7 +385,7 @@ def quad_mirror(qt):
     ch, sh = np.sqrt(np.maximum(0.5 * (1.0 + c), 0.0)), np.sqrt(np.maximum(0.5 * (1.0 - c), 0.0)) / np.where(sn > 1e-12, sn, 1.0)
     z = np.where((sn > 1e-12)[:, None], np.concatenate([ch[:, None], sh[:, None] * ax], axis=1), [[1.0, 0.0, 0.0, 0.0]])
     out = qt.copy()
-    out[:, :4] = np.stack([ec._qmul(z[i], qt[i, :4]) for i in range(len(qt))]) if len(qt) else qt[:, :4]
+    out[:, :4] = rg.qmul(z, qt[:, :4])
     return out
 
 
@@ -472,8 +421,8 @@ def host_quad(intr, dist, wh, px, max_trials=QUAD_TRIALS, fallback=True):
                     pick = (0, 1)
                 else:
                     keep = q1[r] if stalled[r, 0] else q0[r]
-                    nk = rot(keep, np.float64)[0][:, 2]
-                    far = int((rot(ws[1], np.float64)[0][:, 2] @ nk) < (rot(ws[0], np.float64)[0][:, 2] @ nk))
+                    nk = rg.rotation(keep, np.float64)[:, 2]
+                    far = int((rg.rotation(ws[1], np.float64)[:, 2] @ nk) < (rg.rotation(ws[0], np.float64)[:, 2] @ nk))
                     pick = (far, far)
                 for s_, (q, c) in enumerate(((q0, c0), (q1, c1))):
                     j = pick[s_]
@@ -514,22 +463,22 @@ def _geometries(model):
     own normal while it faces the camera (R = Rx(180) Rz(a)): the returned quaternions then come from all four branches
     of quat_from_R."""
     f = _flip()
-    geo = [("frontal", ec._qmul(_axis_quat([1, 0.3, 0], 1.5), f), [0.1, -0.05, 3.0], [0.1285, 0.1285]),
-           ("oblique 80", ec._qmul(_axis_quat([0, 1, 0], 80.0), f), [0.2, 0.1, 2.5], [0.1285, 0.1285]),
-           ("19 px", ec._qmul(_axis_quat([1, 1, 0], 20.0), f), [0.4, -0.3, 8.0], [0.0188, 0.0188]),
-           ("close-up", ec._qmul(_axis_quat([1, -1, 0], 15.0), f), [0.01, 0.02, 0.15], [0.1285, 0.1285]),
-           ("corner", ec._qmul(_axis_quat([0, 1, 0.2], 25.0), f), [1.0, 0.68, 3.0], [0.1165, 0.0923]),
-           ("w != h", ec._qmul(_axis_quat([1, 0, 0], 35.0), f), [-0.3, 0.2, 2.0], [0.21, 0.07])]
+    geo = [("frontal", rg.qmul(_axis_quat([1, 0.3, 0], 1.5), f), [0.1, -0.05, 3.0], [0.1285, 0.1285]),
+           ("oblique 80", rg.qmul(_axis_quat([0, 1, 0], 80.0), f), [0.2, 0.1, 2.5], [0.1285, 0.1285]),
+           ("19 px", rg.qmul(_axis_quat([1, 1, 0], 20.0), f), [0.4, -0.3, 8.0], [0.0188, 0.0188]),
+           ("close-up", rg.qmul(_axis_quat([1, -1, 0], 15.0), f), [0.01, 0.02, 0.15], [0.1285, 0.1285]),
+           ("corner", rg.qmul(_axis_quat([0, 1, 0.2], 25.0), f), [1.0, 0.68, 3.0], [0.1165, 0.0923]),
+           ("w != h", rg.qmul(_axis_quat([1, 0, 0], 35.0), f), [-0.3, 0.2, 2.0], [0.21, 0.07])]
     # Facing the camera, in-plane rotations of 0, 90, 180, 270 degrees.  With the corners in detection order (the tag's
     # normal towards the camera, R = Rx(180) Rz(a), trace -1) only branches 1 and 2 of quat_from_R occur; the same four
     # rotations with the corners in mirrored order (the normal away from the camera, R = Rz(a), trace 1 + 2 cos a), which the
     # solver fits just as well, give branches 0 and 3.
     tilt = _axis_quat([0.3, 1, 0], 6.0)
     for a in (0, 90, 180, 270):
-        geo.append(("facing %d" % a, ec._qmul(tilt, ec._qmul(f, _axis_quat([0, 0, 1], a + 7.0))), [0.05 * (a / 90), -0.1, 2.2],
+        geo.append(("facing %d" % a, rg.qmul(tilt, rg.qmul(f, _axis_quat([0, 0, 1], a + 7.0))), [0.05 * (a / 90), -0.1, 2.2],
                     [0.1285, 0.1285]))
     for a in (0, 90, 180, 270):
-        geo.append(("mirrored %d" % a, ec._qmul(tilt, _axis_quat([0, 0, 1], a + 7.0)), [-0.1, 0.04 * (a / 90), 2.4],
+        geo.append(("mirrored %d" % a, rg.qmul(tilt, _axis_quat([0, 0, 1], a + 7.0)), [-0.1, 0.04 * (a / 90), 2.4],
                     [0.1165, 0.0923]))
     return geo
 
@@ -548,7 +497,7 @@ def quad_batch(model, n, noise_px=NOISE_PX, seed=20270101):
         geo = _geometries(model)
         qt, wh, names = np.zeros((n, 7)), np.zeros((n, 2)), [""] * n
         for i in range(n):
-            q = ec._qmul(ec._small_quat(rng, 0.25), _flip())
+            q = rg.qmul(rg.small_quat(rng, 0.25), _flip())
             qt[i] = np.r_[q / np.linalg.norm(q), rng.uniform(-0.8, 0.8), rng.uniform(-0.5, 0.5), rng.uniform(2.5, 5.0)]
             wh[i] = [0.1285, 0.1285] if rng.random() < 0.5 else [0.1165, 0.0923]
             names[i] = "ordinary"
@@ -583,7 +532,7 @@ def exact_batch(model):
 
 def branches_of(qt):
     """The branch of quat_from_R each pose's rotation takes."""
-    return quat_from_R(rot(qt, np.float64), np.float64)[1]
+    return quat_from_R(rg.rotation(qt, np.float64), np.float64)[1]
 
 
 DEGENERATE = {"coincident": [100.0, 100.0] * 4, "collinear": [100.0, 100.0, 200.0, 100.0, 300.0, 100.0, 400.0, 100.0]}
@@ -591,7 +540,7 @@ DEGENERATE = {"coincident": [100.0, 100.0] * 4, "collinear": [100.0, 100.0, 200.
 
 def recovery_error(qt, qt_gt):
     """Per pose: max |dR| and |dt| against the truth (test_gpu_init.py's measure), longdouble."""
-    dR = np.abs(rot(qt, LD) - rot(qt_gt, LD)).max(axis=(1, 2))
+    dR = np.abs(rg.rotation(qt, LD) - rg.rotation(qt_gt, LD)).max(axis=(1, 2))
     dt = np.abs(np.asarray(qt, LD)[:, 4:] - np.asarray(qt_gt, LD)[:, 4:]).max(axis=1)
     return np.maximum(dR, dt).astype(np.float64)
 
@@ -607,15 +556,11 @@ def exact_references(s):
         # longdouble chain at the true pose and rounded once)
         pc, _ = quad_points(s.qt_gt, s.wh, LD)
         x, y = pc[..., 0] / pc[..., 2], pc[..., 1] / pc[..., 2]
-        k1, k2, p1, p2, k3 = (LD(v) for v in s.dist)
-        r2 = x * x + y * y
-        xd = x * (LD(1) + r2 * (k1 + r2 * (k2 + r2 * k3))) + LD(2) * p1 * x * y + p2 * (r2 + LD(2) * x * x)
-        px[..., 1] = (px[..., 1].astype(LD) - LD(s.intr[1]) * LD(2) * p2 * (xd - x) * y).astype(np.float64)
+        xd = rg.distort(x, y, np.asarray(s.dist, LD), LD)[0]
+        px[..., 1] = (px[..., 1].astype(LD) - LD(s.intr[1]) * LD(2) * LD(s.dist[3]) * (xd - x) * y).astype(np.float64)
     got = []
     for i in range(len(px)):
-        Q = np.zeros((4, 3))
-        Q[:, :2] = ec._CORNER_SIGNS * s.wh[i] / 2
-        R, t = pnp.solvePnP(Q, px[i], tuple(s.intr), tuple(s.dist))
+        R, t = pnp.solvePnP(rg.local_corners(s.wh[i], np.float64)[0], px[i], tuple(s.intr), tuple(s.dist))
         got.append(np.r_[pnp.quat_from_R(R), t])
     refs["A pnp.solvePnP"] = recovery_error(np.array(got), s.qt_gt)
     return refs
@@ -703,18 +648,18 @@ def corridor(model, cross=False, n_cams=12, seed=20270102):
         # every tag 25 degrees out of the wall about the corridor's axis, up and down in turn: the cameras look along the
         # corridor, so no line of sight comes near a tag's normal.  A tag seen frontally has its two planar solutions meet,
         # the two candidates of its first observation then tie to rounding and the pose would be left out
-        tag = np.array([np.r_[ec._qmul(_axis_quat([1.0, 0.0, 0.0], 25.0 if k % 2 else -25.0), ec._small_quat(rng, 0.05)),
+        tag = np.array([np.r_[rg.qmul(_axis_quat([1.0, 0.0, 0.0], 25.0 if k % 2 else -25.0), rg.small_quat(rng, 0.05)),
                               0.45 * k + rng.uniform(-0.05, 0.05), rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)]
                         for k in range(n_tags)])
         tag[0] = IDENTITY_TAG
         wh = np.where(rng.random(n_tags)[:, None] < 0.5, [[0.1285, 0.1285]], [[0.1165, 0.0923]])
-        cam = np.array([np.r_[ec._qmul(ec._small_quat(rng, 0.04), _flip()), -(0.45 * k + 0.3) + rng.uniform(-0.05, 0.05),
+        cam = np.array([np.r_[rg.qmul(rg.small_quat(rng, 0.04), _flip()), -(0.45 * k + 0.3) + rng.uniform(-0.05, 0.05),
                               rng.uniform(-0.1, 0.1), rng.uniform(2.6, 3.2)] for k in range(n_cams)])
         pairs = [(k, t) for k in range(n_cams) for t in ((k, k + 1, k + 3) if cross else (k, k + 1)) if t < n_tags]
         oc, ot = np.array([p[0] for p in pairs], np.int32), np.array([p[1] for p in pairs], np.int32)
-        pc = fm.camera_points(cam[oc], tag[ot], wh[ot])
+        pc = rg.camera_points(cam[oc], tag[ot], wh[ot])
         assert (pc[..., 2] > 0).all() and (fm.radial_slope(dist, pc) > 0).all()
-        clean, px = fm._pixels(rng, intr, dist, cam[oc], tag[ot], wh[ot], NOISE_PX)
+        clean, px = rg.pixels(rng, intr, dist, cam[oc], tag[ot], wh[ot], NOISE_PX)
         tag0 = np.tile(IDENTITY_TAG, (n_tags, 1))
         return Handle(own="both", model=model, intr=intr, dist=dist, cam_qt=np.tile(IDENTITY_CAM, (n_cams, 1)), tag_qt=tag0,
                       tag_wh=wh, fixed_tag=0, obs_cam=oc, obs_tag=ot, obs_px=px, clean_px=clean, cam_gt=cam, tag_gt=tag,
@@ -784,28 +729,22 @@ def scores(fam, h, p, cand, usable, oth_qt, cap_px, dtype=LD, chunk=96):
     wh = np.asarray(h.tag_wh, dtype)[other if fam == "cam" else np.full(len(usable), p)]
     px = np.asarray(h.obs_px, dtype)[usable].reshape(-1, 4, 2)
     cap2 = dtype(np.float64(cap_px) * np.float64(cap_px))
-    local = np.zeros((len(usable), 4, 3), dtype)
-    local[:, :, :2] = ec._CORNER_SIGNS.astype(dtype)[None] * (wh / dtype(2))[:, None, :]
-    Ro = rot(oq, dtype)
+    local = rg.local_corners(wh, dtype)
+    Ro = rg.rotation(oq, dtype)
     if fam == "cam":
         pw = np.einsum("mij,mkj->mki", Ro, local) + oq[:, None, 4:]
     intr, dist = np.asarray(h.intr, dtype), np.asarray(h.dist, dtype)
-    k1, k2, p1, p2, k3 = dist
-    one, two = dtype(1), dtype(2)
     out, below = np.zeros(len(cand), dtype), np.zeros((len(cand), len(usable)), np.int8)
     for b in range(0, len(cand), chunk):
         c = cand[b:b + chunk]
-        Rc = rot(c, dtype)
+        Rc = rg.rotation(c, dtype)
         if fam == "cam":
             pc = np.einsum("cij,mkj->cmki", Rc, pw) + c[:, None, None, 4:]
         else:
             w = np.einsum("cij,mkj->cmki", Rc, local) + c[:, None, None, 4:]
             pc = np.einsum("mij,cmkj->cmki", Ro, w) + oq[None, :, None, 4:]
         x, y = pc[..., 0] / pc[..., 2], pc[..., 1] / pc[..., 2]
-        r2 = x * x + y * y
-        rad = one + r2 * (k1 + r2 * (k2 + r2 * k3))
-        xd = x * rad + two * p1 * x * y + p2 * (r2 + two * x * x)
-        yd = y * rad + two * p2 * x * y + p1 * (r2 + two * y * y)
+        xd, yd, _, _ = rg.distort(x, y, dist, dtype)
         ru, rv = intr[0] * xd + intr[2] - px[None, ..., 0], intr[1] * yd + intr[3] - px[None, ..., 1]
         e2 = ru * ru + rv * rv
         low = e2 < cap2
@@ -927,59 +866,13 @@ def ld_cost(fam, h, p, q, usable, oth_qt):
     return (r * r).sum(dtype=LD)
 
 
-def wave_total(terms):
-    """refine_sums' order for terms (m, 4, ...): lane l adds its observations l, l + 64, ... corner by corner, then
-    wave_sum's butterfly; lane 0's total."""
-    terms = np.asarray(terms)
-    v = np.zeros((64,) + terms.shape[2:], terms.dtype)
-    for lane in range(min(64, len(terms))):
-        for t in terms[lane::64].reshape((-1,) + terms.shape[2:]):
-            v[lane] = v[lane] + t
-    for m in (32, 16, 8, 4, 2, 1):
-        v = v + v[np.arange(64) ^ m]
-    return v[0]
-
-
 def pose_sums_b(fam, h, p, q, usable, oth_qt):
     """refine_sums<., true> in float64: cost, J^T J, J^T r in the device's order."""
     r, J = pose_rows(fam, h, p, q, usable, oth_qt, np.float64)
-    cost = wave_total(r[..., 0] * r[..., 0] + r[..., 1] * r[..., 1])
-    A = wave_total(J[:, :, 0, :, None] * J[:, :, 0, None, :] + J[:, :, 1, :, None] * J[:, :, 1, None, :])
-    g = wave_total(J[:, :, 0] * r[:, :, 0, None] + J[:, :, 1] * r[:, :, 1, None])
+    cost = ra.wave_total(r[..., 0] * r[..., 0] + r[..., 1] * r[..., 1])
+    A = ra.wave_total(J[:, :, 0, :, None] * J[:, :, 0, None, :] + J[:, :, 1, :, None] * J[:, :, 1, None, :])
+    g = ra.wave_total(J[:, :, 0] * r[:, :, 0, None] + J[:, :, 1] * r[:, :, 1, None])
     return cost, A, g
-
-
-def damped_solve_b(A, g, lam):
-    """small_solve.hpp's damped_solve<6>: Cholesky of the damped matrix, forward and backward substitution, one IEEE
-    operation at a time."""
-    n = len(g)
-    D = np.array(A, np.float64)
-    for a in range(n):
-        D[a, a] = A[a, a] + lam * (A[a, a] if A[a, a] > 1e-12 else 1e-12)
-    L = np.zeros((n, n))
-    for j in range(n):
-        d = D[j, j]
-        for k in range(j):
-            d = d - L[j, k] * L[j, k]
-        L[j, j] = np.sqrt(d)
-        inv = 1.0 / L[j, j]
-        for i in range(j + 1, n):
-            v = D[i, j]
-            for k in range(j):
-                v = v - L[i, k] * L[j, k]
-            L[i, j] = v * inv
-    y, x = np.zeros(n), np.zeros(n)
-    for i in range(n):
-        v = -g[i]
-        for k in range(i):
-            v = v - L[i, k] * y[k]
-        y[i] = v / L[i, i]
-    for i in range(n - 1, -1, -1):
-        v = y[i]
-        for k in range(i + 1, n):
-            v = v - L[k, i] * x[k]
-        x[i] = v / L[i, i]
-    return x
 
 
 def _oracle_rows(O, fam, h, p, q, usable, oth_qt):
@@ -999,7 +892,7 @@ def trial(O, fam, h, p, start, usable, oth_qt):
     D = H + LD(LAM_INIT) * np.diag(np.maximum(np.diag(H), LD(1e-12)))
     inv, corr = cc.refined_inverse(D)
     step = -(inv @ g)
-    truth = ah.pose_plus(np.asarray(start, LD), step, LD)
+    truth = rg.pose_plus(start, step, LD)
     scale = np.sqrt(np.diag(H))
     out = dict(truth=truth, scale=scale, step=step, correction=float(np.abs((corr @ g) * scale).max()),
                cost0=(r * r).sum(dtype=LD), cost1=ld_cost(fam, h, p, truth, usable, oth_qt))
@@ -1007,7 +900,7 @@ def trial(O, fam, h, p, start, usable, oth_qt):
     _, A, ga = ys.block_normal(O, _oracle_rows(O, fam, h, p, np.asarray(start, np.float64), usable, oth_qt), False)
     a = O.pose_plus(np.asarray(start, np.float64), ys.plain_step(A, ga, LAM_INIT))
     _, B, gb = pose_sums_b(fam, h, p, start, usable, oth_qt)
-    b = pose_plus_batch(start, damped_solve_b(B, gb, LAM_INIT))[0]
+    b = rg.pose_plus(start, ra.damped_solve(B, gb, LAM_INIT), np.float64)
     b[:4] = b[:4] * (1.0 / np.sqrt((b[:4] * b[:4]).sum()))
     out["refs"] = {"A oracle": trial_deviation(a, out), "B device scheme": trial_deviation(b, out)}
     return out
@@ -1028,7 +921,7 @@ def trial_resolved(tr):
 
 
 def trial_deviation(pose, tr):
-    return float(np.abs(ah.pose_minus(np.asarray(pose, LD), tr["truth"], LD) * tr["scale"]).max())
+    return float(np.abs(rg.pose_minus(pose, tr["truth"], LD) * tr["scale"]).max())
 
 
 def refine_model(fam, h, p, start, usable, oth_qt, max_trials=REFINE_TRIALS):
@@ -1089,15 +982,6 @@ def report_a(O, h, cam_qt, tag_qt, cam_ok, tag_ok):
     return float(np.mean(d)) if d else 0.0
 
 
-def _tree256(v):
-    v = np.asarray(v, np.float64).copy()
-    m = 128
-    while m >= 1:
-        v[:m] = v[:m] + v[m:2 * m]
-        m //= 2
-    return v[0]
-
-
 def report_b(h, cam_qt, tag_qt, cam_ok, tag_ok):
     """Reference B: k_init_stats and k_init_stats_sum in float64 -- per camera thread-private sums over d = thread,
     thread + 256, ... corner by corner, block_sum2's tree, then the cameras' partials the same way."""
@@ -1114,12 +998,12 @@ def report_b(h, cam_qt, tag_qt, cam_ok, tag_ok):
             for k in range(4):
                 s[pos % 256] = s[pos % 256] + d[pos, k]
                 c[pos % 256] += 1.0
-        part_s[p], part_c[p] = _tree256(s), _tree256(c)
+        part_s[p], part_c[p] = ra.tree256(s), ra.tree256(c)
     s, c = np.zeros(256), np.zeros(256)
     for p in range(h.n_cams):
         s[p % 256] = s[p % 256] + part_s[p]
         c[p % 256] = c[p % 256] + part_c[p]
-    total, count = _tree256(s), _tree256(c)
+    total, count = ra.tree256(s), ra.tree256(c)
     return total / count if count > 0 else 0.0
 
 

@@ -7,6 +7,10 @@ lm_bounds), measured against an np.longdouble reference -- never a figure taken 
 """
 import numpy as np
 
+import eval_cases as ec
+from ref_geometry import pose_plus     # Plus of oracle/vmm_oracle.c (vo_pose_plus) in the dtype of the step
+from yardstick import const_sets, free_system
+
 LD = np.longdouble
 U64 = 2.0 ** -53      # unit roundoff of f64
 MARGIN = 8.0          # the kernel is a third sample of the error class of the two CPU references (they differ by up to ~5)
@@ -232,58 +236,13 @@ def cancelling_rows(k, n, seed):
     return np.vstack([Z, (Z * sign[None, :])[perm]]), sign[:, None] != sign[None, :]
 
 
-# ---- one Levenberg-Marquardt step, restated (oracle/vmm_oracle.c: vo_solve) ------------------------------------------
-
-def pose_plus(qt, delta):
-    """Plus of oracle/vmm_oracle.c (vo_pose_plus) for (n, 7) poses and (n, 6) tangent steps, in the dtype of `delta`:
-    translation += delta[:3]; quaternion = exp(delta[3:]) * q (Ceres' QuaternionParameterization::Plus)."""
-    delta = np.asarray(delta)
-    dt = delta.dtype.type
-    qt = np.asarray(qt).astype(dt).reshape(-1, 7)
-    delta = delta.reshape(-1, 6)
-    out = qt.copy()
-    out[:, 4:] = qt[:, 4:] + delta[:, :3]
-    d = delta[:, 3:]
-    nd = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
-    nz = nd > 0
-    safe = np.where(nz, nd, dt(1))
-    s = np.sin(safe) / safe
-    z0, z1, z2, z3 = np.cos(safe), s * d[:, 0], s * d[:, 1], s * d[:, 2]
-    w0, w1, w2, w3 = qt[:, 0], qt[:, 1], qt[:, 2], qt[:, 3]
-    q = np.stack([z0 * w0 - z1 * w1 - z2 * w2 - z3 * w3,
-                  z0 * w1 + z1 * w0 + z2 * w3 - z3 * w2,
-                  z0 * w2 - z1 * w3 + z2 * w0 + z3 * w1,
-                  z0 * w3 + z1 * w2 - z2 * w1 + z3 * w0], axis=1)
-    out[:, :4] = np.where(nz[:, None], q, qt[:, :4])
-    return out
-
+# ---- one Levenberg-Marquardt step, restated (oracle/vmm_oracle.c: vo_solve); Plus is ref_geometry.pose_plus -----------
 
 def blocks_from_oracle(O, s, cam, tag, robustify, fixed_tag):
-    """V, U, W, g, cost from the oracle's per-observation residuals and Jacobians (as test_gpu_kernels.py accumulates
-    them): what BundleAdjuster.eval_blocks returns, without a GPU."""
-    n_c, n_t = len(cam), len(tag)
-    V, U = np.zeros((n_c, 6, 6)), np.zeros((n_t, 6, 6))
-    W = np.zeros((len(s.obs_cam), 6, 6))
-    gc, gt = np.zeros((n_c, 6)), np.zeros((n_t, 6))
-    cost = 0.0
-    for i, (c, t) in enumerate(zip(s.obs_cam, s.obs_tag)):
-        r, Jc, Jt = O.obs_eval(s.intr, s.dist, cam[c], tag[t], s.tag_wh[t], s.obs_px[i])
-        if t == fixed_tag:
-            Jt = np.zeros_like(Jt)
-        for k in range(4):
-            sq = r[2 * k] ** 2 + r[2 * k + 1] ** 2
-            rho = O.huber(1.0, sq) if robustify else np.array([sq, 1.0, 0.0])
-            cost += 0.5 * rho[0]
-            w = np.sqrt(rho[1])
-            Jc[2 * k:2 * k + 2] *= w
-            Jt[2 * k:2 * k + 2] *= w
-            r[2 * k:2 * k + 2] *= w
-        V[c] += Jc.T @ Jc
-        U[t] += Jt.T @ Jt
-        W[i] = Jc.T @ Jt
-        gc[c] += Jc.T @ r
-        gt[t] += Jt.T @ r
-    return dict(V=V, U=U, W=W, g_cam=gc, g_tag=gt, cost=cost)
+    """eval_cases.blocks_from_oracle (reference A of the blocks) at the poses (cam, tag) of a synthetic scene: what
+    BundleAdjuster.eval_blocks returns, without a GPU."""
+    return ec.blocks_from_oracle(O, ec.Scene(intr=s.intr, dist=s.dist, cam_qt=cam, tag_qt=tag, tag_wh=s.tag_wh, fixed_tag=fixed_tag,
+                                             obs_cam=s.obs_cam, obs_tag=s.obs_tag, obs_px=s.obs_px), robust=bool(robustify))
 
 
 class LmProblem:
@@ -299,26 +258,10 @@ class LmProblem:
         self.act_c = np.flatnonzero((np.bincount(obs_cam, minlength=n_c) > 0) & ~cc)
         self.act_t = np.flatnonzero((np.bincount(obs_tag, minlength=n_t) > 0) & ~tc)
         self.n_ac, self.n_at = len(self.act_c), len(self.act_t)
-        pos_c = -np.ones(n_c, int)
-        pos_c[self.act_c] = np.arange(self.n_ac)
-        pos_t = -np.ones(n_t, int)
-        pos_t[self.act_t] = self.n_ac + np.arange(self.n_at)
-        n = 6 * (self.n_ac + self.n_at)
-        H, g = np.zeros((n, n)), np.zeros(n)
-        for c in self.act_c:
-            k = 6 * pos_c[c]
-            H[k:k + 6, k:k + 6] = blk["V"][c]
-            g[k:k + 6] = blk["g_cam"][c]
-        for t in self.act_t:
-            k = 6 * pos_t[t]
-            H[k:k + 6, k:k + 6] = blk["U"][t]
-            g[k:k + 6] = blk["g_tag"][t]
-        for i, (c, t) in enumerate(zip(obs_cam.tolist(), obs_tag.tolist())):
-            if pos_c[c] >= 0 and pos_t[t] >= 0:
-                a, b = 6 * pos_c[c], 6 * pos_t[t]
-                H[a:a + 6, b:b + 6] += blk["W"][i]
-                H[b:b + 6, a:a + 6] += blk["W"][i].T
-        self.H, self.g, self.cost = H, g, blk["cost"]
+        held_c, held_t = np.ones(n_c, bool), np.ones(n_t, bool)
+        held_c[self.act_c], held_t[self.act_t] = False, False
+        self.H, self.g, _, _ = free_system(ec.Scene(obs_cam=obs_cam, obs_tag=obs_tag), blk, held_c, held_t)
+        self.cost = blk["cost"]
         self.x = np.vstack([self.cam[self.act_c], self.tag[self.act_t]])   # (active poses, 7)
 
     def gradient_max_norm(self, dtype):
@@ -458,15 +401,6 @@ def lm_case_id(case):
                                            case["radius"])
 
 
-def constant_sets(s, n_tag_const, n_cam_const):
-    """The flags of test_gpu_constant_poses._const_sets: observation 0's camera and tag, then the first others."""
-    tags = [int(s.obs_tag[0])] + [t for t in range(len(s.tag_init)) if t != s.obs_tag[0]][:n_tag_const - 1]
-    cams = [int(s.obs_cam[0])] + [c for c in range(len(s.cam_init)) if c != s.obs_cam[0]][:n_cam_const - 1]
-    cam_const, tag_const = np.zeros(len(s.cam_init), np.uint8), np.zeros(len(s.tag_init), np.uint8)
-    cam_const[cams], tag_const[tags] = 1, 1
-    return cam_const, tag_const
-
-
 def run_lm_case(eng, case, setenv):
     """One LM iteration on the device (BundleAdjuster.solve, max_num_iterations = 1) and its three restatements from
     the same handle's eval_blocks at the start state.  setenv(name, value) sets a switch that the handle reads when
@@ -477,7 +411,7 @@ def run_lm_case(eng, case, setenv):
         setenv(name, case["env"].get(name))
     cam_const, tag_const = None, np.zeros(len(s.tag_init), np.uint8)
     if case.get("constant"):
-        cam_const, tag_const = constant_sets(s, *case["constant"])
+        cam_const, tag_const = const_sets(s, *case["constant"])
     mode = eng.ELIM_CAMERAS if case["elim"] == "cams" else eng.ELIM_TAGS
     ba = eng.BundleAdjuster(s.intr, s.dist, s.cam_init, s.tag_init, s.tag_wh, s.fixed_tag, s.obs_cam, s.obs_tag,
                             s.obs_px, elimination=mode)

@@ -1,6 +1,7 @@
 """Scenes and the host model of the localisation-accuracy prediction (vmm_ba_predict_localization).  No GPU, and nothing
 of the code under test: the visibility rules are written here from include/vmm_ba.h's words in numpy, H, G_t and the
-sandwich come from oracle.obs_eval's Jacobians, the inverses from cov_cases.refined_inverse.
+sandwich come from oracle.obs_eval's Jacobians, the inverses from cov_cases.refined_inverse; the quaternion product, the
+corner order, [v]x and the functor's polynomial are ref_geometry.py's.
 
 Scenes
   edges   one camera (k1 = -0.3, 640 x 480) at the world's origin and nine hand-placed tags; EDGE_REASONS says which rule
@@ -13,7 +14,9 @@ Scenes
 import numpy as np
 
 import cov_cases as cc
+import ref_geometry as rg
 import yardstick as ys
+from ref_geometry import qmul as quat_mul
 
 OPTIONS = dict(sigma_px=1.0, margin_px=0.0, min_depth=1e-3, max_view_angle_deg=70.0, min_side_px=10.0, min_tags=1)
 RULES = ("facing", "depth", "monotone", "image", "side")
@@ -26,13 +29,6 @@ LANE_TAGS, LANE_POSES = (1, 63, 64, 65, 130), (1, 3, 4, 5)
 
 # ---- poses ------------------------------------------------------------------------------------------------------------
 
-def quat_mul(a, b):
-    w1, x1, y1, z1 = a
-    w2, x2, y2, z2 = b
-    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
-                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
-
-
 def axis_angle(axis, deg):
     axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
     h = np.radians(deg) / 2
@@ -40,7 +36,8 @@ def axis_angle(axis, deg):
 
 
 def quat_from_rotation(R):
-    """The unit quaternion (w >= 0) of a rotation matrix, through its largest component."""
+    """The unit quaternion (w >= 0) of a rotation matrix, through its largest component.  The scene builders' own route:
+    ref_geometry.quat_from_R (the device's trace test, another normalisation) gives the edges scene other bits."""
     K = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2],
                   R[2, 2] - R[0, 0] - R[1, 1]])
     i = int(np.argmax(K))
@@ -86,18 +83,13 @@ def displaced(cam_qt, shift, axis, deg):
 def world_corners(tag_qt, wh):
     """(4, 3): LL, LR, UR, UL."""
     R = ys.rotation(tag_qt)
-    return np.array([R @ [sx * wh[0] / 2, sy * wh[1] / 2, 0.0] + tag_qt[4:] for sx, sy in ((-1, -1), (1, -1), (1, 1), (-1, 1))])
+    return np.array([R @ p + tag_qt[4:] for p in rg.local_corners(wh, np.float64)[0]])
 
 
 def functor_pixel(intr, dist, pc):
     """The pixel of the functor the bundle adjustment minimises, and r^2, of a point in the camera frame."""
-    k1, k2, p1, p2, k3 = dist
-    x, y = pc[0] / pc[2], pc[1] / pc[2]
-    r2 = x * x + y * y
-    rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
-    xd = x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
-    yd = y * rad + 2 * p2 * x * y + p1 * (r2 + 2 * y * y)
-    return np.array([intr[0] * xd + intr[2], intr[1] * yd + intr[3]]), r2
+    xd, yd, r2, _ = rg.distort(pc[0] / pc[2], pc[1] / pc[2], dist, np.float64)
+    return rg.pixel(intr, xd, yd), r2
 
 
 def slacks(intr, dist, size, opt, tag_qt, wh, cam_qt):
@@ -147,8 +139,7 @@ def host_visible(case, opt=None):
 def centre_jacobian(cam_qt):
     """dC / d(dt, dr) (3 x 6) of the camera centre C = -R^T t over the pose's tangent: -R^T [I | 2 [t]x]."""
     R, t = ys.rotation(cam_qt), cam_qt[4:]
-    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
-    return -R.T @ np.hstack([np.eye(3), 2 * tx])
+    return -R.T @ np.hstack([np.eye(3), 2 * rg.skew(t)])
 
 
 RADIANS = 2.0   # the rotation in radians is twice the tangent's rotation part

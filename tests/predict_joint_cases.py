@@ -11,8 +11,8 @@ Truth.  np.longdouble: M as the full double sum over the selected set, symmetris
 H^-1.  S is the matrix the entry reads: the blocks s >= t as given, S_ts = S_st^T (lower_symmetric).
 Reference A.  float64: the oracle's obs_eval Jacobians, the full double sum, numpy.linalg.inv.
 Reference B.  float64 in the device's scheme (kernels_predict_joint.hip's header): per s in ascending order the pairs
-t < s as X_st + X_st^T with X = (G_s S_st) G_t^T, then the diagonal term (G_s S_ss) G_s^T; spd_inverse_f64 and
-sandwich_f64.
+t < s as X_st + X_st^T with X = (G_s S_st) G_t^T, then the diagonal term (G_s S_ss) G_s^T; ref_algebra.py's
+spd_inverse and sandwich.
 
 Joint covariances
   block_diagonal   predict_cases.random_tag_cov's blocks on the diagonal, zero cross blocks
@@ -25,10 +25,10 @@ Joint covariances
 import numpy as np
 
 import cov_cases as cc
-import eval_cases as ec
 import finished_map_cases as fm
 import predict_cases as pc
-import yardstick as ys
+import ref_algebra as ra
+import ref_geometry as rg
 
 LD = cc.LD
 JOINT_TAGS, JOINT_POSES = (1, 2, 63, 64, 65, 129), 9
@@ -79,21 +79,17 @@ def tiled(joint, n_tags, rows):
     return np.ascontiguousarray(np.asarray(joint)[np.ix_(idx, idx)])
 
 
-def skew(v):
-    return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]], dtype=np.asarray(v).dtype)
-
-
 def rigid_tag(tag_qt, dtype=np.float64):
     """A_t: the tangent step of the tag->world pose tag_qt when the world moves by the tangent w = (d, delta), x -> R(2
     delta) x + d: the translation goes to t + d + 2 delta x t, the rotation is left-multiplied (geom.hpp's pose_plus)."""
     A = np.eye(6, dtype=dtype)
-    A[:3, 3:] = -2 * skew(np.asarray(tag_qt[4:], dtype))
+    A[:3, 3:] = -2 * rg.skew(np.asarray(tag_qt[4:], dtype))
     return A
 
 
 def rigid_camera(cam_qt, dtype=np.float64):
     """B: the tangent step of the world->camera pose that moves with the world: R' = R R_w^T, t' = t - R' d."""
-    R = ec._rotation(np.asarray(cam_qt, dtype)[None, :4], dtype)[0]
+    R = rg.rotation(cam_qt, dtype)
     B = np.zeros((6, 6), dtype)
     B[:3, :3] = -R
     B[3:, 3:] = -R
@@ -160,7 +156,7 @@ class JointCase(fm.PredictCase):
     def reference_b(self, p, vis):
         t, Jc, Jt = self._jacobians(p, vis, np.float64)
         P = Jc[:, :, 0, :, None] * Jc[:, :, 0, None, :] + Jc[:, :, 1, :, None] * Jc[:, :, 1, None, :]
-        Hi = fm.spd_inverse_f64(fm._ordered_sum(P.reshape(-1, 6, 6)))
+        Hi = ra.spd_inverse(ra.ordered_sum(P.reshape(-1, 6, 6)))
         cov_px = (self.sigma_px * self.sigma_px) * Hi
         G = np.zeros((len(t), 6, 6))
         for k in range(4):
@@ -171,7 +167,7 @@ class JointCase(fm.PredictCase):
         for s in range(len(t)):
             terms += [X[s, u] + X[s, u].T for u in range(s)]
             terms.append(np.tril(X[s, s]) + np.tril(X[s, s], -1).T)   # the lower triangle, as the kernel forms it
-        prop = fm.sandwich_f64(Hi, fm._ordered_sum(np.array(terms)))
+        prop = ra.sandwich(Hi, ra.ordered_sum(np.array(terms)))
         sp, sr = self._sigmas(self.case["cam_qt"][p], cov_px + prop, np.float64)
         return dict(cov=cov_px, prop=prop, sigma_pos=float(sp), sigma_rot=float(sr))
 

@@ -7,10 +7,12 @@ tangents.  With camera = (R_c R_f, R_c t_f + t_c) and every pose moving as vmm_b
 added, rotation multiplied from the left by the half-angle step):
     a rig step (dt, dth) moves the camera by (R_c dt, R_c dth)                  J_rig = [Jc_t R_c | Jc_r R_c]
     an extrinsic step (ds, dph) moves it by (ds + 2 dph x (R_c t_f), dph)      J_ext = [Jc_t | Jc_r - 2 Jc_t [R_c t_f]x]
-It never calls the code under test.
+The composed pose is ref_geometry.compose_rig with the yardstick's norm; the column turn stays written out here, apart
+from ref_geometry.turn_to_rig / extrinsic_columns, which the truths and references B use.  It never calls the code under test.
 """
 import numpy as np
 
+import ref_geometry as rg
 from yardstick import assemble, dense_lm, free_inverse, plain_step, rotation
 
 # rig->camera: identity; yaw 4 deg, t = (-0.3, 0, 0); yaw -15 deg, t = (0.2, 0.05, 0)
@@ -45,16 +47,7 @@ def rig_scene(name, ext=EXT3, **kw):
 
 def compose(ext, rig):
     """ext o rig as (qw, qx, qy, qz, tx, ty, tz): the Hamilton product of the unit quaternions, t = R_c t_f + t_c."""
-    a, b = ext[:4] / np.linalg.norm(ext[:4]), rig[:4] / np.linalg.norm(rig[:4])
-    q = np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
-                  a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-                  a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1],
-                  a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
-    return np.concatenate([q, rotation(ext) @ rig[4:] + ext[4:]])
-
-
-def _cross(v):
-    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return rg.compose_rig(ext, rig, np.float64, norm="linalg")[0]
 
 
 def rig_rows(O, intr, dist, ext, rig, tag_qt, wh, px):
@@ -62,7 +55,7 @@ def rig_rows(O, intr, dist, ext, rig, tag_qt, wh, px):
     r, Jc, _ = O.obs_eval(intr, dist, compose(ext, rig), tag_qt, wh, px)
     Rc = rotation(ext)
     J_rig = np.hstack([Jc[:, :3] @ Rc, Jc[:, 3:] @ Rc])
-    J_ext = np.hstack([Jc[:, :3], Jc[:, 3:] - 2.0 * Jc[:, :3] @ _cross(Rc @ rig[4:])])
+    J_ext = np.hstack([Jc[:, :3], Jc[:, 3:] - 2.0 * Jc[:, :3] @ rg.skew(Rc @ rig[4:])])
     return r, J_rig, J_ext
 
 

@@ -114,7 +114,7 @@ def test_model_system_references_are_sound(oracle, name, variant):
         assert 0 < dev_cov <= cc.REFERENCE_CAP and 0 < dev_step <= cc.REFERENCE_CAP
     # the oracle's C and g_k against the longdouble sums, in test_gpu_selfcal.py's metric and at its bounds
     from yardstick import BOUND_C, BOUND_COST, BOUND_G
-    A, B, g, C, gk, cost = cc._border_sums(case.scene, case.k, case.robust, case.mask, cc.LD)
+    A, B, g, C, gk, cost = cc.border_sums(case.scene, case.k, case.robust, case.mask, cc.LD)
     o = case.oracle
     live = o["mag_C"] > 0
     assert not o["C"][~live].any() and not C[~live].any()

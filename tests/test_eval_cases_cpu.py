@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import eval_cases as ec
+import ref_geometry as rg
 
 LD = ec.LD
 KAT_UNITS = 64.0
@@ -25,10 +26,10 @@ def _condition(case):
     c = np.array([case["intr"][2], case["intr"][3]], LD)
     px = np.abs(np.array(case["px"], LD).reshape(4, 2))
     pixel = float(np.max((np.abs(proj[0] - c) + np.abs(c) + px) / (np.abs(proj[0]) + px)))
-    Rc = ec._rotation(cam[None, :4], LD)[0]
-    Rt = ec._rotation(tag[None, :4], LD)[0]
+    Rc = rg.rotation(cam, LD)
+    Rt = rg.rotation(tag, LD)
     worst = 1.0
-    for sx, sy in ec._CORNER_SIGNS:
+    for sx, sy in rg.CORNER_SIGNS:
         a = Rt @ np.array([sx * case["wh"][0] / 2, sy * case["wh"][1] / 2, 0.0], LD)
         pw = a + tag[4:]
         b = Rc @ pw

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import finished_map_cases as fm
+import ref_geometry as rg
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +48,7 @@ def _call_rig(eng, case, items=None):
     start, sel = _select(s.start, items)
     frames = range(case.n_items) if items is None else items
     slots = np.concatenate([np.diff(s.img_start[f * K:f * K + K + 1]) for f in frames])
-    rig, cov, inl, res = eng.rig_localize(s.intr, s.dist, s.ext_qt, s.tag_gt, s.tag_wh, fm._start(slots), s.obs_tag[sel], s.obs_px[sel],
+    rig, cov, inl, res = eng.rig_localize(s.intr, s.dist, s.ext_qt, s.tag_gt, s.tag_wh, rg.start(slots), s.obs_tag[sel], s.obs_px[sel],
                                           **_loss_options(case))
     return rig, [cov], inl, res
 
@@ -78,7 +79,7 @@ def _select(start, items):
     if items is None:
         return start, np.arange(int(start[-1]))
     sel = np.concatenate([np.arange(start[i], start[i + 1]) for i in items] + [np.zeros(0, np.int64)]).astype(np.int64)
-    return fm._start([int(start[i + 1] - start[i]) for i in items]), sel
+    return rg.start([int(start[i + 1] - start[i]) for i in items]), sel
 
 
 def _item_bytes(state, covs, inl, res, k, b, e):

@@ -11,6 +11,8 @@ import pytest
 import cov_cases as cc
 import eval_cases as ec
 import finished_map_cases as fm
+import ref_algebra as ra
+import ref_geometry as rg
 
 LD = fm.LD
 AGREE = 8.0     # references A and B within this factor of each other on every case (the issue's figure)
@@ -116,7 +118,7 @@ def test_builder_meets_its_conditions_and_counts(entry, args):
         assert len(relief) < 3 or relief.max() - relief.min() > 0.5                    # not a plane
     # the geometry: every corner in front of its camera, on the rising part of the radial map
     for intr, dist, cam, tag, wh, _ in _observations(s):
-        p_cam = fm.camera_points(cam, tag, wh)
+        p_cam = rg.camera_points(cam, tag, wh)
         assert (p_cam[..., 2] > 0).all() and (fm.radial_slope(dist, p_cam) > 0).all()
     # the pixels: clean ones within inlier_px / 4 of the noise-free corner, replaced ones 10 .. 40 x inlier_px away, all
     # corners alike, at the list positions 0, 63, 64, 255, 256 and m - 1 of every list that is long enough
@@ -207,11 +209,11 @@ def test_restated_algebra_inverts_and_sandwiches(n):
     rng = np.random.default_rng(n)
     A = rng.standard_normal((n, 2 * n))
     A = A @ A.T
-    C = fm.spd_inverse_f64(A)
+    C = ra.spd_inverse(A)
     assert (C == C.T).all()
     np.testing.assert_allclose(C @ A, np.eye(n), atol=1e-12)
     S = rng.standard_normal((n, n))
     S = S @ S.T
-    W = fm.sandwich_f64(C, S)
+    W = ra.sandwich(C, S)
     assert (W == W.T).all()
     np.testing.assert_allclose(W, C @ S @ C, rtol=1e-12, atol=1e-15 * np.abs(W).max())

@@ -9,6 +9,7 @@ import pytest
 import eval_cases as ec
 import finished_map_cases as fm
 import init_cases as ic
+import ref_geometry as rg
 
 LD = ic.LD
 AGREE = 8.0     # references A and B within this factor of each other on every case (the issue's figure)
@@ -61,7 +62,7 @@ def test_quat_from_R_and_the_chains_against_pnp():
     rng = np.random.default_rng(6)
     q = rng.normal(size=(400, 4))
     q /= np.linalg.norm(q, axis=1, keepdims=True)
-    R = ic.rot(q, np.float64)
+    R = rg.rotation(q, np.float64)
     got, branch = ic.quat_from_R(R, np.float64)
     assert set(branch.tolist()) == {0, 1, 2, 3}
     want = np.array([pnp.quat_from_R(r) for r in R])

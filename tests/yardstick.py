@@ -1,6 +1,6 @@
 """The host yardstick of the finished-map and constant-pose tests: numpy around oracle/oracle.py, proven in
 tests/test_yardstick_cpu.py before the GPU tests lean on it (DESIGN.md section 6 lists every piece).  It never imports the
-code under test.
+code under test.  The rotation matrix is ref_geometry.py's (conventions there) with np.linalg.norm's |q|.
 
 obs_eval gives the 8 residuals and the 8 x 6 pose Jacobians of one observation, point_eval the same for a free point,
 huber gives rho, pose_plus moves a pose; the nine columns of the camera model are the closed forms of the cost functor's
@@ -8,6 +8,7 @@ projection (intrinsic_columns).  Everything else here is summation, a damped lin
 """
 import numpy as np
 
+import ref_geometry as rg
 from eval_cases import MARGIN
 
 ALL_FREE = 0x1FF
@@ -39,11 +40,7 @@ REL = 1e-6  # north_star: "within 1e-6 relative"
 
 def rotation(q):
     """The rotation matrix of the quaternion q = (w, x, y, z, ...), normalised first."""
-    q = np.asarray(q, np.float64)[:4]
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    return rg.rotation(q, np.float64, norm="linalg")
 
 
 def pose_gap(a, b):
@@ -477,25 +474,12 @@ def same_bytes(a, b):
     return all(np.asarray(a[key]).tobytes() == np.asarray(b[key]).tobytes() for key in ("cost", "g_k", "C", "r_k", "S_k"))
 
 
-def _world_corners(qt, wh):
-    q = qt[:, :4] / np.linalg.norm(qt[:, :4], axis=1, keepdims=True)
-    w, x, y, z = q.T
-    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                  2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                  2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], axis=1).reshape(-1, 3, 3)
-    out = []
-    for sx, sy in ((-1, -1), (1, -1), (1, 1), (-1, 1)):
-        p = np.stack([sx * wh[:, 0] / 2, sy * wh[:, 1] / 2, np.zeros(len(wh))], axis=1)
-        out.append(np.einsum("nij,nj->ni", R, p) + qt[:, 4:])
-    return np.stack(out, axis=1)
-
-
 def assert_same_solution(cam, tag, sc, wh):
     """The device's poses and world corners against the oracle scene sc after its solve, REL of the largest entry."""
     scale = max(np.abs(sc.cam_qt).max(), np.abs(sc.tag_qt).max())
     np.testing.assert_allclose(cam, sc.cam_qt, rtol=0, atol=REL * scale)
     np.testing.assert_allclose(tag, sc.tag_qt, rtol=0, atol=REL * scale)
-    a, b = _world_corners(tag, wh), _world_corners(sc.tag_qt, wh)
+    a, b = rg.world_corners(tag, wh, np.float64), rg.world_corners(sc.tag_qt, wh, np.float64)
     np.testing.assert_allclose(a, b, rtol=0, atol=REL * np.abs(b).max())
 
 

@@ -290,6 +290,35 @@ int vmm_ba_set_constant_poses(vmm_ba_handle h, const uint8_t* cam_const, const u
 /* Replaces ceres::Solve at src/TagReconstructor.cpp:737-738. */
 int vmm_ba_solve(vmm_ba_handle h, const vmm_ba_options* opt, vmm_ba_summary* summary);
 
+/* ABI 6, additive.  Solves n_problems independent small bundle adjustments in ONE launch: the grid is the batch, one
+ * workgroup runs the whole Levenberg-Marquardt loop of one problem (the shape of vmm_ba_localize), with no host round
+ * trip and no hand-off between workgroups.  Stateless.  The reference's mapping step runs many bundle adjustments of a
+ * few dozen poses (src/TagReconstructor.cpp:233,236,271-277: N + 2 of them, growing from one image and one tag); so do
+ * sub-maps per room, resampled detection sets and leave-one-out re-solves.
+ *   problem     every problems[i] is an independent vmm_ba_problem, with its own camera model, sizes, fixed_tag and
+ *               observations, and is solved as vmm_ba_create + vmm_ba_solve would solve it with VMM_BA_PRECISION_F64 and
+ *               VMM_BA_LANDMARK_TAG_POSES: the same objective, and the same trust-region policy stage for stage.
+ *   constants   cam_const / tag_const: the flags of all problems one after the other (sum n_cams, sum n_tags), or NULL;
+ *               they act as vmm_ba_set_constant_poses: a constant pose comes back bit for bit.
+ *   elimination VMM_BA_ELIM_* for every problem; AUTO picks per problem what vmm_ba_create would pick.  The family that
+ *               is NOT eliminated must have at most VMM_BA_SMALL_MAX_KEPT poses (its reduced system lives in LDS); the
+ *               eliminated family and the observations are bounded only by int32.
+ *   options     every field of vmm_ba_options but num_threads and poll_interval, which are ignored.
+ *   results     cam_qt / tag_qt: the poses of all problems one after the other.  summaries[i]: termination_type,
+ *               iterations, the step and evaluation counts, elimination, initial_cost, final_cost and (where
+ *               summaries[i].trace is set on entry) the trace rows as vmm_ba_solve fills them; time_solve_s is the host
+ *               wall time of the call, the same in every summary; the device phase times, num_sync_timeouts,
+ *               sync_timeout_kernels, block_sparse and tree_ordering are 0.
+ * No output is NaN unless the input poses made the first cost non-finite (VMM_BA_FAILURE, the poses returned as given).
+ * A problem gives the same bits alone, in any batch, at any position and from run to run.  n_problems == 0 returns
+ * VMM_BA_OK without a device call.  VMM_BA_ERR_ARGUMENT (before any device call, vmm_ba_last_error() names the problem):
+ * null pointers, what vmm_ba_create rejects in a problem, a kept family above the limit, an elimination outside the
+ * enum, what vmm_ba_solve rejects in the options.  VMM_BA_ERR_HIP with the byte count if the scratch cannot be allocated. */
+#define VMM_BA_SMALL_MAX_KEPT 24   /* poses of the family that is NOT eliminated: reduced order <= 144 */
+int vmm_ba_solve_small(int32_t n_problems, const vmm_ba_problem* problems, const uint8_t* cam_const, const uint8_t* tag_const,
+                       const vmm_ba_options* o, int32_t elimination, double* cam_qt, double* tag_qt,
+                       vmm_ba_summary* summaries, int device);
+
 /* Cost-only evaluation 1/2 sum rho(|r|^2) at the current state (Ceres Evaluator, cost only). */
 int vmm_ba_cost(vmm_ba_handle h, int robustify, double huber_a, double* cost);
 

@@ -14,6 +14,7 @@ RCCL_ID_BYTES = 128      # VMM_BA_RCCL_ID_BYTES
 PRECISION_F64, PRECISION_F32_ACCUM = 0, 1
 LANDMARK_TAG_POSES, LANDMARK_POINTS = 0, 1
 RIG_MAX_CAMS = 8         # VMM_BA_RIG_MAX_CAMS
+SMALL_MAX_KEPT = 24      # VMM_BA_SMALL_MAX_KEPT
 OK, ERR_ARGUMENT, ERR_HIP, ERR_COLLECTIVE, ERR_STATE, ERR_NUMERIC = 0, 1, 2, 3, 4, 5
 ELIM_AUTO, ELIM_TAGS, ELIM_CAMERAS = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
@@ -189,6 +190,7 @@ SIGNATURES = {
     "vmm_ba_set_observation_mask": (_i, [_h, _a]),
     "vmm_ba_set_constant_poses": (_i, [_h, _a, _a]),
     "vmm_ba_solve": (_i, [_h, _P(Options), _P(Summary)]),
+    "vmm_ba_solve_small": (_i, [_i32, _P(Problem), _a, _a, _P(Options), _i32, _a, _a, _P(Summary), _i]),
     "vmm_ba_cost": (_i, [_h, _i, _d, _P(_d)]),
     "vmm_ba_reprojection_stats": (_i, [_h, _a, _a, _P(_d), _a]),
     "vmm_ba_tag_translation_covariance": (_i, [_h, _i, _d, _a]),
@@ -234,7 +236,7 @@ OPTIONAL = {"vmm_ba_covariance_blocks", "vmm_ba_rig_localize", "vmm_ba_default_r
             "vmm_ba_triangulate", "vmm_ba_locate_tags", "vmm_ba_default_predict_options", "vmm_ba_predict_localization",
             "vmm_ba_predict_localization_joint",
             "vmm_ba_set_intrinsics", "vmm_ba_get_intrinsics", "vmm_ba_intrinsics_system",
-            "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal"}
+            "vmm_ba_default_selfcal_options", "vmm_ba_solve_selfcal", "vmm_ba_solve_small"}
 
 _LIB = None
 

@@ -1,5 +1,5 @@
 // What the host files of libvmm_ba.so share (vmm_ba.hip, covariance.hip, selfcal.hip, initialize.hip, standalone.hip,
-// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip, locate.hip, predict.hip): the error returns and
+// diagnostics.hip, localize.hip, rig.hip, calibrate.hip, triangulate.hip, locate.hip, predict.hip, small_ba.hip): the error returns and
 // argument checks (one walk over an item list, check_list, for images, points and tags), the option fields and the
 // no-device answer that the stateless entries have in common, the host side of an arrowhead refinement, and
 // KnownCameras, the stage of the two entries that take known cameras (MapBatch, the stage of those that take a map, is

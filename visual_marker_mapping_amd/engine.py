@@ -338,6 +338,86 @@ class BundleAdjuster:
         return _struct_dict(t)
 
 
+_PROBLEM_ARGS = ("intr", "dist", "cam_qt", "tag_qt", "tag_wh", "fixed_tag", "obs_cam", "obs_tag", "obs_px")
+
+
+def _const_flags(flags, sizes, what):
+    """The constant flags of a batch as vmm_ba_solve_small takes them: one array per problem (or None) -> one uint8
+    array over all problems, or None when no problem names a constant pose."""
+    if flags is None:
+        return None
+    if len(flags) != len(sizes):
+        raise ValueError("%s needs one entry per problem" % what)
+    out = []
+    for a, n in zip(flags, sizes):
+        if a is None:
+            out.append(np.zeros(n, np.uint8))
+            continue
+        a = np.asarray(a)
+        if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("%s must hold boolean or integer arrays, not %s" % (what, a.dtype))
+        if a.shape != (n,):
+            raise ValueError("%s: an entry must have shape (%d,), not %s" % (what, n, a.shape))
+        out.append(np.ascontiguousarray(a != 0, np.uint8))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def solve_small(problems, cam_const=None, tag_const=None, options=None, elimination=ELIM_AUTO, trace_capacity=0, device=0):
+    """Many independent small bundle adjustments in one launch (vmm_ba_solve_small): one workgroup runs the whole
+    Levenberg-Marquardt loop of one problem.  problems: a list of dicts or tuples with the arguments of
+    BundleAdjuster.__init__ (intr, dist, cam_qt, tag_qt, tag_wh, fixed_tag, obs_cam, obs_tag, obs_px); the family that
+    is not eliminated may have at most _lib.SMALL_MAX_KEPT poses.  cam_const / tag_const: None, or one entry per problem
+    (an array of flags as BundleAdjuster.set_constant_poses takes it, or None).  Returns a list of
+    (cam_qt, tag_qt, summary) per problem, the summary in the vocabulary of BundleAdjuster.solve."""
+    n = len(problems)
+    if n == 0:
+        return []
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    ps, keep = (_lib.Problem * n)(), []
+    for p, src in zip(ps, problems):
+        v = [src[k] for k in _PROBLEM_ARGS] if isinstance(src, dict) else list(src)
+        if len(v) != len(_PROBLEM_ARGS):
+            raise ValueError("a problem needs %s" % ", ".join(_PROBLEM_ARGS))
+        intr, dist = _model_arrays(v[0], v[1])
+        cam_qt = np.ascontiguousarray(v[2], np.float64).reshape(-1, 7)
+        tag_qt = np.ascontiguousarray(v[3], np.float64).reshape(-1, 7)
+        tag_wh = np.ascontiguousarray(v[4], np.float64).reshape(-1, 2)
+        obs_cam = np.ascontiguousarray(v[6], np.int32).reshape(-1)
+        obs_tag = np.ascontiguousarray(v[7], np.int32).reshape(-1)
+        obs_px = np.ascontiguousarray(v[8], np.float64).reshape(-1, 8)
+        if not (len(obs_cam) == len(obs_tag) == len(obs_px)):
+            raise ValueError("observation arrays differ in length")
+        if len(tag_wh) != len(tag_qt):
+            raise ValueError("tag_wh and tag_qt differ in length")
+        keep.append((cam_qt, tag_qt, tag_wh, obs_cam, obs_tag, obs_px))
+        p.intr[:] = list(intr)
+        p.dist[:] = list(dist)
+        p.n_cams, p.n_tags = len(cam_qt), len(tag_qt)
+        p.cam_qt, p.tag_qt, p.tag_wh = dp(cam_qt), dp(tag_qt), dp(tag_wh)
+        p.fixed_tag = int(v[5])
+        p.n_obs, p.obs_cam, p.obs_tag, p.obs_px = len(obs_cam), ip(obs_cam), ip(obs_tag), dp(obs_px)
+    cc = _const_flags(cam_const, [p.n_cams for p in ps], "cam_const")
+    tc = _const_flags(tag_const, [p.n_tags for p in ps], "tag_const")
+    cam = np.zeros((sum(p.n_cams for p in ps), 7))
+    tag = np.zeros((sum(p.n_tags for p in ps), 7))
+    ss, bufs = (_lib.Summary * n)(), []
+    for s in ss:
+        buf = None
+        if trace_capacity > 0:
+            buf = (_lib.Iteration * trace_capacity)()
+            s.trace, s.trace_capacity = buf, trace_capacity
+        bufs.append(buf)
+    o = options or default_options()
+    _lib.check(_lib.lib().vmm_ba_solve_small(n, ps, _ptr(cc), _ptr(tc), C.byref(o), int(elimination), _ptr(cam), _ptr(tag),
+                                             ss, int(device)))
+    out, c0, t0 = [], 0, 0
+    for p, s, buf in zip(ps, ss, bufs):
+        out.append((cam[c0:c0 + p.n_cams].copy(), tag[t0:t0 + p.n_tags].copy(), _summary_dict(s, buf, trace_capacity)))
+        c0, t0 = c0 + p.n_cams, t0 + p.n_tags
+    return out
+
+
 def joint_covariance(caa, cab, cbb):
     """The 12x12 covariance [[Caa, Cab], [Cab^T, Cbb]] of two poses from their marginals and their cross block."""
     caa, cab, cbb = (np.asarray(m, np.float64).reshape(6, 6) for m in (caa, cab, cbb))

@@ -165,6 +165,7 @@ class TagReconstructor:
         self._cached = None                                    # (structure key, BundleAdjuster) of the last call
         self._obs_cache = None                                 # observation list as arrays (see _obs_arrays)
         self._resident = False                                 # device-resident packing (startReconstruction)
+        self._oneLaunch = False                                # startReconstruction(oneLaunch=True) while it runs
         self._full = None                                      # the whole detection set as problem arrays
 
     # -- trivial accessors (src/TagReconstructor.cpp:75-84, 818-842) --
@@ -214,8 +215,11 @@ class TagReconstructor:
     def _model_report(report, intr, dist, cov):
         return dict(report, intrinsics=np.concatenate([intr, dist]), covariance=cov, std=np.sqrt(np.diag(cov)))
 
-    def startReconstruction(self, numThreads=1, deviceResident=True):
-        """deviceResident: ONE device handle holds every image, tag and observation of the detection result for
+    def startReconstruction(self, numThreads=1, deviceResident=True, oneLaunch=False):
+        """oneLaunch: every bundle adjustment of the run whose kept family fits goes through engine.solve_small (see
+        doBundleAdjustment); the default keeps every call as it was.
+
+        deviceResident: ONE device handle holds every image, tag and observation of the detection result for
         the whole run and each of the N+2 bundle adjustments / prunings only sends an observation mask and the
         poses (vmm_ba_set_observation_mask); False rebuilds a handle whenever the problem structure changes.
         Same results either way (tests/test_gpu_driver.py).
@@ -229,8 +233,12 @@ class TagReconstructor:
         The bundle adjustments and the reprojection statistics run on the MI355X through libvmm_ba; the two
         PnP initialisations are host code in pnp.py (OpenCV's role in the reference)."""
         from . import pnp as _pnp
-        with self._resident_frame(deviceResident):
-            self._start_reconstruction(numThreads, _pnp)
+        self._oneLaunch = bool(oneLaunch)
+        try:
+            with self._resident_frame(deviceResident):
+                self._start_reconstruction(numThreads, _pnp)
+        finally:
+            self._oneLaunch = False
 
     @contextlib.contextmanager
     def _resident_frame(self, resident=True):
@@ -929,6 +937,10 @@ class TagReconstructor:
         reconstructed, in file order."""
         if self._resident:
             return self._pack_resident(for_ba)
+        return self._pack_cold(for_ba)
+
+    def _pack_cold(self, for_ba):
+        """_pack without the device-resident variant: the arrays of this step's problem alone."""
         # the cost functor receives the DETECTION tag's width/height but builds the quad from the reconstructed tag's
         # (:713 vs :718); only the quad enters the arithmetic, so tag_wh is the reconstructed tags'
         tag_ids, tag_qt, tag_wh = self._map_arrays()
@@ -1090,8 +1102,12 @@ class TagReconstructor:
             self.reconstructedCameras[cid].t = cam[k, 4:].copy()
 
     def doBundleAdjustment(self, maxNumIterations, ceresThreads=1, robustify=True, printSummary=False,
-                           elimination=_engine.ELIM_AUTO, refineCameraModel=False, refine_mask=0x1FF):
+                           elimination=_engine.ELIM_AUTO, refineCameraModel=False, refine_mask=0x1FF, oneLaunch=False):
         """src/TagReconstructor.cpp:646-743.  Poses are updated in place like the reference's map nodes.
+
+        oneLaunch (or startReconstruction(oneLaunch=True) while it runs): a bundle adjustment whose kept family has at
+        most _lib.SMALL_MAX_KEPT poses is solved by engine.solve_small from this step's own arrays -- one launch, no
+        handle; one that does not fit, and every printSummary or refineCameraModel request, takes the path below.
 
         refineCameraModel (not in the reference, which takes the camera model as given): the parameters of refine_mask
         (bit i = parameter i of fx, fy, cx, cy, k1, k2, p1, p2, k3) are refined together with the poses
@@ -1099,6 +1115,9 @@ class TagReconstructor:
         vmm_ba_selfcal_report plus `intrinsics` (9,), `covariance` (9, 9) and `std` (9,).  lastSummary is then the
         summary of the last inner solve.  The inner solves run with function_tolerance 1e-14 and parameter_tolerance
         1e-12 instead of the defaults, which stop too early for the outer loop's cost comparisons."""
+        if (oneLaunch or self._oneLaunch) and not printSummary and not refineCameraModel \
+                and self._bundle_adjust_in_one_launch(maxNumIterations, ceresThreads, robustify, elimination):
+            return
         p = self._pack_for_ba()
         if p is None:
             return
@@ -1153,6 +1172,33 @@ class TagReconstructor:
                 avg_diag += diag
             avg_diag /= len(p["tag_ids"])
             print("Marker Position RMS = %.6g" % np.linalg.norm(np.sqrt(avg_diag)))
+
+    def _write_back_poses(self, p, cam, tag):
+        self._write_back_cameras(p, cam)
+        for k, tid in zip(p["tag_rows"], p["tag_ids"]):
+            self.reconstructedTags[tid].q = tag[k, :4].copy()
+            self.reconstructedTags[tid].t = tag[k, 4:].copy()
+
+    def _bundle_adjust_in_one_launch(self, maxNumIterations, ceresThreads, robustify, elimination):
+        """doBundleAdjustment through engine.solve_small; False (nothing done) when the kept family does not fit."""
+        p = self._pack_cold(for_ba=True)
+        if self._is_empty(p):
+            return False   # the existing path reports the empty problem
+        n_cams, n_tags = len(p["cam_ids"]), len(p["tag_ids"])
+        elim_cams = n_cams >= n_tags if elimination == _engine.ELIM_AUTO else elimination == _engine.ELIM_CAMERAS
+        if (n_tags if elim_cams else n_cams) > _engine._lib.SMALL_MAX_KEPT:
+            return False
+        opts = _engine.default_options(max_num_iterations=int(maxNumIterations), robustify=int(bool(robustify)),
+                                       num_threads=int(ceresThreads))
+        problem = (p["intr"], p["dist"], p["cam_qt"], p["tag_qt"], p["tag_wh"], p["fixed"], p["obs_cam"], p["obs_tag"],
+                   p["obs_px"])
+        tc = p.get("tag_const")
+        (cam, tag, summary), = _engine.solve_small([problem], tag_const=[tc] if tc is not None and tc.any() else None,
+                                                   options=opts, elimination=elimination, device=self.device)
+        self._write_back_poses(p, cam, tag)
+        self.lastSummary = summary
+        print("Solution %d" % summary["termination_type"])                                   # :740
+        return True
 
     def computePoseCovariances(self, robustify=False, jointTags=False):
         """The 6x6 covariance (tangent order: translation, then rotation) of every reconstructed tag and camera at the
